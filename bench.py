@@ -7,10 +7,16 @@
 
 A step = STFT(noisy) + STFT(clean) -> unet_2 (4 enc/dec convs, 1 GRU group) forward -> mask*spectrum
 -> WO-MALE -> backward -> gradient all-reduce (RCCL) -> Adam, on 64 clips x 4 s per GPU
-(BASELINE.json configs[1]); inputs are synthetic and resident in HBM before the timed region.
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-  roofline     -- the dominant kernel of the step, timed live with HIP events
-  cpu_baseline -- the torch-CPU oracle (a port of the reference; oracle/) on this box's host cores
+(BASELINE.json configs[1]); inputs are synthetic, seeded and resident in HBM before the timed region.
+Prints ONE JSON line on rank 0: metric, value (frames/s), unit, higher_is_better, dtype, ms_per_step (wall time of one timed
+step) and the run's configuration.  A plain run does only that: set up, warm up, time --steps steps, print.
+  --dump-outputs DIR  after the timed steps, run the timed path's step once more from the seeded start state on the last
+                      timed step's inputs and write what it computed (loss, parameters after Adam, their gradients,
+                      BatchNorm running statistics) as DIR/<name>.npy, to compare two builds output for output
+  --full              also measure and check everything beyond the headline, in the same JSON line:
+    roofline     -- the dominant kernel of the step, timed live with HIP events
+    cpu_baseline -- the torch-CPU oracle (a port of the reference; oracle/) on the host's CPU cores
+    parity_rel_l2, secondary rows (other precisions, configurations, batch sizes, trainer path), regressions
 """
 from __future__ import annotations
 
@@ -49,6 +55,12 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="launch the step's kernels eagerly (no HIP graph)")
     ap.add_argument("--graph", action="store_true", help="replay the step from HIP graph(s); default: time both forms during "
                                                           "warm-up and keep the faster")
+    ap.add_argument("--full", action="store_true", help="besides the headline: CPU baseline, oracle parity, per-kernel timing and "
+                                                        "rooflines, secondary rows and the regression check (the --no-* options "
+                                                        "below drop single parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: one step from the seeded start on the "
+                                                                        "last timed step's inputs; its loss, parameters, gradients "
+                                                                        "and BatchNorm running statistics to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the T=401 oracle parity figure (parity_rel_l2)")
@@ -923,6 +935,54 @@ def regression_guard(out, threshold=0.08):
             "rows_missing_now": missing}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def engine_state(eng) -> dict:
+    """The parameters and BatchNorm buffers an engine starts from (taken before its first step)."""
+    return {"params": eng.flat.params.clone(), "buffers": {k: b.clone() for k, b in eng.Bf.items()}}
+
+
+def replay_one_step(eng, start: dict, noisy, clean) -> float:
+    """Put the engine back to `start` with fresh Adam state and run ONE step of the timed path -- same engine, same launch form
+    (the captured graphs when it replays them), same kernels -- on the given inputs; returns that step's loss.
+    Why not dump the last timed step itself: the library's BatchNorm / bias reductions accumulate with atomics, so a step's
+    gradients differ from run to run in the last bits, and every later Adam step carries that on; after tens of chained steps two
+    runs of one build stood 1e-2 apart (rel-L2 of the parameters).  One step from the seeded start state is the same every run
+    up to rounding.  (On every rank: the step all-reduces at world > 1.)"""
+    eng.flat.params.copy_(start["params"])
+    for k, b in start["buffers"].items():
+        eng.Bf[k].copy_(b)
+    for t in (eng.flat.grads, eng.flat.exp_avg, eng.flat.exp_avg_sq, eng._skipped, eng._health, eng._loss_acc):
+        t.zero_()
+    eng.step_count = 0
+    ls = eng.step(noisy, clean)
+    torch.cuda.synchronize()
+    return eng.loss_value(ls)
+
+
+def dump_outputs(out_dir: str, eng, loss: float) -> dict:
+    """What the caller of TrainEngine.step holds after the step of replay_one_step(), as float32 / float64 .npy files: the loss,
+    the parameters after Adam and the step's gradients (each concatenated in model.named_parameters() order, independent of the
+    flat buffer's bucket layout), and the BatchNorm running statistics the forward pass updated.  Returns {name: shape}."""
+    import numpy as np
+    names = [n for n in eng.flat.order if n in eng.flat.G]
+    stats = [b.reshape(-1).float() for k, b in eng.model.named_buffers() if k.endswith((".running_mean", ".running_var"))]
+    arrays = {
+        "loss": np.array([loss], dtype=np.float64),
+        "params": torch.cat([eng.flat.P[n].reshape(-1) for n in names]).float().cpu().numpy(),
+        "grads": torch.cat([eng.flat.G[n].reshape(-1) for n in names]).float().cpu().numpy(),
+        "bn_running_stats": torch.cat(stats).cpu().numpy(),
+    }
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -960,7 +1020,7 @@ def main():
     from cruse_amd.model.cruse_net import unet_2
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         log("cpu baseline (oracle on host cores) ...")
         cpu = cpu_baseline(a.groups)
         log(f"cpu baseline done: {cpu['value']} frames/s on {cpu['cores']} threads")
@@ -968,7 +1028,7 @@ def main():
     torch.manual_seed(0)
     model = unet_2(rnn_groups=a.groups, precision=a.prec).to(dev)
     parity = None
-    if rank == 0 and not a.no_parity:
+    if a.full and rank == 0 and not a.no_parity:
         log("parity figure: this model vs the CPU oracle at T=401, B=8 ...")
         parity = parity_figure(model, a.groups, a.prec)
         log(f"parity_rel_l2 = {parity:.3e}")
@@ -980,6 +1040,7 @@ def main():
     B, L = a.batch, int(a.seconds * 16000)
     T = 1 + L // 160
     pool = [synth_batch(B, L, dev, 1234 + 1000 * rank + s) for s in range(4)]
+    start = engine_state(eng) if a.dump_outputs else None
 
     def sync():
         if world > 1:
@@ -1045,9 +1106,17 @@ def main():
     loss = eng.loss_value(ls)
     status = ops.gru_status() | eng.timeout_steps()      # (the engine latches and clears the device word every step)
     log(f"timed region done: {el / a.steps * 1e3:.2f} ms/step (median step {med_ms:.2f} ms)")
+    skipped = eng.skipped_steps()
+    dumped = None
+    if a.dump_outputs:
+        # after the timed steps (their figures and counters are taken above) and before any --full pass below
+        dump_loss = replay_one_step(eng, start, *pool[(a.steps - 1) % len(pool)])
+        if rank == 0:
+            dumped = dump_outputs(a.dump_outputs, eng, dump_loss)
+            log(f"outputs of one step from the seeded start on the last timed step's inputs written to {a.dump_outputs}: {dumped}")
 
     roof, breakdown = None, None
-    if rank == 0 and not a.no_kernel_timing:
+    if a.full and rank == 0 and not a.no_kernel_timing:
         with KernelTimer(ops, eng) as kt:
             eng._fwd_bwd(*pool[0])                       # un-graphed warm-up: allocator and attribute caches
             torch.cuda.synchronize()
@@ -1093,7 +1162,7 @@ def main():
 
     secondary = None
     frames_per_s_headline = world * B * T * a.steps / el
-    if rank == 0 and world == 1 and not a.no_secondary:
+    if a.full and rank == 0 and world == 1 and not a.no_secondary:
         secondary = secondary_rows(a, dev, pool)
         secondary.update(config_rows(a, dev, pool))
         log("secondary: trainer path (device-resident / host dataset) ...")
@@ -1142,19 +1211,19 @@ def main():
             "value_at_median_step": round(world * B * T / (med_ms * 1e-3), 1),
             "parity_rel_l2": None if parity is None else float(f"{parity:.4g}"),
             "parity_note": "enhanced-spectrum rel-L2 of this model/mode vs the CPU oracle at T=401, B=8 (bar 1e-3)",
-            "final_loss": round(loss, 6), "gru_handoff_timeouts": status, "skipped_steps": eng.skipped_steps(),
+            "final_loss": round(loss, 6), "gru_handoff_timeouts": status, "skipped_steps": skipped,
             "stream_probe": _stream_probe_report(),
             "roofline": roof, "roofline_step": step_roofline(frames / el, a.groups, a.prec, B, T),
-            "kernel_ms_per_step": breakdown, "cpu_baseline": cpu, "secondary": secondary,
+            "kernel_ms_per_step": breakdown, "cpu_baseline": cpu, "secondary": secondary, "full": a.full, "outputs_dumped": dumped,
         }
-        out["regressions"] = regression_guard(out)
+        out["regressions"] = regression_guard(out) if a.full else None
         # one compact line of row -> ms on stderr (the driver's tail of the JSON line itself cuts the secondary rows' head)
         rows = {"headline": out["ms_per_step"]}
         for k_, v_ in (secondary or {}).items():
             if isinstance(v_, dict) and v_.get("ms_per_step") is not None:
                 rows[k_] = v_["ms_per_step"]
         log("ROWS ms/step: " + json.dumps(rows))
-        if out["regressions"].get("flagged"):
+        if out["regressions"] and out["regressions"].get("flagged"):
             log("REGRESSIONS vs " + str(out["regressions"].get("reference")) + ": " + json.dumps(out["regressions"]["flagged"]))
         # RCCL writes a version banner through C stdio; push it out first so that the JSON line is the LAST line of stdout
         import ctypes

@@ -1,5 +1,6 @@
 """CPU: the oracle against the golden vectors produced by the reference's own code
-(tests/golden/make_golden.py).  Bit-exact where the op sequence is identical."""
+(tests/golden/make_golden.py).  Bit-exact where the op sequence is identical and no MKL / oneDNN kernel is involved; within a
+few float32 ulps (_same) where their CPU-dependent kernels are."""
 import numpy as np
 import torch
 
@@ -10,22 +11,31 @@ def _c(a):
     return torch.view_as_complex(torch.from_numpy(a).contiguous())
 
 
+def _same(a, b, tol=1e-5):
+    """An oracle output against the reference's recorded one, where both go through MKL / oneDNN float32 kernels.  On a CPU where MKL
+    runs its Intel AVX-512 kernels (the fixtures' recording host) the two are bit-identical; MKL's generic x86 path (CPUs of other
+    vendors, whatever MKL_CBWR says) sums in another order and moves them by a few float32 ulps of the tensor's scale (at most
+    1.7e-6 of max|b| measured).  A wrong gate, window, bias or layout is off by orders of magnitude more."""
+    a, b = torch.as_tensor(a).detach().double(), torch.as_tensor(b).double()
+    return a.shape == b.shape and float((a - b).abs().max()) <= tol * float(b.abs().max())
+
+
 def test_stft_golden(golden):
     g = golden("g1_stft.npz")
     for L, T in ((3200, 21), (3199, 20), (3201, 21)):
         X = O.stft(torch.from_numpy(g[f"x_{L}"]), 320, 160, 320)
         assert X.shape == (2, 161, T)
-        assert torch.equal(torch.view_as_real(X), torch.from_numpy(g[f"X_{L}"]))
+        assert _same(torch.view_as_real(X), torch.from_numpy(g[f"X_{L}"]))
 
 
 def test_istft_golden(golden):
     g = golden("g7_istft.npz")
     X = _c(g["X"])
     y = O.istft(X, 320, 160, 320, length=3200)
-    assert torch.equal(y, torch.from_numpy(g["y_rt"]))
+    assert _same(y, torch.from_numpy(g["y_rt"]))
     assert (y - torch.from_numpy(g["x"])).abs().max() < 1e-5
     ym = O.istft(X * torch.from_numpy(g["m"]), 320, 160, 320, length=3200)
-    assert torch.equal(ym, torch.from_numpy(g["y_masked"]))
+    assert _same(ym, torch.from_numpy(g["y_masked"]))
 
 
 def test_ggru_golden(golden):
@@ -34,7 +44,7 @@ def test_ggru_golden(golden):
     for grp in (1, 2, 4):
         m = O.GGRU(hidden_size=640, groups=grp)
         O.closed_form_init(m)
-        assert torch.allclose(m(x), torch.from_numpy(g[f"y_g{grp}"]), atol=1e-6)
+        assert _same(m(x), torch.from_numpy(g[f"y_g{grp}"]))
 
 
 def test_unet2_golden(golden):
@@ -69,7 +79,7 @@ def test_state_dict_keys():
 def test_losses_golden(golden):
     g = golden("g5_loss.npz")
     w = O.wo_male(torch.from_numpy(g["ref"]), torch.from_numpy(g["est"]), torch.from_numpy(g["unproc"]))
-    assert torch.equal(w, torch.from_numpy(g["wo_male"]))
+    assert _same(w, torch.from_numpy(g["wo_male"]))
     s1, s2 = torch.from_numpy(g["s1"]), torch.from_numpy(g["s2"])
     assert torch.equal(O.sisnr(s1, s2), torch.from_numpy(g["sisnr"]))
     assert torch.equal(O.si_snr_loss(s1, s2), torch.from_numpy(g["si_snr_loss"]))
@@ -155,7 +165,7 @@ def test_oracle_ext_conv_blocks_and_group_gru(golden):
     m = X.GroupGRU(128, 128, num_layers=3, groups=4, add_outputs=True)
     O.closed_form_init(m, scale=2.0)
     y, s = m(_t(gg["x"]))
-    assert torch.equal(y, _t(gg["g4_l3_add/y"])) and torch.equal(s, _t(gg["g4_l3_add/state"]))
+    assert _same(y, _t(gg["g4_l3_add/y"])) and _same(s, _t(gg["g4_l3_add/state"]))
 
 
 def test_oracle_ext_stft_variants_and_mtfaa(golden):
@@ -165,16 +175,16 @@ def test_oracle_ext_stft_variants_and_mtfaa(golden):
     wav = _t(g["wav"])
     K = X.init_stft_kernel(320, 160)
     m, p, r, i = X.custom_stft(wav, K, 160)
-    assert torch.equal(r, _t(g["custom512/r"])) and torch.equal(m, _t(g["custom512/m"]))
-    assert torch.equal(X.custom_istft(_t(g["custom512/m"]), _t(g["custom512/p"]), K, 160), _t(g["custom512/y"]))
+    assert _same(r, _t(g["custom512/r"])) and _same(m, _t(g["custom512/m"]))
+    assert _same(X.custom_istft(_t(g["custom512/m"]), _t(g["custom512/p"]), K, 160), _t(g["custom512/y"]))
     cs = X.ConvSTFT(320, 160)
     sr, si, mag, _ = cs.stft(wav)
-    assert torch.equal(sr, _t(g["conv/spec_r"])) and torch.equal(si, _t(g["conv/spec_i"]))
+    assert _same(sr, _t(g["conv/spec_r"])) and _same(si, _t(g["conv/spec_i"]))
     assert float((cs.istft(torch.stack([sr, si], 1)) - wav).abs().max()) < 2e-6           # the (decided) inverse inverts
     a = golden("g14_mtfaa.npz")
-    assert torch.equal(X.mtfaa_stft_transform(_t(a["sig"]), 320, 160, 320, "hamm"), _t(a["stft_hamm"]))
+    assert _same(X.mtfaa_stft_transform(_t(a["sig"]), 320, 160, 320, "hamm"), _t(a["stft_hamm"]))
     blk = X.TFCM_Block(24, (3, 3), 4); O.closed_form_init(blk, 2.0); blk.train()
-    assert torch.equal(blk(_t(a["tfcm/x"])), _t(a["tfcm_d4/y_train"]))
+    assert _same(blk(_t(a["tfcm/x"])), _t(a["tfcm_d4/y_train"]))
 
 
 def test_oracle_ext_deepfilter_step(golden):
@@ -183,7 +193,7 @@ def test_oracle_ext_deepfilter_step(golden):
     g = golden("g16_df_step_g1.npz")
     m = O.unet_2(rnn_groups=1); O.closed_form_init(m); m.train()
     loss, aux = X.train_step_loss_df(m, _t(g["noisy"]), _t(g["clean"]))
-    assert torch.equal(loss, _t(g["loss"])) and torch.equal(aux["est"], _t(g["est"]))
+    assert _same(loss, _t(g["loss"])) and _same(aux["est"], _t(g["est"]))
     assert float(aux["est"][:, :, :, 160].abs().max()) > 0.0        # the 11-bin neighbourhood reaches the Nyquist bin
 
 
@@ -192,8 +202,8 @@ def test_oracle_ext_preprocess(golden):
     g = golden("g17_preprocess.npz")
     pp = X.PreProcess(320, 160, 320, "hanning", "complex_mapping", "freq")
     out = pp.pre_stft(_t(g["wav"]))
-    assert torch.equal(out[0], _t(g["stft"])) and torch.equal(out[3], _t(g["mags"]))
-    assert torch.equal(pp.masking(_t(g["mask_real"]), _t(g["mask_imag"])), _t(g["complex_mapping/masked"]))
+    assert _same(out[0], _t(g["stft"])) and _same(out[3], _t(g["mags"]))
+    assert _same(pp.masking(_t(g["mask_real"]), _t(g["mask_imag"])), _t(g["complex_mapping/masked"]))
 
 
 def test_oracle_sdnr_vs_reference_fixture(golden):
@@ -216,7 +226,7 @@ def test_oracle_round3_fixtures(golden):
         m = X.GroupGRU(128, 128, **kw)
         O.closed_form_init(m, scale=2.0)
         y, s = m(x, torch.from_numpy(g[f"{name}/state_in"]))
-        assert torch.equal(y, torch.from_numpy(g[f"{name}/y"])) and torch.equal(s, torch.from_numpy(g[f"{name}/state"])), name
+        assert _same(y, torch.from_numpy(g[f"{name}/y"])) and _same(s, torch.from_numpy(g[f"{name}/state"])), name
     # G22: GroupedGRULayer(bidirectional=True, dropout=0.3) as shipped
     g = golden("g22_grouped_gru_bidirectional.npz")
     x = torch.from_numpy(g["x"])
@@ -224,9 +234,9 @@ def test_oracle_round3_fixtures(golden):
         m = X.GroupedGRULayer(128, 128, grp, dropout=0.3, bidirectional=True).train()
         O.closed_form_init(m, scale=2.0)
         y, st = m(x, torch.from_numpy(g[f"{name}/state_in"]))
-        assert torch.equal(y, torch.from_numpy(g[f"{name}/y"])) and torch.equal(st, torch.from_numpy(g[f"{name}/state"])), name
+        assert _same(y, torch.from_numpy(g[f"{name}/y"])) and _same(st, torch.from_numpy(g[f"{name}/state"])), name
         y0, st0 = m(x)
-        assert torch.equal(y0, torch.from_numpy(g[f"{name}/y_zero_state"])) and torch.equal(st0, torch.from_numpy(g[f"{name}/state_zero_state"]))
+        assert _same(y0, torch.from_numpy(g[f"{name}/y_zero_state"])) and _same(st0, torch.from_numpy(g[f"{name}/state_zero_state"]))
     s = golden("g20_snr_mix_rir.npz")
     for b in range(3):
         noisy, c, n = X.snr_mix(s["clean"][b].copy(), s["noise"][b].copy(), float(s["snr"][b]), rir=s["rir"][b].copy(),
@@ -238,7 +248,7 @@ def test_oracle_round3_fixtures(golden):
         m = X.CRUSE4MagAddSkipUpsample(rnn_groups=grp)
         O.closed_form_init(m)
         m.train()
-        assert torch.equal(m(torch.from_numpy(g["x"])), torch.from_numpy(g[f"g{grp}/mask_train"]))
+        assert _same(m(torch.from_numpy(g["x"])), torch.from_numpy(g[f"g{grp}/mask_train"]))
 
 
 def test_oracle_round4_fixtures(golden):
@@ -254,8 +264,8 @@ def test_oracle_round4_fixtures(golden):
         O.closed_form_init(m, scale=2.0)
         x = x_tb if not kw.get("batch_first", True) else x_tb.transpose(0, 1).contiguous()
         y, s = m(x, torch.from_numpy(g[f"{name}/state_in"]))
-        assert torch.equal(y, torch.from_numpy(g[f"{name}/y"])) and torch.equal(s, torch.from_numpy(g[f"{name}/state"])), name
-        assert torch.equal(m(x)[0], torch.from_numpy(g[f"{name}/y0"]))
+        assert _same(y, torch.from_numpy(g[f"{name}/y"])) and _same(s, torch.from_numpy(g[f"{name}/state"])), name
+        assert _same(m(x)[0], torch.from_numpy(g[f"{name}/y0"]))
     o = O.unet_2(rnn_groups=1)
     O.closed_form_init(o)
     o.train()
