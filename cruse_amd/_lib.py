@@ -132,6 +132,11 @@ SIGNATURES = {
     "cruse_zero": ("pzp", "i"),
     "cruse_accum_f64": ("ppip", "i"),
     "cruse_counters_add": ("piqp", "i"),
+    "cruse_stream_layout": ("iiiiip", "i"),
+    "cruse_stream_tables": ("pp", "i"),
+    "cruse_stream_encode": ("piiiiiipppppp", "i"),
+    "cruse_stream_gru": ("piiiipiippfpiippiip", "i"),
+    "cruse_stream_decode": ("piiiiiippfpppp", "i"),
 }
 
 

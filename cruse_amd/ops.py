@@ -1034,3 +1034,44 @@ def sumsq(x, out=None, accumulate=False):
         out = torch.empty(1, device=x.device, dtype=torch.float64)
     check(lib.cruse_sumsq(_p(x), x.numel(), _p(out), 1 if accumulate else 0, _stream()))
     return out
+
+
+# ======================================================================================================================
+# frame-by-frame streaming of unet_2 (cruse_stream_*; cruse_amd/inferencer/streaming.py drives the chain)
+# ======================================================================================================================
+STREAM_LAYOUT_NAMES = (
+    [f"ch{k}" for k in range(5)] + [f"F{k}" for k in range(5)] + ["H"]
+    + [f"{n}{k}" for n in ("encW", "encB", "skW", "decW", "decB") for k in range(5)]
+    + ["ln1g", "ln1b", "ln2g", "ln2b", "wtotal", "st_hist", "st_tail"] + [f"st_prev{k}" for k in range(4)]
+    + ["st_h1", "st_h2", "st_stride", "wk_re", "wk_im", "wk_x"] + [f"wk_skip{k}" for k in range(5)]
+    + ["wk_h1n", "wk_h2n", "wk_mask", "wk_stride"])
+STREAM_SKIP, STREAM_STORE, STREAM_FRAME, STREAM_FRAME0, STREAM_END = 0, 1, 2, 3, 4
+
+
+def stream_layout(ch) -> Dict[str, int]:
+    """Offsets (floats) of the packed weights and of the per-slot state / work rows of the streaming kernels."""
+    arr = (ctypes.c_int * len(STREAM_LAYOUT_NAMES))()
+    check(lib.cruse_stream_layout(*[int(c) for c in ch], arr))
+    return dict(zip(STREAM_LAYOUT_NAMES, list(arr)))
+
+
+def stream_tables(device) -> torch.Tensor:
+    tab = torch.empty(1120, device=device, dtype=torch.float32)
+    check(lib.cruse_stream_tables(_p(tab), _stream()))
+    return tab
+
+
+def stream_encode(mode, ch, blocks, tab, w, state, work) -> None:
+    check(lib.cruse_stream_encode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(blocks), _p(tab), _p(w), _p(state), _p(work),
+                                  _stream()))
+
+
+def stream_gru(mode, layer, groups, Hg, x, x_off, hprev, h_off, pack, hout, o_off, ln_g=None, ln_b=None, ln_eps=1e-5) -> None:
+    """x / hprev / hout are [S, stride] row tensors read / written at the given float offsets."""
+    check(lib.cruse_stream_gru(_p(mode), mode.numel(), layer, groups, Hg, _p(x), x.shape[1], x_off, _p(ln_g), _p(ln_b), float(ln_eps),
+                               _p(hprev), hprev.shape[1], h_off, _p(pack), _p(hout), hout.shape[1], o_off, _stream()))
+
+
+def stream_decode(mode, ch, tab, w, ln_eps, state, work, out) -> None:
+    check(lib.cruse_stream_decode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state), _p(work),
+                                  _p(out), _stream()))

@@ -732,6 +732,49 @@ int cruse_step_health(unsigned* gru_status, const double* loss_sum, unsigned* he
 /* out (+)= sum x[i]^2 in f64 (total gradient norm for clip_grad_norm_); x 16-byte aligned */
 int cruse_sumsq(const float* x, long long n, double* out, int accumulate, void* stream);
 
+/* ---- frame-by-frame streaming inference of unet_2 (n_fft = win = 320, hop = 160; ABI 13, additive) ---------------------
+ * One hop of S independent streams ("slots"): cruse_stream_encode -> cruse_stream_gru (layer 1) -> cruse_stream_gru (layer 2)
+ * -> cruse_stream_decode, dependent launches on one stream.  mode[S] (device, int) says what each slot does in this chain;
+ * a SKIP slot is not touched.  Per-slot state and work rows are laid out by cruse_stream_layout.  f32 throughout.
+ * Stands for, one frame at a time: feature.stft + PreProcess.pre_stft (train_base/acoustics/feature.py:10-30,
+ * utils/utils.py:397-405), unet_2.forward with GGRU (model/cruse_net.py:14-55,147-165), PreProcess.masking
+ * (utils/utils.py:417-420) and feature.istft (train_base/acoustics/feature.py:33-61). */
+enum {
+    CRUSE_STREAM_MODE_SKIP = 0,   /* slot not active in this chain                                                      */
+    CRUSE_STREAM_MODE_STORE = 1,  /* block 0: store the block in the analysis history, no frame                          */
+    CRUSE_STREAM_MODE_FRAME = 2,  /* frame b from the previous block and this one; the history advances                  */
+    CRUSE_STREAM_MODE_FRAME0 = 3, /* frame 0 (first half reflected, x[160] from this block); the history does not advance */
+    CRUSE_STREAM_MODE_END = 4     /* the end frame: last block and its end reflection; no input                          */
+};
+#define CRUSE_STREAM_LAYOUT_INTS 62
+/* out[CRUSE_STREAM_LAYOUT_INTS] (HOST array): ch[5], F[5], H, packed-weight offsets encW[5], encB[5], skW[5], decW[5], decB[5]
+ * (index = level, 0 unused), ln1g, ln1b, ln2g, ln2b, weight floats; state-row offsets hist, tail, prev[4] (mag, e1, e2, e3), h1,
+ * h2, state stride; work-row offsets re, im, x (GRU input, c*F4+f), skip[5], h1 (new), h2 (new), mask, work stride (floats).
+ * Rejects ch[0] != 1. */
+int cruse_stream_layout(int c0, int c1, int c2, int c3, int c4, int* out);
+/* tab[1120] (device) <- periodic Hann(320), cos / sin(2 pi j / 320), 1 / (w^2(m) + w^2(m+160)); synchronises `stream` */
+int cruse_stream_tables(float* tab, void* stream);
+/* frame assembly from the history, Hann window, 320-point real DFT (re / im of 161 bins -> work), mag = sqrt(re^2+im^2+1e-8) of
+ * bins 0..159, the four encoder convs (2,3) on (previous row, this row) with BatchNorm folded into w and ReLU, the four skip
+ * convs (1,3), the GRU input row; updates history and previous rows.  in[S][160]: this hop's blocks (model/cruse_net.py:147-156,
+ * train_base/acoustics/feature.py:10-30, utils/utils.py:397-405) */
+int cruse_stream_encode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* in, const float* tab,
+                        const float* w, float* state, float* work, void* stream);
+/* one GGRU layer (model/cruse_net.py:22-50), one time step: g groups of Hg units (Hg % 4 == 0, Hg <= 1024), gate order r,z,n,
+ * b_hn inside r*(.).  pack = W_ih [g][3Hg][Hg] | W_hh [g][3Hg][Hg] | b_ih [g][3Hg] | b_hh [g][3Hg].  Slot s reads
+ * x[s*x_stride + x_off + ...] and hprev[s*h_stride + h_off + i*Hg + j], writes hout[s*o_stride + o_off + i*Hg + j].  layer 1:
+ * group i reads x chunk i.  layer 2: x is layer 1's output row (group-contiguous); LN1 (ln_g, ln_b, ln_eps) is applied to its
+ * interleaved view v[j*g+i] (cruse_net.py:43-46) and group i reads chunk i of LN1(v) */
+int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg, const float* x, int x_stride, int x_off,
+                     const float* ln_g, const float* ln_b, float ln_eps, const float* hprev, int h_stride, int h_off,
+                     const float* pack, float* hout, int o_stride, int o_off, void* stream);
+/* LN2 of the layer-2 output + skip4, the four ConvTranspose (1,3) stride 2 levels (last column cropped, BatchNorm folded, ReLU,
+ * + skip; the last one sigmoid: model/cruse_net.py:158-164), the mask on bins 0..159 with bin 160 zero (utils/utils.py:417-420),
+ * 320-point inverse real DFT, window, overlap-add with the stored tail and division by the window envelope
+ * (train_base/acoustics/feature.py:33-61) -> out[S][160]; copies the new GRU states into the state rows */
+int cruse_stream_decode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
+                        float ln_eps, float* state, float* work, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

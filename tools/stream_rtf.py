@@ -1,0 +1,78 @@
+"""Real-time factor of frame-by-frame streaming inference (cruse_amd.inferencer.StreamingInferencer) on one GPU.
+
+For each n_slots: host wall time of one push (160 new samples for every slot) measured around a device synchronise after warm-up,
+over >= `--seconds` of pushes (mean / p50 / p99), device time per hop from events around the push, and RTF = push time / 10 ms
+(one hop at 16 kHz).  Prints one JSON object.  Kernel times: run under `rocprofv3 --kernel-trace --stats -- python tools/stream_rtf.py`.
+
+    python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def closed_form(model):
+    """deterministic weights (the oracle's closed_form_init formula) without importing the test oracle"""
+    import math
+    with torch.no_grad():
+        for i, (name, p) in enumerate(model.named_parameters()):
+            j = torch.arange(p.numel(), dtype=torch.float64)
+            s = torch.sin(0.37 * j + 1.3 * i + 0.1)
+            is_norm = ".ln" in name or "bn" in name
+            if is_norm:
+                v = 1.0 + 0.1 * s if name.endswith("weight") else 0.05 * s
+            else:
+                v = s / math.sqrt(max(p[0].numel() if p.dim() > 1 else p.numel(), 1))
+            p.copy_(v.reshape(p.shape).to(p.dtype))
+
+
+def measure(model, S: int, seconds: float):
+    from cruse_amd.inferencer import StreamingInferencer
+    inf = StreamingInferencer(model, S)
+    blocks = 0.1 * torch.randn(S, 160, device="cuda")
+    for _ in range(50):
+        inf.push(blocks)
+    torch.cuda.synchronize()
+    walls, devs = [], []
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t_end = time.perf_counter() + seconds
+    while time.perf_counter() < t_end or len(walls) < 200:
+        t0 = time.perf_counter()
+        ev0.record()
+        inf.push(blocks)
+        ev1.record()
+        torch.cuda.synchronize()
+        walls.append(time.perf_counter() - t0)
+        devs.append(ev0.elapsed_time(ev1) * 1e-3)
+    w, d = np.array(walls) * 1e6, np.array(devs) * 1e6
+    return {"n_slots": S, "pushes": len(walls), "push_wall_us": {"mean": round(float(w.mean()), 2), "p50": round(float(np.median(w)), 2),
+            "p99": round(float(np.percentile(w, 99)), 2)}, "device_us_per_hop": round(float(d.mean()), 2),
+            "rtf": round(float(w.mean()) / 10000.0, 5), "rtf_per_stream": round(float(w.mean()) / 10000.0 / S, 8)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slots", default="1,16,64,256,1024")
+    ap.add_argument("--seconds", type=float, default=2.0)
+    ap.add_argument("--groups", type=int, default=4)
+    a = ap.parse_args()
+    from cruse_amd.model.cruse_net import unet_2
+    torch.manual_seed(0)
+    m = unet_2(rnn_groups=a.groups, precision="f32")
+    closed_form(m)
+    m = m.cuda().eval()
+    rows = [measure(m, int(s), a.seconds) for s in a.slots.split(",")]
+    print(json.dumps({"model": f"unet_2 ch={m.ch} rnn_groups={a.groups}", "device": torch.cuda.get_device_name(0), "rows": rows}))
+
+
+if __name__ == "__main__":
+    main()
