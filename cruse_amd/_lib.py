@@ -137,6 +137,11 @@ SIGNATURES = {
     "cruse_stream_encode": ("piiiiiipppppp", "i"),
     "cruse_stream_gru": ("piiiipiippfpiippiip", "i"),
     "cruse_stream_decode": ("piiiiiippfpppp", "i"),
+    "cruse_stream_packet_layout": ("iiiiip", "i"),
+    "cruse_stream_encode_n": ("piiiiiiiiipppppp", "i"),
+    "cruse_stream_gru_proj_n": ("piiiiiipiippfppp", "i"),
+    "cruse_stream_gru_rec_n": ("piiiiiippiippiip", "i"),
+    "cruse_stream_decode_n": ("piiiiiiiiippfpppp", "i"),
 }
 
 

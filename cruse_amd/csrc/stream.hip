@@ -401,6 +401,503 @@ int launch_gru(const int* mode, int S, int g, int Hg, const float* x, int xs, in
     return CRUSE_OK;
 }
 
+
+// ---- packets: up to `hops` blocks per slot and call (cruse_stream_*_n) ---------------------------------------------------------
+// Everything of a hop except the two GRU steps is feed-forward in time, so the frames of a packet are computed side by side:
+// one workgroup per slot walks the phases level by level over all frames, with the level's folded weights (or the DFT tables)
+// staged in LDS once per packet.  pk[s] = start (0: the slot holds no block, 1: one block, 2: two or more), pk[S + s] = count of
+// blocks slot s consumes; both live in device memory.  Frame f of slot s has its own work row, work[(s * work_frames + f) * WS],
+// WS = packet_work_stride().
+constexpr int PACKET_LDS_BYTES = 128 * 1024;
+
+struct Pkt {
+    int c;       // blocks consumed
+    int nf;      // frames computed
+    int f0;      // 1: the first frame is frame 0 of the clip (its output block is dropped)
+    int hist;    // 1: the stored block comes first in the sequence of blocks
+};
+
+__device__ __forceinline__ Pkt packet_of(const int* __restrict__ pk, int S, int s, int hops) {
+    const int start = min(max(pk[s], 0), 2), c = min(max(pk[S + s], 0), hops);
+    Pkt p;
+    p.c = c;
+    p.hist = start >= 1;
+    p.f0 = start <= 1;
+    p.nf = c == 0 ? 0 : start == 0 ? (c >= 2 ? c : 0) : start == 1 ? c + 1 : c;
+    return p;
+}
+
+int packet_row_max(const Layout& L) {
+    int m = 2 * NB + 2;                                   // a masked spectrum (re | im) has to fit a row
+    for (int k = 0; k < 5; ++k) m = std::max(m, L.ch[k] * L.F[k]);
+    return m;
+}
+
+// floats of the LDS staging area: the largest padded weight block of any phase, or the cos / sin tables
+int packet_wcap(const Layout& L) {
+    int m = 2 * NFFT;
+    for (int k = 1; k < 5; ++k) {
+        m = std::max(m, L.ch[k] * (L.ch[k - 1] * 6 + 1) + L.ch[k]);
+        m = std::max(m, L.ch[k] * (L.ch[k] * 3 + 1));
+        m = std::max(m, L.ch[k] * L.ch[k - 1] * 3 + L.ch[k - 1]);
+    }
+    return m;
+}
+
+// a frame's work row in a packet: the single-hop work row, then e1 | e2 | e3 (a single hop keeps these in the state rows only)
+int packet_work_stride(const Layout& L, int* eoff) {
+    int o = L.wk_stride;
+    for (int k = 1; k < 4; ++k) {
+        if (eoff) eoff[k] = o;
+        o += (L.ch[k] * L.F[k] + 3) & ~3;
+    }
+    return o;
+}
+
+// largest number of frames whose rows fit the LDS budget beside the staging area (encode needs one more row than decode)
+int packet_max_frames(const Layout& L) {
+    const int avail = PACKET_LDS_BYTES / (int)sizeof(float) - packet_wcap(L) - packet_row_max(L) - 64;
+    return avail <= 0 ? 0 : avail / (2 * packet_row_max(L));
+}
+
+// encoder conv over the frames of a packet, weights in LDS as [Cout][Cin*6 + 1] | bias[Cout]; row f-1 of frame 0 is `prev`
+__device__ void enc_conv_n(const float* Wl, const float* prev, const float* src, float* dst, int rowmax, int nf, int Cin, int Fin,
+                           int Cout, int Fout) {
+    const int ws = Cin * 6 + 1, per = Cout * Fout;
+    const float* bl = Wl + Cout * ws;
+    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
+        const int f = idx / per, r = idx - f * per, co = r / Fout, fo = r - co * Fout;
+        const float* pr = f == 0 ? prev : src + (f - 1) * rowmax;
+        const float* cu = src + f * rowmax;
+        float acc = bl[co];
+        for (int ci = 0; ci < Cin; ++ci) {
+            const float* w = Wl + co * ws + ci * 6;
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                const int fi = 2 * fo - 1 + kw;
+                if (fi < 0 || fi >= Fin) continue;
+                acc = fmaf(w[kw], pr[ci * Fin + fi], acc);
+                acc = fmaf(w[3 + kw], cu[ci * Fin + fi], acc);
+            }
+        }
+        dst[f * rowmax + r] = fmaxf(acc, 0.f);
+    }
+}
+
+// skip conv over the frames of a packet, weights in LDS as [C][C*3 + 1]; frame f's result goes to its work row
+__device__ void skip_conv_n(const float* Wl, const float* src, float* wk, int wk_stride, int off, int rowmax, int nf, int C, int F) {
+    const int ws = C * 3 + 1, per = C * F;
+    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
+        const int f = idx / per, r = idx - f * per, co = r / F, fo = r - co * F;
+        const float* e = src + f * rowmax;
+        float acc = 0.f;
+        for (int ci = 0; ci < C; ++ci) {
+            const float* w = Wl + co * ws + ci * 3;
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                const int fi = fo - 1 + kw;
+                if (fi >= 0 && fi < F) acc = fmaf(w[kw], e[ci * F + fi], acc);
+            }
+        }
+        wk[(size_t)f * wk_stride + off + r] = acc;
+    }
+}
+
+// transposed conv over the frames of a packet, weights in LDS as [Cin][Cout][3] | bias[Cout]; add: frame f's skip row (work)
+__device__ void dec_convt_n(const float* Wl, const float* src, float* dst, const float* wk, int wk_stride, int add_off, int rowmax,
+                            int nf, int Cin, int Fin, int Cout, int act) {
+    const int Fout = 2 * Fin, per = Cout * Fout;
+    const float* bl = Wl + Cin * Cout * 3;
+    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
+        const int f = idx / per, r = idx - f * per, co = r / Fout, fo = r - co * Fout;
+        const float* in = src + f * rowmax;
+        const int fi = fo >> 1;
+        float acc = bl[co];
+        if (fo & 1) {
+            for (int ci = 0; ci < Cin; ++ci) acc = fmaf(Wl[(ci * Cout + co) * 3 + 1], in[ci * Fin + fi], acc);
+        } else {
+            for (int ci = 0; ci < Cin; ++ci) {
+                acc = fmaf(Wl[(ci * Cout + co) * 3 + 0], in[ci * Fin + fi], acc);
+                if (fi >= 1) acc = fmaf(Wl[(ci * Cout + co) * 3 + 2], in[ci * Fin + fi - 1], acc);
+            }
+        }
+        dst[f * rowmax + r] = act == 0 ? fmaxf(acc, 0.f) + wk[(size_t)f * wk_stride + add_off + r] : 1.0f / (1.0f + expf(-acc));
+    }
+}
+
+__global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __restrict__ pk, int S, int hops, int in_hops, int NFW,
+                                                              Layout L, int WS, int e1, int e2, int e3, int rowmax, int wcap,
+                                                              const float* __restrict__ in, const float* __restrict__ tab, const float* __restrict__ w,
+                                                              float* __restrict__ state, float* __restrict__ work) {
+    extern __shared__ float sm[];
+    const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const Pkt p = packet_of(pk, S, s, hops);
+    if (p.c == 0) return;
+    float* st = state + (size_t)s * L.st_stride;
+    float* wk = work + (size_t)s * NFW * WS;
+    const int eoff[4] = {0, e1, e2, e3};
+    const float* blk = in + (size_t)s * in_hops * HOP;
+    float* hist = st + L.st_hist;
+    if (p.nf == 0) {                                      // block 0 of a clip alone: stored, no frame
+        for (int i = tid; i < HOP; i += nt) hist[1 + i] = blk[i];
+        return;
+    }
+    const int nf = p.nf;
+    // LDS: A[NFW][rowmax] | B[NFW][rowmax] | P[rowmax] (row t-1 of the packet's first frame) | Wb[wcap]
+    float* A = sm;
+    float* B = A + NFW * rowmax;
+    float* P = B + NFW * rowmax;
+    float* Wb = P + rowmax;
+    // block v of the sequence (the stored block first where the slot holds one), sample i
+    auto vget = [&](int v, int i) -> float {
+        if (p.hist) return v == 0 ? hist[1 + i] : blk[(v - 1) * HOP + i];
+        return blk[v * HOP + i];
+    };
+    const int nv = p.hist + p.c, off = p.f0 ? 0 : 1;
+    for (int idx = tid; idx < nf * HOP; idx += nt) {
+        const int f = idx / HOP, i = idx - f * HOP;
+        float a, bq;
+        if (p.f0 && f == 0) {                             // x[160], x[159], ..., x[1] | x[0..159]
+            a = i == 0 ? vget(1, 0) : vget(0, HOP - i);
+            bq = vget(0, i);
+        } else {
+            a = vget(f - 1 + off, i);
+            bq = vget(f + off, i);
+        }
+        B[f * rowmax + i] = a * tab[TB_WIN + i];
+        B[f * rowmax + HOP + i] = bq * tab[TB_WIN + HOP + i];
+    }
+    for (int i = tid; i < 2 * NFFT; i += nt) Wb[i] = tab[TB_COS + i];      // cos | sin
+    for (int i = tid; i < F0; i += nt) P[i] = st[L.st_prev[0] + i];
+    const float before = nv >= 2 ? vget(nv - 2, HOP - 1) : hist[0];        // the sample in front of the last block
+    __syncthreads();
+    if (tid == 0) hist[0] = before;
+    for (int i = tid; i < HOP; i += nt) hist[1 + i] = blk[(p.c - 1) * HOP + i];
+    // 320-point real DFT of every frame, bins 0..160; magnitude of bins 0..159
+    for (int idx = tid; idx < nf * NB; idx += nt) {
+        const int f = idx / NB, k = idx - f * NB;
+        const float* fr = B + f * rowmax;
+        float re = 0.f, im = 0.f;
+        int j = 0;
+        for (int n = 0; n < NFFT; ++n) {
+            re = fmaf(fr[n], Wb[j], re);
+            im = fmaf(-fr[n], Wb[NFFT + j], im);
+            j += k;
+            if (j >= NFFT) j -= NFFT;
+        }
+        wk[(size_t)f * WS + L.wk_re + k] = re;
+        wk[(size_t)f * WS + L.wk_im + k] = im;
+        if (k < F0) A[f * rowmax + k] = sqrtf(re * re + im * im + 1e-8f);
+    }
+    __syncthreads();
+    for (int i = tid; i < F0; i += nt) st[L.st_prev[0] + i] = A[(nf - 1) * rowmax + i];
+    float* src = A;
+    float* dst = B;
+    for (int k = 1; k < 5; ++k) {
+        const int Cin = L.ch[k - 1], Cout = L.ch[k], Fin = L.F[k - 1], Fout = L.F[k], per = Cout * Fout;
+        for (int i = tid; i < Cout * Cin * 6; i += nt) Wb[(i / (Cin * 6)) * (Cin * 6 + 1) + i % (Cin * 6)] = w[L.encW[k] + i];
+        for (int i = tid; i < Cout; i += nt) Wb[Cout * (Cin * 6 + 1) + i] = w[L.encB[k] + i];
+        __syncthreads();
+        enc_conv_n(Wb, P, src, dst, rowmax, nf, Cin, Fin, Cout, Fout);
+        __syncthreads();
+        for (int i = tid; i < Cout * Cout * 3; i += nt) Wb[(i / (Cout * 3)) * (Cout * 3 + 1) + i % (Cout * 3)] = w[L.skW[k] + i];
+        if (k < 4)
+            for (int i = tid; i < per; i += nt) P[i] = st[L.st_prev[k] + i];
+        __syncthreads();
+        skip_conv_n(Wb, dst, wk, WS, L.wk_skip[k], rowmax, nf, Cout, Fout);
+        if (k < 4)
+            for (int i = tid; i < per; i += nt) st[L.st_prev[k] + i] = dst[(nf - 1) * rowmax + i];
+        const int eo = k < 4 ? eoff[k] : L.wk_x;                           // e1..e3 of every frame; e4 is the GRU input row, c*F4+f
+        for (int idx = tid; idx < nf * per; idx += nt) {
+            const int f = idx / per, r = idx - f * per;
+            wk[(size_t)f * WS + eo + r] = dst[f * rowmax + r];
+        }
+        __syncthreads();
+        float* t = src; src = dst; dst = t;
+    }
+}
+
+// Input products of one GGRU layer for every frame of a packet: gi[(s * NFW + f) * 3H + c*H + u] = W_ih[c][u] . x + bias, with
+// b_ih + b_hh folded for the gates r and z and b_in for n.  Same workgroup shape as stream_gru_kernel (wave = one unit, its three
+// W_ih rows in registers, tiles of SB rows in LDS); a row is (slot, frame), rows behind a slot's last frame are not computed.
+template <int KQ>
+__global__ void __launch_bounds__(256) stream_gru_proj_n_kernel(const int* __restrict__ pk, int S, int hops, int NFW, int g, int Hg,
+                                                                const float* __restrict__ work, int wk_stride, int x_off,
+                                                                const float* __restrict__ ln_g, const float* __restrict__ ln_b,
+                                                                float ln_eps, const float* __restrict__ pack, float* __restrict__ gi) {
+    extern __shared__ float sm[];
+    const int H = g * Hg, NFC = hops + 1;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int u = blockIdx.y * 4 + wv;
+    const int gidx = u / Hg, j = u - gidx * Hg;
+    const bool ln = ln_g != nullptr;
+    const int xw = ln ? H : Hg;
+    float* xs = sm;                             // [SB][xw]
+    float* st = sm + SB * xw;                   // [SB][2] mean, rstd
+    const size_t gsz = (size_t)3 * Hg * Hg;
+    const float* Wih = pack + gidx * gsz;
+    const float* bih = pack + 2 * g * gsz + gidx * 3 * Hg;
+    const float* bhh = pack + 2 * g * gsz + g * 3 * Hg + gidx * 3 * Hg;
+    float wi[3][KQ], lg[KQ], lb[KQ];
+    int src[KQ];
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) {
+        const int k = lane + 64 * q;
+        const bool ok = k < Hg;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) wi[c][q] = ok ? Wih[(size_t)(c * Hg + j) * Hg + k] : 0.f;
+        const int p = gidx * Hg + k;
+        src[q] = ok ? (ln ? (p % g) * Hg + p / g : k) : 0;
+        lg[q] = (ln && ok) ? ln_g[p] : 0.f;
+        lb[q] = (ln && ok) ? ln_b[p] : 0.f;
+    }
+    const float br = bih[j] + bhh[j], bz = bih[Hg + j] + bhh[Hg + j], bin = bih[2 * Hg + j];
+    const int R = S * NFC, ntiles = (R + SB - 1) / SB;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int r0 = t * SB;
+        __syncthreads();
+        for (int i = threadIdx.x; i < SB * xw; i += blockDim.x) {
+            const int ss = i / xw, k = i - ss * xw, r = r0 + ss;
+            float v = 0.f;
+            if (r < R) {
+                const int s = r / NFC, f = r - s * NFC;
+                v = work[((size_t)s * NFW + f) * wk_stride + x_off + (ln ? 0 : gidx * Hg) + k];
+            }
+            xs[i] = v;
+        }
+        __syncthreads();
+        if (ln) {
+            for (int ss = wv; ss < SB; ss += 4) {
+                float a = 0.f;
+                for (int k = lane; k < H; k += 64) a += xs[ss * H + k];
+                const float mean = wave_sum(a) / H;
+                float v = 0.f;
+                for (int k = lane; k < H; k += 64) { const float d = xs[ss * H + k] - mean; v = fmaf(d, d, v); }
+                const float var = wave_sum(v) / H;
+                if (lane == 0) { st[2 * ss] = mean; st[2 * ss + 1] = 1.0f / sqrtf(var + ln_eps); }
+            }
+            __syncthreads();
+        }
+        for (int ss = 0; ss < SB; ++ss) {
+            const int r = r0 + ss;
+            if (r >= R) break;
+            const int s = r / NFC, f = r - s * NFC;
+            if (f >= packet_of(pk, S, s, hops).nf) continue;
+            float ar = 0.f, az = 0.f, an = 0.f;
+            const float mean = ln ? st[2 * ss] : 0.f, rstd = ln ? st[2 * ss + 1] : 0.f;
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) {
+                const int k = lane + 64 * q;
+                if (k >= Hg) continue;
+                float xv = xs[ss * xw + src[q]];
+                if (ln) xv = fmaf((xv - mean) * rstd, lg[q], lb[q]);
+                ar = fmaf(wi[0][q], xv, ar);
+                az = fmaf(wi[1][q], xv, az);
+                an = fmaf(wi[2][q], xv, an);
+            }
+            ar = wave_sum(ar); az = wave_sum(az); an = wave_sum(an);
+            if (lane == 0) {
+                float* o = gi + ((size_t)s * NFW + f) * 3 * H + u;
+                o[0] = ar + br;
+                o[H] = az + bz;
+                o[2 * H] = an + bin;
+            }
+        }
+    }
+}
+
+// One recurrent step (frame `frame` of the packet) of one GGRU layer for every slot that computes that frame: W_hh . h, gates,
+// new h into the frame's work row.  h comes from the state row for the packet's first frame, else from the previous frame's row.
+template <int KQ>
+__global__ void __launch_bounds__(256) stream_gru_rec_n_kernel(const int* __restrict__ pk, int S, int hops, int NFW, int frame, int g,
+                                                               int Hg, const float* __restrict__ gi, const float* __restrict__ state,
+                                                               int st_stride, int st_off, const float* __restrict__ pack,
+                                                               float* __restrict__ work, int wk_stride, int h_off) {
+    extern __shared__ float sm[];
+    const int H = g * Hg;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int u = blockIdx.y * 4 + wv;
+    const int gidx = u / Hg, j = u - gidx * Hg;
+    float* hs = sm;                             // [SB][Hg]
+    const size_t gsz = (size_t)3 * Hg * Hg;
+    const float* Whh = pack + g * gsz + gidx * gsz;
+    const float bhn = pack[2 * g * gsz + g * 3 * Hg + gidx * 3 * Hg + 2 * Hg + j];
+    float wh[3][KQ];
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) {
+        const int k = lane + 64 * q;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) wh[c][q] = k < Hg ? Whh[(size_t)(c * Hg + j) * Hg + k] : 0.f;
+    }
+    const int ntiles = (S + SB - 1) / SB;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int s0 = t * SB;
+        __syncthreads();
+        for (int i = threadIdx.x; i < SB * Hg; i += blockDim.x) {
+            const int ss = i / Hg, k = i - ss * Hg, s = s0 + ss;
+            float v = 0.f;
+            if (s < S)
+                v = frame == 0 ? state[(size_t)s * st_stride + st_off + gidx * Hg + k]
+                               : work[((size_t)s * NFW + frame - 1) * wk_stride + h_off + gidx * Hg + k];
+            hs[i] = v;
+        }
+        __syncthreads();
+        for (int ss = 0; ss < SB; ++ss) {
+            const int s = s0 + ss;
+            if (s >= S) break;
+            if (frame >= packet_of(pk, S, s, hops).nf) continue;
+            float ar = 0.f, az = 0.f, an = 0.f;
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) {
+                const int k = lane + 64 * q;
+                if (k >= Hg) continue;
+                const float hv = hs[ss * Hg + k];
+                ar = fmaf(wh[0][q], hv, ar);
+                az = fmaf(wh[1][q], hv, az);
+                an = fmaf(wh[2][q], hv, an);
+            }
+            ar = wave_sum(ar); az = wave_sum(az); an = wave_sum(an);
+            if (lane == 0) {
+                const float* gv = gi + ((size_t)s * NFW + frame) * 3 * H + u;
+                const float r = 1.0f / (1.0f + expf(-(gv[0] + ar)));
+                const float z = 1.0f / (1.0f + expf(-(gv[H] + az)));
+                const float n = tanhf(gv[2 * H] + r * (an + bhn));
+                work[((size_t)s * NFW + frame) * wk_stride + h_off + u] = (1.0f - z) * n + z * hs[ss * Hg + j];
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __restrict__ pk, int S, int hops, int out_hops, int NFW,
+                                                              Layout L, int WS, int rowmax, int wcap, const float* __restrict__ tab,
+                                                              const float* __restrict__ w, float ln_eps, float* __restrict__ state,
+                                                              float* __restrict__ work, float* __restrict__ out) {
+    extern __shared__ float sm[];
+    const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const Pkt p = packet_of(pk, S, s, hops);
+    const int nf = p.nf;
+    if (nf == 0) return;
+    float* st = state + (size_t)s * L.st_stride;
+    float* wk = work + (size_t)s * NFW * WS;
+    // LDS: A[NFW][rowmax] | B[NFW][rowmax] | Wb[wcap] | stats[NFW][2]
+    float* A = sm;
+    float* B = A + NFW * rowmax;
+    float* Wb = B + NFW * rowmax;
+    float* stats = Wb + wcap;
+    const int lane = tid & 63, wv = tid >> 6, nw = nt >> 6;
+    // LN2 statistics of every frame's layer-2 output (one wave per frame, two passes, biased variance)
+    for (int f = wv; f < nf; f += nw) {
+        const float* h2 = wk + (size_t)f * WS + L.wk_h2n;
+        float a = 0.f;
+        for (int i = lane; i < L.H; i += 64) a += h2[i];
+        const float mean = wave_sum(a) / L.H;
+        float v = 0.f;
+        for (int i = lane; i < L.H; i += 64) { const float d = h2[i] - mean; v = fmaf(d, d, v); }
+        const float var = wave_sum(v) / L.H;
+        if (lane == 0) { stats[2 * f] = mean; stats[2 * f + 1] = 1.0f / sqrtf(var + ln_eps); }
+    }
+    __syncthreads();
+    // LN2 + skip4 -> decoder input [C4][F4] of every frame
+    for (int idx = tid; idx < nf * L.H; idx += nt) {
+        const int f = idx / L.H, i = idx - f * L.H;
+        const float* row = wk + (size_t)f * WS;
+        A[f * rowmax + i] = fmaf((row[L.wk_h2n + i] - stats[2 * f]) * stats[2 * f + 1], w[L.ln2g + i], w[L.ln2b + i]) + row[L.wk_skip[4] + i];
+    }
+    // the recurrent state of the packet's last frame becomes the state of the next call
+    for (int i = tid; i < L.H; i += nt) {
+        st[L.st_h1 + i] = wk[(size_t)(nf - 1) * WS + L.wk_h1n + i];
+        st[L.st_h2 + i] = wk[(size_t)(nf - 1) * WS + L.wk_h2n + i];
+    }
+    float* src = A;
+    float* dst = B;
+    for (int k = 4; k >= 1; --k) {
+        const int nwf = L.ch[k] * L.ch[k - 1] * 3;
+        for (int i = tid; i < nwf; i += nt) Wb[i] = w[L.decW[k] + i];
+        for (int i = tid; i < L.ch[k - 1]; i += nt) Wb[nwf + i] = w[L.decB[k] + i];
+        __syncthreads();
+        dec_convt_n(Wb, src, dst, wk, WS, k > 1 ? L.wk_skip[k - 1] : 0, rowmax, nf, L.ch[k], L.F[k], L.ch[k - 1], k > 1 ? 0 : 1);
+        __syncthreads();
+        float* t = src; src = dst; dst = t;
+    }
+    // src: the masks.  Masked spectrum re[161] | im[161] of every frame into dst (bin 160 zero), cos / sin tables into Wb
+    for (int idx = tid; idx < nf * NB; idx += nt) {
+        const int f = idx / NB, k = idx - f * NB;
+        float* row = wk + (size_t)f * WS;
+        const float m = k < F0 ? src[f * rowmax + k] : 0.f;
+        if (k < F0) row[L.wk_mask + k] = m;
+        dst[f * rowmax + k] = row[L.wk_re + k] * m;
+        dst[f * rowmax + NB + k] = row[L.wk_im + k] * m;
+    }
+    for (int i = tid; i < 2 * NFFT; i += nt) Wb[i] = tab[TB_COS + i];
+    __syncthreads();
+    // 320-point inverse real DFT (imaginary parts of bins 0 and 160 ignored, as irfft) and window: y of every frame into src
+    for (int idx = tid; idx < nf * NFFT; idx += nt) {
+        const int f = idx / NFFT, n = idx - f * NFFT;
+        const float* re = dst + f * rowmax;
+        const float* im = re + NB;
+        float acc = 0.f;
+        int j = n;
+        for (int k = 1; k < F0; ++k) {
+            acc = fmaf(re[k], Wb[j], acc);
+            acc = fmaf(-im[k], Wb[NFFT + j], acc);
+            j += n;
+            if (j >= NFFT) j -= NFFT;
+        }
+        src[f * rowmax + n] = (re[0] + 2.0f * acc + ((n & 1) ? -re[F0] : re[F0])) * (1.0f / NFFT) * tab[TB_WIN + n];
+    }
+    __syncthreads();
+    // overlap-add: a chain over the packet's frames (tail -> block -> new tail), division by the window envelope
+    for (int i = tid; i < HOP; i += nt) {
+        float tail = st[L.st_tail + i];
+        const float ienv = tab[TB_IENV + i];
+        for (int f = 0; f < nf; ++f) {
+            const float o = (tail + src[f * rowmax + i]) * ienv;
+            const int ob = f - p.f0;                                       // frame 0's block lies in front of the clip
+            if (ob >= 0) out[((size_t)s * out_hops + ob) * HOP + i] = o;
+            tail = src[f * rowmax + HOP + i];
+        }
+        st[L.st_tail + i] = tail;
+    }
+}
+
+template <int KQ>
+int launch_gru_proj_n(const int* pk, int S, int hops, int NFW, int g, int Hg, const float* work, int wks, int xo, const float* lng,
+                      const float* lnb, float eps, const float* pack, float* gi, hipStream_t st) {
+    const int H = g * Hg, units = H / 4, ntiles = (S * (hops + 1) + SB - 1) / SB;
+    const int grid_x = std::max(1, std::min(ntiles, (2048 + units - 1) / units));
+    const size_t lds = (size_t)(SB * (lng ? H : Hg) + 2 * SB) * sizeof(float);
+    int rc = cruse_ensure_dyn_lds((const void*)stream_gru_proj_n_kernel<KQ>, lds, "cruse_stream_gru_proj_n");
+    if (rc) return rc;
+    hipLaunchKernelGGL(stream_gru_proj_n_kernel<KQ>, dim3(grid_x, units), dim3(256), lds, st, pk, S, hops, NFW, g, Hg, work, wks, xo, lng,
+                       lnb, eps, pack, gi);
+    CRUSE_LAUNCH_CHECK("cruse_stream_gru_proj_n");
+    return CRUSE_OK;
+}
+
+template <int KQ>
+int launch_gru_rec_n(const int* pk, int S, int hops, int NFW, int frame, int g, int Hg, const float* gi, const float* state, int sts,
+                     int sto, const float* pack, float* work, int wks, int ho, hipStream_t st) {
+    const int units = g * Hg / 4, ntiles = (S + SB - 1) / SB;
+    const int grid_x = std::max(1, std::min(ntiles, (2048 + units - 1) / units));
+    const size_t lds = (size_t)(SB * Hg) * sizeof(float);
+    int rc = cruse_ensure_dyn_lds((const void*)stream_gru_rec_n_kernel<KQ>, lds, "cruse_stream_gru_rec_n");
+    if (rc) return rc;
+    hipLaunchKernelGGL(stream_gru_rec_n_kernel<KQ>, dim3(grid_x, units), dim3(256), lds, st, pk, S, hops, NFW, frame, g, Hg, gi, state,
+                       sts, sto, pack, work, wks, ho);
+    CRUSE_LAUNCH_CHECK("cruse_stream_gru_rec_n");
+    return CRUSE_OK;
+}
+
+// shared argument checks of the packet entry points
+int packet_args(const char* who, int S, int hops, int NFW, const Layout& L) {
+    CRUSE_REQUIRE(S > 0 && hops >= 1 && NFW >= hops + 1, CRUSE_E_SHAPE, "%s: S = %d, hops = %d, work_frames = %d (need work_frames >= hops + 1)",
+                  who, S, hops, NFW);
+    const int maxf = packet_max_frames(L);
+    CRUSE_REQUIRE(NFW <= maxf, CRUSE_E_SHAPE, "%s: %d frames per slot exceed the %d whose rows fit in LDS (max_hops %d for these channels)", who,
+                  NFW, maxf, maxf - 1);
+    return CRUSE_OK;
+}
+
 }  // namespace
 
 extern "C" int cruse_stream_layout(int c0, int c1, int c2, int c3, int c4, int* out) {
@@ -482,5 +979,93 @@ extern "C" int cruse_stream_decode(const int* mode, int S, int c0, int c1, int c
     if (rc) return rc;
     hipLaunchKernelGGL(stream_decode_kernel, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, tab, w, ln_eps, state, work, out);
     CRUSE_LAUNCH_CHECK("cruse_stream_decode");
+    return CRUSE_OK;
+}
+
+extern "C" int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4, int* out) {
+    CRUSE_REQUIRE(out, CRUSE_E_SHAPE, "stream_packet_layout: null output");
+    Layout L;
+    const int rc = make_layout(c0, c1, c2, c3, c4, L);
+    if (rc) return rc;
+    int eoff[4] = {0, 0, 0, 0};
+    out[0] = std::max(0, packet_max_frames(L) - 1);
+    out[1] = packet_work_stride(L, eoff);
+    for (int k = 1; k < 4; ++k) out[1 + k] = eoff[k];
+    return CRUSE_OK;
+}
+
+extern "C" int cruse_stream_encode_n(const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                                     const float* in, const float* tab, const float* w, float* state, float* work, void* stream) {
+    Layout L;
+    int rc = make_layout(c0, c1, c2, c3, c4, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(pk && in && tab && w && state && work, CRUSE_E_SHAPE, "stream_encode_n: null buffer");
+    rc = packet_args("stream_encode_n", S, hops, work_frames, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(in_hops >= hops, CRUSE_E_SHAPE, "stream_encode_n: in_hops = %d < hops = %d", in_hops, hops);
+    const int rowmax = packet_row_max(L), wcap = packet_wcap(L);
+    int eoff[4];
+    const int WS = packet_work_stride(L, eoff);
+    const size_t lds = (size_t)((2 * work_frames + 1) * rowmax + wcap) * sizeof(float);
+    rc = cruse_ensure_dyn_lds((const void*)stream_encode_n_kernel, lds, "cruse_stream_encode_n");
+    if (rc) return rc;
+    hipLaunchKernelGGL(stream_encode_n_kernel, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, in_hops, work_frames, L,
+                       WS, eoff[1], eoff[2], eoff[3], rowmax, wcap, in, tab, w, state, work);
+    CRUSE_LAUNCH_CHECK("cruse_stream_encode_n");
+    return CRUSE_OK;
+}
+
+extern "C" int cruse_stream_gru_proj_n(const int* pk, int S, int hops, int work_frames, int layer, int g, int Hg, const float* work,
+                                       int wk_stride, int x_off, const float* ln_g, const float* ln_b, float ln_eps, const float* pack,
+                                       float* gi, void* stream) {
+    CRUSE_REQUIRE(S > 0 && hops >= 1 && work_frames >= hops + 1 && g > 0 && Hg > 0 && Hg % 4 == 0 && Hg <= 1024, CRUSE_E_SHAPE,
+                  "stream_gru_proj_n: S = %d, hops = %d, work_frames = %d, g = %d, Hg = %d (need work_frames >= hops + 1, Hg %% 4 == 0, "
+                  "Hg <= 1024)", S, hops, work_frames, g, Hg);
+    CRUSE_REQUIRE(layer == 1 || layer == 2, CRUSE_E_SHAPE, "stream_gru_proj_n: layer %d", layer);
+    CRUSE_REQUIRE(x_off >= 0 && x_off + g * Hg <= wk_stride, CRUSE_E_SHAPE, "stream_gru_proj_n: x_off %d + %d floats outside a work row of %d",
+                  x_off, g * Hg, wk_stride);
+    CRUSE_REQUIRE(pk && work && pack && gi && (layer == 1 || (ln_g && ln_b)), CRUSE_E_SHAPE, "stream_gru_proj_n: null buffer");
+    if (layer == 1) ln_g = ln_b = nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (Hg <= 192) return launch_gru_proj_n<3>(pk, S, hops, work_frames, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps, pack, gi, st);
+    if (Hg <= 320) return launch_gru_proj_n<5>(pk, S, hops, work_frames, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps, pack, gi, st);
+    if (Hg <= 640) return launch_gru_proj_n<10>(pk, S, hops, work_frames, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps, pack, gi, st);
+    return launch_gru_proj_n<16>(pk, S, hops, work_frames, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps, pack, gi, st);
+}
+
+extern "C" int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_frames, int frame, int g, int Hg, const float* gi,
+                                      const float* state, int st_stride, int st_off, const float* pack, float* work, int wk_stride,
+                                      int h_off, void* stream) {
+    CRUSE_REQUIRE(S > 0 && hops >= 1 && work_frames >= hops + 1 && g > 0 && Hg > 0 && Hg % 4 == 0 && Hg <= 1024, CRUSE_E_SHAPE,
+                  "stream_gru_rec_n: S = %d, hops = %d, work_frames = %d, g = %d, Hg = %d (need work_frames >= hops + 1, Hg %% 4 == 0, "
+                  "Hg <= 1024)", S, hops, work_frames, g, Hg);
+    CRUSE_REQUIRE(frame >= 0 && frame <= hops, CRUSE_E_SHAPE, "stream_gru_rec_n: frame %d outside [0, %d]", frame, hops);
+    CRUSE_REQUIRE(st_off >= 0 && st_off + g * Hg <= st_stride && h_off >= 0 && h_off + g * Hg <= wk_stride, CRUSE_E_SHAPE,
+                  "stream_gru_rec_n: st_off %d / h_off %d + %d floats outside a state row of %d / work row of %d", st_off, h_off, g * Hg,
+                  st_stride, wk_stride);
+    CRUSE_REQUIRE(pk && gi && state && pack && work, CRUSE_E_SHAPE, "stream_gru_rec_n: null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    if (Hg <= 192) return launch_gru_rec_n<3>(pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work, wk_stride, h_off, st);
+    if (Hg <= 320) return launch_gru_rec_n<5>(pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work, wk_stride, h_off, st);
+    if (Hg <= 640) return launch_gru_rec_n<10>(pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work, wk_stride, h_off, st);
+    return launch_gru_rec_n<16>(pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work, wk_stride, h_off, st);
+}
+
+extern "C" int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                                     const float* tab, const float* w, float ln_eps, float* state, float* work, float* out, void* stream) {
+    Layout L;
+    int rc = make_layout(c0, c1, c2, c3, c4, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(pk && tab && w && state && work && out, CRUSE_E_SHAPE, "stream_decode_n: null buffer");
+    rc = packet_args("stream_decode_n", S, hops, work_frames, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(out_hops >= hops, CRUSE_E_SHAPE, "stream_decode_n: out_hops = %d < hops = %d", out_hops, hops);
+    const int rowmax = packet_row_max(L), wcap = packet_wcap(L), WS = packet_work_stride(L, nullptr);
+    const size_t lds = (size_t)(2 * work_frames * rowmax + wcap + 2 * work_frames) * sizeof(float);
+    rc = cruse_ensure_dyn_lds((const void*)stream_decode_n_kernel, lds, "cruse_stream_decode_n");
+    if (rc) return rc;
+    hipLaunchKernelGGL(stream_decode_n_kernel, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, out_hops, work_frames, L,
+                       WS, rowmax, wcap, tab, w, ln_eps, state, work, out);
+    CRUSE_LAUNCH_CHECK("cruse_stream_decode_n");
     return CRUSE_OK;
 }

@@ -13,6 +13,11 @@ Block contract (n_fft = win = 320, hop = 160), per slot:
   flush computes the end frame (the last block and its end reflection), returns the last output block and resets the slot.
 Pushes + flush return exactly L samples, equal to Inferencer.mag_mask_to_wave on the same clip when L is a multiple of 160
 (the caller zero-pads a partial final block) and L >= 320.
+
+Packets (max_hops > 1): push_packet consumes up to max_hops blocks per slot in one chain of cruse_stream_*_n kernels that computes
+the feed-forward part of all frames of the packet side by side and walks only the GRU recurrences frame by frame; enhance()
+runs whole clips through it in bounded memory.  The schedule is packets.packet_plan; state rows and the block counter are those
+of push, so push, push_packet and flush may be mixed freely on a slot.
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .packets import packet_plan, padded_blocks
 
 
 def _bn_fold(bn):
@@ -42,7 +48,7 @@ class StreamingInferencer:
     HOP = 160
 
     def __init__(self, model: torch.nn.Module, n_slots: int, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
-                 device="cuda", use_graph: bool = True):
+                 device="cuda", use_graph: bool = True, max_hops: int = 1):
         from ..model.cruse_net import unet_2
         if (n_fft, hop_length, win_length) != (320, 160, 320):
             raise ValueError(f"StreamingInferencer supports n_fft = win_length = 320, hop_length = 160 only "
@@ -77,6 +83,23 @@ class StreamingInferencer:
         self.tab = ops.stream_tables(dev)
         self.nblk = np.zeros(S, dtype=np.int64)                                 # blocks pushed per slot since its last reset
         self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self.max_hops = int(max_hops)
+        self._last_frames = np.zeros(S, dtype=np.int64)                         # frames of the slot's last packet (0: a push / flush)
+        self._last_f0 = np.zeros(S, dtype=bool)                                 # that packet began with frame 0 of the clip
+        if self.max_hops != 1:
+            play = ops.stream_packet_layout(self.ch)
+            if not 1 <= self.max_hops <= play["max_hops"]:
+                raise ValueError(f"max_hops must be in [1, {play['max_hops']}] for ch = {self.ch} (the packet kernels keep "
+                                 f"max_hops + 1 frames of a slot in LDS), got {max_hops}")
+            K = self.max_hops
+            self.play = play
+            self.pblocks = torch.zeros(S, K, self.HOP, device=dev)
+            self.pout = torch.zeros(S, K, self.HOP, device=dev)
+            self.pwork = torch.zeros(S, K + 1, play["wk_stride"], device=dev)   # one work row per frame of a packet
+            self.gi = torch.zeros(S, K + 1, 3 * self.H, device=dev)             # GRU input products of the layer in flight
+            self.pk = torch.zeros(2, S, device=dev, dtype=torch.int32)          # row 0: min(blocks held, 2), row 1: counts
+            self._pk_host = torch.zeros(2, S, dtype=torch.int32).pin_memory()
+            self._pk_free = None
         self.refresh()
 
     # -- weights ----------------------------------------------------------------------------------------------------------
@@ -180,6 +203,7 @@ class StreamingInferencer:
         m1 = np.where(act, np.where(b == 0, ops.STREAM_STORE, ops.STREAM_FRAME), ops.STREAM_SKIP).astype(np.int32)
         valid = act & (b >= 1)
         self.nblk += act
+        self._last_frames[act] = 0
         self._run(m0, m1)
         return self.out.clone(), torch.from_numpy(valid)
 
@@ -195,6 +219,7 @@ class StreamingInferencer:
                 raise ValueError(f"cannot flush slot {s}: it holds {self.nblk[s]} block(s), a clip needs at least 2 (L >= 320)")
         m1 = np.zeros(self.S, dtype=np.int32)
         m1[slots] = ops.STREAM_END
+        self._last_frames[slots] = 0
         self._run(np.zeros(self.S, dtype=np.int32), m1)
         idx = torch.tensor(slots, device=self.device, dtype=torch.long)
         last = self.out.index_select(0, idx)
@@ -210,11 +235,153 @@ class StreamingInferencer:
         if slots:
             self.state.index_fill_(0, torch.tensor(slots, device=self.device, dtype=torch.long), 0.0)
         self.nblk[slots] = 0
+        self._last_frames[slots] = 0
+
+    # -- packets ----------------------------------------------------------------------------------------------------------
+    def _packet_chain(self, hops: int, nf: int) -> None:
+        """One linear chain for packets of up to `hops` blocks of which the longest slot computes `nf` frames."""
+        pk, lay, g, Hg, H, wk = self.pk, self.lay, self.g, self.Hg, self.H, self.pwork
+        ops.stream_encode_n(pk, hops, self.ch, self.pblocks, self.tab, self.w, self.state, wk)
+        if nf == 0:                                                             # nothing but first blocks to store
+            return
+        ops.stream_gru_proj_n(pk, hops, 1, g, Hg, wk, lay["wk_x"], self.gru_pack1, self.gi)
+        for f in range(nf):
+            ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, lay["st_h1"], self.gru_pack1, wk, lay["wk_h1n"])
+        ops.stream_gru_proj_n(pk, hops, 2, g, Hg, wk, lay["wk_h1n"], self.gru_pack2, self.gi,
+                              ln_g=self.w[lay["ln1g"]:lay["ln1g"] + H], ln_b=self.w[lay["ln1b"]:lay["ln1b"] + H], ln_eps=self.ln1_eps)
+        for f in range(nf):
+            ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, lay["st_h2"], self.gru_pack2, wk, lay["wk_h2n"])
+        ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout)
+
+    def _launch_packet(self, hops: int, nf: int) -> None:
+        if not self.use_graph:
+            self._packet_chain(hops, nf)
+            return
+        key = ("packet", hops, nf)
+        gr = self._graphs.get(key)
+        if gr is None:
+            torch.cuda.synchronize(self.device)
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                self._packet_chain(hops, nf)
+            self._graphs[key] = gr
+        gr.replay()
+
+    @torch.no_grad()
+    def push_packet(self, blocks: torch.Tensor, counts=None):
+        """blocks [n_slots, K, 160] or [n_slots, K*160], 1 <= K <= max_hops; counts: an int per slot in [0, K] (None: K for every
+        slot; 0: the slot is inactive and its state untouched).  Slot s consumes its first counts[s] blocks.  Returns
+        (out [n_slots, K, 160] on the device, n_out [n_slots] int64 on the host): out[s, :n_out[s]] are the next enhanced blocks
+        of slot s, in order.  n_out[s] = counts[s] where the slot already held a block, else max(counts[s] - 1, 0)."""
+        S, HOP = self.S, self.HOP
+        if blocks.dim() == 2 and blocks.shape[0] == S and blocks.shape[1] % HOP == 0 and blocks.shape[1] > 0:
+            blocks = blocks.reshape(S, blocks.shape[1] // HOP, HOP)
+        if blocks.dim() != 3 or blocks.shape[0] != S or blocks.shape[2] != HOP or blocks.shape[1] < 1:
+            raise ValueError(f"push_packet expects blocks of shape ({S}, K, {HOP}) or ({S}, K*{HOP}), got {tuple(blocks.shape)}")
+        K = int(blocks.shape[1])
+        if K > self.max_hops:
+            raise ValueError(f"push_packet: a packet of {K} blocks exceeds max_hops = {self.max_hops}")
+        if counts is None:
+            cnt = np.full(S, K, dtype=np.int64)
+        else:
+            cnt = (counts.cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)).reshape(-1)
+            if cnt.size != S:
+                raise ValueError(f"counts must have {S} entries, got {cnt.size}")
+            if not np.issubdtype(cnt.dtype, np.integer) and not np.all(cnt == np.floor(cnt)):
+                raise ValueError("counts must be integers")
+            cnt = cnt.astype(np.int64)
+            if cnt.min() < 0 or cnt.max() > K:
+                raise ValueError(f"counts must lie in [0, {K}] (the packet has {K} blocks), got min {cnt.min()}, max {cnt.max()}")
+        if self.max_hops == 1:                                                  # one block per call: the single-hop chain
+            out, valid = self.push(blocks[:, 0], cnt > 0)
+            return out.unsqueeze(1), valid.to(torch.int64)
+        plans = [packet_plan(int(b), int(c)) for b, c in zip(self.nblk, cnt)]
+        n_out = np.array([p.n_out for p in plans], dtype=np.int64)
+        frames = np.array([p.n_frames for p in plans], dtype=np.int64)
+        hops = int(cnt.max())
+        if hops == 0:
+            return torch.zeros(S, K, HOP, device=self.device), torch.from_numpy(n_out)
+        self.pblocks[:, :K].copy_(blocks.to(torch.float32), non_blocking=True)
+        if self._pk_free is not None:
+            self._pk_free.synchronize()
+        hp = self._pk_host.numpy()
+        hp[0], hp[1] = [p.start for p in plans], cnt
+        self.pk.copy_(self._pk_host, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._pk_free = ev
+        self.nblk += cnt
+        act = cnt > 0
+        self._last_frames[act] = frames[act]
+        self._last_f0[act] = np.array([p.first_frame == 0 for p in plans])[act]
+        self._launch_packet(hops, int(frames.max()))
+        return self.pout[:, :K].clone(), torch.from_numpy(n_out)
+
+    @torch.no_grad()
+    def enhance(self, waves: torch.Tensor, hops=None) -> torch.Tensor:
+        """Whole clips waves [n, L] (n <= n_slots, L >= 320, device or host) through push_packet with `hops` (default max_hops)
+        blocks per call, then flush; -> [n, L] on the device.  Uses slots 0..n-1: resets them first and leaves them reset.  When L
+        is not a multiple of 160 the clip is zero-padded to the next multiple and the result trimmed to L, so it equals the
+        offline result OF THE PADDED CLIP (the end reflection then mirrors the padding).  Only one packet of the clip is on the
+        device's work buffers at a time: memory beyond the input and output waveforms does not grow with L."""
+        if waves.dim() != 2:
+            raise ValueError(f"enhance expects waves of shape (n, L), got {tuple(waves.shape)}")
+        n, L = int(waves.shape[0]), int(waves.shape[1])
+        hops = self.max_hops if hops is None else int(hops)
+        if not 1 <= n <= self.S:
+            raise ValueError(f"enhance: {n} clips for {self.S} slots")
+        if L < 2 * self.HOP:
+            raise ValueError(f"enhance: clips of {L} samples are shorter than 320")
+        if not 1 <= hops <= self.max_hops:
+            raise ValueError(f"enhance: hops = {hops} outside [1, max_hops = {self.max_hops}]")
+        S, HOP = self.S, self.HOP
+        nb = padded_blocks(L)
+        slots = list(range(n))
+        self.reset(slots)
+        res = torch.empty(n, nb * HOP, device=self.device)
+        pkt = torch.zeros(S, hops * HOP, device=self.device)
+        counts = np.zeros(S, dtype=np.int64)
+        done = 0                                                                # output blocks written
+        for b0 in range(0, nb, hops):
+            c = min(hops, nb - b0)
+            lo, hi = b0 * HOP, min((b0 + c) * HOP, L)
+            pkt[:n, :hi - lo].copy_(waves[:, lo:hi], non_blocking=True)
+            if hi - lo < hops * HOP:
+                pkt[:n, hi - lo:].zero_()
+            counts[:n] = c
+            out, n_out = self.push_packet(pkt, counts)
+            k = int(n_out[0])
+            res[:, done * HOP:(done + k) * HOP] = out[:n, :k].reshape(n, k * HOP)
+            done += k
+        res[:, done * HOP:] = self.flush(slots)
+        return res[:, :L]
 
     # -- inspection ---------------------------------------------------------------------------------------------------------
-    def stage(self, slot: int) -> Dict[str, torch.Tensor]:
-        """Views of slot `slot`'s last computed frame: re / im (161), e1..e4, skip1..skip4, gru1 / gru2 (group-contiguous), mask."""
+    def stage(self, slot: int, frame: int = -1) -> Dict[str, torch.Tensor]:
+        """Views of one computed frame of slot `slot`: re / im (161), e1..e4, skip1..skip4, gru1 / gru2 (group-contiguous), mask.
+        After push / flush: the frame just computed.  After push_packet: frame `frame` of the slot's packet (0 .. frames - 1 or
+        negative from the end; default the last one) and its output block as "block" (absent for frame 0 of a clip)."""
         lay, ch, F = self.lay, self.ch, [160 >> k for k in range(5)]
+        nfr = int(self._last_frames[slot])
+        if nfr > 0:
+            if not -nfr <= frame < nfr:
+                raise ValueError(f"stage: frame {frame} outside the {nfr} frames of slot {slot}'s last packet")
+            f = frame % nfr
+            wk = self.pwork[slot, f]
+            out = {"re": wk[lay["wk_re"]:lay["wk_re"] + 161], "im": wk[lay["wk_im"]:lay["wk_im"] + 161],
+                   "gru1": wk[lay["wk_h1n"]:lay["wk_h1n"] + self.H], "gru2": wk[lay["wk_h2n"]:lay["wk_h2n"] + self.H],
+                   "mask": wk[lay["wk_mask"]:lay["wk_mask"] + 160], "e4": wk[lay["wk_x"]:lay["wk_x"] + self.H]}
+            for k in range(1, 5):
+                n = ch[k] * F[k]
+                out[f"skip{k}"] = wk[lay[f"wk_skip{k}"]:lay[f"wk_skip{k}"] + n]
+                if k < 4:
+                    out[f"e{k}"] = wk[self.play[f"wk_e{k}"]:self.play[f"wk_e{k}"] + n]
+            first = int(self._last_f0[slot])                                    # frame 0 of a clip yields no output block
+            if f - first >= 0:
+                out["block"] = self.pout[slot, f - first]
+            return out
+        if frame not in (-1, 0):
+            raise ValueError(f"stage: slot {slot}'s last call computed one frame, frame {frame} does not exist")
         wk, st = self.work[slot], self.state[slot]
         out = {"re": wk[lay["wk_re"]:lay["wk_re"] + 161], "im": wk[lay["wk_im"]:lay["wk_im"] + 161],
                "gru1": wk[lay["wk_h1n"]:lay["wk_h1n"] + self.H], "gru2": wk[lay["wk_h2n"]:lay["wk_h2n"] + self.H],

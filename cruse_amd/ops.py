@@ -1075,3 +1075,34 @@ def stream_gru(mode, layer, groups, Hg, x, x_off, hprev, h_off, pack, hout, o_of
 def stream_decode(mode, ch, tab, w, ln_eps, state, work, out) -> None:
     check(lib.cruse_stream_decode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state), _p(work),
                                   _p(out), _stream()))
+
+
+# packets: up to `hops` blocks per slot in one chain (cruse_stream_*_n).  pk is the [2, S] int32 device tensor of the header
+# (row 0: blocks held, clamped to 2; row 1: blocks consumed); work is [S, work_frames, wk_stride], one row per frame.
+def stream_packet_layout(ch) -> Dict[str, int]:
+    """max_hops: the largest `hops` (work_frames - 1) whose rows fit the LDS of the packet kernels for these channels; wk_stride:
+    floats of a frame's work row in a packet (the single-hop row, then e1 | e2 | e3 at wk_e1..wk_e3)."""
+    arr = (ctypes.c_int * 5)()
+    check(lib.cruse_stream_packet_layout(*[int(c) for c in ch], arr))
+    return dict(zip(("max_hops", "wk_stride", "wk_e1", "wk_e2", "wk_e3"), list(arr)))
+
+
+def stream_encode_n(pk, hops, ch, blocks, tab, w, state, work) -> None:
+    check(lib.cruse_stream_encode_n(_p(pk), pk.shape[1], int(hops), blocks.shape[1], work.shape[1], *[int(c) for c in ch], _p(blocks),
+                                    _p(tab), _p(w), _p(state), _p(work), _stream()))
+
+
+def stream_gru_proj_n(pk, hops, layer, groups, Hg, work, x_off, pack, gi, ln_g=None, ln_b=None, ln_eps=1e-5) -> None:
+    """gi [S, work_frames, 3H] <- the layer's input products of every frame's work row at float offset x_off."""
+    check(lib.cruse_stream_gru_proj_n(_p(pk), pk.shape[1], int(hops), work.shape[1], layer, groups, Hg, _p(work), work.shape[2], x_off,
+                                      _p(ln_g), _p(ln_b), float(ln_eps), _p(pack), _p(gi), _stream()))
+
+
+def stream_gru_rec_n(pk, hops, frame, groups, Hg, gi, state, st_off, pack, work, h_off) -> None:
+    check(lib.cruse_stream_gru_rec_n(_p(pk), pk.shape[1], int(hops), work.shape[1], int(frame), groups, Hg, _p(gi), _p(state),
+                                     state.shape[1], st_off, _p(pack), _p(work), work.shape[2], h_off, _stream()))
+
+
+def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out) -> None:
+    check(lib.cruse_stream_decode_n(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab), _p(w),
+                                    float(ln_eps), _p(state), _p(work), _p(out), _stream()))

@@ -775,6 +775,40 @@ int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg, const flo
 int cruse_stream_decode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
                         float ln_eps, float* state, float* work, float* out, void* stream);
 
+/* ---- packets: up to `hops` blocks per slot in one chain (additive; state rows and cruse_stream_layout are shared with the
+ * single-hop entry points above, so both kinds of call may be mixed on a slot) -------------------------------------------------
+ * pk[2*S] (device, int): pk[s] = blocks slot s held before the call, clamped to 2 (0: none, 1: block 0 only, 2: two or more);
+ * pk[S + s] = count of blocks slot s consumes, 0..hops (0: the slot is not touched).  A slot computes nf frames: count if it
+ * held two or more blocks, count + 1 if it held one (frame 0 and the frames of the new blocks), count if it held none and
+ * count >= 2 (frames 0..count-1), none if it held none and count == 1 (the block is stored).  Frame f of slot s has its own work
+ * row work[(s * work_frames + f) * WS] (work_frames >= hops + 1): the row of cruse_stream_layout followed by e1 | e2 | e3.  The chain is encode_n -> gru_proj_n (layer 1) ->
+ * gru_rec_n for frame 0..nf_max-1 -> gru_proj_n (layer 2) -> gru_rec_n ... -> decode_n, dependent launches on one stream.
+ * One workgroup per slot holds two rows per frame and one level's weights in LDS (128 KiB budget), which bounds work_frames;
+ * more is CRUSE_E_SHAPE. */
+/* out[5] (HOST array): the largest supported hops (work_frames - 1), the packet work-row stride WS (floats), the offsets of
+ * e1, e2, e3 in that row */
+int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4, int* out);
+/* cruse_stream_encode for every frame of the packet, level by level over the frames with the level's folded weights staged in
+ * LDS: frames from the history and in[S][in_hops][160] (frame 0's reflection where the packet starts a clip), DFT, magnitude,
+ * encoder and skip convs, GRU input rows; history and previous rows advance to the last consumed block / frame */
+int cruse_stream_encode_n(const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                          const float* in, const float* tab, const float* w, float* state, float* work, void* stream);
+/* input products of one GGRU layer (pack as cruse_stream_gru) for every (slot, frame): gi[(s * work_frames + f) * 3H + c*H + u] =
+ * W_ih[c][u] . x + b_ih (+ b_hh for c = r, z), x = the frame's work row at x_off (layer 2: LN1 of its interleaved view first) */
+int cruse_stream_gru_proj_n(const int* pk, int S, int hops, int work_frames, int layer, int g, int Hg, const float* work,
+                            int wk_stride, int x_off, const float* ln_g, const float* ln_b, float ln_eps, const float* pack,
+                            float* gi, void* stream);
+/* recurrent step `frame` of that layer for every slot with frame < nf: h' from gi, W_hh . h and b_hn into the frame's work row at
+ * h_off; h is the state row at st_off for frame 0, the previous frame's work row else */
+int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_frames, int frame, int g, int Hg, const float* gi,
+                           const float* state, int st_stride, int st_off, const float* pack, float* work, int wk_stride, int h_off,
+                           void* stream);
+/* cruse_stream_decode for every frame of the packet side by side, then the overlap-add as a chain over the frames:
+ * out[S][out_hops][160], slot s's blocks in order from index 0 (frame 0 of a clip yields none); the GRU rows of the slot's last
+ * frame become its state */
+int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                          const float* tab, const float* w, float ln_eps, float* state, float* work, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

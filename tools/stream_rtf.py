@@ -4,7 +4,11 @@ For each n_slots: host wall time of one push (160 new samples for every slot) me
 over >= `--seconds` of pushes (mean / p50 / p99), device time per hop from events around the push, and RTF = push time / 10 ms
 (one hop at 16 kHz).  Prints one JSON object.  Kernel times: run under `rocprofv3 --kernel-trace --stats -- python tools/stream_rtf.py`.
 
-    python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4]
+With --hops (e.g. 1,2,4,8) every (n_slots, hops) cell is measured: wall time per call and per hop (call / hops), device time per
+hop and RTF = call time / (hops * 10 ms).  The hops = 1 row goes through the unchanged push, hops > 1 through push_packet on an
+instance built with max_hops = hops; --out writes the JSON to a file as well (profiles/stream_packet_rtf.json).
+
+    python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--out FILE]
 """
 from __future__ import annotations
 
@@ -59,19 +63,62 @@ def measure(model, S: int, seconds: float):
             "rtf": round(float(w.mean()) / 10000.0, 5), "rtf_per_stream": round(float(w.mean()) / 10000.0 / S, 8)}
 
 
+def measure_packets(model, S: int, hops: int, seconds: float):
+    """one (n_slots, hops) cell; hops = 1 is the single-hop push chain"""
+    from cruse_amd.inferencer import StreamingInferencer
+    inf = StreamingInferencer(model, S, max_hops=hops)
+    blocks = 0.1 * torch.randn(S, hops, 160, device="cuda")
+    call = (lambda: inf.push(blocks[:, 0])) if hops == 1 else (lambda: inf.push_packet(blocks))
+    for _ in range(50):
+        call()
+    torch.cuda.synchronize()
+    walls, devs = [], []
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t_end = time.perf_counter() + seconds
+    while time.perf_counter() < t_end or len(walls) < 200:
+        t0 = time.perf_counter()
+        ev0.record()
+        call()
+        ev1.record()
+        torch.cuda.synchronize()
+        walls.append(time.perf_counter() - t0)
+        devs.append(ev0.elapsed_time(ev1) * 1e-3)
+    w, d = np.array(walls) * 1e6, np.array(devs) * 1e6
+    r = lambda v: round(float(v), 2)
+    return {"n_slots": S, "hops": hops, "path": "push" if hops == 1 else "push_packet", "calls": len(walls),
+            "call_wall_us": {"mean": r(w.mean()), "p50": r(np.median(w)), "p99": r(np.percentile(w, 99))},
+            "wall_us_per_hop": {"mean": r(w.mean() / hops), "p50": r(np.median(w) / hops), "p99": r(np.percentile(w, 99) / hops)},
+            "device_us_per_hop": r(d.mean() / hops), "rtf": round(float(w.mean()) / (10000.0 * hops), 5)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--slots", default="1,16,64,256,1024")
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--groups", type=int, default=4)
+    ap.add_argument("--hops", default=None, help="comma-separated packet sizes, e.g. 1,2,4,8: measure every (slots, hops) cell")
+    ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()
     from cruse_amd.model.cruse_net import unet_2
     torch.manual_seed(0)
     m = unet_2(rnn_groups=a.groups, precision="f32")
     closed_form(m)
     m = m.cuda().eval()
-    rows = [measure(m, int(s), a.seconds) for s in a.slots.split(",")]
-    print(json.dumps({"model": f"unet_2 ch={m.ch} rnn_groups={a.groups}", "device": torch.cuda.get_device_name(0), "rows": rows}))
+    if a.hops is None:
+        rows = [measure(m, int(s), a.seconds) for s in a.slots.split(",")]
+    else:
+        rows = [measure_packets(m, int(s), int(h), a.seconds) for s in a.slots.split(",") for h in a.hops.split(",")]
+        base = {r["n_slots"]: r["wall_us_per_hop"]["mean"] for r in rows if r["hops"] == 1}
+        for r in rows:                                              # per hop against the push path measured in the same run
+            if r["n_slots"] in base:
+                r["per_hop_vs_push"] = round(r["wall_us_per_hop"]["mean"] / base[r["n_slots"]], 3)
+    res = {"model": f"unet_2 ch={m.ch} rnn_groups={a.groups}", "device": torch.cuda.get_device_name(0), "rows": rows}
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
