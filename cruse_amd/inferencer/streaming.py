@@ -70,6 +70,9 @@ class StreamingInferencer:
         if self.H % self.g or (self.H // self.g) % 4:
             raise ValueError(f"StreamingInferencer needs hidden_size / rnn_groups divisible by 4 (hidden {self.H}, groups {self.g})")
         self.Hg = self.H // self.g
+        if self.Hg > ops.STREAM_MAX_HG:     # cruse_stream_gru* refuse it: say so here, not from the first push's graph capture
+            raise ValueError(f"StreamingInferencer needs hidden_size / rnn_groups <= {ops.STREAM_MAX_HG} (hidden {self.H}, groups "
+                             f"{self.g}: {self.Hg} per group; the GRU kernels hold a unit's weight rows in 16 registers per lane)")
         self.lay = ops.stream_layout(self.ch)
         self.use_graph = use_graph
         S, dev = self.S, self.device

@@ -1046,6 +1046,7 @@ STREAM_LAYOUT_NAMES = (
     + ["st_h1", "st_h2", "st_stride", "wk_re", "wk_im", "wk_x"] + [f"wk_skip{k}" for k in range(5)]
     + ["wk_h1n", "wk_h2n", "wk_mask", "wk_stride"])
 STREAM_SKIP, STREAM_STORE, STREAM_FRAME, STREAM_FRAME0, STREAM_END = 0, 1, 2, 3, 4
+STREAM_MAX_HG = 1024        # widest GRU group of cruse_stream_gru / _gru_proj_n / _gru_rec_n (16 slices of 64 lanes)
 
 
 def stream_layout(ch) -> Dict[str, int]:

@@ -4,8 +4,13 @@ Runs the oracle's modules (oracle.cruse_oracle.unet_2, eval mode) one frame at a
 the previous input row of each encoder level, one h per GRU, the analysis history and the overlap-add tail.  Frame t covers
 x[160t-160 .. 160t+159] of the reflect-padded clip: frame 0's first half is x[160], ..., x[1], the end frame's second half
 x[L-2], ..., x[L-161].  Returns the L output samples and every frame's intermediates.
+
+dtype: float32 (default) or float64.  For float64 pass a `.double()` copy of the module (as_double): the window, the state and
+all arithmetic are then float64, the reference the f32 kernels are measured against at new shapes.
 """
 from __future__ import annotations
+
+import copy
 
 import torch
 import torch.nn.functional as F
@@ -25,9 +30,10 @@ def frame_of(x: torch.Tensor, t: int) -> torch.Tensor:
 
 
 @torch.no_grad()
-def frame_step(model, fr: torch.Tensor, st: dict) -> dict:
+def frame_step(model, fr: torch.Tensor, st: dict, dtype=torch.float32) -> dict:
     """one frame through unet_2 with streaming state st (updated in place); returns the frame's intermediates"""
-    win = torch.hann_window(NFFT, dtype=torch.float32)
+    win = torch.hann_window(NFFT, dtype=dtype)
+    fr = fr.to(dtype)
     spec = torch.fft.rfft(fr * win)
     re, im = spec.real.contiguous(), spec.imag.contiguous()
     mag = torch.sqrt(re ** 2 + im ** 2 + 1e-8)[:160].view(1, 1, 1, 160)
@@ -63,8 +69,8 @@ def frame_step(model, fr: torch.Tensor, st: dict) -> dict:
         d = torch.relu(getattr(model, f"bn{k}_t")(getattr(model, f"conv{k}_t")(d)[..., :-1])) + out[f"skip{k - 1}"]
     mask = torch.sigmoid(model.conv1_t(d)[..., :-1]).reshape(-1)
     out["mask"] = mask
-    er = torch.cat([mask * re[:160], torch.zeros(1)])
-    ei = torch.cat([mask * im[:160], torch.zeros(1)])
+    er = torch.cat([mask * re[:160], torch.zeros(1, dtype=dtype)])
+    ei = torch.cat([mask * im[:160], torch.zeros(1, dtype=dtype)])
     y = torch.fft.irfft(torch.complex(er, ei), n=NFFT) * win
     env = win[:HOP] ** 2 + win[HOP:] ** 2
     out["block"] = (st["tail"] + y[:HOP]) / env                             # output block t-1
@@ -72,26 +78,35 @@ def frame_step(model, fr: torch.Tensor, st: dict) -> dict:
     return out
 
 
-def new_state(model) -> dict:
+def new_state(model, dtype=torch.float32) -> dict:
     ch, g = [model.conv1.in_channels] + [getattr(model, f"conv{k}").out_channels for k in range(1, 5)], model.gru.groups
     Hg = model.gru.gru_list1[0].hidden_size
-    return {"prev": [torch.zeros(1, ch[k], 1, 160 >> k) for k in range(4)], "h1": [torch.zeros(1, 1, Hg) for _ in range(g)],
-            "h2": [torch.zeros(1, 1, Hg) for _ in range(g)], "tail": torch.zeros(HOP)}
+    z = lambda *shape: torch.zeros(*shape, dtype=dtype)
+    return {"prev": [z(1, ch[k], 1, 160 >> k) for k in range(4)], "h1": [z(1, 1, Hg) for _ in range(g)],
+            "h2": [z(1, 1, Hg) for _ in range(g)], "tail": z(HOP)}
 
 
 @torch.no_grad()
-def stream_clip(model, x: torch.Tensor):
-    """x [L] (L a multiple of 160, >= 320) -> (enhanced [L], [intermediates of frames 0..L/160])"""
+def stream_clip(model, x: torch.Tensor, dtype=torch.float32):
+    """x [L] (L a multiple of 160, >= 320) -> (enhanced [L], [intermediates of frames 0..L/160]), both in `dtype`"""
     model.eval()
+    if model.conv1.weight.dtype != dtype:
+        raise ValueError(f"stream_clip: the module's weights are {model.conv1.weight.dtype}, dtype is {dtype} (see as_double)")
+    x = x.to(dtype)
     nb = x.numel() // HOP
-    st = new_state(model)
+    st = new_state(model, dtype)
     frames, blocks = [], []
     for t in range(nb + 1):
-        o = frame_step(model, frame_of(x, t), st)
+        o = frame_step(model, frame_of(x, t), st, dtype)
         frames.append(o)
         if t >= 1:
             blocks.append(o["block"])
     return torch.cat(blocks), frames
+
+
+def as_double(model):
+    """a float64 copy of the module, for stream_clip(..., dtype=torch.float64)"""
+    return copy.deepcopy(model).double().eval()
 
 
 def nontrivial_bn(model, seed: int = 3) -> None:

@@ -32,3 +32,12 @@ def test_engine_steps_under_the_guard_allocator():
     three losses, with torch's allocator replaced by one hipMalloc block per tensor, end-aligned (tools/guard_alloc)"""
     rc, out = _run([os.path.join(ROOT, "tools", "engine_guard_run.py"), os.path.join(ROOT, "tools", "guard_engine_steps.py")], 1500)
     assert rc == 0 and "guard steps ok" in out, out[-3000:]
+
+
+def test_stream_chains_under_the_guard_allocator():
+    """tools/engine_guard_run.py tools/guard_stream_steps.py: the streaming chains (push + flush, push_packet at max_hops 2 and at the LDS
+    bound, enhance) at one and three slots for odd channel counts, Hg < 64 and the widest rows, eager launches, every tensor end-aligned in
+    its own hipMalloc block; every output also compared with the float64 CPU restatement"""
+    rc, out = _run([os.path.join(ROOT, "tools", "engine_guard_run.py"), os.path.join(ROOT, "tools", "guard_stream_steps.py")], 1500)
+    lines = out.strip().splitlines()
+    assert rc == 0 and lines and lines[-1].startswith("guard stream ok"), out[-3000:]
