@@ -142,6 +142,9 @@ SIGNATURES = {
     "cruse_stream_gru_proj_n": ("piiiiiipiippfppp", "i"),
     "cruse_stream_gru_rec_n": ("piiiiiippiippiip", "i"),
     "cruse_stream_decode_n": ("piiiiiiiiippfpppp", "i"),
+    "cruse_stream_gru_f16": ("piiiipiippfpiipppiip", "i"),
+    "cruse_stream_gru_proj_n_f16": ("piiiiiipiippfpppp", "i"),
+    "cruse_stream_gru_rec_n_f16": ("piiiiiippiipppiip", "i"),
 }
 
 

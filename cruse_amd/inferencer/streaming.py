@@ -41,18 +41,23 @@ def _bn_fold(bn):
 class StreamingInferencer:
     """Streaming unet_2 over `n_slots` independent streams.
 
-    Streaming always computes in f32 (f32 operands, f32 accumulation), whatever the module's `precision`; BatchNorm uses the
-    running statistics (eval mode).  Call refresh() after changing the module's weights.
+    precision = "f32" (default): f32 operands, f32 accumulation throughout.  precision = "f16": the two GRU layers run on f16-operand
+    MFMA kernels (cruse_stream_gru*_f16) -- the operand copies of x, h and the GRU weights are rounded to f16; accumulation, biases,
+    LayerNorm, the gates, the carried state and every row stage() shows stay f32, and encode / decode are the f32 kernels.  It is
+    meant for servers with many slots.  The module's own `precision` is not consulted in either mode; BatchNorm uses
+    the running statistics (eval mode).  Call refresh() after changing the module's weights.
     """
 
     HOP = 160
 
     def __init__(self, model: torch.nn.Module, n_slots: int, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
-                 device="cuda", use_graph: bool = True, max_hops: int = 1):
+                 device="cuda", use_graph: bool = True, max_hops: int = 1, precision: str = "f32"):
         from ..model.cruse_net import unet_2
         if (n_fft, hop_length, win_length) != (320, 160, 320):
             raise ValueError(f"StreamingInferencer supports n_fft = win_length = 320, hop_length = 160 only "
                              f"(got n_fft={n_fft}, hop_length={hop_length}, win_length={win_length})")
+        if precision not in ("f32", "f16"):
+            raise ValueError(f"StreamingInferencer precision must be \"f32\" or \"f16\", got {precision!r}")
         if type(model) is not unet_2:
             raise ValueError(f"StreamingInferencer streams cruse_net.unet_2 only (the upsample decoder of "
                              f"{type(model).__name__} is not supported)")
@@ -62,6 +67,7 @@ class StreamingInferencer:
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1, got {n_slots}")
         self.model = model
+        self.precision = precision
         self.S = int(n_slots)
         self.device = torch.device(device)
         self.ch = tuple(model.ch)
@@ -109,7 +115,7 @@ class StreamingInferencer:
     @torch.no_grad()
     def refresh(self) -> None:
         """Re-pack the module's weights: BatchNorm folded into the convs (running statistics, bn.eps), GRU weights per layer as
-        W_ih [g][3Hg][Hg] | W_hh | b_ih [g][3Hg] | b_hh."""
+        W_ih [g][3Hg][Hg] | W_hh | b_ih [g][3Hg] | b_hh; in f16 mode also each layer's weights as f16 MFMA fragments (ops.stream_pack_f16)."""
         m, lay, ch = self.model, self.lay, self.ch
         w = torch.zeros(lay["wtotal"], dtype=torch.float64)
 
@@ -137,22 +143,38 @@ class StreamingInferencer:
         put("ln2b", m.gru.ln2.bias)
         self.ln1_eps, self.ln2_eps = float(m.gru.ln1.eps), float(m.gru.ln2.eps)
         w = w.float().to(self.device)
-        packs = []
+        packs, packs16 = [], []
         for lst in (m.gru.gru_list1, m.gru.gru_list2):
             parts = [torch.stack([gr.weight_ih_l0 for gr in lst]), torch.stack([gr.weight_hh_l0 for gr in lst]),
                      torch.stack([gr.bias_ih_l0 for gr in lst]), torch.stack([gr.bias_hh_l0 for gr in lst])]
             packs.append(torch.cat([p.detach().float().reshape(-1).to(self.device) for p in parts]))
+            if self.precision == "f16":
+                packs16.append(ops.stream_pack_f16(parts[0], parts[1]).to(self.device))
         if hasattr(self, "w"):                      # captured graphs hold these buffers: update them in place
             self.w.copy_(w)
             self.gru_pack1.copy_(packs[0])
             self.gru_pack2.copy_(packs[1])
         else:
             self.w, (self.gru_pack1, self.gru_pack2) = w, packs
+        if packs16:
+            if hasattr(self, "gru_pack1_f16"):
+                self.gru_pack1_f16.copy_(packs16[0])
+                self.gru_pack2_f16.copy_(packs16[1])
+            else:
+                self.gru_pack1_f16, self.gru_pack2_f16 = packs16
 
     # -- the hop ----------------------------------------------------------------------------------------------------------
     def _chain(self, row: int) -> None:
         mode, lay, g, Hg = self.mode[row], self.lay, self.g, self.Hg
         ops.stream_encode(mode, self.ch, self.blocks, self.tab, self.w, self.state, self.work)
+        if self.precision == "f16":
+            ln1 = dict(ln_g=self.w[lay["ln1g"]:lay["ln1g"] + self.H], ln_b=self.w[lay["ln1b"]:lay["ln1b"] + self.H], ln_eps=self.ln1_eps)
+            ops.stream_gru_f16(mode, 1, g, Hg, self.work, lay["wk_x"], self.state, lay["st_h1"], self.gru_pack1, self.gru_pack1_f16,
+                               self.work, lay["wk_h1n"])
+            ops.stream_gru_f16(mode, 2, g, Hg, self.work, lay["wk_h1n"], self.state, lay["st_h2"], self.gru_pack2, self.gru_pack2_f16,
+                               self.work, lay["wk_h2n"], **ln1)
+            ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out)
+            return
         ops.stream_gru(mode, 1, g, Hg, self.work, lay["wk_x"], self.state, lay["st_h1"], self.gru_pack1, self.work, lay["wk_h1n"])
         ops.stream_gru(mode, 2, g, Hg, self.work, lay["wk_h1n"], self.state, lay["st_h2"], self.gru_pack2, self.work, lay["wk_h2n"],
                        ln_g=self.w[lay["ln1g"]:lay["ln1g"] + self.H], ln_b=self.w[lay["ln1b"]:lay["ln1b"] + self.H],
@@ -246,6 +268,16 @@ class StreamingInferencer:
         pk, lay, g, Hg, H, wk = self.pk, self.lay, self.g, self.Hg, self.H, self.pwork
         ops.stream_encode_n(pk, hops, self.ch, self.pblocks, self.tab, self.w, self.state, wk)
         if nf == 0:                                                             # nothing but first blocks to store
+            return
+        if self.precision == "f16":
+            ln1 = dict(ln_g=self.w[lay["ln1g"]:lay["ln1g"] + H], ln_b=self.w[lay["ln1b"]:lay["ln1b"] + H], ln_eps=self.ln1_eps)
+            for layer, x_off, st_off, h_off, pack, pack16, kw in (
+                    (1, lay["wk_x"], lay["st_h1"], lay["wk_h1n"], self.gru_pack1, self.gru_pack1_f16, {}),
+                    (2, lay["wk_h1n"], lay["st_h2"], lay["wk_h2n"], self.gru_pack2, self.gru_pack2_f16, ln1)):
+                ops.stream_gru_proj_n_f16(pk, hops, layer, g, Hg, wk, x_off, pack, pack16, self.gi, **kw)
+                for f in range(nf):
+                    ops.stream_gru_rec_n_f16(pk, hops, f, g, Hg, self.gi, self.state, st_off, pack, pack16, wk, h_off)
+            ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout)
             return
         ops.stream_gru_proj_n(pk, hops, 1, g, Hg, wk, lay["wk_x"], self.gru_pack1, self.gi)
         for f in range(nf):

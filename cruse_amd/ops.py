@@ -1107,3 +1107,36 @@ def stream_gru_rec_n(pk, hops, frame, groups, Hg, gi, state, st_off, pack, work,
 def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out) -> None:
     check(lib.cruse_stream_decode_n(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab), _p(w),
                                     float(ln_eps), _p(state), _p(work), _p(out), _stream()))
+
+
+# f16-operand MFMA GRU of the streaming chains (cruse_stream_gru*_f16): same rows and arguments as stream_gru / _gru_proj_n / _gru_rec_n,
+# plus the layer's fragment-ordered f16 weights; `pack` (f32) still supplies the biases
+def stream_pack_f16(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
+    """W_ih, W_hh [g, 3*Hg, Hg] (any float dtype / device) -> the flat f16 pack16 of the header, on the inputs' device:
+    [ih | hh][g][gate][UT][KS][lane][8], units padded to 16 and K to 32 with zeros."""
+    g, three_hg, Hg = w_ih.shape
+    assert three_hg == 3 * Hg and w_hh.shape == w_ih.shape, (w_ih.shape, w_hh.shape)
+    UT, KS = (Hg + 15) // 16, (Hg + 31) // 32
+    w = torch.stack([w_ih, w_hh]).detach().float().reshape(2, g, 3, Hg, Hg)
+    p = torch.zeros(2, g, 3, UT * 16, KS * 32, dtype=torch.float32, device=w.device)
+    p[..., :Hg, :Hg] = w
+    # unit = ut*16 + r, k = ks*32 + q*8 + j, lane = q*16 + r
+    p = p.reshape(2, g, 3, UT, 16, KS, 4, 8).permute(0, 1, 2, 3, 5, 6, 4, 7)
+    return p.contiguous().reshape(-1).to(torch.float16)
+
+
+def stream_gru_f16(mode, layer, groups, Hg, x, x_off, hprev, h_off, pack, pack16, hout, o_off, ln_g=None, ln_b=None, ln_eps=1e-5) -> None:
+    """one GGRU layer, one step, for every slot whose mode computes a frame; layer 2 applies LN1 (ln_g, ln_b) to layer 1's row"""
+    check(lib.cruse_stream_gru_f16(_p(mode), mode.numel(), layer, groups, Hg, _p(x), x.shape[1], x_off, _p(ln_g), _p(ln_b), float(ln_eps),
+                                   _p(hprev), hprev.shape[1], h_off, _p(pack), _p(pack16), _p(hout), hout.shape[1], o_off, _stream()))
+
+
+def stream_gru_proj_n_f16(pk, hops, layer, groups, Hg, work, x_off, pack, pack16, gi, ln_g=None, ln_b=None, ln_eps=1e-5) -> None:
+    """gi [S, frames, 3H] (f32) <- the input products of one GGRU layer for every frame of the packet"""
+    check(lib.cruse_stream_gru_proj_n_f16(_p(pk), pk.shape[1], int(hops), work.shape[1], layer, groups, Hg, _p(work), work.shape[2], x_off,
+                                          _p(ln_g), _p(ln_b), float(ln_eps), _p(pack), _p(pack16), _p(gi), _stream()))
+
+
+def stream_gru_rec_n_f16(pk, hops, frame, groups, Hg, gi, state, st_off, pack, pack16, work, h_off) -> None:
+    check(lib.cruse_stream_gru_rec_n_f16(_p(pk), pk.shape[1], int(hops), work.shape[1], int(frame), groups, Hg, _p(gi), _p(state),
+                                         state.shape[1], st_off, _p(pack), _p(pack16), _p(work), work.shape[2], h_off, _stream()))

@@ -809,6 +809,26 @@ int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_frames, int 
 int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                           const float* tab, const float* w, float ln_eps, float* state, float* work, float* out, void* stream);
 
+/* ---- f16-operand MFMA GRU of the streaming chains (additive; rows, mode / pk semantics and the f32 pack are those above, so these
+ * may replace their f32 counterparts call by call) ------------------------------------------------------------------------------
+ * pack16 (device, f16): the layer's weights as MFMA A fragments, [W_ih | W_hh][g][gate r,z,n][UT][KS][64 lanes][8], UT =
+ * ceil(Hg / 16) unit tiles, KS = ceil(Hg / 32) k steps; lane l of (ut, ks) holds W[gate][ut*16 + (l & 15)][ks*32 + (l >> 4)*8 + 0..7],
+ * zero where the unit or k is >= Hg.  Rounded to f16: the operand copies of x (after LN1 in layer 2), of h and the weights; accumulation,
+ * biases (read from `pack`), LN1 statistics, gates and every row written are f32, and the gates read h_prev in f32.
+ * Same refusals as the f32 entry points (S >= 1, Hg % 4 == 0, Hg <= 1024), before any launch. */
+/* cruse_stream_gru on v_mfma_f32_16x16x32_f16: one GGRU layer (model/cruse_net.py:22-50), one time step */
+int cruse_stream_gru_f16(const int* mode, int S, int layer, int g, int Hg, const float* x, int x_stride, int x_off,
+                         const float* ln_g, const float* ln_b, float ln_eps, const float* hprev, int h_stride, int h_off,
+                         const float* pack, const void* pack16, float* hout, int o_stride, int o_off, void* stream);
+/* cruse_stream_gru_proj_n on the same MFMA: the input products of every (slot, frame) of a packet; gi stays f32 */
+int cruse_stream_gru_proj_n_f16(const int* pk, int S, int hops, int work_frames, int layer, int g, int Hg, const float* work,
+                                int wk_stride, int x_off, const float* ln_g, const float* ln_b, float ln_eps, const float* pack,
+                                const void* pack16, float* gi, void* stream);
+/* cruse_stream_gru_rec_n on the same MFMA: W_hh . h and the gates of frame `frame` of a packet */
+int cruse_stream_gru_rec_n_f16(const int* pk, int S, int hops, int work_frames, int frame, int g, int Hg, const float* gi,
+                               const float* state, int st_stride, int st_off, const float* pack, const void* pack16, float* work,
+                               int wk_stride, int h_off, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,11 @@ With --hops (e.g. 1,2,4,8) every (n_slots, hops) cell is measured: wall time per
 hop and RTF = call time / (hops * 10 ms).  The hops = 1 row goes through the unchanged push, hops > 1 through push_packet on an
 instance built with max_hops = hops; --out writes the JSON to a file as well (profiles/stream_packet_rtf.json).
 
-    python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--out FILE]
+With --precision f32,f16 every cell is measured for both modes of StreamingInferencer in the same process, f32 first; every row then
+carries "precision", and f16 rows "vs_f32" = their wall time per hop over the f32 row's of the same cell (profiles/stream_f16_rtf.json).
+The default, f32 alone, prints what it always printed.
+
+    python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--precision f32,f16] [--out FILE]
 """
 from __future__ import annotations
 
@@ -39,9 +43,13 @@ def closed_form(model):
             p.copy_(v.reshape(p.shape).to(p.dtype))
 
 
-def measure(model, S: int, seconds: float):
+def _inferencer(model, S: int, precision: str, **kw):
     from cruse_amd.inferencer import StreamingInferencer
-    inf = StreamingInferencer(model, S)
+    return StreamingInferencer(model, S, **kw) if precision == "f32" else StreamingInferencer(model, S, precision=precision, **kw)
+
+
+def measure(model, S: int, seconds: float, precision: str = "f32"):
+    inf = _inferencer(model, S, precision)
     blocks = 0.1 * torch.randn(S, 160, device="cuda")
     for _ in range(50):
         inf.push(blocks)
@@ -63,10 +71,9 @@ def measure(model, S: int, seconds: float):
             "rtf": round(float(w.mean()) / 10000.0, 5), "rtf_per_stream": round(float(w.mean()) / 10000.0 / S, 8)}
 
 
-def measure_packets(model, S: int, hops: int, seconds: float):
+def measure_packets(model, S: int, hops: int, seconds: float, precision: str = "f32"):
     """one (n_slots, hops) cell; hops = 1 is the single-hop push chain"""
-    from cruse_amd.inferencer import StreamingInferencer
-    inf = StreamingInferencer(model, S, max_hops=hops)
+    inf = _inferencer(model, S, precision, max_hops=hops)
     blocks = 0.1 * torch.randn(S, hops, 160, device="cuda")
     call = (lambda: inf.push(blocks[:, 0])) if hops == 1 else (lambda: inf.push_packet(blocks))
     for _ in range(50):
@@ -97,6 +104,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--groups", type=int, default=4)
     ap.add_argument("--hops", default=None, help="comma-separated packet sizes, e.g. 1,2,4,8: measure every (slots, hops) cell")
+    ap.add_argument("--precision", default="f32", help="f32 (default), f16 or f32,f16: the StreamingInferencer modes to measure")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()
     from cruse_amd.model.cruse_net import unet_2
@@ -104,14 +112,29 @@ def main():
     m = unet_2(rnn_groups=a.groups, precision="f32")
     closed_form(m)
     m = m.cuda().eval()
-    if a.hops is None:
-        rows = [measure(m, int(s), a.seconds) for s in a.slots.split(",")]
-    else:
-        rows = [measure_packets(m, int(s), int(h), a.seconds) for s in a.slots.split(",") for h in a.hops.split(",")]
-        base = {r["n_slots"]: r["wall_us_per_hop"]["mean"] for r in rows if r["hops"] == 1}
-        for r in rows:                                              # per hop against the push path measured in the same run
-            if r["n_slots"] in base:
-                r["per_hop_vs_push"] = round(r["wall_us_per_hop"]["mean"] / base[r["n_slots"]], 3)
+    precs = a.precision.split(",")
+    if any(p not in ("f32", "f16") for p in precs):
+        ap.error(f"--precision takes f32, f16 or f32,f16, got {a.precision}")
+    rows = []
+    for prec in precs:
+        if a.hops is None:
+            part = [measure(m, int(s), a.seconds, prec) for s in a.slots.split(",")]
+        else:
+            part = [measure_packets(m, int(s), int(h), a.seconds, prec) for s in a.slots.split(",") for h in a.hops.split(",")]
+            base = {r["n_slots"]: r["wall_us_per_hop"]["mean"] for r in part if r["hops"] == 1}
+            for r in part:                                          # per hop against the push path of the same mode and run
+                if r["n_slots"] in base:
+                    r["per_hop_vs_push"] = round(r["wall_us_per_hop"]["mean"] / base[r["n_slots"]], 3)
+        if precs != ["f32"]:
+            for r in part:
+                r["precision"] = prec
+        rows += part
+    if "f32" in precs and "f16" in precs:
+        per_hop = lambda r: r["wall_us_per_hop"]["mean"] if "wall_us_per_hop" in r else r["push_wall_us"]["mean"]
+        f32 = {(r["n_slots"], r.get("hops", 1)): per_hop(r) for r in rows if r["precision"] == "f32"}
+        for r in rows:
+            if r["precision"] == "f16":
+                r["vs_f32"] = round(per_hop(r) / f32[(r["n_slots"], r.get("hops", 1))], 3)
     res = {"model": f"unet_2 ch={m.ch} rnn_groups={a.groups}", "device": torch.cuda.get_device_name(0), "rows": rows}
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
