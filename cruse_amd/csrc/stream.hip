@@ -10,9 +10,11 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
-#include "common.h"
+#include "stream_common.h"
 
 namespace {
+
+using namespace cruse_stream;
 
 constexpr int NFFT = 320, HOP = 160, NB = 161, F0 = 160;
 // one workgroup per slot in encode / decode: 16 waves, so that the per-slot chain of small convolutions has enough loads in
@@ -83,68 +85,104 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return s;
 }
 
-// level-k encoder conv (2,3), stride (1,2), frequency padding 1, BN folded, ReLU: out[co][f] from the previous and current
-// input rows [Cin][Fin]
-__device__ void enc_conv(const float* __restrict__ W, const float* __restrict__ b, const float* prev, const float* cur,
-                         float* out, int Cin, int Fin, int Cout, int Fout) {
-    for (int idx = threadIdx.x; idx < Cout * Fout; idx += blockDim.x) {
-        const int co = idx / Fout, f = idx - co * Fout;
+// The convolutions run over the nf frames of a packet (nf = 1: the single hop); frame f's rows are fs floats apart.  Weight rows are ws
+// floats apart: the packed stride from global memory (single hop), one more in the padded LDS copy of the packet kernels.  The helpers
+// are inlined, so the single hop's literal nf = 1 folds the frame index away.
+
+// level-k encoder conv (2,3), stride (1,2), frequency padding 1, BN folded, ReLU: dst[f][co][fo] from input rows [Cin][Fin] f-1 and f
+// of src; row -1 is `prev`.  W: [Cout][ws], ws >= Cin*6
+__device__ __forceinline__ void enc_conv(const float* __restrict__ W, int ws, const float* __restrict__ b, const float* prev, const float* src, float* dst, int fs,
+                                         int nf, int Cin, int Fin, int Cout, int Fout) {
+    const int per = Cout * Fout;
+    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
+        const int f = nf == 1 ? 0 : idx / per, r = idx - f * per, co = r / Fout, fo = r - co * Fout;
+        const float* pr = f == 0 ? prev : src + (f - 1) * fs;
+        const float* cu = src + f * fs;
         float acc = b[co];
         for (int ci = 0; ci < Cin; ++ci) {
-            const float* w = W + (co * Cin + ci) * 6;
+            const float* w = W + co * ws + ci * 6;
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
-                const int fi = 2 * f - 1 + kw;
+                const int fi = 2 * fo - 1 + kw;
                 if (fi < 0 || fi >= Fin) continue;
-                acc = fmaf(w[kw], prev[ci * Fin + fi], acc);
-                acc = fmaf(w[3 + kw], cur[ci * Fin + fi], acc);
+                acc = fmaf(w[kw], pr[ci * Fin + fi], acc);
+                acc = fmaf(w[3 + kw], cu[ci * Fin + fi], acc);
             }
         }
-        out[idx] = fmaxf(acc, 0.f);
+        dst[f * fs + r] = fmaxf(acc, 0.f);
     }
 }
 
-// skip conv (1,3), padding (0,1), no bias: [C][F] -> [C][F]
-__device__ void skip_conv(const float* __restrict__ W, const float* e, float* out, int C, int F) {
-    for (int idx = threadIdx.x; idx < C * F; idx += blockDim.x) {
-        const int co = idx / F, f = idx - co * F;
+// skip conv (1,3), padding (0,1), no bias: [C][F] -> [C][F]; frame f's result goes to out + f * os.  W: [C][ws], ws >= C*3
+__device__ __forceinline__ void skip_conv(const float* __restrict__ W, int ws, const float* src, int fs, float* out, size_t os, int nf, int C, int F) {
+    const int per = C * F;
+    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
+        const int f = nf == 1 ? 0 : idx / per, r = idx - f * per, co = r / F, fo = r - co * F;
+        const float* e = src + f * fs;
         float acc = 0.f;
         for (int ci = 0; ci < C; ++ci) {
-            const float* w = W + (co * C + ci) * 3;
+            const float* w = W + co * ws + ci * 3;
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
-                const int fi = f - 1 + kw;
+                const int fi = fo - 1 + kw;
                 if (fi >= 0 && fi < F) acc = fmaf(w[kw], e[ci * F + fi], acc);
             }
         }
-        out[idx] = acc;
+        out[f * os + r] = acc;
     }
 }
 
 // ConvTranspose (1,3), stride (1,2), last column cropped: [Cin][Fin] -> [Cout][2*Fin]; W packed [Cin][Cout][3] (BN folded)
-// act 0: ReLU then + add[co][fo]; act 1: sigmoid
-__device__ void dec_convt(const float* __restrict__ W, const float* __restrict__ b, const float* in, float* out,
-                          const float* __restrict__ add, int Cin, int Fin, int Cout, int act) {
-    const int Fout = 2 * Fin;
-    for (int idx = threadIdx.x; idx < Cout * Fout; idx += blockDim.x) {
-        const int co = idx / Fout, fo = idx - co * Fout;
+// act 0: ReLU then + add[f * as + co*Fout + fo] (the frame's skip row); act 1: sigmoid
+__device__ __forceinline__ void dec_convt(const float* __restrict__ W, const float* __restrict__ b, const float* src, float* dst, int fs,
+                                          const float* __restrict__ add, size_t as,
+                                          int nf, int Cin, int Fin, int Cout, int act) {
+    const int Fout = 2 * Fin, per = Cout * Fout;
+    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
+        const int f = nf == 1 ? 0 : idx / per, r = idx - f * per, co = r / Fout, fo = r - co * Fout;
+        const float* in = src + f * fs;
+        const int fi = fo >> 1;
         float acc = b[co];
         if (fo & 1) {
-            const int fi = fo >> 1;
             for (int ci = 0; ci < Cin; ++ci) acc = fmaf(W[(ci * Cout + co) * 3 + 1], in[ci * Fin + fi], acc);
         } else {
-            const int fi = fo >> 1;
             for (int ci = 0; ci < Cin; ++ci) {
                 acc = fmaf(W[(ci * Cout + co) * 3 + 0], in[ci * Fin + fi], acc);
                 if (fi >= 1) acc = fmaf(W[(ci * Cout + co) * 3 + 2], in[ci * Fin + fi - 1], acc);
             }
         }
-        out[idx] = act == 0 ? fmaxf(acc, 0.f) + add[idx] : 1.0f / (1.0f + expf(-acc));
+        dst[f * fs + r] = act == 0 ? fmaxf(acc, 0.f) + add[f * as + r] : 1.0f / (1.0f + expf(-acc));
     }
 }
 
 // tables: [0,320) periodic Hann, [320,640) cos(2 pi j / 320), [640,960) sin(2 pi j / 320), [960,1120) 1 / (w^2(m) + w^2(m+160))
 constexpr int TB_WIN = 0, TB_COS = 320, TB_SIN = 640, TB_IENV = 960, TB_TOTAL = 1120;
+
+// bin k of the 320-point real DFT of fr[320]; cs: cos[320] | sin[320] (tab + TB_COS, or its LDS copy)
+__device__ __forceinline__ void rdft320(const float* fr, const float* cs, int k, float& re, float& im) {
+    re = 0.f;
+    im = 0.f;
+    int j = 0;
+    for (int n = 0; n < NFFT; ++n) {
+        re = fmaf(fr[n], cs[j], re);
+        im = fmaf(-fr[n], cs[NFFT + j], im);
+        j += k;
+        if (j >= NFFT) j -= NFFT;
+    }
+}
+
+// sample n of the 320-point inverse real DFT of re[161], im[161] (imaginary parts of bins 0 and 160 ignored, as irfft)
+__device__ __forceinline__ float irdft320(const float* re, const float* im, const float* cs, int n) {
+    float acc = 0.f;
+    int j = n;
+    for (int k = 1; k < F0; ++k) {
+        acc = fmaf(re[k], cs[j], acc);
+        acc = fmaf(-im[k], cs[NFFT + j], acc);
+        j += n;
+        if (j >= NFFT) j -= NFFT;
+    }
+    return (re[0] + 2.0f * acc + ((n & 1) ? -re[F0] : re[F0])) * (1.0f / NFFT);
+}
 
 __global__ void __launch_bounds__(1024) stream_encode_kernel(const int* __restrict__ mode, Layout L, const float* __restrict__ in,
                                                             const float* __restrict__ tab, const float* __restrict__ w,
@@ -197,14 +235,8 @@ __global__ void __launch_bounds__(1024) stream_encode_kernel(const int* __restri
     }
     // 320-point real DFT, bins 0..160; magnitude of bins 0..159
     for (int k = tid; k < NB; k += blockDim.x) {
-        float re = 0.f, im = 0.f;
-        int j = 0;
-        for (int n = 0; n < NFFT; ++n) {
-            re = fmaf(fr[n], tab[TB_COS + j], re);
-            im = fmaf(-fr[n], tab[TB_SIN + j], im);
-            j += k;
-            if (j >= NFFT) j -= NFFT;
-        }
+        float re, im;
+        rdft320(fr, tab + TB_COS, k, re, im);
         spec[k] = re;
         spec[NB + k] = im;
         wk[L.wk_re + k] = re;
@@ -213,110 +245,139 @@ __global__ void __launch_bounds__(1024) stream_encode_kernel(const int* __restri
     }
     __syncthreads();
     for (int k = 1; k < 5; ++k) {
-        enc_conv(w + L.encW[k], w + L.encB[k], prv[k - 1], cur[k - 1], cur[k], L.ch[k - 1], L.F[k - 1], L.ch[k], L.F[k]);
+        enc_conv(w + L.encW[k], L.ch[k - 1] * 6, w + L.encB[k], prv[k - 1], cur[k - 1], cur[k], 0, 1, L.ch[k - 1], L.F[k - 1], L.ch[k], L.F[k]);
         __syncthreads();
     }
-    for (int k = 1; k < 5; ++k) skip_conv(w + L.skW[k], cur[k], wk + L.wk_skip[k], L.ch[k], L.F[k]);
+    for (int k = 1; k < 5; ++k) skip_conv(w + L.skW[k], L.ch[k] * 3, cur[k], 0, wk + L.wk_skip[k], 0, 1, L.ch[k], L.F[k]);
     for (int i = tid; i < L.H; i += blockDim.x) wk[L.wk_x + i] = cur[4][i];        // GRU input row, c*F4+f
     for (int k = 0; k < 4; ++k)
         for (int i = tid; i < L.ch[k] * L.F[k]; i += blockDim.x) st[L.st_prev[k] + i] = cur[k][i];
 }
 
-// One GGRU layer, one time step, for every slot whose mode computes a frame.  Workgroup: 4 waves, wave w owns hidden unit
-// blockIdx.y*4 + w (all three gates); its lanes hold that unit's six weight rows (W_ih, W_hh x r,z,n) in registers, k = lane + 64q,
-// and loop over tiles of SB slots whose input / state chunks are staged in LDS.  Layer 2 (LN1 != nullptr) stages the whole
-// layer-1 output row and applies LN1 to the interleaved vector v[j*g+i] = h1[i*Hg+j] on the fly.
+// One GGRU layer over the rows of GruArgs (stream_common.h), in three kinds.  STEP: one time step for every slot whose mode computes a
+// frame.  PROJ: gi[row] = W_ih . x + bias for every (slot, frame) of a packet, with b_ih + b_hh folded for the gates r and z and b_in
+// for n; rows behind a slot's last frame are not computed.  REC: frame `frame` of the packet for every slot that computes it: W_hh . h,
+// gates, new h into the frame's work row.  Workgroup: 4 waves, wave w owns hidden unit blockIdx.y*4 + w (all three gates); its lanes
+// hold that unit's weight rows (W_ih and / or W_hh x r,z,n) in registers, k = lane + 64q, and loop over tiles of SB rows whose input /
+// state chunks are staged in LDS.  Layer 2 (ln_g != nullptr) stages the whole layer-1 output row and applies LN1 to the interleaved
+// vector v[j*g+i] = h1[i*Hg+j] on the fly.  A kind holds only the registers and LDS regions it uses.
 constexpr int SB = 8;
 
-template <int KQ>
-__global__ void __launch_bounds__(256) stream_gru_kernel(const int* __restrict__ mode, int S, int g, int Hg,
-                                                         const float* __restrict__ x, int x_stride, int x_off,
-                                                         const float* __restrict__ ln_g, const float* __restrict__ ln_b, float ln_eps,
-                                                         const float* __restrict__ hprev, int h_stride, int h_off,
-                                                         const float* __restrict__ pack, float* __restrict__ hout, int o_stride, int o_off) {
+template <int KIND, int KQ>
+__global__ void __launch_bounds__(256) stream_gru_f32_kernel(GruArgs a) {
     extern __shared__ float sm[];
-    const int H = g * Hg;
+    constexpr bool HAS_X = KIND != KIND_REC, HAS_H = KIND != KIND_PROJ;
+    constexpr int XQ = HAS_X ? KQ : 1, HQ = HAS_H ? KQ : 1;
+    const int g = a.g, Hg = a.Hg, H = g * Hg;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int u = blockIdx.y * 4 + wv;          // unit of the whole layer: group gi, unit j within it
-    const int gi = u / Hg, j = u - gi * Hg;
-    const bool ln = ln_g != nullptr;
-    const int xw = ln ? H : Hg;                 // floats staged per slot for the input
+    const int u = blockIdx.y * 4 + wv;          // unit of the whole layer: group gidx, unit j within it
+    const int gidx = u / Hg, j = u - gidx * Hg;
+    const bool ln = HAS_X && a.ln_g != nullptr;
+    const int xw = HAS_X ? (ln ? H : Hg) : 0;   // floats staged per row for the input
     float* xs = sm;                             // [SB][xw]
     float* hs = sm + SB * xw;                   // [SB][Hg]
-    float* st = hs + SB * Hg;                   // [SB][2] mean, rstd
+    float* st = hs + (HAS_H ? SB * Hg : 0);     // [SB][2] mean, rstd
     const size_t gsz = (size_t)3 * Hg * Hg;
-    const float* Wih = pack + gi * gsz;
-    const float* Whh = pack + g * gsz + gi * gsz;
-    const float* bih = pack + 2 * g * gsz + gi * 3 * Hg;
-    const float* bhh = pack + 2 * g * gsz + g * 3 * Hg + gi * 3 * Hg;
-    float wi[3][KQ], wh[3][KQ], lg[KQ], lb[KQ];
-    int src[KQ];
+    const float* Wih = a.pack + gidx * gsz;
+    const float* Whh = a.pack + g * gsz + gidx * gsz;
+    const float* bih = a.pack + 2 * g * gsz + gidx * 3 * Hg;
+    const float* bhh = a.pack + 2 * g * gsz + g * 3 * Hg + gidx * 3 * Hg;
+    float wi[3][XQ], wh[3][HQ], lg[XQ], lb[XQ];
+    int src[XQ];
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
         const int k = lane + 64 * q;
         const bool ok = k < Hg;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            wi[c][q] = ok ? Wih[(size_t)(c * Hg + j) * Hg + k] : 0.f;
-            wh[c][q] = ok ? Whh[(size_t)(c * Hg + j) * Hg + k] : 0.f;
+            if constexpr (HAS_X) wi[c][q] = ok ? Wih[(size_t)(c * Hg + j) * Hg + k] : 0.f;
+            if constexpr (HAS_H) wh[c][q] = ok ? Whh[(size_t)(c * Hg + j) * Hg + k] : 0.f;
         }
-        const int p = gi * Hg + k;              // position in the LN1 output vector this layer-2 group reads
-        src[q] = ok ? (ln ? (p % g) * Hg + p / g : k) : 0;
-        lg[q] = (ln && ok) ? ln_g[p] : 0.f;
-        lb[q] = (ln && ok) ? ln_b[p] : 0.f;
+        if constexpr (HAS_X) {
+            const int p = gidx * Hg + k;          // position in the LN1 output vector this layer-2 group reads
+            src[q] = ok ? (ln ? (p % g) * Hg + p / g : k) : 0;
+            lg[q] = (ln && ok) ? a.ln_g[p] : 0.f;
+            lb[q] = (ln && ok) ? a.ln_b[p] : 0.f;
+        }
     }
-    const float br = bih[j] + bhh[j], bz = bih[Hg + j] + bhh[Hg + j], bin = bih[2 * Hg + j], bhn = bhh[2 * Hg + j];
-    const int ntiles = (S + SB - 1) / SB;
+    float br = 0.f, bz = 0.f, bin = 0.f, bhn = 0.f;
+    if constexpr (HAS_X) { br = bih[j] + bhh[j]; bz = bih[Hg + j] + bhh[Hg + j]; bin = bih[2 * Hg + j]; }
+    if constexpr (HAS_H) bhn = bhh[2 * Hg + j];
+    const int ntiles = (a.R + SB - 1) / SB;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int s0 = t * SB;
+        const int r0 = t * SB;
         __syncthreads();
-        for (int i = threadIdx.x; i < SB * xw; i += blockDim.x) {
-            const int ss = i / xw, k = i - ss * xw, s = s0 + ss;
-            xs[i] = s < S ? x[(size_t)s * x_stride + x_off + (ln ? 0 : gi * Hg) + k] : 0.f;
+        if constexpr (HAS_X) {
+            for (int i = threadIdx.x; i < SB * xw; i += blockDim.x) {
+                const int ss = i / xw, k = i - ss * xw, r = r0 + ss;
+                xs[i] = r < a.R ? a.x[row_index<KIND>(a, r) * a.x_stride + a.x_off + (ln ? 0 : gidx * Hg) + k] : 0.f;
+            }
         }
-        for (int i = threadIdx.x; i < SB * Hg; i += blockDim.x) {
-            const int ss = i / Hg, k = i - ss * Hg, s = s0 + ss;
-            hs[i] = s < S ? hprev[(size_t)s * h_stride + h_off + gi * Hg + k] : 0.f;
+        if constexpr (HAS_H) {
+            for (int i = threadIdx.x; i < SB * Hg; i += blockDim.x) {
+                const int ss = i / Hg, k = i - ss * Hg, r = r0 + ss;
+                hs[i] = r < a.R ? a.h[row_index<KIND>(a, r) * a.h_stride + a.h_off + gidx * Hg + k] : 0.f;
+            }
         }
         __syncthreads();
         if (ln) {                               // LN1 statistics of each staged row (two passes, biased variance)
             for (int ss = wv; ss < SB; ss += 4) {
-                float a = 0.f;
-                for (int k = lane; k < H; k += 64) a += xs[ss * H + k];
-                const float mean = wave_sum(a) / H;
+                float s1 = 0.f;
+                for (int k = lane; k < H; k += 64) s1 += xs[ss * H + k];
+                const float mean = wave_sum(s1) / H;
                 float v = 0.f;
                 for (int k = lane; k < H; k += 64) { const float d = xs[ss * H + k] - mean; v = fmaf(d, d, v); }
                 const float var = wave_sum(v) / H;
-                if (lane == 0) { st[2 * ss] = mean; st[2 * ss + 1] = 1.0f / sqrtf(var + ln_eps); }
+                if (lane == 0) { st[2 * ss] = mean; st[2 * ss + 1] = 1.0f / sqrtf(var + a.ln_eps); }
             }
             __syncthreads();
         }
         for (int ss = 0; ss < SB; ++ss) {
-            const int s = s0 + ss;
-            if (s >= S) break;
-            const int m = mode[s];
-            if (m != CRUSE_STREAM_MODE_FRAME && m != CRUSE_STREAM_MODE_FRAME0 && m != CRUSE_STREAM_MODE_END) continue;
+            const int r = r0 + ss;
+            if (r >= a.R) break;
+            long long rr;
+            if (!row_of<KIND>(a, r, rr)) continue;
+            // r and z: the input and the recurrent product share one accumulator, interleaved per q
             float ar = 0.f, az = 0.f, ain = 0.f, ahn = 0.f;
             const float mean = ln ? st[2 * ss] : 0.f, rstd = ln ? st[2 * ss + 1] : 0.f;
 #pragma unroll
             for (int q = 0; q < KQ; ++q) {
                 const int k = lane + 64 * q;
                 if (k >= Hg) continue;
-                float xv = xs[ss * xw + src[q]];
-                if (ln) xv = fmaf((xv - mean) * rstd, lg[q], lb[q]);
-                const float hv = hs[ss * Hg + k];
-                ar = fmaf(wi[0][q], xv, ar); ar = fmaf(wh[0][q], hv, ar);
-                az = fmaf(wi[1][q], xv, az); az = fmaf(wh[1][q], hv, az);
-                ain = fmaf(wi[2][q], xv, ain);
-                ahn = fmaf(wh[2][q], hv, ahn);
+                float xv = 0.f, hv = 0.f;
+                if constexpr (HAS_X) {
+                    xv = xs[ss * xw + src[q]];
+                    if (ln) xv = fmaf((xv - mean) * rstd, lg[q], lb[q]);
+                }
+                if constexpr (HAS_H) hv = hs[ss * Hg + k];
+                if constexpr (HAS_X) ar = fmaf(wi[0][q], xv, ar);
+                if constexpr (HAS_H) ar = fmaf(wh[0][q], hv, ar);
+                if constexpr (HAS_X) az = fmaf(wi[1][q], xv, az);
+                if constexpr (HAS_H) az = fmaf(wh[1][q], hv, az);
+                if constexpr (HAS_X) ain = fmaf(wi[2][q], xv, ain);
+                if constexpr (HAS_H) ahn = fmaf(wh[2][q], hv, ahn);
             }
-            ar = wave_sum(ar); az = wave_sum(az); ain = wave_sum(ain); ahn = wave_sum(ahn);
-            if (lane == 0) {
-                const float r = 1.0f / (1.0f + expf(-(ar + br)));
-                const float z = 1.0f / (1.0f + expf(-(az + bz)));
-                const float n = tanhf(ain + bin + r * (ahn + bhn));
-                const float hp = hs[ss * Hg + j];
-                hout[(size_t)s * o_stride + o_off + u] = (1.0f - z) * n + z * hp;
+            ar = wave_sum(ar); az = wave_sum(az);
+            if constexpr (HAS_X) ain = wave_sum(ain);
+            if constexpr (HAS_H) ahn = wave_sum(ahn);
+            if (lane != 0) continue;
+            if constexpr (KIND == KIND_PROJ) {
+                float* o = a.gi + rr * a.gi_stride + u;
+                o[0] = ar + br;
+                o[H] = az + bz;
+                o[2 * H] = ain + bin;
+            } else {
+                float pr, pz, pn;
+                if constexpr (KIND == KIND_STEP) {
+                    pr = ar + br; pz = az + bz; pn = ain + bin;
+                } else {
+                    const float* gv = a.gi + rr * a.gi_stride + u;
+                    pr = gv[0] + ar; pz = gv[H] + az; pn = gv[2 * H];
+                }
+                const float r_ = 1.0f / (1.0f + expf(-pr));
+                const float z = 1.0f / (1.0f + expf(-pz));
+                const float n = tanhf(pn + r_ * (ahn + bhn));
+                a.out[rr * a.o_stride + a.o_off + u] = (1.0f - z) * n + z * hs[ss * Hg + j];
             }
         }
     }
@@ -327,7 +388,7 @@ __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restri
                                                             float* __restrict__ work, float* __restrict__ out) {
     extern __shared__ float sm[];
     const int s = blockIdx.x, m = mode[s];
-    if (m != CRUSE_STREAM_MODE_FRAME && m != CRUSE_STREAM_MODE_FRAME0 && m != CRUSE_STREAM_MODE_END) return;
+    if (!mode_computes_frame(m)) return;
     float* st = state + (size_t)s * L.st_stride;
     float* wk = work + (size_t)s * L.wk_stride;
     const int tid = threadIdx.x;
@@ -357,7 +418,7 @@ __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restri
     }
     __syncthreads();
     for (int k = 4; k >= 1; --k) {
-        dec_convt(w + L.decW[k], w + L.decB[k], row[k], row[k - 1], k > 1 ? wk + L.wk_skip[k - 1] : nullptr, L.ch[k], L.F[k],
+        dec_convt(w + L.decW[k], w + L.decB[k], row[k], row[k - 1], 0, k > 1 ? wk + L.wk_skip[k - 1] : nullptr, 0, 1, L.ch[k], L.F[k],
                   L.ch[k - 1], k > 1 ? 0 : 1);
         __syncthreads();
     }
@@ -369,17 +430,8 @@ __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restri
     }
     if (tid == 0) { re[F0] = 0.f; im[F0] = 0.f; }
     __syncthreads();
-    for (int n = tid; n < NFFT; n += blockDim.x) {
-        float acc = 0.f;
-        int j = n;
-        for (int k = 1; k < F0; ++k) {
-            acc = fmaf(re[k], tab[TB_COS + j], acc);
-            acc = fmaf(-im[k], tab[TB_SIN + j], acc);
-            j += n;
-            if (j >= NFFT) j -= NFFT;
-        }
-        y[n] = (re[0] + 2.0f * acc + ((n & 1) ? -re[F0] : re[F0])) * (1.0f / NFFT) * tab[TB_WIN + n];
-    }
+    for (int n = tid; n < NFFT; n += blockDim.x)
+        y[n] = irdft320(re, im, tab + TB_COS, n) * tab[TB_WIN + n];
     __syncthreads();
     // overlap-add with the stored tail, divide by the window envelope: output block; the second half becomes the tail
     for (int i = tid; i < HOP; i += blockDim.x) {
@@ -388,17 +440,28 @@ __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restri
     }
 }
 
-template <int KQ>
-int launch_gru(const int* mode, int S, int g, int Hg, const float* x, int xs, int xo, const float* lng, const float* lnb, float eps,
-               const float* hp, int hs, int ho, const float* pack, float* out, int os, int oo, int grid_x, hipStream_t st) {
-    const int H = g * Hg;
-    const size_t lds = (size_t)(SB * ((lng ? H : Hg) + Hg) + 2 * SB) * sizeof(float);
-    int rc = cruse_ensure_dyn_lds((const void*)stream_gru_kernel<KQ>, lds, "cruse_stream_gru");
+template <int KIND, int KQ>
+int launch(const GruArgs& a, const char* name, hipStream_t st) {
+    constexpr bool HAS_X = KIND != KIND_REC, HAS_H = KIND != KIND_PROJ;
+    // enough workgroups to cover the device, each keeping its unit's weights in registers across several row tiles
+    const int H = a.g * a.Hg, units = H / 4, ntiles = (a.R + SB - 1) / SB;
+    const int grid_x = std::max(1, std::min(ntiles, (2048 + units - 1) / units));
+    const size_t lds = (size_t)((HAS_X ? SB * (a.ln_g ? H : a.Hg) + 2 * SB : 0) + (HAS_H ? SB * a.Hg : 0)) * sizeof(float);
+    int rc = cruse_ensure_dyn_lds((const void*)stream_gru_f32_kernel<KIND, KQ>, lds, name);
     if (rc) return rc;
-    hipLaunchKernelGGL(stream_gru_kernel<KQ>, dim3(grid_x, H / 4), dim3(256), lds, st, mode, S, g, Hg, x, xs, xo, lng, lnb, eps, hp, hs,
-                       ho, pack, out, os, oo);
-    CRUSE_LAUNCH_CHECK("cruse_stream_gru");
+    hipLaunchKernelGGL((stream_gru_f32_kernel<KIND, KQ>), dim3(grid_x, units), dim3(256), lds, st, a);
+    CRUSE_LAUNCH_CHECK(name);
     return CRUSE_OK;
+}
+
+// KQ: the 64-lane slices of a group's row a lane holds in registers
+template <int KIND>
+int dispatch_kq(const GruArgs& a, const char* name, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (a.Hg <= 192) return launch<KIND, 3>(a, name, st);
+    if (a.Hg <= 320) return launch<KIND, 5>(a, name, st);
+    if (a.Hg <= 640) return launch<KIND, 10>(a, name, st);
+    return launch<KIND, 16>(a, name, st);
 }
 
 
@@ -409,23 +472,6 @@ int launch_gru(const int* mode, int S, int g, int Hg, const float* x, int xs, in
 // blocks slot s consumes; both live in device memory.  Frame f of slot s has its own work row, work[(s * work_frames + f) * WS],
 // WS = packet_work_stride().
 constexpr int PACKET_LDS_BYTES = 128 * 1024;
-
-struct Pkt {
-    int c;       // blocks consumed
-    int nf;      // frames computed
-    int f0;      // 1: the first frame is frame 0 of the clip (its output block is dropped)
-    int hist;    // 1: the stored block comes first in the sequence of blocks
-};
-
-__device__ __forceinline__ Pkt packet_of(const int* __restrict__ pk, int S, int s, int hops) {
-    const int start = min(max(pk[s], 0), 2), c = min(max(pk[S + s], 0), hops);
-    Pkt p;
-    p.c = c;
-    p.hist = start >= 1;
-    p.f0 = start <= 1;
-    p.nf = c == 0 ? 0 : start == 0 ? (c >= 2 ? c : 0) : start == 1 ? c + 1 : c;
-    return p;
-}
 
 int packet_row_max(const Layout& L) {
     int m = 2 * NB + 2;                                   // a masked spectrum (re | im) has to fit a row
@@ -458,71 +504,6 @@ int packet_work_stride(const Layout& L, int* eoff) {
 int packet_max_frames(const Layout& L) {
     const int avail = PACKET_LDS_BYTES / (int)sizeof(float) - packet_wcap(L) - packet_row_max(L) - 64;
     return avail <= 0 ? 0 : avail / (2 * packet_row_max(L));
-}
-
-// encoder conv over the frames of a packet, weights in LDS as [Cout][Cin*6 + 1] | bias[Cout]; row f-1 of frame 0 is `prev`
-__device__ void enc_conv_n(const float* Wl, const float* prev, const float* src, float* dst, int rowmax, int nf, int Cin, int Fin,
-                           int Cout, int Fout) {
-    const int ws = Cin * 6 + 1, per = Cout * Fout;
-    const float* bl = Wl + Cout * ws;
-    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
-        const int f = idx / per, r = idx - f * per, co = r / Fout, fo = r - co * Fout;
-        const float* pr = f == 0 ? prev : src + (f - 1) * rowmax;
-        const float* cu = src + f * rowmax;
-        float acc = bl[co];
-        for (int ci = 0; ci < Cin; ++ci) {
-            const float* w = Wl + co * ws + ci * 6;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int fi = 2 * fo - 1 + kw;
-                if (fi < 0 || fi >= Fin) continue;
-                acc = fmaf(w[kw], pr[ci * Fin + fi], acc);
-                acc = fmaf(w[3 + kw], cu[ci * Fin + fi], acc);
-            }
-        }
-        dst[f * rowmax + r] = fmaxf(acc, 0.f);
-    }
-}
-
-// skip conv over the frames of a packet, weights in LDS as [C][C*3 + 1]; frame f's result goes to its work row
-__device__ void skip_conv_n(const float* Wl, const float* src, float* wk, int wk_stride, int off, int rowmax, int nf, int C, int F) {
-    const int ws = C * 3 + 1, per = C * F;
-    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
-        const int f = idx / per, r = idx - f * per, co = r / F, fo = r - co * F;
-        const float* e = src + f * rowmax;
-        float acc = 0.f;
-        for (int ci = 0; ci < C; ++ci) {
-            const float* w = Wl + co * ws + ci * 3;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int fi = fo - 1 + kw;
-                if (fi >= 0 && fi < F) acc = fmaf(w[kw], e[ci * F + fi], acc);
-            }
-        }
-        wk[(size_t)f * wk_stride + off + r] = acc;
-    }
-}
-
-// transposed conv over the frames of a packet, weights in LDS as [Cin][Cout][3] | bias[Cout]; add: frame f's skip row (work)
-__device__ void dec_convt_n(const float* Wl, const float* src, float* dst, const float* wk, int wk_stride, int add_off, int rowmax,
-                            int nf, int Cin, int Fin, int Cout, int act) {
-    const int Fout = 2 * Fin, per = Cout * Fout;
-    const float* bl = Wl + Cin * Cout * 3;
-    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
-        const int f = idx / per, r = idx - f * per, co = r / Fout, fo = r - co * Fout;
-        const float* in = src + f * rowmax;
-        const int fi = fo >> 1;
-        float acc = bl[co];
-        if (fo & 1) {
-            for (int ci = 0; ci < Cin; ++ci) acc = fmaf(Wl[(ci * Cout + co) * 3 + 1], in[ci * Fin + fi], acc);
-        } else {
-            for (int ci = 0; ci < Cin; ++ci) {
-                acc = fmaf(Wl[(ci * Cout + co) * 3 + 0], in[ci * Fin + fi], acc);
-                if (fi >= 1) acc = fmaf(Wl[(ci * Cout + co) * 3 + 2], in[ci * Fin + fi - 1], acc);
-            }
-        }
-        dst[f * rowmax + r] = act == 0 ? fmaxf(acc, 0.f) + wk[(size_t)f * wk_stride + add_off + r] : 1.0f / (1.0f + expf(-acc));
-    }
 }
 
 __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __restrict__ pk, int S, int hops, int in_hops, int NFW,
@@ -576,15 +557,8 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
     // 320-point real DFT of every frame, bins 0..160; magnitude of bins 0..159
     for (int idx = tid; idx < nf * NB; idx += nt) {
         const int f = idx / NB, k = idx - f * NB;
-        const float* fr = B + f * rowmax;
-        float re = 0.f, im = 0.f;
-        int j = 0;
-        for (int n = 0; n < NFFT; ++n) {
-            re = fmaf(fr[n], Wb[j], re);
-            im = fmaf(-fr[n], Wb[NFFT + j], im);
-            j += k;
-            if (j >= NFFT) j -= NFFT;
-        }
+        float re, im;
+        rdft320(B + f * rowmax, Wb, k, re, im);
         wk[(size_t)f * WS + L.wk_re + k] = re;
         wk[(size_t)f * WS + L.wk_im + k] = im;
         if (k < F0) A[f * rowmax + k] = sqrtf(re * re + im * im + 1e-8f);
@@ -598,13 +572,13 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
         for (int i = tid; i < Cout * Cin * 6; i += nt) Wb[(i / (Cin * 6)) * (Cin * 6 + 1) + i % (Cin * 6)] = w[L.encW[k] + i];
         for (int i = tid; i < Cout; i += nt) Wb[Cout * (Cin * 6 + 1) + i] = w[L.encB[k] + i];
         __syncthreads();
-        enc_conv_n(Wb, P, src, dst, rowmax, nf, Cin, Fin, Cout, Fout);
+        enc_conv(Wb, Cin * 6 + 1, Wb + Cout * (Cin * 6 + 1), P, src, dst, rowmax, nf, Cin, Fin, Cout, Fout);
         __syncthreads();
         for (int i = tid; i < Cout * Cout * 3; i += nt) Wb[(i / (Cout * 3)) * (Cout * 3 + 1) + i % (Cout * 3)] = w[L.skW[k] + i];
         if (k < 4)
             for (int i = tid; i < per; i += nt) P[i] = st[L.st_prev[k] + i];
         __syncthreads();
-        skip_conv_n(Wb, dst, wk, WS, L.wk_skip[k], rowmax, nf, Cout, Fout);
+        skip_conv(Wb, Cout * 3 + 1, dst, rowmax, wk + L.wk_skip[k], WS, nf, Cout, Fout);
         if (k < 4)
             for (int i = tid; i < per; i += nt) st[L.st_prev[k] + i] = dst[(nf - 1) * rowmax + i];
         const int eo = k < 4 ? eoff[k] : L.wk_x;                           // e1..e3 of every frame; e4 is the GRU input row, c*F4+f
@@ -614,157 +588,6 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
         }
         __syncthreads();
         float* t = src; src = dst; dst = t;
-    }
-}
-
-// Input products of one GGRU layer for every frame of a packet: gi[(s * NFW + f) * 3H + c*H + u] = W_ih[c][u] . x + bias, with
-// b_ih + b_hh folded for the gates r and z and b_in for n.  Same workgroup shape as stream_gru_kernel (wave = one unit, its three
-// W_ih rows in registers, tiles of SB rows in LDS); a row is (slot, frame), rows behind a slot's last frame are not computed.
-template <int KQ>
-__global__ void __launch_bounds__(256) stream_gru_proj_n_kernel(const int* __restrict__ pk, int S, int hops, int NFW, int g, int Hg,
-                                                                const float* __restrict__ work, int wk_stride, int x_off,
-                                                                const float* __restrict__ ln_g, const float* __restrict__ ln_b,
-                                                                float ln_eps, const float* __restrict__ pack, float* __restrict__ gi) {
-    extern __shared__ float sm[];
-    const int H = g * Hg, NFC = hops + 1;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int u = blockIdx.y * 4 + wv;
-    const int gidx = u / Hg, j = u - gidx * Hg;
-    const bool ln = ln_g != nullptr;
-    const int xw = ln ? H : Hg;
-    float* xs = sm;                             // [SB][xw]
-    float* st = sm + SB * xw;                   // [SB][2] mean, rstd
-    const size_t gsz = (size_t)3 * Hg * Hg;
-    const float* Wih = pack + gidx * gsz;
-    const float* bih = pack + 2 * g * gsz + gidx * 3 * Hg;
-    const float* bhh = pack + 2 * g * gsz + g * 3 * Hg + gidx * 3 * Hg;
-    float wi[3][KQ], lg[KQ], lb[KQ];
-    int src[KQ];
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        const int k = lane + 64 * q;
-        const bool ok = k < Hg;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) wi[c][q] = ok ? Wih[(size_t)(c * Hg + j) * Hg + k] : 0.f;
-        const int p = gidx * Hg + k;
-        src[q] = ok ? (ln ? (p % g) * Hg + p / g : k) : 0;
-        lg[q] = (ln && ok) ? ln_g[p] : 0.f;
-        lb[q] = (ln && ok) ? ln_b[p] : 0.f;
-    }
-    const float br = bih[j] + bhh[j], bz = bih[Hg + j] + bhh[Hg + j], bin = bih[2 * Hg + j];
-    const int R = S * NFC, ntiles = (R + SB - 1) / SB;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int r0 = t * SB;
-        __syncthreads();
-        for (int i = threadIdx.x; i < SB * xw; i += blockDim.x) {
-            const int ss = i / xw, k = i - ss * xw, r = r0 + ss;
-            float v = 0.f;
-            if (r < R) {
-                const int s = r / NFC, f = r - s * NFC;
-                v = work[((size_t)s * NFW + f) * wk_stride + x_off + (ln ? 0 : gidx * Hg) + k];
-            }
-            xs[i] = v;
-        }
-        __syncthreads();
-        if (ln) {
-            for (int ss = wv; ss < SB; ss += 4) {
-                float a = 0.f;
-                for (int k = lane; k < H; k += 64) a += xs[ss * H + k];
-                const float mean = wave_sum(a) / H;
-                float v = 0.f;
-                for (int k = lane; k < H; k += 64) { const float d = xs[ss * H + k] - mean; v = fmaf(d, d, v); }
-                const float var = wave_sum(v) / H;
-                if (lane == 0) { st[2 * ss] = mean; st[2 * ss + 1] = 1.0f / sqrtf(var + ln_eps); }
-            }
-            __syncthreads();
-        }
-        for (int ss = 0; ss < SB; ++ss) {
-            const int r = r0 + ss;
-            if (r >= R) break;
-            const int s = r / NFC, f = r - s * NFC;
-            if (f >= packet_of(pk, S, s, hops).nf) continue;
-            float ar = 0.f, az = 0.f, an = 0.f;
-            const float mean = ln ? st[2 * ss] : 0.f, rstd = ln ? st[2 * ss + 1] : 0.f;
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                const int k = lane + 64 * q;
-                if (k >= Hg) continue;
-                float xv = xs[ss * xw + src[q]];
-                if (ln) xv = fmaf((xv - mean) * rstd, lg[q], lb[q]);
-                ar = fmaf(wi[0][q], xv, ar);
-                az = fmaf(wi[1][q], xv, az);
-                an = fmaf(wi[2][q], xv, an);
-            }
-            ar = wave_sum(ar); az = wave_sum(az); an = wave_sum(an);
-            if (lane == 0) {
-                float* o = gi + ((size_t)s * NFW + f) * 3 * H + u;
-                o[0] = ar + br;
-                o[H] = az + bz;
-                o[2 * H] = an + bin;
-            }
-        }
-    }
-}
-
-// One recurrent step (frame `frame` of the packet) of one GGRU layer for every slot that computes that frame: W_hh . h, gates,
-// new h into the frame's work row.  h comes from the state row for the packet's first frame, else from the previous frame's row.
-template <int KQ>
-__global__ void __launch_bounds__(256) stream_gru_rec_n_kernel(const int* __restrict__ pk, int S, int hops, int NFW, int frame, int g,
-                                                               int Hg, const float* __restrict__ gi, const float* __restrict__ state,
-                                                               int st_stride, int st_off, const float* __restrict__ pack,
-                                                               float* __restrict__ work, int wk_stride, int h_off) {
-    extern __shared__ float sm[];
-    const int H = g * Hg;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int u = blockIdx.y * 4 + wv;
-    const int gidx = u / Hg, j = u - gidx * Hg;
-    float* hs = sm;                             // [SB][Hg]
-    const size_t gsz = (size_t)3 * Hg * Hg;
-    const float* Whh = pack + g * gsz + gidx * gsz;
-    const float bhn = pack[2 * g * gsz + g * 3 * Hg + gidx * 3 * Hg + 2 * Hg + j];
-    float wh[3][KQ];
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        const int k = lane + 64 * q;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) wh[c][q] = k < Hg ? Whh[(size_t)(c * Hg + j) * Hg + k] : 0.f;
-    }
-    const int ntiles = (S + SB - 1) / SB;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int s0 = t * SB;
-        __syncthreads();
-        for (int i = threadIdx.x; i < SB * Hg; i += blockDim.x) {
-            const int ss = i / Hg, k = i - ss * Hg, s = s0 + ss;
-            float v = 0.f;
-            if (s < S)
-                v = frame == 0 ? state[(size_t)s * st_stride + st_off + gidx * Hg + k]
-                               : work[((size_t)s * NFW + frame - 1) * wk_stride + h_off + gidx * Hg + k];
-            hs[i] = v;
-        }
-        __syncthreads();
-        for (int ss = 0; ss < SB; ++ss) {
-            const int s = s0 + ss;
-            if (s >= S) break;
-            if (frame >= packet_of(pk, S, s, hops).nf) continue;
-            float ar = 0.f, az = 0.f, an = 0.f;
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                const int k = lane + 64 * q;
-                if (k >= Hg) continue;
-                const float hv = hs[ss * Hg + k];
-                ar = fmaf(wh[0][q], hv, ar);
-                az = fmaf(wh[1][q], hv, az);
-                an = fmaf(wh[2][q], hv, an);
-            }
-            ar = wave_sum(ar); az = wave_sum(az); an = wave_sum(an);
-            if (lane == 0) {
-                const float* gv = gi + ((size_t)s * NFW + frame) * 3 * H + u;
-                const float r = 1.0f / (1.0f + expf(-(gv[0] + ar)));
-                const float z = 1.0f / (1.0f + expf(-(gv[H] + az)));
-                const float n = tanhf(gv[2 * H] + r * (an + bhn));
-                work[((size_t)s * NFW + frame) * wk_stride + h_off + u] = (1.0f - z) * n + z * hs[ss * Hg + j];
-            }
-        }
     }
 }
 
@@ -815,7 +638,7 @@ __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __rest
         for (int i = tid; i < nwf; i += nt) Wb[i] = w[L.decW[k] + i];
         for (int i = tid; i < L.ch[k - 1]; i += nt) Wb[nwf + i] = w[L.decB[k] + i];
         __syncthreads();
-        dec_convt_n(Wb, src, dst, wk, WS, k > 1 ? L.wk_skip[k - 1] : 0, rowmax, nf, L.ch[k], L.F[k], L.ch[k - 1], k > 1 ? 0 : 1);
+        dec_convt(Wb, Wb + nwf, src, dst, rowmax, wk + (k > 1 ? L.wk_skip[k - 1] : 0), WS, nf, L.ch[k], L.F[k], L.ch[k - 1], k > 1 ? 0 : 1);
         __syncthreads();
         float* t = src; src = dst; dst = t;
     }
@@ -834,16 +657,7 @@ __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __rest
     for (int idx = tid; idx < nf * NFFT; idx += nt) {
         const int f = idx / NFFT, n = idx - f * NFFT;
         const float* re = dst + f * rowmax;
-        const float* im = re + NB;
-        float acc = 0.f;
-        int j = n;
-        for (int k = 1; k < F0; ++k) {
-            acc = fmaf(re[k], Wb[j], acc);
-            acc = fmaf(-im[k], Wb[NFFT + j], acc);
-            j += n;
-            if (j >= NFFT) j -= NFFT;
-        }
-        src[f * rowmax + n] = (re[0] + 2.0f * acc + ((n & 1) ? -re[F0] : re[F0])) * (1.0f / NFFT) * tab[TB_WIN + n];
+        src[f * rowmax + n] = irdft320(re, re + NB, Wb, n) * tab[TB_WIN + n];
     }
     __syncthreads();
     // overlap-add: a chain over the packet's frames (tail -> block -> new tail), division by the window envelope
@@ -858,34 +672,6 @@ __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __rest
         }
         st[L.st_tail + i] = tail;
     }
-}
-
-template <int KQ>
-int launch_gru_proj_n(const int* pk, int S, int hops, int NFW, int g, int Hg, const float* work, int wks, int xo, const float* lng,
-                      const float* lnb, float eps, const float* pack, float* gi, hipStream_t st) {
-    const int H = g * Hg, units = H / 4, ntiles = (S * (hops + 1) + SB - 1) / SB;
-    const int grid_x = std::max(1, std::min(ntiles, (2048 + units - 1) / units));
-    const size_t lds = (size_t)(SB * (lng ? H : Hg) + 2 * SB) * sizeof(float);
-    int rc = cruse_ensure_dyn_lds((const void*)stream_gru_proj_n_kernel<KQ>, lds, "cruse_stream_gru_proj_n");
-    if (rc) return rc;
-    hipLaunchKernelGGL(stream_gru_proj_n_kernel<KQ>, dim3(grid_x, units), dim3(256), lds, st, pk, S, hops, NFW, g, Hg, work, wks, xo, lng,
-                       lnb, eps, pack, gi);
-    CRUSE_LAUNCH_CHECK("cruse_stream_gru_proj_n");
-    return CRUSE_OK;
-}
-
-template <int KQ>
-int launch_gru_rec_n(const int* pk, int S, int hops, int NFW, int frame, int g, int Hg, const float* gi, const float* state, int sts,
-                     int sto, const float* pack, float* work, int wks, int ho, hipStream_t st) {
-    const int units = g * Hg / 4, ntiles = (S + SB - 1) / SB;
-    const int grid_x = std::max(1, std::min(ntiles, (2048 + units - 1) / units));
-    const size_t lds = (size_t)(SB * Hg) * sizeof(float);
-    int rc = cruse_ensure_dyn_lds((const void*)stream_gru_rec_n_kernel<KQ>, lds, "cruse_stream_gru_rec_n");
-    if (rc) return rc;
-    hipLaunchKernelGGL(stream_gru_rec_n_kernel<KQ>, dim3(grid_x, units), dim3(256), lds, st, pk, S, hops, NFW, frame, g, Hg, gi, state,
-                       sts, sto, pack, work, wks, ho);
-    CRUSE_LAUNCH_CHECK("cruse_stream_gru_rec_n");
-    return CRUSE_OK;
 }
 
 // shared argument checks of the packet entry points
@@ -951,19 +737,10 @@ extern "C" int cruse_stream_encode(const int* mode, int S, int c0, int c1, int c
 extern "C" int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg, const float* x, int x_stride, int x_off,
                                 const float* ln_g, const float* ln_b, float ln_eps, const float* hprev, int h_stride, int h_off,
                                 const float* pack, float* hout, int o_stride, int o_off, void* stream) {
-    CRUSE_REQUIRE(S > 0 && g > 0 && Hg > 0 && Hg % 4 == 0 && Hg <= 1024, CRUSE_E_SHAPE,
-                  "stream_gru: S = %d, g = %d, Hg = %d (need Hg %% 4 == 0, Hg <= 1024)", S, g, Hg);
-    CRUSE_REQUIRE(layer == 1 || layer == 2, CRUSE_E_SHAPE, "stream_gru: layer %d", layer);
-    CRUSE_REQUIRE(mode && x && hprev && pack && hout && (layer == 1 || (ln_g && ln_b)), CRUSE_E_SHAPE, "stream_gru: null buffer");
-    if (layer == 1) ln_g = ln_b = nullptr;
-    // enough workgroups to cover the device, each keeping its unit's weights in registers across several slot tiles
-    const int units = g * Hg / 4, ntiles = (S + SB - 1) / SB;
-    const int grid_x = std::max(1, std::min(ntiles, (2048 + units - 1) / units));
-    hipStream_t st = (hipStream_t)stream;
-    if (Hg <= 192) return launch_gru<3>(mode, S, g, Hg, x, x_stride, x_off, ln_g, ln_b, ln_eps, hprev, h_stride, h_off, pack, hout, o_stride, o_off, grid_x, st);
-    if (Hg <= 320) return launch_gru<5>(mode, S, g, Hg, x, x_stride, x_off, ln_g, ln_b, ln_eps, hprev, h_stride, h_off, pack, hout, o_stride, o_off, grid_x, st);
-    if (Hg <= 640) return launch_gru<10>(mode, S, g, Hg, x, x_stride, x_off, ln_g, ln_b, ln_eps, hprev, h_stride, h_off, pack, hout, o_stride, o_off, grid_x, st);
-    return launch_gru<16>(mode, S, g, Hg, x, x_stride, x_off, ln_g, ln_b, ln_eps, hprev, h_stride, h_off, pack, hout, o_stride, o_off, grid_x, st);
+    GruArgs a = {};
+    const int rc = gru_step_args("stream_gru", mode, S, layer, g, Hg, x, x_stride, x_off, ln_g, ln_b, ln_eps, hprev, h_stride, h_off, pack,
+                                 hout, o_stride, o_off, a);
+    return rc ? rc : dispatch_kq<KIND_STEP>(a, "cruse_stream_gru", stream);
 }
 
 extern "C" int cruse_stream_decode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
@@ -1018,37 +795,19 @@ extern "C" int cruse_stream_encode_n(const int* pk, int S, int hops, int in_hops
 extern "C" int cruse_stream_gru_proj_n(const int* pk, int S, int hops, int work_frames, int layer, int g, int Hg, const float* work,
                                        int wk_stride, int x_off, const float* ln_g, const float* ln_b, float ln_eps, const float* pack,
                                        float* gi, void* stream) {
-    CRUSE_REQUIRE(S > 0 && hops >= 1 && work_frames >= hops + 1 && g > 0 && Hg > 0 && Hg % 4 == 0 && Hg <= 1024, CRUSE_E_SHAPE,
-                  "stream_gru_proj_n: S = %d, hops = %d, work_frames = %d, g = %d, Hg = %d (need work_frames >= hops + 1, Hg %% 4 == 0, "
-                  "Hg <= 1024)", S, hops, work_frames, g, Hg);
-    CRUSE_REQUIRE(layer == 1 || layer == 2, CRUSE_E_SHAPE, "stream_gru_proj_n: layer %d", layer);
-    CRUSE_REQUIRE(x_off >= 0 && x_off + g * Hg <= wk_stride, CRUSE_E_SHAPE, "stream_gru_proj_n: x_off %d + %d floats outside a work row of %d",
-                  x_off, g * Hg, wk_stride);
-    CRUSE_REQUIRE(pk && work && pack && gi && (layer == 1 || (ln_g && ln_b)), CRUSE_E_SHAPE, "stream_gru_proj_n: null buffer");
-    if (layer == 1) ln_g = ln_b = nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (Hg <= 192) return launch_gru_proj_n<3>(pk, S, hops, work_frames, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps, pack, gi, st);
-    if (Hg <= 320) return launch_gru_proj_n<5>(pk, S, hops, work_frames, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps, pack, gi, st);
-    if (Hg <= 640) return launch_gru_proj_n<10>(pk, S, hops, work_frames, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps, pack, gi, st);
-    return launch_gru_proj_n<16>(pk, S, hops, work_frames, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps, pack, gi, st);
+    GruArgs a = {};
+    const int rc = gru_proj_args("stream_gru_proj_n", pk, S, hops, work_frames, layer, g, Hg, work, wk_stride, x_off, ln_g, ln_b, ln_eps,
+                                 pack, gi, a);
+    return rc ? rc : dispatch_kq<KIND_PROJ>(a, "cruse_stream_gru_proj_n", stream);
 }
 
 extern "C" int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_frames, int frame, int g, int Hg, const float* gi,
                                       const float* state, int st_stride, int st_off, const float* pack, float* work, int wk_stride,
                                       int h_off, void* stream) {
-    CRUSE_REQUIRE(S > 0 && hops >= 1 && work_frames >= hops + 1 && g > 0 && Hg > 0 && Hg % 4 == 0 && Hg <= 1024, CRUSE_E_SHAPE,
-                  "stream_gru_rec_n: S = %d, hops = %d, work_frames = %d, g = %d, Hg = %d (need work_frames >= hops + 1, Hg %% 4 == 0, "
-                  "Hg <= 1024)", S, hops, work_frames, g, Hg);
-    CRUSE_REQUIRE(frame >= 0 && frame <= hops, CRUSE_E_SHAPE, "stream_gru_rec_n: frame %d outside [0, %d]", frame, hops);
-    CRUSE_REQUIRE(st_off >= 0 && st_off + g * Hg <= st_stride && h_off >= 0 && h_off + g * Hg <= wk_stride, CRUSE_E_SHAPE,
-                  "stream_gru_rec_n: st_off %d / h_off %d + %d floats outside a state row of %d / work row of %d", st_off, h_off, g * Hg,
-                  st_stride, wk_stride);
-    CRUSE_REQUIRE(pk && gi && state && pack && work, CRUSE_E_SHAPE, "stream_gru_rec_n: null buffer");
-    hipStream_t st = (hipStream_t)stream;
-    if (Hg <= 192) return launch_gru_rec_n<3>(pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work, wk_stride, h_off, st);
-    if (Hg <= 320) return launch_gru_rec_n<5>(pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work, wk_stride, h_off, st);
-    if (Hg <= 640) return launch_gru_rec_n<10>(pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work, wk_stride, h_off, st);
-    return launch_gru_rec_n<16>(pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work, wk_stride, h_off, st);
+    GruArgs a = {};
+    const int rc = gru_rec_args("stream_gru_rec_n", pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work,
+                                wk_stride, h_off, a);
+    return rc ? rc : dispatch_kq<KIND_REC>(a, "cruse_stream_gru_rec_n", stream);
 }
 
 extern "C" int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,

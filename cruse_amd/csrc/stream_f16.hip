@@ -12,59 +12,19 @@
 // fragments from L2 for every pass over NT row tiles (holding them in registers across tiles is impossible at Hg = 640; a layer's
 // pack is 1.2 MB at the default shape and stays in L2).  Measurements: DESIGN 12b.
 #include <algorithm>
-#include "common.h"
+#include "stream_common.h"
 
 namespace {
 
-enum { KIND_STEP = 0, KIND_PROJ = 1, KIND_REC = 2 };
+using namespace cruse_stream;
+
 // workgroups of a launch before its columns stride over the row tiles (two per CU).  A first choice: not swept
 constexpr int GRID_WG = 512;
 
-struct Args {
-    const int* ctl;                 // STEP: mode[S]; PROJ / REC: pk[2][S]
-    int R, S, hops, NFW, frame;     // rows; PROJ: R = S * (hops + 1), row r is frame r % (hops + 1) of slot r / (hops + 1)
-    int g, Hg, Kp, UT;              // K padded to 32, unit tiles of 16
-    const float* x;                 // input rows: x + row * x_stride + x_off (STEP, PROJ)
-    long long x_stride;
-    int x_off;
-    const float* ln_g;              // LN1 over the interleaved input row (layer 2), or null
-    const float* ln_b;
-    float ln_eps;
-    const float* h;                 // previous h rows (STEP, REC)
-    long long h_stride;
-    int h_off;
-    const float* pack;              // f32 pack of the layer (biases)
+struct Args : GruArgs {
     const _Float16* pack16;
-    float* out;                     // new h rows (STEP, REC)
-    long long o_stride;
-    int o_off;
-    float* gi;                      // [.., 3H] input products: written by PROJ, read by REC
-    long long gi_stride;
+    int Kp, UT;                     // K padded to 32, unit tiles of 16
 };
-
-// frames a slot computes in a packet: the `nf` of packet_of() in stream.hip, restated (that file's kernels decide which frames encode /
-// decode produce; a change there must be made here too, or the f16 GRU and encode / decode disagree about which frames exist)
-__device__ __forceinline__ int pk_frames(const int* __restrict__ pk, int S, int s, int hops) {
-    const int start = min(max(pk[s], 0), 2), c = min(max(pk[S + s], 0), hops);
-    return c == 0 ? 0 : start == 0 ? (c >= 2 ? c : 0) : start == 1 ? c + 1 : c;
-}
-
-// does row r (< R) compute anything; rr: its index into the row arrays
-template <int KIND>
-__device__ __forceinline__ bool row_of(const Args& a, int r, long long& rr) {
-    if (KIND == KIND_STEP) {
-        rr = r;
-        const int m = a.ctl[r];
-        return m == CRUSE_STREAM_MODE_FRAME || m == CRUSE_STREAM_MODE_FRAME0 || m == CRUSE_STREAM_MODE_END;
-    }
-    if (KIND == KIND_PROJ) {
-        const int nfc = a.hops + 1, s = r / nfc, f = r - s * nfc;
-        rr = (long long)s * a.NFW + f;
-        return f < pk_frames(a.ctl, a.S, s, a.hops);
-    }
-    rr = r;
-    return a.frame < pk_frames(a.ctl, a.S, r, a.hops);
-}
 
 template <int KIND, int NT>
 __global__ void __launch_bounds__(256) stream_gru_f16_kernel(Args a) {
@@ -242,7 +202,9 @@ int launch(const Args& a, const char* name, hipStream_t st) {
 // at Kp = 1024.  Both are ABOVE 64 KB: they rely on the 160 KB of LDS per CU of gfx950 (cruse_ensure_dyn_lds raises the limit) and leave
 // two workgroups per CU by LDS; a 64 KB part needs other thresholds.  The thresholds (R > 16, Kp <= 512) are first choices, not swept.
 template <int KIND>
-int dispatch(Args& a, const char* name, hipStream_t st) {
+int dispatch(Args& a, const void* pack16, const char* name, hipStream_t st) {
+    CRUSE_REQUIRE(pack16, CRUSE_E_SHAPE, "%s: null pack16", name);
+    a.pack16 = (const _Float16*)pack16;
     a.Kp = (a.Hg + 31) & ~31;
     a.UT = (a.Hg + 15) / 16;
     if (a.R > 16 && a.Kp <= 512) return launch<KIND, 2>(a, name, st);
@@ -254,64 +216,26 @@ int dispatch(Args& a, const char* name, hipStream_t st) {
 extern "C" int cruse_stream_gru_f16(const int* mode, int S, int layer, int g, int Hg, const float* x, int x_stride, int x_off,
                                     const float* ln_g, const float* ln_b, float ln_eps, const float* hprev, int h_stride, int h_off,
                                     const float* pack, const void* pack16, float* hout, int o_stride, int o_off, void* stream) {
-    CRUSE_REQUIRE(S > 0 && g > 0 && Hg > 0 && Hg % 4 == 0 && Hg <= 1024, CRUSE_E_SHAPE,
-                  "stream_gru_f16: S = %d, g = %d, Hg = %d (need S >= 1, Hg %% 4 == 0, Hg <= 1024)", S, g, Hg);
-    CRUSE_REQUIRE(layer == 1 || layer == 2, CRUSE_E_SHAPE, "stream_gru_f16: layer %d", layer);
-    CRUSE_REQUIRE(x_off >= 0 && x_off + g * Hg <= x_stride && h_off >= 0 && h_off + g * Hg <= h_stride && o_off >= 0 &&
-                  o_off + g * Hg <= o_stride, CRUSE_E_SHAPE,
-                  "stream_gru_f16: x_off %d / h_off %d / o_off %d + %d floats outside rows of %d / %d / %d", x_off, h_off, o_off, g * Hg,
-                  x_stride, h_stride, o_stride);
-    CRUSE_REQUIRE(mode && x && hprev && pack && pack16 && hout && (layer == 1 || (ln_g && ln_b)), CRUSE_E_SHAPE,
-                  "stream_gru_f16: null buffer");
     Args a = {};
-    a.ctl = mode; a.R = S; a.S = S; a.g = g; a.Hg = Hg;
-    a.x = x; a.x_stride = x_stride; a.x_off = x_off;
-    a.ln_g = layer == 2 ? ln_g : nullptr; a.ln_b = layer == 2 ? ln_b : nullptr; a.ln_eps = ln_eps;
-    a.h = hprev; a.h_stride = h_stride; a.h_off = h_off;
-    a.pack = pack; a.pack16 = (const _Float16*)pack16;
-    a.out = hout; a.o_stride = o_stride; a.o_off = o_off;
-    return dispatch<KIND_STEP>(a, "cruse_stream_gru_f16", (hipStream_t)stream);
+    const int rc = gru_step_args("stream_gru_f16", mode, S, layer, g, Hg, x, x_stride, x_off, ln_g, ln_b, ln_eps, hprev, h_stride, h_off,
+                                 pack, hout, o_stride, o_off, a);
+    return rc ? rc : dispatch<KIND_STEP>(a, pack16, "cruse_stream_gru_f16", (hipStream_t)stream);
 }
 
 extern "C" int cruse_stream_gru_proj_n_f16(const int* pk, int S, int hops, int work_frames, int layer, int g, int Hg, const float* work,
                                            int wk_stride, int x_off, const float* ln_g, const float* ln_b, float ln_eps, const float* pack,
                                            const void* pack16, float* gi, void* stream) {
-    CRUSE_REQUIRE(S > 0 && hops >= 1 && work_frames >= hops + 1 && g > 0 && Hg > 0 && Hg % 4 == 0 && Hg <= 1024, CRUSE_E_SHAPE,
-                  "stream_gru_proj_n_f16: S = %d, hops = %d, work_frames = %d, g = %d, Hg = %d (need S >= 1, work_frames >= hops + 1, "
-                  "Hg %% 4 == 0, Hg <= 1024)", S, hops, work_frames, g, Hg);
-    CRUSE_REQUIRE(layer == 1 || layer == 2, CRUSE_E_SHAPE, "stream_gru_proj_n_f16: layer %d", layer);
-    CRUSE_REQUIRE(x_off >= 0 && x_off + g * Hg <= wk_stride, CRUSE_E_SHAPE,
-                  "stream_gru_proj_n_f16: x_off %d + %d floats outside a work row of %d", x_off, g * Hg, wk_stride);
-    CRUSE_REQUIRE((long long)S * (hops + 1) <= 0x7fffffffLL, CRUSE_E_SHAPE, "stream_gru_proj_n_f16: S * (hops + 1) overflows");
-    CRUSE_REQUIRE(pk && work && pack && pack16 && gi && (layer == 1 || (ln_g && ln_b)), CRUSE_E_SHAPE,
-                  "stream_gru_proj_n_f16: null buffer");
     Args a = {};
-    a.ctl = pk; a.R = S * (hops + 1); a.S = S; a.hops = hops; a.NFW = work_frames; a.g = g; a.Hg = Hg;
-    a.x = work; a.x_stride = wk_stride; a.x_off = x_off;
-    a.ln_g = layer == 2 ? ln_g : nullptr; a.ln_b = layer == 2 ? ln_b : nullptr; a.ln_eps = ln_eps;
-    a.pack = pack; a.pack16 = (const _Float16*)pack16;
-    a.gi = gi; a.gi_stride = (long long)3 * g * Hg;
-    return dispatch<KIND_PROJ>(a, "cruse_stream_gru_proj_n_f16", (hipStream_t)stream);
+    const int rc = gru_proj_args("stream_gru_proj_n_f16", pk, S, hops, work_frames, layer, g, Hg, work, wk_stride, x_off, ln_g, ln_b,
+                                 ln_eps, pack, gi, a);
+    return rc ? rc : dispatch<KIND_PROJ>(a, pack16, "cruse_stream_gru_proj_n_f16", (hipStream_t)stream);
 }
 
 extern "C" int cruse_stream_gru_rec_n_f16(const int* pk, int S, int hops, int work_frames, int frame, int g, int Hg, const float* gi,
                                           const float* state, int st_stride, int st_off, const float* pack, const void* pack16,
                                           float* work, int wk_stride, int h_off, void* stream) {
-    CRUSE_REQUIRE(S > 0 && hops >= 1 && work_frames >= hops + 1 && g > 0 && Hg > 0 && Hg % 4 == 0 && Hg <= 1024, CRUSE_E_SHAPE,
-                  "stream_gru_rec_n_f16: S = %d, hops = %d, work_frames = %d, g = %d, Hg = %d (need S >= 1, work_frames >= hops + 1, "
-                  "Hg %% 4 == 0, Hg <= 1024)", S, hops, work_frames, g, Hg);
-    CRUSE_REQUIRE(frame >= 0 && frame <= hops, CRUSE_E_SHAPE, "stream_gru_rec_n_f16: frame %d outside [0, %d]", frame, hops);
-    CRUSE_REQUIRE(st_off >= 0 && st_off + g * Hg <= st_stride && h_off >= 0 && h_off + g * Hg <= wk_stride, CRUSE_E_SHAPE,
-                  "stream_gru_rec_n_f16: st_off %d / h_off %d + %d floats outside a state row of %d / work row of %d", st_off, h_off,
-                  g * Hg, st_stride, wk_stride);
-    CRUSE_REQUIRE(pk && gi && state && pack && pack16 && work, CRUSE_E_SHAPE, "stream_gru_rec_n_f16: null buffer");
     Args a = {};
-    a.ctl = pk; a.R = S; a.S = S; a.hops = hops; a.NFW = work_frames; a.frame = frame; a.g = g; a.Hg = Hg;
-    const long long slot = (long long)work_frames * wk_stride;       // floats between two slots' work rows of one frame
-    if (frame == 0) { a.h = state; a.h_stride = st_stride; a.h_off = st_off; }
-    else { a.h = work + (size_t)(frame - 1) * wk_stride; a.h_stride = slot; a.h_off = h_off; }
-    a.pack = pack; a.pack16 = (const _Float16*)pack16;
-    a.out = work + (size_t)frame * wk_stride; a.o_stride = slot; a.o_off = h_off;
-    a.gi = const_cast<float*>(gi) + (size_t)frame * 3 * g * Hg; a.gi_stride = (long long)work_frames * 3 * g * Hg;
-    return dispatch<KIND_REC>(a, "cruse_stream_gru_rec_n_f16", (hipStream_t)stream);
+    const int rc = gru_rec_args("stream_gru_rec_n_f16", pk, S, hops, work_frames, frame, g, Hg, gi, state, st_stride, st_off, pack, work,
+                                wk_stride, h_off, a);
+    return rc ? rc : dispatch<KIND_REC>(a, pack16, "cruse_stream_gru_rec_n_f16", (hipStream_t)stream);
 }

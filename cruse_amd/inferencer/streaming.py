@@ -162,40 +162,37 @@ class StreamingInferencer:
                 self.gru_pack2_f16.copy_(packs16[1])
             else:
                 self.gru_pack1_f16, self.gru_pack2_f16 = packs16
+        # the two GRU layers of a chain: (layer, x_off, st_off, h_off, pack, pack16 or None, LN1 kwargs)
+        ln1 = lambda n: self.w[lay[n]:lay[n] + self.H]
+        self._layers = ((1, lay["wk_x"], lay["st_h1"], lay["wk_h1n"], self.gru_pack1, getattr(self, "gru_pack1_f16", None), {}),
+                        (2, lay["wk_h1n"], lay["st_h2"], lay["wk_h2n"], self.gru_pack2, getattr(self, "gru_pack2_f16", None),
+                         dict(ln_g=ln1("ln1g"), ln_b=ln1("ln1b"), ln_eps=self.ln1_eps)))
 
     # -- the hop ----------------------------------------------------------------------------------------------------------
     def _chain(self, row: int) -> None:
-        mode, lay, g, Hg = self.mode[row], self.lay, self.g, self.Hg
+        mode, g, Hg = self.mode[row], self.g, self.Hg
         ops.stream_encode(mode, self.ch, self.blocks, self.tab, self.w, self.state, self.work)
-        if self.precision == "f16":
-            ln1 = dict(ln_g=self.w[lay["ln1g"]:lay["ln1g"] + self.H], ln_b=self.w[lay["ln1b"]:lay["ln1b"] + self.H], ln_eps=self.ln1_eps)
-            ops.stream_gru_f16(mode, 1, g, Hg, self.work, lay["wk_x"], self.state, lay["st_h1"], self.gru_pack1, self.gru_pack1_f16,
-                               self.work, lay["wk_h1n"])
-            ops.stream_gru_f16(mode, 2, g, Hg, self.work, lay["wk_h1n"], self.state, lay["st_h2"], self.gru_pack2, self.gru_pack2_f16,
-                               self.work, lay["wk_h2n"], **ln1)
-            ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out)
-            return
-        ops.stream_gru(mode, 1, g, Hg, self.work, lay["wk_x"], self.state, lay["st_h1"], self.gru_pack1, self.work, lay["wk_h1n"])
-        ops.stream_gru(mode, 2, g, Hg, self.work, lay["wk_h1n"], self.state, lay["st_h2"], self.gru_pack2, self.work, lay["wk_h2n"],
-                       ln_g=self.w[lay["ln1g"]:lay["ln1g"] + self.H], ln_b=self.w[lay["ln1b"]:lay["ln1b"] + self.H],
-                       ln_eps=self.ln1_eps)
+        for layer, x_off, st_off, h_off, pack, pack16, ln1 in self._layers:
+            ops.stream_gru(mode, layer, g, Hg, self.work, x_off, self.state, st_off, pack, self.work, h_off, pack16=pack16, **ln1)
         ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out)
 
-    def _launch(self, passes: int) -> None:
-        rows = (0, 1) if passes == 2 else (1,)
+    def _replay(self, key, fn) -> None:
+        """run fn(): directly, or as the graph captured from it on the first call with this key"""
         if not self.use_graph:
-            for r in rows:
-                self._chain(r)
+            fn()
             return
-        gr = self._graphs.get(passes)
+        gr = self._graphs.get(key)
         if gr is None:
             torch.cuda.synchronize(self.device)
             gr = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gr):
-                for r in rows:
-                    self._chain(r)
-            self._graphs[passes] = gr
+                fn()
+            self._graphs[key] = gr
         gr.replay()
+
+    def _launch(self, passes: int) -> None:
+        rows = (0, 1) if passes == 2 else (1,)
+        self._replay(passes, lambda: [self._chain(r) for r in rows])
 
     def _run(self, m0: np.ndarray, m1: np.ndarray) -> None:
         if self._host_free is not None:
@@ -265,42 +262,15 @@ class StreamingInferencer:
     # -- packets ----------------------------------------------------------------------------------------------------------
     def _packet_chain(self, hops: int, nf: int) -> None:
         """One linear chain for packets of up to `hops` blocks of which the longest slot computes `nf` frames."""
-        pk, lay, g, Hg, H, wk = self.pk, self.lay, self.g, self.Hg, self.H, self.pwork
+        pk, g, Hg, wk = self.pk, self.g, self.Hg, self.pwork
         ops.stream_encode_n(pk, hops, self.ch, self.pblocks, self.tab, self.w, self.state, wk)
         if nf == 0:                                                             # nothing but first blocks to store
             return
-        if self.precision == "f16":
-            ln1 = dict(ln_g=self.w[lay["ln1g"]:lay["ln1g"] + H], ln_b=self.w[lay["ln1b"]:lay["ln1b"] + H], ln_eps=self.ln1_eps)
-            for layer, x_off, st_off, h_off, pack, pack16, kw in (
-                    (1, lay["wk_x"], lay["st_h1"], lay["wk_h1n"], self.gru_pack1, self.gru_pack1_f16, {}),
-                    (2, lay["wk_h1n"], lay["st_h2"], lay["wk_h2n"], self.gru_pack2, self.gru_pack2_f16, ln1)):
-                ops.stream_gru_proj_n_f16(pk, hops, layer, g, Hg, wk, x_off, pack, pack16, self.gi, **kw)
-                for f in range(nf):
-                    ops.stream_gru_rec_n_f16(pk, hops, f, g, Hg, self.gi, self.state, st_off, pack, pack16, wk, h_off)
-            ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout)
-            return
-        ops.stream_gru_proj_n(pk, hops, 1, g, Hg, wk, lay["wk_x"], self.gru_pack1, self.gi)
-        for f in range(nf):
-            ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, lay["st_h1"], self.gru_pack1, wk, lay["wk_h1n"])
-        ops.stream_gru_proj_n(pk, hops, 2, g, Hg, wk, lay["wk_h1n"], self.gru_pack2, self.gi,
-                              ln_g=self.w[lay["ln1g"]:lay["ln1g"] + H], ln_b=self.w[lay["ln1b"]:lay["ln1b"] + H], ln_eps=self.ln1_eps)
-        for f in range(nf):
-            ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, lay["st_h2"], self.gru_pack2, wk, lay["wk_h2n"])
+        for layer, x_off, st_off, h_off, pack, pack16, ln1 in self._layers:
+            ops.stream_gru_proj_n(pk, hops, layer, g, Hg, wk, x_off, pack, self.gi, pack16=pack16, **ln1)
+            for f in range(nf):
+                ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, st_off, pack, wk, h_off, pack16=pack16)
         ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout)
-
-    def _launch_packet(self, hops: int, nf: int) -> None:
-        if not self.use_graph:
-            self._packet_chain(hops, nf)
-            return
-        key = ("packet", hops, nf)
-        gr = self._graphs.get(key)
-        if gr is None:
-            torch.cuda.synchronize(self.device)
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr):
-                self._packet_chain(hops, nf)
-            self._graphs[key] = gr
-        gr.replay()
 
     @torch.no_grad()
     def push_packet(self, blocks: torch.Tensor, counts=None):
@@ -349,7 +319,8 @@ class StreamingInferencer:
         act = cnt > 0
         self._last_frames[act] = frames[act]
         self._last_f0[act] = np.array([p.first_frame == 0 for p in plans])[act]
-        self._launch_packet(hops, int(frames.max()))
+        nf = int(frames.max())
+        self._replay(("packet", hops, nf), lambda: self._packet_chain(hops, nf))
         return self.pout[:, :K].clone(), torch.from_numpy(n_out)
 
     @torch.no_grad()
@@ -402,22 +373,13 @@ class StreamingInferencer:
             if not -nfr <= frame < nfr:
                 raise ValueError(f"stage: frame {frame} outside the {nfr} frames of slot {slot}'s last packet")
             f = frame % nfr
-            wk = self.pwork[slot, f]
-            out = {"re": wk[lay["wk_re"]:lay["wk_re"] + 161], "im": wk[lay["wk_im"]:lay["wk_im"] + 161],
-                   "gru1": wk[lay["wk_h1n"]:lay["wk_h1n"] + self.H], "gru2": wk[lay["wk_h2n"]:lay["wk_h2n"] + self.H],
-                   "mask": wk[lay["wk_mask"]:lay["wk_mask"] + 160], "e4": wk[lay["wk_x"]:lay["wk_x"] + self.H]}
-            for k in range(1, 5):
-                n = ch[k] * F[k]
-                out[f"skip{k}"] = wk[lay[f"wk_skip{k}"]:lay[f"wk_skip{k}"] + n]
-                if k < 4:
-                    out[f"e{k}"] = wk[self.play[f"wk_e{k}"]:self.play[f"wk_e{k}"] + n]
-            first = int(self._last_f0[slot])                                    # frame 0 of a clip yields no output block
-            if f - first >= 0:
-                out["block"] = self.pout[slot, f - first]
-            return out
-        if frame not in (-1, 0):
-            raise ValueError(f"stage: slot {slot}'s last call computed one frame, frame {frame} does not exist")
-        wk, st = self.work[slot], self.state[slot]
+            wk = e = self.pwork[slot, f]                                        # a packet keeps e1..e3 in the frame's work row
+            eoff = {k: self.play[f"wk_e{k}"] for k in range(1, 4)}
+        else:
+            if frame not in (-1, 0):
+                raise ValueError(f"stage: slot {slot}'s last call computed one frame, frame {frame} does not exist")
+            wk, e = self.work[slot], self.state[slot]                           # a single hop in the state rows only
+            eoff = {k: lay[f"st_prev{k}"] for k in range(1, 4)}
         out = {"re": wk[lay["wk_re"]:lay["wk_re"] + 161], "im": wk[lay["wk_im"]:lay["wk_im"] + 161],
                "gru1": wk[lay["wk_h1n"]:lay["wk_h1n"] + self.H], "gru2": wk[lay["wk_h2n"]:lay["wk_h2n"] + self.H],
                "mask": wk[lay["wk_mask"]:lay["wk_mask"] + 160], "e4": wk[lay["wk_x"]:lay["wk_x"] + self.H]}
@@ -425,5 +387,9 @@ class StreamingInferencer:
             n = ch[k] * F[k]
             out[f"skip{k}"] = wk[lay[f"wk_skip{k}"]:lay[f"wk_skip{k}"] + n]
             if k < 4:
-                out[f"e{k}"] = st[lay[f"st_prev{k}"]:lay[f"st_prev{k}"] + n]
+                out[f"e{k}"] = e[eoff[k]:eoff[k] + n]
+        if nfr > 0:
+            first = int(self._last_f0[slot])                                    # frame 0 of a clip yields no output block
+            if f - first >= 0:
+                out["block"] = self.pout[slot, f - first]
         return out

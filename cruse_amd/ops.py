@@ -1067,10 +1067,18 @@ def stream_encode(mode, ch, blocks, tab, w, state, work) -> None:
                                   _stream()))
 
 
-def stream_gru(mode, layer, groups, Hg, x, x_off, hprev, h_off, pack, hout, o_off, ln_g=None, ln_b=None, ln_eps=1e-5) -> None:
-    """x / hprev / hout are [S, stride] row tensors read / written at the given float offsets."""
-    check(lib.cruse_stream_gru(_p(mode), mode.numel(), layer, groups, Hg, _p(x), x.shape[1], x_off, _p(ln_g), _p(ln_b), float(ln_eps),
-                               _p(hprev), hprev.shape[1], h_off, _p(pack), _p(hout), hout.shape[1], o_off, _stream()))
+def _f16_args(name, pack16):
+    """the f32 entry point `name`, or its f16-operand twin with pack16 after `pack` in its parameter list"""
+    return (getattr(lib, name), ()) if pack16 is None else (getattr(lib, name + "_f16"), (_p(pack16),))
+
+
+def stream_gru(mode, layer, groups, Hg, x, x_off, hprev, h_off, pack, hout, o_off, ln_g=None, ln_b=None, ln_eps=1e-5, pack16=None) -> None:
+    """One GGRU layer, one step, for every slot whose mode computes a frame; layer 2 applies LN1 (ln_g, ln_b) to layer 1's row.
+    x / hprev / hout are [S, stride] row tensors read / written at the given float offsets.  pack16 (stream_pack_f16): run the
+    f16-operand MFMA kernel; `pack` (f32) still supplies the biases."""
+    fn, p16 = _f16_args("cruse_stream_gru", pack16)
+    check(fn(_p(mode), mode.numel(), layer, groups, Hg, _p(x), x.shape[1], x_off, _p(ln_g), _p(ln_b), float(ln_eps), _p(hprev),
+             hprev.shape[1], h_off, _p(pack), *p16, _p(hout), hout.shape[1], o_off, _stream()))
 
 
 def stream_decode(mode, ch, tab, w, ln_eps, state, work, out) -> None:
@@ -1093,15 +1101,17 @@ def stream_encode_n(pk, hops, ch, blocks, tab, w, state, work) -> None:
                                     _p(tab), _p(w), _p(state), _p(work), _stream()))
 
 
-def stream_gru_proj_n(pk, hops, layer, groups, Hg, work, x_off, pack, gi, ln_g=None, ln_b=None, ln_eps=1e-5) -> None:
-    """gi [S, work_frames, 3H] <- the layer's input products of every frame's work row at float offset x_off."""
-    check(lib.cruse_stream_gru_proj_n(_p(pk), pk.shape[1], int(hops), work.shape[1], layer, groups, Hg, _p(work), work.shape[2], x_off,
-                                      _p(ln_g), _p(ln_b), float(ln_eps), _p(pack), _p(gi), _stream()))
+def stream_gru_proj_n(pk, hops, layer, groups, Hg, work, x_off, pack, gi, ln_g=None, ln_b=None, ln_eps=1e-5, pack16=None) -> None:
+    """gi [S, work_frames, 3H] (f32) <- the layer's input products of every frame's work row at float offset x_off"""
+    fn, p16 = _f16_args("cruse_stream_gru_proj_n", pack16)
+    check(fn(_p(pk), pk.shape[1], int(hops), work.shape[1], layer, groups, Hg, _p(work), work.shape[2], x_off, _p(ln_g), _p(ln_b),
+             float(ln_eps), _p(pack), *p16, _p(gi), _stream()))
 
 
-def stream_gru_rec_n(pk, hops, frame, groups, Hg, gi, state, st_off, pack, work, h_off) -> None:
-    check(lib.cruse_stream_gru_rec_n(_p(pk), pk.shape[1], int(hops), work.shape[1], int(frame), groups, Hg, _p(gi), _p(state),
-                                     state.shape[1], st_off, _p(pack), _p(work), work.shape[2], h_off, _stream()))
+def stream_gru_rec_n(pk, hops, frame, groups, Hg, gi, state, st_off, pack, work, h_off, pack16=None) -> None:
+    fn, p16 = _f16_args("cruse_stream_gru_rec_n", pack16)
+    check(fn(_p(pk), pk.shape[1], int(hops), work.shape[1], int(frame), groups, Hg, _p(gi), _p(state), state.shape[1], st_off, _p(pack),
+             *p16, _p(work), work.shape[2], h_off, _stream()))
 
 
 def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out) -> None:
@@ -1109,8 +1119,7 @@ def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out) -> None:
                                     float(ln_eps), _p(state), _p(work), _p(out), _stream()))
 
 
-# f16-operand MFMA GRU of the streaming chains (cruse_stream_gru*_f16): same rows and arguments as stream_gru / _gru_proj_n / _gru_rec_n,
-# plus the layer's fragment-ordered f16 weights; `pack` (f32) still supplies the biases
+# the layer's fragment-ordered f16 weights for the f16-operand MFMA GRU (the pack16 argument of stream_gru / _gru_proj_n / _gru_rec_n)
 def stream_pack_f16(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
     """W_ih, W_hh [g, 3*Hg, Hg] (any float dtype / device) -> the flat f16 pack16 of the header, on the inputs' device:
     [ih | hh][g][gate][UT][KS][lane][8], units padded to 16 and K to 32 with zeros."""
@@ -1123,20 +1132,3 @@ def stream_pack_f16(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
     # unit = ut*16 + r, k = ks*32 + q*8 + j, lane = q*16 + r
     p = p.reshape(2, g, 3, UT, 16, KS, 4, 8).permute(0, 1, 2, 3, 5, 6, 4, 7)
     return p.contiguous().reshape(-1).to(torch.float16)
-
-
-def stream_gru_f16(mode, layer, groups, Hg, x, x_off, hprev, h_off, pack, pack16, hout, o_off, ln_g=None, ln_b=None, ln_eps=1e-5) -> None:
-    """one GGRU layer, one step, for every slot whose mode computes a frame; layer 2 applies LN1 (ln_g, ln_b) to layer 1's row"""
-    check(lib.cruse_stream_gru_f16(_p(mode), mode.numel(), layer, groups, Hg, _p(x), x.shape[1], x_off, _p(ln_g), _p(ln_b), float(ln_eps),
-                                   _p(hprev), hprev.shape[1], h_off, _p(pack), _p(pack16), _p(hout), hout.shape[1], o_off, _stream()))
-
-
-def stream_gru_proj_n_f16(pk, hops, layer, groups, Hg, work, x_off, pack, pack16, gi, ln_g=None, ln_b=None, ln_eps=1e-5) -> None:
-    """gi [S, frames, 3H] (f32) <- the input products of one GGRU layer for every frame of the packet"""
-    check(lib.cruse_stream_gru_proj_n_f16(_p(pk), pk.shape[1], int(hops), work.shape[1], layer, groups, Hg, _p(work), work.shape[2], x_off,
-                                          _p(ln_g), _p(ln_b), float(ln_eps), _p(pack), _p(pack16), _p(gi), _stream()))
-
-
-def stream_gru_rec_n_f16(pk, hops, frame, groups, Hg, gi, state, st_off, pack, pack16, work, h_off) -> None:
-    check(lib.cruse_stream_gru_rec_n_f16(_p(pk), pk.shape[1], int(hops), work.shape[1], int(frame), groups, Hg, _p(gi), _p(state),
-                                         state.shape[1], st_off, _p(pack), _p(pack16), _p(work), work.shape[2], h_off, _stream()))

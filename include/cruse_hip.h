@@ -764,7 +764,8 @@ int cruse_stream_encode(const int* mode, int S, int c0, int c1, int c2, int c3, 
  * b_hn inside r*(.).  pack = W_ih [g][3Hg][Hg] | W_hh [g][3Hg][Hg] | b_ih [g][3Hg] | b_hh [g][3Hg].  Slot s reads
  * x[s*x_stride + x_off + ...] and hprev[s*h_stride + h_off + i*Hg + j], writes hout[s*o_stride + o_off + i*Hg + j].  layer 1:
  * group i reads x chunk i.  layer 2: x is layer 1's output row (group-contiguous); LN1 (ln_g, ln_b, ln_eps) is applied to its
- * interleaved view v[j*g+i] (cruse_net.py:43-46) and group i reads chunk i of LN1(v) */
+ * interleaved view v[j*g+i] (cruse_net.py:43-46) and group i reads chunk i of LN1(v).  Refused with CRUSE_E_SHAPE before any launch:
+ * S < 1, g < 1, Hg % 4 != 0, Hg > 1024, and x_off / h_off / o_off < 0 or + g*Hg beyond x_stride / h_stride / o_stride */
 int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg, const float* x, int x_stride, int x_off,
                      const float* ln_g, const float* ln_b, float ln_eps, const float* hprev, int h_stride, int h_off,
                      const float* pack, float* hout, int o_stride, int o_off, void* stream);
@@ -794,12 +795,15 @@ int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4, int* out)
 int cruse_stream_encode_n(const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                           const float* in, const float* tab, const float* w, float* state, float* work, void* stream);
 /* input products of one GGRU layer (pack as cruse_stream_gru) for every (slot, frame): gi[(s * work_frames + f) * 3H + c*H + u] =
- * W_ih[c][u] . x + b_ih (+ b_hh for c = r, z), x = the frame's work row at x_off (layer 2: LN1 of its interleaved view first) */
+ * W_ih[c][u] . x + b_ih (+ b_hh for c = r, z), x = the frame's work row at x_off (layer 2: LN1 of its interleaved view first).
+ * Refused with CRUSE_E_SHAPE: the shapes cruse_stream_gru refuses, hops < 1, work_frames < hops + 1, x_off + g*Hg beyond wk_stride,
+ * S * (hops + 1) beyond INT_MAX */
 int cruse_stream_gru_proj_n(const int* pk, int S, int hops, int work_frames, int layer, int g, int Hg, const float* work,
                             int wk_stride, int x_off, const float* ln_g, const float* ln_b, float ln_eps, const float* pack,
                             float* gi, void* stream);
 /* recurrent step `frame` of that layer for every slot with frame < nf: h' from gi, W_hh . h and b_hn into the frame's work row at
- * h_off; h is the state row at st_off for frame 0, the previous frame's work row else */
+ * h_off; h is the state row at st_off for frame 0, the previous frame's work row else.  Refused with CRUSE_E_SHAPE: as gru_proj_n, frame
+ * outside [0, hops], st_off + g*Hg beyond st_stride, h_off + g*Hg beyond wk_stride */
 int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_frames, int frame, int g, int Hg, const float* gi,
                            const float* state, int st_stride, int st_off, const float* pack, float* work, int wk_stride, int h_off,
                            void* stream);
@@ -815,7 +819,7 @@ int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work
  * ceil(Hg / 16) unit tiles, KS = ceil(Hg / 32) k steps; lane l of (ut, ks) holds W[gate][ut*16 + (l & 15)][ks*32 + (l >> 4)*8 + 0..7],
  * zero where the unit or k is >= Hg.  Rounded to f16: the operand copies of x (after LN1 in layer 2), of h and the weights; accumulation,
  * biases (read from `pack`), LN1 statistics, gates and every row written are f32, and the gates read h_prev in f32.
- * Same refusals as the f32 entry points (S >= 1, Hg % 4 == 0, Hg <= 1024), before any launch. */
+ * The refusals are those of the f32 entry point of the same kind (one check serves both), plus a null pack16; all before any launch. */
 /* cruse_stream_gru on v_mfma_f32_16x16x32_f16: one GGRU layer (model/cruse_net.py:22-50), one time step */
 int cruse_stream_gru_f16(const int* mode, int S, int layer, int g, int Hg, const float* x, int x_stride, int x_off,
                          const float* ln_g, const float* ln_b, float ln_eps, const float* hprev, int h_stride, int h_off,

@@ -1,8 +1,8 @@
 """Test-only: the shape matrix of the streaming kernels (cruse_stream_*), shared by tests/test_stream_host.py (CPU pins of the
 reference at these shapes), tests/test_gpu_stream_shapes.py and tools/guard_stream_steps.py.
 
-The three GRU kernels of cruse_amd/csrc/stream.hip are templates on KQ, the number of 64-lane slices of a group's row a lane holds in
-registers; kq_of restates the dispatchers' thresholds.  Every row names what it is there for:
+The f32 GRU kernel of cruse_amd/csrc/stream.hip (step, packet projection, packet recurrent step) is a template on KQ, the number of 64-lane
+slices of a group's row a lane holds in registers; kq_of restates the dispatcher's thresholds.  Every row names what it is there for:
   KQ 3 / 5 / 10 / 16 each at a width that is not a multiple of 64 (a partly masked slice) and at its upper edge, Hg < 64 (one wave
   holds a whole row), odd channel counts (layout padding, odd LDS row strides), g = 3 and 5, the widest rows the layout accepts,
   and a model whose packet bound is small enough to run packets at exactly that bound.

@@ -347,6 +347,28 @@ def test_refusals():
     assert float(buf.abs().sum()) == 0.0                                    # nothing was launched
 
 
+def test_offsets_that_leave_a_row_are_refused():
+    """f32 and f16 forms alike: S = 1, g = 1, Hg = 4 in rows of 8 floats; an offset of 6 leaves the row"""
+    from cruse_amd import _lib
+    lib = _lib.lib
+    buf = torch.zeros(1 << 12, device="cuda")
+    ctl = torch.zeros(64, device="cuda", dtype=torch.int32)
+    p16 = torch.zeros(1 << 12, device="cuda", dtype=torch.float16)
+    f, i, h = buf.data_ptr(), ctl.data_ptr(), p16.data_ptr()
+    for p16_arg, who in (((), b"stream_gru"), ((h,), b"stream_gru_f16")):
+        step = lib.cruse_stream_gru_f16 if p16_arg else lib.cruse_stream_gru
+        rec = lib.cruse_stream_gru_rec_n_f16 if p16_arg else lib.cruse_stream_gru_rec_n
+        for x_off, h_off, o_off in ((6, 0, 0), (0, 6, 0), (0, 0, 6)):
+            rc = step(i, 1, 1, 1, 4, f, 8, x_off, None, None, 1e-5, f, 8, h_off, f, *p16_arg, f, 8, o_off, None)
+            msg = lib.cruse_last_error()
+            assert rc == -1 and who + b":" in msg and b"outside rows of 8 / 8 / 8" in msg, (who, x_off, h_off, o_off, rc, msg)
+        rc = rec(i, 1, 1, 2, 0, 1, 4, f, f, 8, 0, f, *p16_arg, f, 8, 6, None)          # h_off past the work row
+        msg = lib.cruse_last_error()
+        assert rc == -1 and who.replace(b"gru", b"gru_rec_n") + b":" in msg and b"outside a state row of 8 / work row of 8" in msg, (who, rc, msg)
+    torch.cuda.synchronize()
+    assert float(buf.abs().sum()) == 0.0                                    # refused before any launch
+
+
 # ---- 8. bounds --------------------------------------------------------------------------------------------------------------------------
 def test_f16_chains_under_the_guard_allocator():
     """tools/engine_guard_run.py tools/guard_stream_f16.py, once, in a subprocess under a time limit: the f16 chains at one and three slots
