@@ -27,6 +27,12 @@
 //     elementwise kernel from dh (cruse_gru_gate_grads).
 //   * all workgroups of a launch must be co-resident: grid <= number of CUs
 //     (one 256-thread workgroup per CU); larger batches are split into launches.
+//
+// Kernels of this file: gru_fwd_kernel / gru_bwd_kernel<PREC, NKW> (generic: every precision and width),
+// gru_fwd_lean_kernel<NKW, FULL, WLO, TIMED, TF, GIH> and gru_bwd_rs_kernel<NP, FULL, TIMED> (bf16, chains of 8, Hg <= 640).
+// gru_tf.hip and gru_w16.hip hold the tag-free and the wide-chain kernels.  Which of them a call runs is decided in ONE place,
+// select_route() below: it fills a Route (plan, kernel family, panel size, first-poll delay, who writes dgi) that the launch loop,
+// cruse_gru_plan and cruse_gru_seq_bwd_ex read; the workspace size follows from the same per-family panel-size function.
 #include "common.h"
 #include "gru_common.h"
 
@@ -34,6 +40,10 @@ namespace {
 
 using namespace cruse_gru;
 
+// threads per workgroup, for __launch_bounds__ and for the launch: four compute waves plus the helper / loader wave -- which the lean
+// forward kernel drops where two weight planes of Hg > 384 leave no registers for a fifth wave
+constexpr int lean_threads(bool wlo, int nkw) { return (wlo && nkw > 3) ? 256 : 320; }
+constexpr int RS_THREADS = 320;
 
 template <int PREC>
 __device__ __forceinline__ void store_coef(void* base, long long off, float2 v) {
@@ -234,7 +244,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(GruArgs a) {
 //     masks); block-wide agreement comes from the panel barrier that is needed anyway;
 //   * the k-loop is fully unrolled (NKW = Hg/128 k-steps per wave, all valid).
 // ---------------------------------------------------------------------------------
-// NKW = ceil(Hg/32 / 4) k-steps per wave, NS = ceil(Hg/128) sweep slots per thread; FULL: Hg % 128 == 0, every k-step
+// NKW = ceil(Hg/128) k-steps per wave (= sweep slots per thread of the tagged hand-off); FULL: Hg % 128 == 0, every k-step
 // of every wave exists (the guards below then vanish at compile time -- as run-time tests they cost the bench shape
 // 0.9 us per step: the compiler no longer overlaps the fragment reads of one k-step with the MFMAs of the previous)
 // WLO: W_hh is carried as TWO bf16 planes (hi + lo, ~2^-17 relative) and every k-step issues a second MFMA with the low
@@ -254,25 +264,23 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(GruArgs a) {
 // the publish latency hidden under the load's way out.)
 // TIMED (profiling, library option gru_dbg = 32 at Hg = 640): s_memtime stamps at the four phase boundaries of a step, summed by
 // workgroup (chain 0, part 0) into the status header (tools/gru_probe.py prints them).
-// GIB: the gi rows are bf16 (a compile-time variant: the f32 instances stay instruction for instruction what they were -- this
-// kernel sits at the 256-register edge, and a run-time switch in the helper wave moved spills into the compute waves' step loop:
-// 2.2 us per step instead of 1.39).
-// TF: the TAG-FREE hand-off of gru_tf.hip (the epoch bit inside every published bf16, half the sweep and publish bytes: 3 instead of
-// 5 sweep loads per thread at Hg = 640) under this kernel's K-split step -- at Hg = 640 the K-split-free step of gru_fwd_tf_kernel
-// measured slower (1.36 against 1.27 us per step), the hand-off alone pays.  Needs h0 == NULL (|h| < 1).
-// RD (with TF): REGISTER-DIRECT sweep -- no LDS image of the panel.  A wave sweeps exactly the 16-byte chunks that ARE its MFMA B fragments
-// (its k-steps wv + 4 i of every clip: NKW loads per lane) and checks its own tags; the panel is laid out CLIP-MINOR ([k chunk of 8][clip][8])
-// so that the 8 clips of one (k-step, lane group) are one 128-byte line and a load instruction is 512 contiguous bytes.  The panel barrier
-// stays (the helper wave's hand-over point), the image write, the wait for it and the fragment reads go.
-// GIH (with GIB, round 6): the 2-byte gi rows are IEEE f16, not bf16 (written by cruse_gemm_nt_out16; 11 significant bits: the enhanced spectrum
-// at T = 401 moves 4.10e-4 -> 4.25e-4 / 2.81e-4 -> 2.81e-4, where bf16 rows leave the G6 fixture's bar) -- the helper wave widens with v_cvt_f32_f16.
-template <int NKW, int NS, bool FULL, bool WLO, bool TIMED = false, bool GIB = false, bool TF = false, bool RD = false, bool GIH = false>
-__global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_kernel(GruArgs a) {
-    static_assert(!GIH || GIB, "f16 gi rows use the 2-byte row geometry of the bf16 form");
-    static_assert(!TF || FULL, "tag-free sweeps are built for Hg % 128 == 0");
-    static_assert(!RD || (TF && !WLO), "register-direct sweep: tag-free hand-off");
-    constexpr int NSW = TF ? (NKW * 128 + 255) / 256 : NS;      // sweep slots per thread
-    constexpr bool HW = !(WLO && NKW > 3);
+// TF: the TAG-FREE hand-off of gru_tf.hip (the epoch bit inside every published bf16, half the sweep and publish bytes) under this kernel's
+// K-split step -- at Hg = 640 the K-split-free step of gru_fwd_tf_kernel measured slower (1.36 against 1.27 us per step), the hand-off alone
+// pays.  Needs h0 == NULL (|h| < 1).  Its sweep is REGISTER-DIRECT -- no LDS image of the panel: a wave sweeps exactly the 16-byte chunks that ARE
+// its MFMA B fragments (its k-steps wv + 4 i of every clip, two k-steps per load: ceil(NKW / 2) loads per lane) and checks its own tags; the
+// panel is laid out CLIP-MINOR ([k chunk of 8][clip][8]) so that the 8 clips of one (k-step, lane group) are one 128-byte line and a load
+// instruction is 512 contiguous bytes.  The panel barrier stays (the helper wave's hand-over point), the image write, the wait for it and the
+// fragment reads go.  (A tag-free sweep through the LDS image was the first form; it went when this one measured faster.)
+// GIH (with TF, round 6): the gi rows are IEEE f16 (written by cruse_gemm_nt_out16; 11 significant bits: the enhanced spectrum at T = 401 moves
+// 4.10e-4 -> 4.25e-4 / 2.81e-4 -> 2.81e-4, where bf16 rows left the G6 fixture's bar) -- the helper wave widens with v_cvt_f32_f16.  A
+// compile-time variant: the f32 instances stay instruction for instruction what they were -- this kernel sits at the 256-register edge, and
+// a run-time switch in the helper wave moved spills into the compute waves' step loop: 2.2 us per step instead of 1.39.
+// Built instances: <1..5, FULL, WLO> for every width up to 640; <5, true, false, TIMED> with and without TF; <5, true, false, false, TF, GIH>.
+template <int NKW, bool FULL, bool WLO, bool TIMED = false, bool TF = false, bool GIH = false>
+__global__ __launch_bounds__(lean_threads(WLO, NKW)) void gru_fwd_lean_kernel(GruArgs a) {
+    static_assert(!TF || (FULL && !WLO), "tag-free register-direct sweep: Hg % 128 == 0, one weight plane");
+    static_assert(!GIH || TF, "f16 gi rows are built for the tag-free kernel only");
+    constexpr bool HW = lean_threads(WLO, NKW) == 320;
     unsigned long long tph[5] = {0, 0, 0, 0, 0}, tq0 = 0, tq1 = 0;
     (void)tph; (void)tq0; (void)tq1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -300,8 +308,8 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
     const long long nrow = (long long)(a.B - 1) * a.TS + a.T;           // rows reachable from the (advanced) base pointers
     const unsigned tot_h = (unsigned)min(nrow * H * 4, 0xffffffffll);
     const unsigned tot_g = (unsigned)min(nrow * a.G * 3 * Hg * 4, 0xffffffffll);
-    constexpr bool gib = GIB;                                           // bf16 gi rows: the coefficient rows' geometry
-    const __amdgpu_buffer_rsrc_t rs_gi = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.gi), 0, gib ? tot_g >> 1 : tot_g, 0x00020000);
+    // (f16 gi rows: the coefficient rows' geometry)
+    const __amdgpu_buffer_rsrc_t rs_gi = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.gi), 0, GIH ? tot_g >> 1 : tot_g, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(a.h, 0, tot_h, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_an = __builtin_amdgcn_make_buffer_rsrc(a.an, 0, a.an ? tot_h : 0u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(a.z, 0, a.z ? tot_h : 0u, 0x00020000);
@@ -331,10 +339,10 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
             cv[i2] = (unsigned)((((long long)(b0 + (cl < nb ? cl : 0)) * a.TS * a.G + grp) * 3 * Hg + gate * Hg + u0 + 8 * chk) * 2);
             csrc[i2] = (unsigned)(((1 + gate) * 8 + cl) * 32 + chk * 8);
         }
-        // bf16 gi: 8 clips x 3 gates x 4 chunks of 8 bf16 = 96 lane-loads per step (the coefficient rows' lane map, cv[] below),
+        // f16 gi: 8 clips x 3 gates x 4 chunks of 8 halves = 96 lane-loads per step (the coefficient rows' lane map, cv[] above),
         // widened to the same f32 ring
         unsigned gdb[2] = {0u, 0u};
-        if constexpr (gib) {
+        if constexpr (GIH) {
 #pragma unroll
             for (int i2 = 0; i2 < 2; ++i2) {
                 const int idx = min(lane + 64 * i2, 95), cl = idx / 12, rem = idx % 12, gate = rem >> 2, chk = rem & 3;
@@ -343,7 +351,7 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
         }
         struct GiSet { u32x4 v[3]; };
         auto issue = [&](int t, GiSet& o) {
-            if constexpr (gib) {
+            if constexpr (GIH) {
                 const unsigned so = (unsigned)min(t, a.T - 1) * crow_bytes;
                 o.v[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_gi, cv[0], so, 0);
                 if (lane < 32) o.v[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_gi, cv[1], so, 0);
@@ -355,22 +363,15 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
         };
         auto put = [&](int t, const GiSet& o) {
             float* d = &gi_r[t & 3][0][0];
-            if constexpr (gib) {
+            if constexpr (GIH) {
+                auto lo16 = [](unsigned x) -> float { return (float)__builtin_bit_cast(_Float16, (unsigned short)(x & 0xffffu)); };
+                auto hi16 = [](unsigned x) -> float { return (float)__builtin_bit_cast(_Float16, (unsigned short)(x >> 16)); };
 #pragma unroll
                 for (int i2 = 0; i2 < 2; ++i2) {
                     if (i2 == 1 && lane >= 32) break;
                     const u32x4 w = o.v[i2];
-                    if constexpr (GIH) {
-                        auto lo16 = [](unsigned x) -> float { return (float)__builtin_bit_cast(_Float16, (unsigned short)(x & 0xffffu)); };
-                        auto hi16 = [](unsigned x) -> float { return (float)__builtin_bit_cast(_Float16, (unsigned short)(x >> 16)); };
-                        *reinterpret_cast<float4*>(d + gdb[i2]) = make_float4(lo16(w.x), hi16(w.x), lo16(w.y), hi16(w.y));
-                        *reinterpret_cast<float4*>(d + gdb[i2] + 4) = make_float4(lo16(w.z), hi16(w.z), lo16(w.w), hi16(w.w));
-                        continue;
-                    }
-                    const u32x4 lo = {w.x << 16, w.x & 0xffff0000u, w.y << 16, w.y & 0xffff0000u};
-                    const u32x4 hi = {w.z << 16, w.z & 0xffff0000u, w.w << 16, w.w & 0xffff0000u};
-                    *reinterpret_cast<u32x4*>(d + gdb[i2]) = lo;
-                    *reinterpret_cast<u32x4*>(d + gdb[i2] + 4) = hi;
+                    *reinterpret_cast<float4*>(d + gdb[i2]) = make_float4(lo16(w.x), hi16(w.x), lo16(w.y), hi16(w.y));
+                    *reinterpret_cast<float4*>(d + gdb[i2] + 4) = make_float4(lo16(w.z), hi16(w.z), lo16(w.w), hi16(w.w));
                 }
                 return;
             }
@@ -409,7 +410,7 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
         // step t: two barriers (t > 0).  The gi set for step t + 2 goes to its ring slot, the set is re-issued for step
         // t + 4; the saves of step t - 1 are in LDS once the first barrier of step t has passed.
         const bool h0_step = a.h0 != nullptr;              // step 0 then runs its MFMA phase too (two barriers like any other)
-        // (RD: the panel barrier stays although nothing is shared through it any more -- it is the helper wave's hand-over point.  With
+        // (TF: the panel barrier stays although nothing is shared through it any more -- it is the helper wave's hand-over point.  With
         //  per-wave "sweep done" flags in LDS instead, the helper started only after the LAST wave's sweep and became the long pole of the
         //  second barrier: 1.25 against 1.18 us per step.)
         for (int t = 0; t < a.T; t += 2) {
@@ -445,16 +446,15 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
         }
     }
 
-    // sweep slots: load e = tid + 256*j covers clip e / (Hg/4), units 4*(e % (Hg/4)) ..+3 (clamped for short chains:
-    // the last valid granule is then fetched and stored twice)
-    // (TF: a 16-byte load carries 8 values)
-    const int per = TF ? Hg >> 3 : Hg >> 2, nload = nb * per;
-    unsigned sw_v[NSW];
-    int sw_l[NSW];
+    // sweep slots of the tagged hand-off (NKW per thread): load e = tid + 256*j covers clip e / (Hg/4), units 4*(e % (Hg/4)) ..+3
+    // (clamped for short chains: the last valid granule is then fetched and stored twice)
+    const int per = Hg >> 2, nload = nb * per;
+    unsigned sw_v[NKW];
+    int sw_l[NKW];
 #pragma unroll
-    for (int j = 0; j < NSW; ++j) {
+    for (int j = 0; j < NKW; ++j) {
         const int e = min(tid + 256 * j, nload - 1);
-        const int bl = e / per, v = (TF ? 8 : 4) * (e - bl * per);
+        const int bl = e / per, v = 4 * (e - bl * per);
         sw_v[j] = (unsigned)e * 16u;
         sw_l[j] = bl * LD + v;
     }
@@ -471,8 +471,8 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
     const unsigned own_v = (unsigned)(((long long)(b0 + blc) * a.TS * H + grp * Hg + u0 + u) * 4);                    // + t*frame_bytes
     const unsigned g_v = (unsigned)((((long long)(b0 + blc) * a.TS * a.G + grp) * 3 * Hg + u0 + u) * 4);               // + t*grow_bytes
     const unsigned hg4 = (unsigned)Hg * 4u;
-    const unsigned pub_v = RD ? (unsigned)(((((u0 + u) >> 3) * 8 + bl) * 8 + (u & 7)) * 2) : (unsigned)((bl * Hg + u0 + u) >> 1) * (TF ? 4u : 8u);
-    const unsigned rd_v = (unsigned)(((wv * 4 + (lane >> 4)) * 8 + (lane & 7)) * 16);         // RD: + i * 2048 bytes = k-step wv + 4 i
+    const unsigned pub_v = TF ? (unsigned)(((((u0 + u) >> 3) * 8 + bl) * 8 + (u & 7)) * 2) : (unsigned)((bl * Hg + u0 + u) >> 1) * 8u;
+    const unsigned rd_v = (unsigned)(((wv * 4 + (lane >> 4)) * 8 + (lane & 7)) * 16);         // TF: + i * 2048 bytes = k-step wv + 4 i
     const unsigned rd_v2 = rd_v + (((lane >> 3) & 1) ? 2048u : 0u);                           // (columns 8..15: the odd k-step of a pair)
     const bool rd_ok = (lane & 7) < nb;
     const bool pub_lane = act && !(u & 1);
@@ -483,7 +483,7 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
     if (!TF && has_h0) {                                   // the panel of step 0 is the initial state (bf16, like any h_{t-1})
         __syncthreads();                                   // (the zero fill above)
 #pragma unroll
-        for (int j = 0; j < NS && j < NSW; ++j) {
+        for (int j = 0; j < NKW; ++j) {
             const int e = min(tid + 256 * j, nload - 1);
             const int bl_ = e / per, v = 4 * (e - bl_ * per);
             const float4 hv = *reinterpret_cast<const float4*>(a.h0 + (long long)(b0 + bl_) * a.h0_bs + grp * Hg + v);
@@ -492,9 +492,8 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
         }
         if (act) hp = a.h0[(long long)(b0 + bl) * a.h0_bs + grp * Hg + u0 + u];
     }
-    auto ldgi = [&](int g, unsigned so) -> float {        // one gi value of this thread's (clip, unit): f32, or bf16 widened
+    auto ldgi = [&](int g, unsigned so) -> float {        // one gi value of this thread's (clip, unit): f32, or f16 widened
         if constexpr (GIH) return (float)__builtin_bit_cast(_Float16, (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs_gi, (g_v + g * hg4) >> 1, so >> 1, 0));
-        if constexpr (gib) return __uint_as_float((unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rs_gi, (g_v + g * hg4) >> 1, so >> 1, 0) << 16);
         return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_gi, g_v + g * hg4, so, 0));
     };
     if constexpr (!HW) {
@@ -511,9 +510,9 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
 
     for (int t = 0; t < a.T; ++t) {
         if constexpr (TIMED) tq0 = __builtin_amdgcn_s_memtime();
-        constexpr int NLR = RD ? (NKW + 1) / 2 : 1;       // RD: two k-steps per load -- columns 8..15 of the MFMA fetch the odd one (gru_bwd_ag_kernel)
+        constexpr int NLR = TF ? (NKW + 1) / 2 : 1;       // TF: two k-steps per load -- columns 8..15 of the MFMA fetch the odd one (gru_bwd_ag_kernel)
         u32x4 gr[NLR];
-        if (RD && t > 0) {
+        if (TF && t > 0) {
             const unsigned soff = cbase + (unsigned)((t - 1) & 1) * panel_bytes;
             const bool expect1 = tag_bit((unsigned)t) != 0u;
             unsigned spins = 0;
@@ -544,28 +543,20 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
             }
             if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[0] += tq1 - tq0; tq0 = tq1; }
         }
-        if (!RD && t > 0) {
+        if (!TF && t > 0) {
             const unsigned soff = cbase + (unsigned)((t - 1) & 1) * panel_bytes;
-            u32x4 g[NSW];
+            u32x4 g[NKW];
             unsigned spins = 0;
-            const unsigned flip = tag_bit((unsigned)t) ? 0xffffffffu : 0u;
             for (;;) {
 #pragma unroll
-                for (int j = 0; j < NSW; ++j) g[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, sw_v[j], soff, 16);
-                for (int rep = 0; rep < a.xsweep; ++rep) {      // profiling (gru_xsweep): the sweep volume of an all-gather backward
+                for (int j = 0; j < NKW; ++j) g[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, sw_v[j], soff, 16);
+                for (int rep = 0; rep < a.xsweep; ++rep) {      // profiling (a.xsweep): the sweep volume of an all-gather backward
 #pragma unroll
-                    for (int j = 0; j < NSW; ++j) { const u32x4 gx = __builtin_amdgcn_raw_buffer_load_b128(rs, sw_v[j], soff, 16); xsink ^= gx.x ^ gx.w; }
+                    for (int j = 0; j < NKW; ++j) { const u32x4 gx = __builtin_amdgcn_raw_buffer_load_b128(rs, sw_v[j], soff, 16); xsink ^= gx.x ^ gx.w; }
                 }
                 bool ok = true;
-                if constexpr (TF) {
-                    unsigned bad = 0u;
 #pragma unroll
-                    for (int j = 0; j < NSW; ++j) bad |= (g[j].x ^ flip) | (g[j].y ^ flip) | (g[j].z ^ flip) | (g[j].w ^ flip);
-                    ok = (bad & TAGM) == 0u;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < NSW; ++j) ok = ok & (g[j].x == (unsigned)t) & (g[j].z == (unsigned)t);
-                }
+                for (int j = 0; j < NKW; ++j) ok = ok & (g[j].x == (unsigned)t) & (g[j].z == (unsigned)t);
                 if (__all(ok || nowait)) break;
                 if (++spins >= SPIN_LIMIT) {
                     if (lane == 0) __hip_atomic_store(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -576,14 +567,9 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
             }
             if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[0] += tq1 - tq0; tq0 = tq1; }
 #pragma unroll
-            for (int j = 0; j < NSW; ++j) {
-                if constexpr (TF) {
-                    const u32x4 w = {g[j].x & ~TAGM, g[j].y & ~TAGM, g[j].z & ~TAGM, g[j].w & ~TAGM};
-                    *reinterpret_cast<u32x4*>(hB + sw_l[j]) = w;
-                } else {
-                    const u32x2 w = {g[j].y, g[j].w};               // already bf16 pairs: the LDS image as is
-                    *reinterpret_cast<u32x2*>(hB + sw_l[j]) = w;
-                }
+            for (int j = 0; j < NKW; ++j) {
+                const u32x2 w = {g[j].y, g[j].w};               // already bf16 pairs: the LDS image as is
+                *reinterpret_cast<u32x2*>(hB + sw_l[j]) = w;
             }
             // saves of step t-1: issued after the sweep has returned, old by the time of the next one
             // (helper-wave variants: the helper writes them from LDS)
@@ -609,7 +595,7 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
         }
         float gh[3] = {bias[0], bias[1], bias[2]};
         if (t > 0 || has_h0) {
-            __syncthreads();                               // panel complete (RD: the helper wave's hand-over point)
+            __syncthreads();                               // panel complete (TF: the helper wave's hand-over point)
             if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[1] += tq1 - tq0; tq0 = tq1; }
             f32x4 acc[6];
 #pragma unroll
@@ -618,8 +604,8 @@ __global__ __launch_bounds__((WLO && NKW > 3) ? 256 : 320) void gru_fwd_lean_ker
             for (int i = 0; i < NKW; ++i) {
                 if (FULL || wv + 4 * i < KS) {              // wave-uniform
                     bf16x8 fb;
-                    if constexpr (RD) {
-                        const u32x4 gg = gr[RD ? (i >> 1) : 0];
+                    if constexpr (TF) {
+                        const u32x4 gg = gr[i >> 1];
                         u32x4 w = {gg.x & ~TAGM, gg.y & ~TAGM, gg.z & ~TAGM, gg.w & ~TAGM};
                         if (i & 1) { w.x = dpp_ror8(w.x); w.y = dpp_ror8(w.y); w.z = dpp_ror8(w.z); w.w = dpp_ror8(w.w); }     // columns 8..15 -> 0..7
                         fb = __builtin_bit_cast(bf16x8, w);
@@ -863,7 +849,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(GruArgs a) {
 // np + 1's MFMAs before pair np is converted and stored; four accumulators in rotation; compiling the step loop twice instead
 // of choosing plain / write-through stores by two scalar branches per store; delaying the first poll by 64-384 cycles.
 template <int NP, bool FULL, bool TIMED = false>
-__global__ __launch_bounds__(320) void gru_bwd_rs_kernel(GruArgs a) {
+__global__ __launch_bounds__(RS_THREADS) void gru_bwd_rs_kernel(GruArgs a) {
     unsigned long long tph[5] = {0, 0, 0, 0, 0}, tq0 = 0, tq1 = 0;
     (void)tph; (void)tq0; (void)tq1;
     constexpr int KP = 96 + 8;                   // panel row stride (bf16): 208 B, de-phases the 16 rows of a b128 read
@@ -1292,14 +1278,12 @@ int num_cus() {
     return cached;
 }
 
-struct Plan { int Bg, P, nbg, bg_per_launch, nlaunch; bool wide; };
-
 }  // namespace
 namespace cruse_gru {       // gru_tf.hip: the tag-free hand-off kernels (bf16, chains of 8, Hg in {160, 320, 640})
-bool fwd_tf_eligible(int Bg, int Hg, int prec, bool has_h0, bool gi_bf16);
+bool fwd_tf_eligible(int Bg, int Hg, int prec, bool has_h0, bool gi_f16);
 bool bwd_tf_eligible(int Bg, int Hg, int prec);
 int dispatch_fwd_tf(const GruArgs& a, int grid, bool wlo, hipStream_t s);
-int dispatch_bwd_tf(const GruArgs& a, int grid, hipStream_t s);
+int dispatch_bwd_ag(const GruArgs& a, int grid, hipStream_t s);
 // gru_w16.hip: wide chains (16 clips), tag-free register-direct hand-off, epochs continuing across time chunks
 bool w16_eligible(int Hg, int prec);
 size_t w16_panel_bytes_per_parity(int Hg, bool fwd);
@@ -1308,57 +1292,41 @@ int dispatch_bwd_w16(const GruArgs& a, int grid, hipStream_t s);
 }
 namespace {
 
-bool bwd_rs_eligible(int Bg, int Hg, int prec);
-bool fwd_lean_eligible(int Bg, int Hg, int prec);
+// ---------------------------------------------------------------------------------
+// ROUTE: everything a call decides about which kernel runs and on what panels -- computed once per call (select_route); the launch
+// loop, cruse_gru_plan and the gate-gradient follow-up read it.
+// ---------------------------------------------------------------------------------
+enum Family {
+    FAM_GENERIC,            // gru_fwd_kernel / gru_bwd_kernel<PREC>: every precision and width, chains of 8 or 16
+    FAM_LEAN,               // forward, bf16, chains of 8, Hg <= 640: gru_fwd_lean_kernel on the tagged hand-off
+    FAM_LEAN_TF,            //   ... Hg = 640, h0 = NULL, one weight plane: the same step on the tag-free register-direct hand-off
+    FAM_TF,                 //   ... Hg = 160 / 320, h0 = NULL: gru_fwd_tf_kernel (gru_tf.hip)
+    FAM_RS,                 // backward, bf16, chains of 8, Hg <= 640: gru_bwd_rs_kernel
+    FAM_AG,                 //   ... Hg = 160 / 320 / 640: gru_bwd_ag_kernel (gru_tf.hip)
+    FAM_W16                 // wide chains, either direction (gru_w16.hip)
+};
+struct Route {
+    int Bg, P, nbg, bg_per_launch, nlaunch; bool wide;     // the plan (cruse_gru_plan)
+    bool fwd;
+    Family fam;
+    bool wlo;               // forward bf16 kernels: W_hh as two bf16 planes
+    size_t gpp;             // hand-off granules (8 bytes) per parity and chain
+    int poll_delay;         // GruArgs::poll_delay
+    bool writes_dgi;        // backward: the kernel's loader wave writes the gate-gradient rows itself (else cruse_gru_gate_grads_bf16 follows)
+};
 
-// Chains of 8 clips while the batch's chains fit the CUs.  A larger batch: WIDE chains (16 clips per chain, one launch of
-// half the workgroups, gru_w16.hip) where that kernel applies (wide_ok) and needs fewer launches; otherwise several launches on
-// chains of 8 (the generic kernels: chains of 16).  chain_clips = 16 asks for wide chains outright (the GGRU wavefront: both
-// layers' recurrences co-resident).
-int make_plan(int B, int G, int Hg, int prec, bool fwd, int chain_clips, bool wide_ok, Plan& pl) {
-    pl.P = Hg / U;
-    const int maxblk = num_cus();
-    if (G * pl.P > maxblk) return -1;
-    wide_ok = wide_ok && w16_eligible(Hg, prec);
-    pl.wide = chain_clips == 16 && wide_ok;
-    pl.Bg = pl.wide ? 16 : 8;
-    pl.nbg = cdiv(B, pl.Bg);
-    int per_launch = ((maxblk / pl.P) / 8 * 8) / G;        // chains per launch padded to a multiple of 8
-    if (per_launch < 1) per_launch = 1;
-    if (pl.nbg * G * pl.P > maxblk && chain_clips != 8 && pl.Bg == 8) {
-        const bool fast8 = fwd ? fwd_lean_eligible(8, Hg, prec) : bwd_rs_eligible(8, Hg, prec);
-        const int n8 = cdiv(pl.nbg, per_launch), n16 = cdiv(cdiv(B, 16), per_launch);
-        if (wide_ok && n16 < n8) { pl.wide = true; pl.Bg = 16; pl.nbg = cdiv(B, 16); }
-        else if (!fast8) { pl.Bg = 16; pl.nbg = cdiv(B, 16); }          // the generic kernels serve chains of 16
-    }
-    pl.bg_per_launch = per_launch;
-    if (pl.bg_per_launch > pl.nbg) pl.bg_per_launch = pl.nbg;
-    pl.nlaunch = cdiv(pl.nbg, pl.bg_per_launch);
-    return 0;
-}
-
-constexpr int MAX_LAUNCH_TICKETS = 64;      // launches of one call that get their own ticket counters
-// (sized for chains of 8 or of 16 clips: a 16-clip chain takes the room of two chains of 8)
-int chains8(int B) { return 2 * cdiv(B, 16); }
-size_t xid_bytes_total(int B, int G) { return (size_t)chains8(B) * G * 64 * 8; }
-
-// granules (8 bytes) of one parity of one chain: all-gather forms keep up to 16 rows of Hg values; the
-// reduce-scatter backward keeps [consumer P][clip 8][pair 16][producer P]
 bool bwd_rs_eligible(int Bg, int Hg, int prec) {
     if (cruse_opt("gru_bwd_rs", 1) == 0) return false;    // A/B switch (tests, probes)
     return prec == CRUSE_PREC_BF16 && Bg == 8 && Hg % 32 == 0 && Hg <= 640;
 }
-size_t rs_gran_per_parity(int Hg) { const size_t P = Hg / 32; return P * 8 * 16 * P; }
-size_t xg_bytes_total(int B, int G, int Hg) {
-    size_t per = (size_t)16 * Hg;
-    if (Hg % 32 == 0 && Hg <= 640 && rs_gran_per_parity(Hg) > per) per = rs_gran_per_parity(Hg);
-    return (size_t)chains8(B) * G * 2 * per * 8;
-}
-
-
 bool fwd_lean_eligible(int Bg, int Hg, int prec) {
     if (cruse_opt("gru_fwd_lean", 1) == 0) return false;   // A/B switch (tests, probes)
     return prec == CRUSE_PREC_BF16 && Bg == 8 && Hg % 32 == 0 && Hg <= 640;
+}
+// Hg = 640: the lean kernel's K-split step on the tag-free hand-off with the register-direct sweep (library option gru_tf = 0: the tagged
+// hand-off); needs |h| < 1 (h0 = NULL) and is built for one weight plane
+bool fwd_lean_tf_eligible(int Hg, bool wlo, bool has_h0) {
+    return Hg == 640 && !wlo && !has_h0 && cruse_opt("gru_tf", 1) != 0;
 }
 // W_hh low plane in the lean forward recurrence: CRUSE_GRU_WLO = 1 always, 0 never; default: when the second plane is
 // nearly free (Hg <= 320: at most 48 extra registers and 12 extra MFMAs per wave and step)
@@ -1367,41 +1335,110 @@ bool fwd_wlo(int Hg) {
     if (e >= 0) return e != 0;
     return Hg <= 320;
 }
-template <bool WLO, bool GIB>
-int dispatch_fwd_lean_w(const GruArgs& a, int grid, size_t lds, hipStream_t s) {
-    const int n = (a.Hg + 127) / 128;            // = k-steps per wave = sweep slots per thread
-    if (a.Hg % 128 == 0) {
-        switch (n) {
-            case 1: return launch_one(gru_fwd_lean_kernel<1, 1, true, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 1 > 3) ? 256 : 320);
-            case 2: return launch_one(gru_fwd_lean_kernel<2, 2, true, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 2 > 3) ? 256 : 320);
-            case 3: return launch_one(gru_fwd_lean_kernel<3, 3, true, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 3 > 3) ? 256 : 320);
-            case 4: return launch_one(gru_fwd_lean_kernel<4, 4, true, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 4 > 3) ? 256 : 320);
-            default: return launch_one(gru_fwd_lean_kernel<5, 5, true, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 5 > 3) ? 256 : 320);
-        }
-    }
-    switch (n) {
-        case 1: return launch_one(gru_fwd_lean_kernel<1, 1, false, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 1 > 3) ? 256 : 320);
-        case 2: return launch_one(gru_fwd_lean_kernel<2, 2, false, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 2 > 3) ? 256 : 320);
-        case 3: return launch_one(gru_fwd_lean_kernel<3, 3, false, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 3 > 3) ? 256 : 320);
-        case 4: return launch_one(gru_fwd_lean_kernel<4, 4, false, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 4 > 3) ? 256 : 320);
-        default: return launch_one(gru_fwd_lean_kernel<5, 5, false, WLO, false, GIB>, a, grid, lds, s, "gru_seq_fwd", (WLO && 5 > 3) ? 256 : 320);
-    }
+
+// granules (8 bytes) of one parity of one chain.  The all-gather forms keep Bg rows of Hg values; the reduce-scatter backward keeps
+// [consumer P][clip 8][pair 16][producer P], and the tag-free all-gather backward -- whose panels are half that size -- runs in the same
+// regions; the wide kernels keep [k chunk][clip 16] 16-byte pieces.
+size_t family_gpp(Family f, bool fwd, int Bg, int Hg) {
+    if (f == FAM_W16) return w16_panel_bytes_per_parity(Hg, fwd) / 8;
+    if (f == FAM_RS || f == FAM_AG) { const size_t P = Hg / 32; return P * 8 * 16 * P; }
+    return (size_t)Bg * Hg;
 }
-int dispatch_fwd_lean(const GruArgs& a, int grid, size_t lds, hipStream_t s) {
-    // Hg = 640: the K-split step on the tag-free hand-off with the register-direct sweep (library option gru_tf = 0: the tagged hand-off)
-    const bool tf640 = a.Hg == 640 && !fwd_wlo(a.Hg) && a.h0 == nullptr && cruse_opt("gru_tf", 1) != 0;
-    if (a.gi_bf16 == 2) {
-        // f16 gi rows: built for the bench step's kernel only (Hg = 640, chains of 8, tag-free register-direct hand-off, h0 = 0)
-        if (!tf640) { cruse_set_error("gru_seq_fwd: f16 gi rows are served at Hg = 640 with h0 = NULL on chains of 8 only (cruse_gru_plan)"); return CRUSE_E_SHAPE; }
-        return launch_one(gru_fwd_lean_kernel<5, 5, true, false, false, true, true, true, true>, a, grid, lds, s, "gru_seq_fwd", 320);
+// Workspace: the size may not depend on precision or A/B options, so every chain slot has room for the largest panel of any family
+// the WIDTH admits (the shape part of the predicates): the generic kernels' chains of 16 everywhere, the bf16 families on chains of 8 up
+// to Hg = 640, the wide kernels on whole 128-unit k groups.
+size_t max_gpp(int Hg) {
+    size_t m = family_gpp(FAM_GENERIC, true, 16, Hg);
+    if (Hg % 32 == 0 && Hg <= 640)
+        for (Family f : {FAM_LEAN, FAM_LEAN_TF, FAM_TF, FAM_RS, FAM_AG}) m = std::max(m, family_gpp(f, true, 8, Hg));      // (the direction matters to the wide panels only)
+    if (w16_eligible(Hg, CRUSE_PREC_BF16))
+        for (bool fwd : {true, false}) m = std::max(m, family_gpp(FAM_W16, fwd, 16, Hg));
+    return m;
+}
+constexpr int MAX_LAUNCH_TICKETS = 64;      // launches of one call that get their own ticket counters
+// (sized for chains of 8 or of 16 clips: a 16-clip chain takes the room of two chains of 8)
+int chains8(int B) { return 2 * cdiv(B, 16); }
+size_t xid_bytes_total(int B, int G) { return (size_t)chains8(B) * G * 64 * 8; }
+size_t xg_bytes_total(int B, int G, int Hg) { return (size_t)chains8(B) * G * 2 * max_gpp(Hg) * 8; }
+
+// Chains of 8 clips while the batch's chains fit the CUs.  A larger batch: WIDE chains (16 clips per chain, one launch of
+// half the workgroups, gru_w16.hip) where that kernel applies (wide_ok) and needs fewer launches; otherwise several launches on
+// chains of 8 where those have a fast kernel (fast8), else on the generic kernels' chains of 16.  chain_clips = 16 asks for wide chains
+// outright (the GGRU wavefront: both layers' recurrences co-resident).
+int make_plan(int B, int G, int Hg, int chain_clips, bool wide_ok, bool fast8, Route& r) {
+    r.P = Hg / U;
+    const int maxblk = num_cus();
+    if (G * r.P > maxblk) return -1;
+    r.wide = chain_clips == 16 && wide_ok;
+    r.Bg = r.wide ? 16 : 8;
+    r.nbg = cdiv(B, r.Bg);
+    int per_launch = ((maxblk / r.P) / 8 * 8) / G;        // chains per launch padded to a multiple of 8
+    if (per_launch < 1) per_launch = 1;
+    if (r.nbg * G * r.P > maxblk && chain_clips != 8 && r.Bg == 8) {
+        const int n8 = cdiv(r.nbg, per_launch), n16 = cdiv(cdiv(B, 16), per_launch);
+        if (wide_ok && n16 < n8) { r.wide = true; r.Bg = 16; r.nbg = cdiv(B, 16); }
+        else if (!fast8) { r.Bg = 16; r.nbg = cdiv(B, 16); }
     }
-    if (tf640) {
-        if (a.dbg == 32) return launch_one(gru_fwd_lean_kernel<5, 5, true, false, true, false, true, true>, a, grid, lds, s, "gru_seq_fwd", 320);
-        return launch_one(gru_fwd_lean_kernel<5, 5, true, false, false, false, true, true>, a, grid, lds, s, "gru_seq_fwd", 320);
+    r.bg_per_launch = per_launch;
+    if (r.bg_per_launch > r.nbg) r.bg_per_launch = r.nbg;
+    r.nlaunch = cdiv(r.nbg, r.bg_per_launch);
+    return 0;
+}
+
+// The one place that decides which kernel a call runs: the only caller of the *_eligible() predicates.
+// wide_ok: the caller admits wide chains (their tag-free hand-off needs |h| < 1); gi_f16: the gi rows are IEEE f16.
+int select_route(const char* name, int B, int G, int Hg, int prec, bool fwd, int chain_clips, bool wide_ok, bool has_h0, bool gi_f16,
+                 Route& r) {
+    CRUSE_REQUIRE(!gi_f16 || (prec == CRUSE_PREC_BF16 && Hg == 640), CRUSE_E_SHAPE,
+                  "gru_seq_fwd_gi16: f16 gi rows need CRUSE_PREC_BF16 and Hg = 640");
+    const bool fast8 = fwd ? fwd_lean_eligible(8, Hg, prec) : bwd_rs_eligible(8, Hg, prec);
+    CRUSE_REQUIRE(make_plan(B, G, Hg, chain_clips, wide_ok && w16_eligible(Hg, prec), fast8, r) == 0, CRUSE_E_SHAPE,
+                  "%s: G*Hg/32 exceeds the CU count", name);
+    r.fwd = fwd;
+    r.wlo = fwd && fwd_wlo(Hg);
+    r.poll_delay = 0;
+    const bool fast = fast8 && !r.wide;                      // (a plan with a fast kernel for chains of 8 never widens them to the generic 16)
+    if (gi_f16 && !fast) {
+        cruse_set_error("gru_seq_fwd: f16 gi rows are served at Hg = 640, CRUSE_PREC_BF16, on chains of 8 clips only (B <= 96: cruse_gru_plan)");
+        return CRUSE_E_SHAPE;
     }
-    if (a.dbg == 32 && a.Hg == 640 && !fwd_wlo(a.Hg))
-        return launch_one(gru_fwd_lean_kernel<5, 5, true, false, true>, a, grid, lds, s, "gru_seq_fwd", 320);
-    return fwd_wlo(a.Hg) ? dispatch_fwd_lean_w<true, false>(a, grid, lds, s) : dispatch_fwd_lean_w<false, false>(a, grid, lds, s);
+    if (r.wide) {
+        r.fam = FAM_W16;
+        if (!fwd) r.poll_delay = 6;                          // (tools/gru_wide_probe.py: 1.62 us per step at 5..8 periods, 1.67 at 0, 1.71 at 12)
+    } else if (!fast) {
+        r.fam = FAM_GENERIC;
+    } else if (fwd) {
+        if (fwd_tf_eligible(r.Bg, Hg, prec, has_h0, gi_f16)) { r.fam = FAM_TF; r.poll_delay = cruse_opt("gru_poll_fwd", 8); }
+        else { r.fam = fwd_lean_tf_eligible(Hg, r.wlo, has_h0) ? FAM_LEAN_TF : FAM_LEAN; r.poll_delay = cruse_opt("gru_poll_fwd", 0); }
+        // f16 gi rows: built for the bench step's kernel only
+        if (gi_f16 && r.fam != FAM_LEAN_TF) { cruse_set_error("gru_seq_fwd: f16 gi rows are served at Hg = 640 with h0 = NULL on chains of 8 only (cruse_gru_plan)"); return CRUSE_E_SHAPE; }
+    } else {
+        if (bwd_tf_eligible(r.Bg, Hg, prec)) { r.fam = FAM_AG; r.poll_delay = cruse_opt("gru_poll_bwd", Hg == 640 ? 5 : 7); }
+        else r.fam = FAM_RS;
+    }
+    r.gpp = family_gpp(r.fam, fwd, r.Bg, Hg);
+    r.writes_dgi = !fwd && (r.fam == FAM_W16 || r.fam == FAM_RS || r.fam == FAM_AG);
+    return CRUSE_OK;
+}
+
+template <int N, bool FULL, bool WLO>
+int launch_fwd_lean(const GruArgs& a, int grid, size_t lds, hipStream_t s) {
+    return launch_one(gru_fwd_lean_kernel<N, FULL, WLO>, a, grid, lds, s, "gru_seq_fwd", lean_threads(WLO, N));
+}
+int dispatch_fwd_lean(const GruArgs& a, const Route& r, int grid, size_t lds, hipStream_t s) {
+    if (r.fam == FAM_LEAN_TF) {                  // Hg = 640, one weight plane
+        if (a.gi_bf16 == 2) return launch_one(gru_fwd_lean_kernel<5, true, false, false, true, true>, a, grid, lds, s, "gru_seq_fwd", lean_threads(false, 5));
+        if (a.dbg == 32) return launch_one(gru_fwd_lean_kernel<5, true, false, true, true>, a, grid, lds, s, "gru_seq_fwd", lean_threads(false, 5));
+        return launch_one(gru_fwd_lean_kernel<5, true, false, false, true>, a, grid, lds, s, "gru_seq_fwd", lean_threads(false, 5));
+    }
+    if (a.dbg == 32 && a.Hg == 640 && !r.wlo)
+        return launch_one(gru_fwd_lean_kernel<5, true, false, true>, a, grid, lds, s, "gru_seq_fwd", lean_threads(false, 5));
+    const bool full = a.Hg % 128 == 0, wlo = r.wlo;
+    return dispatch_int<1, 2, 3, 4, 5>((a.Hg + 127) / 128, [&](auto nkw) {      // k-steps per wave
+        constexpr int N = decltype(nkw)::value;
+        if (full) return wlo ? launch_fwd_lean<N, true, true>(a, grid, lds, s) : launch_fwd_lean<N, true, false>(a, grid, lds, s);
+        return wlo ? launch_fwd_lean<N, false, true>(a, grid, lds, s) : launch_fwd_lean<N, false, false>(a, grid, lds, s);
+    });
 }
 
 template <int PREC>
@@ -1420,26 +1457,33 @@ int dispatch_bwd(const GruArgs& a, int grid, size_t lds, hipStream_t s) {
     if (nkw <= 15) return launch_one(gru_bwd_kernel<PREC, 15>, a, grid, lds, s, "gru_seq_bwd");
     return launch_one(gru_bwd_kernel<PREC, 24>, a, grid, lds, s, "gru_seq_bwd");
 }
+template <int PREC>
+int dispatch_generic(const GruArgs& a, bool fwd, int grid, size_t lds, hipStream_t s) {
+    return fwd ? dispatch_fwd<PREC>(a, grid, lds, s) : dispatch_bwd<PREC>(a, grid, lds, s);
+}
 
 int dispatch_bwd_rs(const GruArgs& a, int grid, hipStream_t s) {
-    const int P = a.Hg / 32, np = (P + 3) / 4;   // tile pairs per wavefront
-    if (a.dbg >= 32 && a.dbg <= 35 && a.Hg == 640) return launch_one(gru_bwd_rs_kernel<5, true, true>, a, grid, 0, s, "gru_seq_bwd", 320);
-    if (P % 4 == 0) {
-        switch (np) {
-            case 1: return launch_one(gru_bwd_rs_kernel<1, true>, a, grid, 0, s, "gru_seq_bwd", 320);
-            case 2: return launch_one(gru_bwd_rs_kernel<2, true>, a, grid, 0, s, "gru_seq_bwd", 320);
-            case 3: return launch_one(gru_bwd_rs_kernel<3, true>, a, grid, 0, s, "gru_seq_bwd", 320);
-            case 4: return launch_one(gru_bwd_rs_kernel<4, true>, a, grid, 0, s, "gru_seq_bwd", 320);
-            default: return launch_one(gru_bwd_rs_kernel<5, true>, a, grid, 0, s, "gru_seq_bwd", 320);
-        }
+    const int P = a.Hg / 32;
+    if (a.dbg >= 32 && a.dbg <= 35 && a.Hg == 640) return launch_one(gru_bwd_rs_kernel<5, true, true>, a, grid, 0, s, "gru_seq_bwd", RS_THREADS);
+    return dispatch_int<1, 2, 3, 4, 5>((P + 3) / 4, [&](auto np) {               // tile pairs per wavefront
+        constexpr int NP = decltype(np)::value;
+        return P % 4 == 0 ? launch_one(gru_bwd_rs_kernel<NP, true>, a, grid, 0, s, "gru_seq_bwd", RS_THREADS)
+                          : launch_one(gru_bwd_rs_kernel<NP, false>, a, grid, 0, s, "gru_seq_bwd", RS_THREADS);
+    });
+}
+
+int dispatch_route(const GruArgs& a, const Route& r, int prec, int grid, size_t lds, hipStream_t s) {
+    switch (r.fam) {
+        case FAM_W16: return r.fwd ? dispatch_fwd_w16(a, grid, s) : dispatch_bwd_w16(a, grid, s);
+        case FAM_TF: return dispatch_fwd_tf(a, grid, r.wlo, s);
+        case FAM_LEAN: case FAM_LEAN_TF: return dispatch_fwd_lean(a, r, grid, lds, s);
+        case FAM_AG: return dispatch_bwd_ag(a, grid, s);
+        case FAM_RS: return dispatch_bwd_rs(a, grid, s);
+        default: break;
     }
-    switch (np) {
-        case 1: return launch_one(gru_bwd_rs_kernel<1, false>, a, grid, 0, s, "gru_seq_bwd", 320);
-        case 2: return launch_one(gru_bwd_rs_kernel<2, false>, a, grid, 0, s, "gru_seq_bwd", 320);
-        case 3: return launch_one(gru_bwd_rs_kernel<3, false>, a, grid, 0, s, "gru_seq_bwd", 320);
-        case 4: return launch_one(gru_bwd_rs_kernel<4, false>, a, grid, 0, s, "gru_seq_bwd", 320);
-        default: return launch_one(gru_bwd_rs_kernel<5, false>, a, grid, 0, s, "gru_seq_bwd", 320);
-    }
+    if (prec == CRUSE_PREC_F32) return dispatch_generic<CRUSE_PREC_F32>(a, r.fwd, grid, lds, s);
+    if (prec == CRUSE_PREC_BF16X3) return dispatch_generic<CRUSE_PREC_BF16X3>(a, r.fwd, grid, lds, s);
+    return dispatch_generic<CRUSE_PREC_BF16>(a, r.fwd, grid, lds, s);
 }
 
 int check_common(int B, int T, int G, int Hg, int prec, const char* name) {
@@ -1451,61 +1495,32 @@ int check_common(int B, int T, int G, int Hg, int prec, const char* name) {
     return CRUSE_OK;
 }
 
-template <bool FWD>
-int run_launches(GruArgs& a, const Plan& pl, int G, int Hg, int prec, void* panels, unsigned* status, int xcd_rot,
-                 size_t lds, hipStream_t s) {
+int run_launches(GruArgs& a, const Route& r, int G, int Hg, int prec, void* panels, unsigned* status, int xcd_rot, size_t lds,
+                 hipStream_t s) {
     a.status = status;
     a.xcd_rot = xcd_rot & 7;
     char* xid_base = (char*)panels;
     char* xg_base = xid_base + xid_bytes_total(a.B, G);
     unsigned* tickets_base = (unsigned*)(xg_base + xg_bytes_total(a.B, G, Hg));        // [launch][8]
-    a.Bg = pl.Bg; a.P = pl.P;
+    a.Bg = r.Bg; a.P = r.P;
+    a.poll_delay = r.poll_delay;
     a.dbg = cruse_opt("gru_dbg", 0);
-    int rc = CRUSE_OK;
-    CRUSE_REQUIRE(pl.nlaunch <= MAX_LAUNCH_TICKETS, CRUSE_E_SHAPE, "gru_seq: batch %d needs %d launches (max %d)", a.B, pl.nlaunch,
+    CRUSE_REQUIRE(r.nlaunch <= MAX_LAUNCH_TICKETS, CRUSE_E_SHAPE, "gru_seq: batch %d needs %d launches (max %d)", a.B, r.nlaunch,
                   MAX_LAUNCH_TICKETS);
-    for (int L = 0; L < pl.nlaunch; ++L) {
-        const int bg_off = L * pl.bg_per_launch;
-        const int nbg_here = (pl.nbg - bg_off) < pl.bg_per_launch ? (pl.nbg - bg_off) : pl.bg_per_launch;
+    for (int L = 0; L < r.nlaunch; ++L) {
+        const int bg_off = L * r.bg_per_launch;
+        const int nbg_here = (r.nbg - bg_off) < r.bg_per_launch ? (r.nbg - bg_off) : r.bg_per_launch;
         a.bg_off = bg_off;
         a.nchains = nbg_here * G;
         // every launch gets its own panel region: chain index inside the launch + offset
         a.xid = (unsigned long long*)xid_base + (size_t)bg_off * G * 64;
         a.tickets = tickets_base + (size_t)L * 8;
-        const bool rs_form = !FWD && !pl.wide && bwd_rs_eligible(pl.Bg, Hg, prec);
-        const size_t gpp = pl.wide ? w16_panel_bytes_per_parity(Hg, FWD) / 8 : rs_form ? rs_gran_per_parity(Hg) : (size_t)pl.Bg * Hg;      // granules per parity and chain
-        a.xg = (unsigned long long*)xg_base + (size_t)bg_off * G * 2 * gpp;
-        a.xg_bytes = (unsigned)((size_t)a.nchains * 2 * gpp * 8);
-        const int grid = cdiv(a.nchains, 8) * 8 * pl.P;
-        if (FWD && a.gi_bf16 == 2 && (pl.wide || !fwd_lean_eligible(pl.Bg, Hg, prec))) {
-            cruse_set_error("gru_seq_fwd: f16 gi rows are served at Hg = 640, CRUSE_PREC_BF16, on chains of 8 clips only (B <= 96: cruse_gru_plan)");
-            return CRUSE_E_SHAPE;
-        }
-        if (FWD && pl.wide) {
-            a.poll_delay = 0;
-            rc = dispatch_fwd_w16(a, grid, s);
-        } else if (FWD && fwd_lean_eligible(pl.Bg, Hg, prec)) {
-            if (fwd_tf_eligible(pl.Bg, Hg, prec, a.h0 != nullptr, a.gi_bf16 != 0)) { a.poll_delay = cruse_opt("gru_poll_fwd", 8); rc = dispatch_fwd_tf(a, grid, fwd_wlo(Hg), s); }
-            else { a.poll_delay = cruse_opt("gru_poll_fwd", 0); rc = dispatch_fwd_lean(a, grid, lds, s); }
-        } else if (FWD) {
-            if (prec == CRUSE_PREC_F32) rc = dispatch_fwd<CRUSE_PREC_F32>(a, grid, lds, s);
-            else if (prec == CRUSE_PREC_BF16X3) rc = dispatch_fwd<CRUSE_PREC_BF16X3>(a, grid, lds, s);
-            else rc = dispatch_fwd<CRUSE_PREC_BF16>(a, grid, lds, s);
-        } else if (pl.wide) {
-            a.poll_delay = 6;                         // (tools/gru_wide_probe.py: 1.62 us per step at 5..8 periods, 1.67 at 0, 1.71 at 12)
-            rc = dispatch_bwd_w16(a, grid, s);
-        } else if (rs_form) {
-            // (the tag-free kernel's panels are half the size of the reduce-scatter kernel's: the same regions hold them)
-            if (bwd_tf_eligible(pl.Bg, Hg, prec)) { a.poll_delay = cruse_opt("gru_poll_bwd", Hg == 640 ? 5 : 7); rc = dispatch_bwd_tf(a, grid, s); }
-            else rc = dispatch_bwd_rs(a, grid, s);
-        } else {
-            if (prec == CRUSE_PREC_F32) rc = dispatch_bwd<CRUSE_PREC_F32>(a, grid, lds, s);
-            else if (prec == CRUSE_PREC_BF16X3) rc = dispatch_bwd<CRUSE_PREC_BF16X3>(a, grid, lds, s);
-            else rc = dispatch_bwd<CRUSE_PREC_BF16>(a, grid, lds, s);
-        }
+        a.xg = (unsigned long long*)xg_base + (size_t)bg_off * G * 2 * r.gpp;
+        a.xg_bytes = (unsigned)((size_t)a.nchains * 2 * r.gpp * 8);
+        const int rc = dispatch_route(a, r, prec, cdiv(a.nchains, 8) * 8 * r.P, lds, s);
         if (rc) return rc;
     }
-    return rc;
+    return CRUSE_OK;
 }
 
 
@@ -1513,8 +1528,9 @@ int run_launches(GruArgs& a, const Plan& pl, int G, int Hg, int prec, void* pane
 
 extern "C" int cruse_gru_plan(int B, int G, int Hg, int prec, int fwd, int* out) {
     CRUSE_REQUIRE(out != nullptr && B >= 1 && G >= 1 && Hg >= 32 && Hg % 32 == 0, CRUSE_E_SHAPE, "gru_plan: B = %d, G = %d, Hg = %d", B, G, Hg);
-    Plan pl;
-    CRUSE_REQUIRE(make_plan(B, G, Hg, prec, fwd != 0, 0, true, pl) == 0, CRUSE_E_SHAPE, "gru_plan: G*Hg/32 exceeds the CU count");
+    Route pl;
+    int rc = select_route("gru_plan", B, G, Hg, prec, fwd != 0, 0, true, false, false, pl);
+    if (rc) return rc;
     out[0] = pl.Bg; out[1] = pl.nbg; out[2] = pl.bg_per_launch; out[3] = pl.nlaunch; out[4] = pl.P; out[5] = pl.wide ? 1 : 0;
     return CRUSE_OK;
 }
@@ -1535,11 +1551,12 @@ static int gru_seq_fwd_impl(const float* gi, const float* const* w_hh, const flo
                   "gru_seq_fwd: h0 needs a clip stride >= G*Hg (multiple of 4 floats) and 16-byte alignment");
     CRUSE_REQUIRE((coef == nullptr) == (an == nullptr) && (coef == nullptr) == (z == nullptr), CRUSE_E_SHAPE,
                   "gru_seq_fwd: coef, an, z must all be given or all be NULL");
-    Plan pl;
+    Route r;
     // wide chains: f32 gi rows; their tag-free hand-off needs |h| < 1, so an initial state is taken only where the caller asks for
     // wide chains outright and thereby vouches for |h0| < 1 (the continuation of a sequence that started from zero)
     const bool wide_ok = h0 == nullptr || chain_clips == 16;
-    CRUSE_REQUIRE(make_plan(B, G, Hg, prec, true, chain_clips, wide_ok, pl) == 0, CRUSE_E_SHAPE, "gru_seq_fwd: G*Hg/32 exceeds the CU count");
+    rc = select_route("gru_seq_fwd", B, G, Hg, prec, true, chain_clips, wide_ok, h0 != nullptr, gi_dtype == CRUSE_DT_F16, r);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     CRUSE_REQUIRE(panels != nullptr && status != nullptr, CRUSE_E_SHAPE, "gru_seq_fwd: workspace / status pointer is NULL");
     // (the status word is sticky: never cleared here.  panels_zeroed: the caller cleared the scratch itself -- e.g. the scratches of
@@ -1553,7 +1570,7 @@ static int gru_seq_fwd_impl(const float* gi, const float* const* w_hh, const flo
     a.gi_bf16 = gi_dtype == CRUSE_DT_F16 ? 2 : 0;
     const size_t esz = prec == CRUSE_PREC_F32 ? 4 : 2, npl = prec == CRUSE_PREC_BF16X3 ? 2 : 1;
     const size_t lds = (size_t)16 * (Hg + (prec == CRUSE_PREC_F32 ? 4 : 8)) * esz * npl + 4 * 6 * RED_TS * sizeof(float);
-    return run_launches<true>(a, pl, G, Hg, prec, panels, status, xcd_rot, lds, s);
+    return run_launches(a, r, G, Hg, prec, panels, status, xcd_rot, lds, s);
 }
 
 extern "C" int cruse_gru_seq_fwd_ex(const float* gi, const float* const* w_hh, const float* const* b_hh,
@@ -1572,8 +1589,6 @@ extern "C" int cruse_gru_seq_fwd_gi16(const void* gi, int gi_dtype, const float*
                                       int B, int T, int TS, int G, int Hg, int prec, void* panels,
                                       int panels_zeroed, unsigned* status, int xcd_rot, void* stream) {
     CRUSE_REQUIRE(gi_dtype == CRUSE_DT_F16 || gi_dtype == CRUSE_DT_F32, CRUSE_E_DTYPE, "gru_seq_fwd_gi16: gi_dtype %d (CRUSE_DT_F32, CRUSE_DT_F16)", gi_dtype);
-    CRUSE_REQUIRE(gi_dtype == CRUSE_DT_F32 || (prec == CRUSE_PREC_BF16 && Hg == 640), CRUSE_E_SHAPE,
-                  "gru_seq_fwd_gi16: f16 gi rows need CRUSE_PREC_BF16 and Hg = 640");
     return gru_seq_fwd_impl(reinterpret_cast<const float*>(gi), w_hh, b_hh, h, coef, an, z, nullptr, 0, B, T, TS, G, Hg, prec, 0, panels,
                             panels_zeroed, status, xcd_rot, stream, gi_dtype);
 }
@@ -1604,8 +1619,9 @@ extern "C" int cruse_gru_seq_bwd_ex(const float* dout, const float* const* w_hh,
     CRUSE_REQUIRE(chain_clips == 0 || chain_clips == 8 || chain_clips == 16, CRUSE_E_SHAPE, "gru_seq_bwd: chain_clips = %d (0, 8, 16)", chain_clips);
     if (rc) return rc;
     CRUSE_REQUIRE(TS >= T, CRUSE_E_SHAPE, "gru_seq_bwd: clip stride %d frames < %d steps", TS, T);
-    Plan pl;
-    CRUSE_REQUIRE(make_plan(B, G, Hg, prec, false, chain_clips, true, pl) == 0, CRUSE_E_SHAPE, "gru_seq_bwd: G*Hg/32 exceeds the CU count");
+    Route r;
+    rc = select_route("gru_seq_bwd", B, G, Hg, prec, false, chain_clips, true, false, false, r);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     CRUSE_REQUIRE(panels != nullptr && status != nullptr, CRUSE_E_SHAPE, "gru_seq_bwd: workspace / status pointer is NULL");
     if (!panels_zeroed) { int zrc = cruse_zero_async(panels, cruse_gru_ws_bytes(B, G, Hg) - 256, s, "gru_seq_bwd memset"); if (zrc) return zrc; }   // the status word is sticky: never cleared here
@@ -1619,14 +1635,14 @@ extern "C" int cruse_gru_seq_bwd_ex(const float* dout, const float* const* w_hh,
     CRUSE_REQUIRE(lds <= 160 * 1024, CRUSE_E_SHAPE, "gru_seq_bwd: Hg=%d needs %zu B of LDS", Hg, lds);
     CRUSE_REQUIRE(dgi == nullptr || (an != nullptr && prec == CRUSE_PREC_BF16), CRUSE_E_SHAPE,
                   "gru_seq_bwd: dgi needs the a_n rows and CRUSE_PREC_BF16");
-    // the reduce-scatter kernel's loader wave writes dgi itself; the other kernels are followed by the gate-gradient pass
-    const bool in_kernel = dgi != nullptr && (pl.wide || bwd_rs_eligible(pl.Bg, Hg, prec));
+    // the bf16 kernels' loader wave writes dgi itself; the generic kernels are followed by the gate-gradient pass
+    const bool in_kernel = dgi != nullptr && r.writes_dgi;
     CRUSE_REQUIRE(dg_slabs == 3 || (dg_slabs == 4 && (dgi == nullptr || in_kernel)), CRUSE_E_SHAPE,
                   "gru_seq_bwd: dg_slabs = %d (3, or 4 with the reduce-scatter kernels: bf16, Hg <= 640)", dg_slabs);
     a.ans = in_kernel ? an : nullptr;
     a.dgi = in_kernel ? dgi : nullptr;
     a.dg_slabs = dg_slabs;
-    rc = run_launches<false>(a, pl, G, Hg, prec, panels, status, xcd_rot, lds, s);
+    rc = run_launches(a, r, G, Hg, prec, panels, status, xcd_rot, lds, s);
     if (rc || dgi == nullptr || in_kernel) return rc;
     CRUSE_REQUIRE(TS == T, CRUSE_E_SHAPE, "gru_seq_bwd: dgi on a sub-sequence needs the reduce-scatter kernel (bf16, Hg <= 640)");
     const long long rows = (long long)B * T;

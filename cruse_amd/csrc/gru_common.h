@@ -3,6 +3,8 @@
 #pragma once
 #include "common.h"
 #include <stdlib.h>
+#include <algorithm>
+#include <type_traits>
 
 namespace cruse_gru {
 
@@ -27,7 +29,8 @@ struct GruPtrs { const float* w_hh[MAXG]; const float* b_hh[MAXG]; };
 struct GruArgs {
     // forward
     const float* gi; float* h; void* coef; float* an; float* z;
-    int gi_bf16;                      // gi rows are bf16 (written by cruse_gemm_bf16_nt_obf16): half the bytes; widened on load
+    int gi_bf16;                      // 0: f32 gi rows; 2: IEEE f16 rows (cruse_gemm_nt_out16: half the bytes, widened on load) -- the tag-free lean
+                                      // kernel only.  (1 was bf16 rows: no caller sets it; the generic forward kernel still reads any non-zero value so)
     // backward
     const float* dout; const void* coefs; const float* zs; float* dh;
     const float* ans; void* dgi;      // optional (reduce-scatter kernel): a_n rows in, dgi = dh * (c_r, c_z, a_n) rows out
@@ -44,8 +47,9 @@ struct GruArgs {
     int prio;                         // s_setprio level of the compute waves (option gru_prio): the recurrence's instructions issue ahead of
                                       // co-resident side-stream waves on the same SIMD
     int poll_delay;                   // tag-free kernels: s_sleep(1) periods between a step's publish and its first poll
-    int xsweep;                       // profiling: extra sweep / publish repetitions per step of the forward lean kernel (gru_xsweep)
-    int poll_stagger;                 // backward tag-free kernel: > 0 = two polls in flight, this many s_sleep(1) periods apart
+    int xsweep;                       // profiling: extra sweep / publish repetitions per step of the forward lean kernel (always 0: its
+                                      // option is gone; the loops over it stay so that the kernels' code is what was measured)
+    int poll_stagger;                 // unused (two polls in flight in the backward tag-free kernel: measured slower, removed)
     int dbg;                          // profiling only (CRUSE_GRU_DBG): 1 = do not wait for tags, 2 = also skip MFMA
     // sub-sequences (cruse_gru_seq_*_ex): T steps of tensors whose clips are TS frames apart (TS >= T; the pointers are
     // already advanced to the first frame of the run)
@@ -350,6 +354,14 @@ constexpr unsigned TAGM = 0x40004000u;            // bit 14 of both bf16 halves 
 __device__ __forceinline__ unsigned tag_bit(unsigned epoch) { return ((epoch + 1u) >> 1) & 1u; }
 // (x & ~TAGM) | tag  in one VOP3 (v_and_or_b32)
 __device__ __forceinline__ unsigned with_tag(unsigned x, unsigned tagm) { return (x & ~TAGM) | tagm; }
+
+// Run-time integer -> template parameter: f(std::integral_constant<int, V>{}) for the first V of the list equal to v, for the LAST one
+// if none is (the kernels' largest instance serves as the default).
+template <int V0, int... Vs, typename F>
+inline int dispatch_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<Vs...>(v, f);
+}
 
 template <typename Kern>
 inline int launch_one(Kern k, const GruArgs& a, int grid, size_t lds, hipStream_t s, const char* name, int threads = 256) {

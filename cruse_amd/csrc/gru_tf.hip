@@ -18,15 +18,20 @@
 //      accumulators hold all three gates of its (clip, unit pair) -- NK = Hg/32 k-steps, 2 NK MFMAs per wave and step (40 at
 //      Hg = 640 against 30), 8 NK weight registers per lane (160).  The accumulators ARE the gate pre-activations (bias
 //      preloaded); one DPP row rotate hands the second unit of a pair to the idle column lane (the MFMA leaves clips in 8
-//      of its 16 columns) and every lane runs one gate evaluation.  One barrier per step (the LDS image of the panel is
-//      double-buffered by step parity).
+//      of its 16 columns) and every lane runs one gate evaluation.  One barrier per step.
 //
+// Both kernels sweep REGISTER-DIRECT: the panel is clip-minor and every wave loads the chunks that are its MFMA B fragments; the forms
+// that went through an LDS image of the panel measured slower and are gone.
+// gru_fwd_tf_kernel<NK, WLO, TIMED> (Hg = 160 / 320), gru_bwd_ag_kernel<P, TIMED, DGI> (Hg = 160 / 320 / 640); gru.hip's select_route()
+// decides when they run.
 // The helper wave (gi ring, saves) is the one of gru_fwd_lean; the loader wave that of gru_bwd_rs.
 #include "gru_common.h"
 
 namespace {
 
 using namespace cruse_gru;
+
+constexpr int TF_THREADS = 320;             // four compute waves + the helper / loader wave
 
 // lanes 8..15 of every 16-lane row take `src` of lane - 8, lanes 0..7 keep `old` (v_mov_b32_dpp row_ror:8, bank_mask 0xC)
 __device__ __forceinline__ float take_hi8(float old, float src) {
@@ -36,21 +41,15 @@ __device__ __forceinline__ float take_hi8(float old, float src) {
 // ---------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------
-// NK = Hg / 32 k-steps; NS = ceil(Hg / 256) sweep slots per compute thread; WLO: W_hh as hi + lo bf16 planes (Hg <= 320)
-// RD: register-direct sweep (see gru_fwd_lean_kernel / gru_bwd_ag_kernel): clip-minor panel, every wave loads ITS B fragments -- here the
+// NK = Hg / 32 k-steps; WLO: W_hh as hi + lo bf16 planes (Hg <= 320)
+// The sweep is REGISTER-DIRECT (see gru_fwd_lean_kernel / gru_bwd_ag_kernel): clip-minor panel, every wave loads ITS B fragments -- here the
 // whole K: ceil(NK / 2) 16-byte loads per lane, the MFMA's idle columns 8..15 fetching the odd k-step of each pair -- no LDS image.
-template <int NK, int NS, bool WLO, bool TIMED = false, bool RD = false>
-__global__ __launch_bounds__(320) void gru_fwd_tf_kernel(GruArgs a) {
+template <int NK, bool WLO, bool TIMED = false>
+__global__ __launch_bounds__(TF_THREADS) void gru_fwd_tf_kernel(GruArgs a) {
     static_assert(!WLO || NK <= 10, "two weight planes fit 256 registers up to Hg = 320");
-    // Row stride of the LDS image: a ds_read_b128 is served in groups of 16 lanes over 64 banks, and a group holds the fragments
-    // of all 8 clips for two neighbouring 16-byte k-chunks (lane >> 4 = q, q + 1): bank quad = (clip * R + q + 4 ks) mod 16 with R the
-    // row stride in 16-byte units -- R = 2 (mod 16) makes the 16 lanes of a group cover all 64 banks (with R = 1 (mod 16), Hg + 8,
-    // clip c chunk q + 1 collided with clip c + 1 chunk q: 2-way conflicts on every fragment read, 1435 instead of ~800 cycles)
-    constexpr int Hg = NK * 32, LD = 8 * (((NK * 4 - 2 + 15) / 16) * 16 + 2);
-    static_assert(LD >= Hg && (LD / 8) % 16 == 2, "LDS row stride");
+    constexpr int Hg = NK * 32;
     unsigned long long tph[5] = {0, 0, 0, 0, 0}, tq0 = 0, tq1 = 0;
     (void)tph; (void)tq0; (void)tq1;
-    __shared__ __attribute__((aligned(16))) __bf16 hB[2][8 * LD];                 // B operand (h_{t-1}) by step parity
     // clip strides of 8 (mod 32) floats: a compute wave's 32-lane half touches 8 clips x 4 units per access -- with strides of
     // 96 / 32 floats all 8 clips of a unit fell on ONE bank (8-way conflicts on the 3 gi reads and the 6 saves of every step,
     // ~450 cycles per step that no phase stamp showed)
@@ -190,24 +189,10 @@ __global__ __launch_bounds__(320) void gru_fwd_tf_kernel(GruArgs a) {
         biasB = (f32x4){bh[2 * Hg + un], bh[2 * Hg + un + 1], 0.f, 0.f};
     }
 
-    // sweep slots: 16-byte load e = tid + 256 j covers clip e / (Hg/8), units 8 (e % (Hg/8)) .. +7 (clamped for short chains and
-    // for the slots beyond the panel: the last valid load is then fetched and stored twice)
-    constexpr int per = Hg >> 3;
-    const int nload = nb * per;
-    unsigned sw_v[NS];
-    int sw_l[NS];
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        const int e = min(tid + 256 * j, nload - 1);
-        const int bl = e / per, v = 8 * (e - bl * per);
-        sw_v[j] = (unsigned)e * 16u;
-        sw_l[j] = bl * LD + v;
-    }
-    const unsigned pub_v = RD ? (unsigned)(((((u0 >> 3) + wv) * 8 + clipc) * 8 + 2 * q) * 2) : (unsigned)(clipc * Hg + u0 + 8 * wv + 2 * q) * 2u;
+    const unsigned pub_v = (unsigned)(((((u0 >> 3) + wv) * 8 + clipc) * 8 + 2 * q) * 2);
     const bool pub_lane = act && c16 < 8;
     constexpr int NLR = (NK + 1) / 2;
     const unsigned rd_v = (unsigned)((q * 8 + clip) * 16), rd_v2 = rd_v + ((c16 >> 3) ? 512u : 0u);     // + j * 1024: k-steps 2 j, 2 j + 1
-    const int fb_off = clip * LD + q * 8;                     // B fragment of k-step ks: + ks * 32 (columns 8..15 re-read clips 0..7)
     float* const sl0 = &sv_l[0][0][clipc][uw];
     const float* const gi0 = &gi_r[0][clipc][uw];
 
@@ -222,27 +207,27 @@ __global__ __launch_bounds__(320) void gru_fwd_tf_kernel(GruArgs a) {
         float gic[3];
 #pragma unroll
         for (int g = 0; g < 3; ++g) gic[g] = gi0[(t & 3) * (8 * GS) + g * 32];
-        __bf16* const hb = hB[t & 1];
-        u32x4 gr[RD ? NLR : 1];
-        if (RD && t > 0) {
+        const int par = t & 1;                                 // this step's publish panel and save slots
+        u32x4 gr[NLR];
+        if (t > 0) {
             const unsigned soff = cbase + (unsigned)((t - 1) & 1) * panel_bytes;
             const bool expect1 = tag_bit((unsigned)t) != 0u;
             unsigned spins = 0;
             for (int i = 0; i < a.poll_delay; ++i) __builtin_amdgcn_s_sleep(1);     // (see poll_delay)
             for (;;) {
 #pragma unroll
-                for (int j = 0; j < (RD ? NLR : 1); ++j)
+                for (int j = 0; j < NLR; ++j)
                     gr[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, (2 * j + 1 < NK || j + 1 < NLR) ? rd_v2 : rd_v, soff + (unsigned)(j * 1024), 16);
                 unsigned bad;
                 if (expect1) {
                     unsigned n = 0xffffffffu;
 #pragma unroll
-                    for (int j = 0; j < (RD ? NLR : 1); ++j) n = n & (gr[j].x & gr[j].y) & (gr[j].z & gr[j].w);
+                    for (int j = 0; j < NLR; ++j) n = n & (gr[j].x & gr[j].y) & (gr[j].z & gr[j].w);
                     bad = ~n;
                 } else {
                     unsigned o = 0u;
 #pragma unroll
-                    for (int j = 0; j < (RD ? NLR : 1); ++j) o = o | (gr[j].x | gr[j].y) | (gr[j].z | gr[j].w);
+                    for (int j = 0; j < NLR; ++j) o = o | (gr[j].x | gr[j].y) | (gr[j].z | gr[j].w);
                     bad = o;
                 }
                 if (__all((bad & TAGM) == 0u || !act || nowait)) break;
@@ -255,93 +240,35 @@ __global__ __launch_bounds__(320) void gru_fwd_tf_kernel(GruArgs a) {
             }
             if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[0] += tq1 - tq0; tq0 = tq1; }
         }
-        if (!RD && t > 0) {
-            const unsigned soff = cbase + (unsigned)((t - 1) & 1) * panel_bytes;
-            const unsigned flip = tag_bit((unsigned)t) ? 0xffffffffu : 0u;
-            u32x4 g[NS];
-            unsigned spins = 0;
-            for (int i = 0; i < a.poll_delay; ++i) __builtin_amdgcn_s_sleep(1);     // (see poll_delay)
-            for (;;) {
-#pragma unroll
-                for (int j = 0; j < NS; ++j) g[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, sw_v[j], soff, 16);
-                unsigned bad = 0u;
-#pragma unroll
-                for (int j = 0; j < NS; ++j) bad |= (g[j].x ^ flip) | (g[j].y ^ flip) | (g[j].z ^ flip) | (g[j].w ^ flip);
-                if (__all((bad & TAGM) == 0u || nowait)) break;
-                if (++spins >= SPIN_LIMIT) {
-                    if (lane == 0) __hip_atomic_store(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    nowait = true;
-                }
-                if constexpr (TIMED) tph[4] += 1;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[0] += tq1 - tq0; tq0 = tq1; }
-#pragma unroll
-            for (int j = 0; j < NS; ++j) {
-                const u32x4 w = {g[j].x & ~TAGM, g[j].y & ~TAGM, g[j].z & ~TAGM, g[j].w & ~TAGM};
-                *reinterpret_cast<u32x4*>(hb + sw_l[j]) = w;
-            }
-        }
-        __syncthreads();                                       // panel of step t complete (and the helper's ring / saves hand-over)
+        __syncthreads();                                       // every wave's sweep has returned: the helper's ring / saves hand-over
         if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[1] += tq1 - tq0; tq0 = tq1; }
         f32x4 aA = biasA, aB = biasB;
         if (t > 0) {
             f32x4 aA1 = (f32x4){0.f, 0.f, 0.f, 0.f}, aB1 = aA1;
-            // Fragment reads run PF k-steps ahead of their MFMAs; sched_barrier(0) after every k-step pins that order.  (Left to
-            // itself the scheduler keeps two fragment registers and issues each pair of reads right in front of its MFMAs: every
-            // second k-step exposed a full LDS round trip, 1370 cycles for the 40 MFMAs of Hg = 640 instead of ~700 -- s_memtime
-            // stamps, gru_dbg = 32; sched_group_barrier pipelines were followed for six k-steps and then abandoned.)
-            constexpr int PF = NK < 6 ? NK : 6;
             bf16x8 fr[NK];
-            if constexpr (RD) {
 #pragma unroll
-                for (int ks = 0; ks < NK; ++ks) {
-                    const u32x4 gg = gr[ks >> 1];
-                    u32x4 w = {gg.x & ~TAGM, gg.y & ~TAGM, gg.z & ~TAGM, gg.w & ~TAGM};
-                    if (ks & 1) { w.x = dpp_ror8(w.x); w.y = dpp_ror8(w.y); w.z = dpp_ror8(w.z); w.w = dpp_ror8(w.w); }     // columns 8..15 -> 0..7
-                    fr[ks] = __builtin_bit_cast(bf16x8, w);
-                }
+            for (int ks = 0; ks < NK; ++ks) {
+                const u32x4 gg = gr[ks >> 1];
+                u32x4 w = {gg.x & ~TAGM, gg.y & ~TAGM, gg.z & ~TAGM, gg.w & ~TAGM};
+                if (ks & 1) { w.x = dpp_ror8(w.x); w.y = dpp_ror8(w.y); w.z = dpp_ror8(w.z); w.w = dpp_ror8(w.w); }     // columns 8..15 -> 0..7
+                fr[ks] = __builtin_bit_cast(bf16x8, w);
+            }
 #pragma unroll
-                for (int ks = 0; ks < NK; ++ks) {
-                    if ((ks & 1) == 0) {
-                        aA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfA[ks], fr[ks], aA, 0, 0, 0);
-                        aB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfB[ks], fr[ks], aB, 0, 0, 0);
-                        if constexpr (WLO) {
-                            aA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlA[ks], fr[ks], aA, 0, 0, 0);
-                            aB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlB[ks], fr[ks], aB, 0, 0, 0);
-                        }
-                    } else {
-                        aA1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfA[ks], fr[ks], aA1, 0, 0, 0);
-                        aB1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfB[ks], fr[ks], aB1, 0, 0, 0);
-                        if constexpr (WLO) {
-                            aA1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlA[ks], fr[ks], aA1, 0, 0, 0);
-                            aB1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlB[ks], fr[ks], aB1, 0, 0, 0);
-                        }
+            for (int ks = 0; ks < NK; ++ks) {
+                if ((ks & 1) == 0) {
+                    aA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfA[ks], fr[ks], aA, 0, 0, 0);
+                    aB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfB[ks], fr[ks], aB, 0, 0, 0);
+                    if constexpr (WLO) {
+                        aA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlA[ks], fr[ks], aA, 0, 0, 0);
+                        aB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlB[ks], fr[ks], aB, 0, 0, 0);
                     }
-                }
-            } else {
-    #pragma unroll
-                for (int ks = 0; ks < PF; ++ks) fr[ks] = *reinterpret_cast<const bf16x8*>(hb + fb_off + ks * 32);
-                __builtin_amdgcn_sched_barrier(0);
-    #pragma unroll
-                for (int ks = 0; ks < NK; ++ks) {
-                    if ((ks & 1) == 0) {
-                        aA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfA[ks], fr[ks], aA, 0, 0, 0);
-                        aB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfB[ks], fr[ks], aB, 0, 0, 0);
-                        if constexpr (WLO) {
-                            aA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlA[ks], fr[ks], aA, 0, 0, 0);
-                            aB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlB[ks], fr[ks], aB, 0, 0, 0);
-                        }
-                    } else {
-                        aA1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfA[ks], fr[ks], aA1, 0, 0, 0);
-                        aB1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfB[ks], fr[ks], aB1, 0, 0, 0);
-                        if constexpr (WLO) {
-                            aA1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlA[ks], fr[ks], aA1, 0, 0, 0);
-                            aB1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlB[ks], fr[ks], aB1, 0, 0, 0);
-                        }
+                } else {
+                    aA1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfA[ks], fr[ks], aA1, 0, 0, 0);
+                    aB1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfB[ks], fr[ks], aB1, 0, 0, 0);
+                    if constexpr (WLO) {
+                        aA1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlA[ks], fr[ks], aA1, 0, 0, 0);
+                        aB1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlB[ks], fr[ks], aB1, 0, 0, 0);
                     }
-                    if (ks + PF < NK) fr[ks + PF] = *reinterpret_cast<const bf16x8*>(hb + fb_off + (ks + PF) * 32);
-                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
             aA += aA1; aB += aB1;
@@ -359,7 +286,7 @@ __global__ __launch_bounds__(320) void gru_fwd_tf_kernel(GruArgs a) {
             const float hn = __uint_as_float(dpp_ror8(__float_as_uint(h)));       // unit 2q + 1 of the clip, from lane + 8
             if (pub_lane) {
                 const unsigned w = with_tag(pack2(h, hn), tag_bit((unsigned)(t + 1)) ? TAGM : 0u);
-                const unsigned soff = cbase + (unsigned)(t & 1) * panel_bytes;
+                const unsigned soff = cbase + (unsigned)par * panel_bytes;
                 if (plain) __builtin_amdgcn_raw_buffer_store_b32(w, rs, pub_v, soff, 0);
                 else __builtin_amdgcn_raw_buffer_store_b32(w, rs, pub_v, soff, 16);
             }
@@ -367,7 +294,7 @@ __global__ __launch_bounds__(320) void gru_fwd_tf_kernel(GruArgs a) {
         if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[3] += tq1 - tq0; tq0 = tq1; }
         const float an = (1.f - z) * (1.f - n * n);
         if (act) {                                             // saves into parity t & 1 (the helper reads them after the next barrier)
-            float* sl = sl0 + (t & 1) * (6 * 8 * SS);
+            float* sl = sl0 + par * (6 * 8 * SS);
             sl[0 * 8 * SS] = h;
             sl[1 * 8 * SS] = an * ghn * r * (1.f - r);
             sl[2 * 8 * SS] = (hp - n) * z * (1.f - z);
@@ -388,7 +315,8 @@ __global__ __launch_bounds__(320) void gru_fwd_tf_kernel(GruArgs a) {
 }
 
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+// bytes of dynamic LDS in front of the all-gather backward kernel's reduction buffer: [8 clips][3 Hg + 8] bf16
+constexpr size_t ag_img_bytes(int Hg) { return (size_t)8 * (3 * Hg + 8) * 2; }
 
 // ---------------------------------------------------------------------------------
 // backward, ALL-GATHER form on the tag-free hand-off (round 4).  dh_{s-1} = dout_{s-1} + z_s . dh_s + (dh_s . c_s) W_hh:
@@ -396,29 +324,30 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // product panel p_s = (dh_s . c_r, dh_s . c_z, dh_s . c_n) as its B operand and W_hh^T as the resident A operand:
 //   * publish: the 3 x 32 products of the own units per clip, bf16 with the epoch bit in bit 14, scaled by 2^-64 (exact; the
 //     reduced sum is multiplied by 2^64): 1.5 KB per workgroup and step instead of the reduce-scatter form's 10 KB;
-//   * sweep: the whole panel [clip][gate][Hg] (30 KB at Hg = 640, 8 x 16-byte loads per thread) straight into the LDS image --
-//     measured on the forward kernel (gru_xsweep: 30 KB swept + 3 publishes per step): sweep 590 -> 890 cycles, against the
+//   * sweep: the whole panel (30 KB at Hg = 640), each wave the chunks of its own k-steps -- measured beforehand on the forward
+//     kernel with repeated sweeps / publishes (30 KB swept + 3 publishes per step): sweep 590 -> 890 cycles, against the
 //     1520 cycles the reduce-scatter kernel waits for its 20 producers' partial sums;
 //   * 3 Hg / 32 k-steps split over the four waves (15 each at Hg = 640), two 16-unit tiles: 30 MFMAs per wave and step as
 //     before, the K reduction through LDS is two tiles per wave instead of the forward's six;
 //   * the partial sums are never rounded: f32 accumulation over the whole K (the reduce-scatter form exchanged 20 bf16 partials).
-// The loader wave (operand ring, dh / gate-gradient rows to HBM) is that of gru_bwd_tf_kernel with the forward helper's two
+// The loader wave (operand ring, dh / gate-gradient rows to HBM) is that of gru_bwd_rs_kernel with the forward helper's two
 // barriers per step.
 // ---------------------------------------------------------------------------------
 // DGI: 0 = dh only; 3 / 4 = the gate-gradient rows too (a.dg_slabs slabs) -- compile-time, so that the loader wave's loop is
 // straight-line code and the compiler's in-order vmcnt counts are EXACT (see the loader)
-// RD: no LDS image -- a wave sweeps exactly the chunks that ARE its MFMA B fragments (k-steps wv + 4 i of every clip: NKW 16-byte loads per
-// lane, one base address + immediate offsets) straight into registers and checks its own tags; the tag bits are cleared beside the MFMAs.
-template <int P, bool TIMED = false, int DGI = 0, bool RD = false>
-__global__ __launch_bounds__(320) void gru_bwd_ag_kernel(GruArgs a) {
-    constexpr int Hg = P * 32, K3 = 3 * Hg, NKS = K3 / 32, NKW = (NKS + 3) / 4, LD = K3 + 8;
-    constexpr int NCH = K3 / 8, NS = (8 * NCH + 255) / 256;         // 16-byte chunks per clip row; sweep slots per thread
+// The sweep is REGISTER-DIRECT, no LDS image -- a wave sweeps exactly the chunks that ARE its MFMA B fragments (k-steps wv + 4 i of every clip:
+// NKW 16-byte loads per lane, one base address + immediate offsets) straight into registers and checks its own tags; the tag bits are cleared
+// beside the MFMAs.
+template <int P, bool TIMED = false, int DGI = 0>
+__global__ __launch_bounds__(TF_THREADS) void gru_bwd_ag_kernel(GruArgs a) {
+    constexpr int Hg = P * 32, K3 = 3 * Hg, NKS = K3 / 32, NKW = (NKS + 3) / 4;
     constexpr float SC = 5.421010862427522e-20f, ISC = 1.8446744073709552e19f;     // 2^-64, 2^64
     unsigned long long tph[5] = {0, 0, 0, 0, 0}, tq0 = 0, tq1 = 0;
     (void)tph; (void)tq0; (void)tq1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    __bf16* const pB = reinterpret_cast<__bf16*>(smem_raw);                             // [8 clips][LD]: B operand (p_s)
-    float* const red = reinterpret_cast<float*>(pB + 8 * LD);                           // [4 waves][2 tiles][RED_TS]
+    // (the first ag_img_bytes(Hg) of the dynamic LDS were the LDS-image form's copy of the panel; the room and its zero fill are kept so
+    //  that the kernels stay instruction for instruction, and LDS byte for byte, what was measured)
+    float* const red = reinterpret_cast<float*>(smem_raw + ag_img_bytes(Hg));           // [4 waves][2 tiles][RED_TS]
     constexpr int RS = 36;
     __shared__ __attribute__((aligned(16))) float op_d[4][8][RS], op_z[4][8][RS];       // ring slot = iteration & 3
     __shared__ __attribute__((aligned(16))) __bf16 op_c[4][8][96];
@@ -437,7 +366,7 @@ __global__ __launch_bounds__(320) void gru_bwd_ag_kernel(GruArgs a) {
     constexpr unsigned panel_bytes = (unsigned)(8 * K3) * 2u;          // [clip][gate][Hg] bf16, the tag inside
     const unsigned cbase = (unsigned)chain * 2u * panel_bytes;
 
-    for (int i = tid; i < 8 * LD / 8; i += 320) reinterpret_cast<u32x4*>(pB)[i] = (u32x4){0u, 0u, 0u, 0u};
+    for (int i = tid; i < (int)(ag_img_bytes(Hg) / 16); i += 320) reinterpret_cast<u32x4*>(smem_raw)[i] = (u32x4){0u, 0u, 0u, 0u};
 
     const unsigned frame_bytes = (unsigned)H * 4u, crow_bytes = (unsigned)(a.G * K3) * 2u;
     const long long nrow = (long long)(a.B - 1) * a.TS + a.T;           // rows reachable from the (advanced) base pointers
@@ -567,39 +496,24 @@ __global__ __launch_bounds__(320) void gru_bwd_ag_kernel(GruArgs a) {
         }
     }
 
-    // sweep slots: 16-byte chunk e = tid + 256 j of the panel = clip e / NCH, elements 8 (e % NCH) .. + 7 of its row (clamped for
-    // short chains and beyond the panel: the last valid chunk is then fetched and stored twice)
-    const int nload = nb * NCH;
-    unsigned sw_v[NS];
-    int sw_l[NS];
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        const int e = min(tid + 256 * j, nload - 1);
-        const int bl_ = e / NCH, v = 8 * (e - bl_ * NCH);
-        sw_v[j] = (unsigned)e * 16u;
-        sw_l[j] = bl_ * LD + v;
-    }
-
     // pointwise: thread = (clip bl, unit u)
     const int u = tid & 31, bl = tid >> 5;
     const bool act = bl < nb;
     const int blc = act ? bl : 0;
     const int half = u >> 4, ru = u & 15;
     const int lp = (ru >> 2) * 16 + bl;
-    const unsigned pub_v = RD ? (unsigned)(((((u0 + u) >> 3) * 8 + blc) * 8 + (u & 7)) * 2)           // + gate * (Hg / 8) * 128
-                              : (unsigned)((blc * 3) * Hg + u0 + u) * 2u;                            // + gate * Hg * 2
-    constexpr unsigned pub_gs = RD ? (unsigned)(Hg / 8) * 128u : (unsigned)Hg * 2u;
+    const unsigned pub_v = (unsigned)(((((u0 + u) >> 3) * 8 + blc) * 8 + (u & 7)) * 2);              // + gate * (Hg / 8) * 128
+    constexpr unsigned pub_gs = (unsigned)(Hg / 8) * 128u;
     const bool pub_lane = act && !(u & 1);
-    const int fb_off = (lane & 7) * LD + (lane >> 4) * 8;                 // (columns 8..15 re-read clips 0..7)
     // (NKS % 4 != 0 -- Hg = 160, 320: the last waves' missing k-steps re-read k-step NKS - 1 (valid tags, finite data) against zero weights)
-    // RD panel layout: CLIP-MINOR -- [k chunk of 8 elements][clip][8] -- so that the 8 clips of one (k-step, lane group) are one 128-byte
+    // panel layout: CLIP-MINOR -- [k chunk of 8 elements][clip][8] -- so that the 8 clips of one (k-step, lane group) are one 128-byte
     // line and a wave's load instruction is 512 contiguous bytes (clip-major rows made every 16-lane pass touch 8 lines: 4500-cycle sweeps)
     const unsigned rd_v = (unsigned)(((wv * 4 + (lane >> 4)) * 8 + (lane & 7)) * 16);         // + i * 2048 bytes: k-step wv + 4 i
     // (columns 8..15: the odd k-step of the pair, + 2048; in the last, half-empty pair they re-read the even one)
     const unsigned rd_v2 = rd_v + (((lane >> 3) & 1) ? 2048u : 0u), rd_v2l = rd_v;
     constexpr int NL_ = (NKW + 1) / 2;
-    unsigned rd_o[(RD && NKS % 4 != 0) ? NL_ : 1];          // per-load byte offsets where k-steps have to be clamped
-    if constexpr (RD && NKS % 4 != 0) {
+    unsigned rd_o[NKS % 4 != 0 ? NL_ : 1];                  // per-load byte offsets where k-steps have to be clamped
+    if constexpr (NKS % 4 != 0) {
 #pragma unroll
         for (int j = 0; j < NL_; ++j) {
             const int i = min(2 * j + ((lane >> 3) & 1), NKW - 1);
@@ -619,7 +533,7 @@ __global__ __launch_bounds__(320) void gru_bwd_ag_kernel(GruArgs a) {
         const int s = a.T - 1 - k;
         float m = 0.f;
         if constexpr (TIMED) tq0 = __builtin_amdgcn_s_memtime();
-        if (k > 0 && RD) {
+        if (k > 0) {
             // NL = ceil(NKW / 2) loads per lane: columns 0..7 of the MFMA (lanes with (lane & 15) < 8) fetch the fragment of k-step 2 j, the
             // otherwise idle columns 8..15 that of k-step 2 j + 1 of the same clip; a DPP row rotate brings it over when its MFMAs are due.
             // (With every lane loading its own column's fragment -- columns 8..15 duplicates -- the 60 load instructions of a workgroup
@@ -683,67 +597,6 @@ __global__ __launch_bounds__(320) void gru_bwd_ag_kernel(GruArgs a) {
             for (int w = 0; w < 4; ++w) m += red[(w * 2 + half) * RED_TS + red_vec(lp) + (ru & 3)];
             m *= ISC;
         }
-        if (k > 0 && !RD) {
-            const unsigned soff = cbase + (unsigned)((k - 1) & 1) * panel_bytes;
-            const unsigned flip = tag_bit((unsigned)k) ? 0xffffffffu : 0u;
-            u32x4 g[NS];
-            unsigned spins = 0;
-            for (int i = 0; i < a.poll_delay; ++i) __builtin_amdgcn_s_sleep(1);     // (see poll_delay)
-            for (;;) {
-#pragma unroll
-                for (int j = 0; j < NS; ++j) g[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, sw_v[j], soff, 16);
-                unsigned bad = 0u;
-#pragma unroll
-                for (int j = 0; j < NS; ++j) bad |= (g[j].x ^ flip) | (g[j].y ^ flip) | (g[j].z ^ flip) | (g[j].w ^ flip);
-                if (__all((bad & TAGM) == 0u || nowait)) break;
-                if (++spins >= SPIN_LIMIT) {
-                    if (lane == 0) __hip_atomic_store(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    nowait = true;
-                }
-                if constexpr (TIMED) tph[4] += 1;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[0] += tq1 - tq0; tq0 = tq1; }
-#pragma unroll
-            for (int j = 0; j < NS; ++j) {
-                const u32x4 w = {g[j].x & ~TAGM, g[j].y & ~TAGM, g[j].z & ~TAGM, g[j].w & ~TAGM};
-                *reinterpret_cast<u32x4*>(pB + sw_l[j]) = w;
-            }
-            __syncthreads();                                   // image complete
-            if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[1] += tq1 - tq0; tq0 = tq1; }
-            // four accumulator chains (two per tile): with two, every MFMA waited for the one issued just before its predecessor
-            // (1445 cycles for the 30 MFMAs against the forward kernel's 1040 with six chains, s_memtime stamps)
-            f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
-            // fragment reads run PF k-steps ahead of their MFMAs, pinned by sched_barrier (left alone the scheduler keeps two fragment
-            // registers and exposes an LDS round trip every second k-step -- as in gru_fwd_tf_kernel)
-            constexpr int PF = NKW < 6 ? NKW : 6;
-            bf16x8 fr[NKW];
-#pragma unroll
-            for (int i = 0; i < PF; ++i) fr[i] = *reinterpret_cast<const bf16x8*>(pB + fb_off + min(wv + 4 * i, NKS - 1) * 32);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < NKW; ++i) {
-                if (NKS % 4 == 0 || wv + 4 * i < NKS) {        // wave-uniform (weights beyond NKS are zero anyway)
-                    if (i & 1) {
-                        acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][i], fr[i], acc2, 0, 0, 0);
-                        acc3 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1][i], fr[i], acc3, 0, 0, 0);
-                    } else {
-                        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][i], fr[i], acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1][i], fr[i], acc1, 0, 0, 0);
-                    }
-                }
-                if (i + PF < NKW) fr[i + PF] = *reinterpret_cast<const bf16x8*>(pB + fb_off + min(wv + 4 * (i + PF), NKS - 1) * 32);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            acc0 += acc2; acc1 += acc3;
-            *reinterpret_cast<f32x4*>(red + (wv * 2 + 0) * RED_TS + red_vec(lane)) = acc0;
-            *reinterpret_cast<f32x4*>(red + (wv * 2 + 1) * RED_TS + red_vec(lane)) = acc1;
-            __syncthreads();
-            if constexpr (TIMED) { tq1 = __builtin_amdgcn_s_memtime(); tph[2] += tq1 - tq0; tq0 = tq1; }
-#pragma unroll
-            for (int w = 0; w < 4; ++w) m += red[(w * 2 + half) * RED_TS + red_vec(lp) + (ru & 3)];
-            m *= ISC;
-        }
         dh = dd + zz * dh + m;
         if (act) dh_l[k & 1][bl][u] = dh;                      // the loader wave writes it (and the gate gradients) to HBM
         if (s == 0) break;                                     // nothing consumes the products of time 0
@@ -789,18 +642,19 @@ __global__ __launch_bounds__(320) void gru_bwd_ag_kernel(GruArgs a) {
 
 namespace cruse_gru {
 
-bool fwd_tf_eligible(int Bg, int Hg, int prec, bool has_h0, bool gi_bf16) {
+bool fwd_tf_eligible(int Bg, int Hg, int prec, bool has_h0, bool gi_f16) {
     if (cruse_opt("gru_tf", 1) == 0) return false;             // A/B switch (tests, probes): 0 = the tagged kernels of gru.hip
     // Hg = 640: the K-split-free step measured slower than the lean kernel's (1.36 against 1.27 us per step; 40 instead of 30 MFMAs
     // per wave on the serial chain) -- there the lean kernel runs on the tag-free hand-off instead (gru.hip, TF)
-    return prec == CRUSE_PREC_BF16 && Bg == 8 && !has_h0 && !gi_bf16 && (Hg == 160 || Hg == 320);
+    return prec == CRUSE_PREC_BF16 && Bg == 8 && !has_h0 && !gi_f16 && (Hg == 160 || Hg == 320);
 }
 
 int dispatch_fwd_tf(const GruArgs& a, int grid, bool wlo, hipStream_t s) {
-    if (a.Hg == 160) return wlo ? launch_one(gru_fwd_tf_kernel<5, 1, true, false, true>, a, grid, 0, s, "gru_seq_fwd", 320)
-                                : launch_one(gru_fwd_tf_kernel<5, 1, false, false, true>, a, grid, 0, s, "gru_seq_fwd", 320);
-    return wlo ? launch_one(gru_fwd_tf_kernel<10, 2, true, false, true>, a, grid, 0, s, "gru_seq_fwd", 320)
-               : launch_one(gru_fwd_tf_kernel<10, 2, false, false, true>, a, grid, 0, s, "gru_seq_fwd", 320);
+    return dispatch_int<5, 10>(a.Hg / 32, [&](auto nk) {
+        constexpr int NK = decltype(nk)::value;
+        return wlo ? launch_one(gru_fwd_tf_kernel<NK, true>, a, grid, 0, s, "gru_seq_fwd", TF_THREADS)
+                   : launch_one(gru_fwd_tf_kernel<NK, false>, a, grid, 0, s, "gru_seq_fwd", TF_THREADS);
+    });
 }
 
 bool bwd_tf_eligible(int Bg, int Hg, int prec) {
@@ -808,21 +662,20 @@ bool bwd_tf_eligible(int Bg, int Hg, int prec) {
     return prec == CRUSE_PREC_BF16 && Bg == 8 && (Hg == 160 || Hg == 320 || Hg == 640);
 }
 
-size_t bwd_ag_lds(int Hg) { return (size_t)8 * (3 * Hg + 8) * 2 + (size_t)4 * 2 * RED_TS * 4; }
+size_t bwd_ag_lds(int Hg) { return ag_img_bytes(Hg) + (size_t)4 * 2 * RED_TS * 4; }
 
-// the all-gather kernel with the register-direct sweep (the LDS-image form and the tag-free reduce-scatter kernel measured slower: r4)
-int dispatch_bwd_tf(const GruArgs& a, int grid, hipStream_t s) {
-#define CRUSE_AG_LAUNCH(PV)                                                                                                             \
-    do {                                                                                                                                \
-        if (a.dbg == 32) return launch_one(gru_bwd_ag_kernel<PV, true, 0, true>, a, grid, bwd_ag_lds(32 * PV), s, "gru_seq_bwd", 320);   \
-        if (a.dgi == nullptr) return launch_one(gru_bwd_ag_kernel<PV, false, 0, true>, a, grid, bwd_ag_lds(32 * PV), s, "gru_seq_bwd", 320); \
-        if (a.dg_slabs == 4) return launch_one(gru_bwd_ag_kernel<PV, false, 4, true>, a, grid, bwd_ag_lds(32 * PV), s, "gru_seq_bwd", 320); \
-        return launch_one(gru_bwd_ag_kernel<PV, false, 3, true>, a, grid, bwd_ag_lds(32 * PV), s, "gru_seq_bwd", 320);                   \
-    } while (0)
-    if (a.Hg == 640) CRUSE_AG_LAUNCH(20);
-    if (a.Hg == 320) CRUSE_AG_LAUNCH(10);
-    CRUSE_AG_LAUNCH(5);
-#undef CRUSE_AG_LAUNCH
+template <int P>
+static int launch_bwd_ag(const GruArgs& a, int grid, hipStream_t s) {
+    const size_t lds = bwd_ag_lds(32 * P);
+    if (a.dbg == 32) return launch_one(gru_bwd_ag_kernel<P, true, 0>, a, grid, lds, s, "gru_seq_bwd", TF_THREADS);
+    if (a.dgi == nullptr) return launch_one(gru_bwd_ag_kernel<P, false, 0>, a, grid, lds, s, "gru_seq_bwd", TF_THREADS);
+    if (a.dg_slabs == 4) return launch_one(gru_bwd_ag_kernel<P, false, 4>, a, grid, lds, s, "gru_seq_bwd", TF_THREADS);
+    return launch_one(gru_bwd_ag_kernel<P, false, 3>, a, grid, lds, s, "gru_seq_bwd", TF_THREADS);
+}
+
+// the all-gather kernel (a form with an LDS image of the panel and a tag-free reduce-scatter kernel measured slower: r4)
+int dispatch_bwd_ag(const GruArgs& a, int grid, hipStream_t s) {
+    return dispatch_int<20, 10, 5>(a.Hg / 32, [&](auto p) { return launch_bwd_ag<decltype(p)::value>(a, grid, s); });
 }
 
 }  // namespace cruse_gru

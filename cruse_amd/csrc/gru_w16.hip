@@ -11,11 +11,11 @@
 //     clip-minor, [k chunk of 8 elements][clip 16][8 bf16], so the B fragment of (k-step, lane group q, clip c) is the 16 bytes at
 //     ((ks * 4 + q) * 16 + c) * 16: lane (c = lane & 15, q = lane >> 4) loads ITS fragment of each of its k-steps, one load instruction
 //     of a wave is 1 KB contiguous, and no LDS image of the panel exists;
-//   * forward (gru_fwd_w16_kernel): gru_fwd_lean_kernel<.., TF, RD>'s step -- K split over four waves, 6 x NKW MFMAs per wave, K
+//   * forward (gru_fwd_w16_kernel): gru_fwd_lean_kernel<.., TF>'s step -- K split over four waves, 6 x NKW MFMAs per wave, K
 //     reduction through LDS in the same order: h, coefficients, a_n and z are BIT-IDENTICAL to the chains of 8 -- with two (clip, unit)
 //     pairs of gate math per thread (adjacent units: every LDS access of the gate phase is 8 bytes) and a helper wave that streams
 //     16 clips of gi rows / saves;
-//   * backward (gru_bwd_w16_kernel): gru_bwd_ag_kernel<.., RD>'s all-gather step on EIGHT compute waves (K = 3 Hg split eight ways:
+//   * backward (gru_bwd_w16_kernel): gru_bwd_ag_kernel's all-gather step on EIGHT compute waves (K = 3 Hg split eight ways:
 //     16 weight + 8 fragment vectors per lane instead of 30 + 15, which would not fit the 256 registers a five-wave workgroup
 //     leaves) plus the loader wave: 9 waves, <= 168 registers, one (clip, unit) of pointwise work per thread;
 //   * a sequence may be run as consecutive time chunks (cruse_gru_seq_*_ex sub-sequences): the first step of a continuation takes its
@@ -26,13 +26,16 @@ namespace {
 
 using namespace cruse_gru;
 
+constexpr int W16_FWD_THREADS = 320;         // four compute waves + the helper wave
+constexpr int W16_BWD_NW = 8;                // compute waves of the backward kernel
+constexpr int W16_BWD_THREADS = (W16_BWD_NW + 1) * 64;       // ... + the loader wave
 constexpr unsigned OOB = 0xfffffff0u;            // voffset beyond every buffer: raw-buffer loads return 0, stores are dropped
 
 // ---------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------
 template <int NKW, bool TIMED = false>
-__global__ __launch_bounds__(320) void gru_fwd_w16_kernel(GruArgs a) {
+__global__ __launch_bounds__(W16_FWD_THREADS) void gru_fwd_w16_kernel(GruArgs a) {
     constexpr int Hg = NKW * 128, NCHK = Hg / 8;
     // clip strides: 100 floats = 36 (mod 64) -- the 16 clips of a 32-lane group land on 16 different bank quads and the two unit
     // pairs (e2) on the halves of a quad: every ds_read_b64 of the gate phase is conflict-free
@@ -309,8 +312,8 @@ __global__ __launch_bounds__(320) void gru_fwd_w16_kernel(GruArgs a) {
 // of its own (clip, unit).  DGI: 0 = dh only; 3 / 4 = the loader wave also writes the gate-gradient rows (a.dg_slabs slabs).
 // ---------------------------------------------------------------------------------
 template <int P, int DGI, bool TIMED = false>
-__global__ __launch_bounds__(576) void gru_bwd_w16_kernel(GruArgs a) {
-    constexpr int Hg = P * 32, K3 = 3 * Hg, NKS = K3 / 32, NW = 8, NKW = (NKS + NW - 1) / NW, NCHK = K3 / 8;
+__global__ __launch_bounds__(W16_BWD_THREADS) void gru_bwd_w16_kernel(GruArgs a) {
+    constexpr int Hg = P * 32, K3 = 3 * Hg, NKS = K3 / 32, NW = W16_BWD_NW, NKW = (NKS + NW - 1) / NW, NCHK = K3 / 8;
     constexpr float SC = 5.421010862427522e-20f, ISC = 1.8446744073709552e19f;     // 2^-64, 2^64
     constexpr unsigned panel_bytes = (unsigned)NCHK * 256u;            // [k chunk][clip 16][8 bf16]
     constexpr int RS = 40;                                             // clip stride of the operand rings (floats)
@@ -609,32 +612,22 @@ bool w16_eligible(int Hg, int prec) {
 size_t w16_panel_bytes_per_parity(int Hg, bool fwd) { return (size_t)(fwd ? Hg : 3 * Hg) / 8 * 256; }
 
 int dispatch_fwd_w16(const GruArgs& a, int grid, hipStream_t s) {
-    if (a.dbg == 32 && a.Hg == 640) return launch_one(gru_fwd_w16_kernel<5, true>, a, grid, 0, s, "gru_seq_fwd", 320);
-    switch (a.Hg / 128) {
-        case 1: return launch_one(gru_fwd_w16_kernel<1>, a, grid, 0, s, "gru_seq_fwd", 320);
-        case 2: return launch_one(gru_fwd_w16_kernel<2>, a, grid, 0, s, "gru_seq_fwd", 320);
-        case 3: return launch_one(gru_fwd_w16_kernel<3>, a, grid, 0, s, "gru_seq_fwd", 320);
-        case 4: return launch_one(gru_fwd_w16_kernel<4>, a, grid, 0, s, "gru_seq_fwd", 320);
-        default: return launch_one(gru_fwd_w16_kernel<5>, a, grid, 0, s, "gru_seq_fwd", 320);
-    }
+    if (a.dbg == 32 && a.Hg == 640) return launch_one(gru_fwd_w16_kernel<5, true>, a, grid, 0, s, "gru_seq_fwd", W16_FWD_THREADS);
+    return dispatch_int<1, 2, 3, 4, 5>(a.Hg / 128, [&](auto nkw) {
+        return launch_one(gru_fwd_w16_kernel<decltype(nkw)::value>, a, grid, 0, s, "gru_seq_fwd", W16_FWD_THREADS);
+    });
 }
 
 template <int P>
 static int launch_bwd_w16(const GruArgs& a, int grid, hipStream_t s) {
-    if (a.dbg == 32) return launch_one(gru_bwd_w16_kernel<P, 0, true>, a, grid, 0, s, "gru_seq_bwd", 576);
-    if (a.dgi == nullptr) return launch_one(gru_bwd_w16_kernel<P, 0>, a, grid, 0, s, "gru_seq_bwd", 576);
-    if (a.dg_slabs == 4) return launch_one(gru_bwd_w16_kernel<P, 4>, a, grid, 0, s, "gru_seq_bwd", 576);
-    return launch_one(gru_bwd_w16_kernel<P, 3>, a, grid, 0, s, "gru_seq_bwd", 576);
+    if (a.dbg == 32) return launch_one(gru_bwd_w16_kernel<P, 0, true>, a, grid, 0, s, "gru_seq_bwd", W16_BWD_THREADS);
+    if (a.dgi == nullptr) return launch_one(gru_bwd_w16_kernel<P, 0>, a, grid, 0, s, "gru_seq_bwd", W16_BWD_THREADS);
+    if (a.dg_slabs == 4) return launch_one(gru_bwd_w16_kernel<P, 4>, a, grid, 0, s, "gru_seq_bwd", W16_BWD_THREADS);
+    return launch_one(gru_bwd_w16_kernel<P, 3>, a, grid, 0, s, "gru_seq_bwd", W16_BWD_THREADS);
 }
 
 int dispatch_bwd_w16(const GruArgs& a, int grid, hipStream_t s) {
-    switch (a.Hg / 128) {
-        case 1: return launch_bwd_w16<4>(a, grid, s);
-        case 2: return launch_bwd_w16<8>(a, grid, s);
-        case 3: return launch_bwd_w16<12>(a, grid, s);
-        case 4: return launch_bwd_w16<16>(a, grid, s);
-        default: return launch_bwd_w16<20>(a, grid, s);
-    }
+    return dispatch_int<1, 2, 3, 4, 5>(a.Hg / 128, [&](auto n) { return launch_bwd_w16<4 * decltype(n)::value>(a, grid, s); });
 }
 
 }  // namespace cruse_gru

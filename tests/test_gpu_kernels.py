@@ -1112,6 +1112,43 @@ def test_gru_all_gather_backward_on_grouped_widths(ops, G, B, T):
     assert torch.equal(out[2][1].view(-1), dgi_ref.view(-1))
 
 
+@pytest.mark.parametrize("G", [4, 2])
+def test_gru_all_gather_backward_writes_four_gate_slabs_on_grouped_widths(ops, G):
+    """gru_bwd_ag_kernel<5 | 10, .., DGI = 4>: the all-gather backward at Hg = 160 / 320 with the loader wave writing FOUR gate-gradient
+    slabs (r, z, n_i, n_h) -- the one built variant no other test launches (the neighbours take 3 slabs there, 4 only at Hg = 640).
+    B = 9: one full and one ragged chain; T = 5: both panel parities and the wrap-around.
+    Against the generic f32 kernels and their gate-gradient pass: dh within 1e-2 (the neighbouring tests' bound for this kernel), the
+    four slabs within 3e-2 (the bound test_gru_sequence_fwd_bwd sets for bf16-mode results: the slabs are dh times coefficients of the
+    bf16 FORWARD pass, stored as bf16).  As in test_gru_bwd_writes_gate_gradients_itself: the same dh as without gate gradients, slabs
+    0-2 bit-identical to the bf16 gate-gradient pass on that dh; slab 3 is the bf16 product dh * c_n (one multiplication, one rounding)."""
+    H, B, T = 640, 9, 5
+    Hg = H // G
+    rows = B * T
+    torch.manual_seed(G * 100 + 4)
+    gi = (0.5 * torch.randn(B, T, 3 * H)).cuda()
+    w = [(torch.randn(3 * Hg, Hg) / Hg ** 0.5).cuda() for _ in range(G)]; b = [(0.1 * torch.randn(3 * Hg)).cuda() for _ in range(G)]
+    dout = (2.0 * torch.randn(B, T, H)).cuda()
+    f32 = ops.gru_seq_fwd(gi, w, b, B, T, G, Hg, "f32")
+    ref = ops.gru_seq_bwd(dout, w, f32[1], f32[3], B, T, G, Hg, "f32")
+    dgi_f32, dgh_f32 = ops.gru_gate_grads(ref, f32[1], f32[2], rows, G, Hg, "f32")
+    ref4 = torch.cat([dgi_f32.view(rows, G, 3, Hg), dgh_f32.view(rows, G, 3, Hg)[:, :, 2:]], dim=2)      # r, z, n_i, n_h
+    h, coef, an, z = ops.gru_seq_fwd(gi, w, b, B, T, G, Hg, "bf16")
+    dh, dgi = ops.gru_seq_bwd(dout, w, coef, z, B, T, G, Hg, "bf16", an=an, want_dgi=True, dg_slabs=4)
+    plain = ops.gru_seq_bwd(dout, w, coef, z, B, T, G, Hg, "bf16")
+    torch.cuda.synchronize()
+    assert ops.gru_status() == 0 and torch.equal(plain, dh)
+    dgi = dgi.view(rows, G, 4, Hg)
+    e_dh, e_dgi = rel_l2(dh, ref), rel_l2(dgi.float(), ref4)
+    print(f"[gru ag 4 slabs Hg={Hg}] rel-L2 vs the f32 kernels: dh {e_dh:.2e}, gate-gradient slabs {e_dgi:.2e}")
+    assert torch.isfinite(dh).all() and e_dh < 1e-2
+    assert torch.isfinite(dgi.float()).all() and e_dgi < 3e-2
+    db_i = [torch.zeros(3 * Hg).cuda() for _ in range(G)]; db_h = [torch.zeros(3 * Hg).cuda() for _ in range(G)]
+    dgi3, _, _ = ops.gru_gate_grads_bf16(dh, coef, an, rows, G, Hg, db_i, db_h)
+    assert torch.equal(dgi[:, :, :3].contiguous().view(torch.int16), dgi3.view(rows, G, 3, Hg).contiguous().view(torch.int16))
+    want3 = (dh.view(rows, G, Hg) * coef.view(rows, G, 3, Hg)[:, :, 2].float()).to(torch.bfloat16)
+    assert torch.equal(dgi[:, :, 3].contiguous().view(torch.int16), want3.view(torch.int16))
+
+
 @pytest.mark.parametrize("B,T", [(9, 12), (3, 1), (5, 2), (8, 3), (20, 37), (64, 60)])
 def test_gru_register_direct_sweeps_and_all_gather_backward(ops, B, T):
     """Round-4 recurrence kernels at Hg = 640 (bf16 mode).  Forward: the tag-free register-direct sweep (default) gives the bits of the
