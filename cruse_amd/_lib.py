@@ -145,6 +145,10 @@ SIGNATURES = {
     "cruse_stream_gru_f16": ("piiiipiippfpiipppiip", "i"),
     "cruse_stream_gru_proj_n_f16": ("piiiiiipiippfpppp", "i"),
     "cruse_stream_gru_rec_n_f16": ("piiiiiippiipppiip", "i"),
+    "cruse_stream_encode_io": ("piiiiiipippppp", "i"),
+    "cruse_stream_decode_io": ("piiiiiippfpppippp", "i"),
+    "cruse_stream_encode_n_io": ("piiiiiiiiipippppp", "i"),
+    "cruse_stream_decode_n_io": ("piiiiiiiiippfpppippp", "i"),
 }
 
 

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include "stream_common.h"
 
 namespace {
@@ -83,6 +84,31 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     float s = 0.f;
     for (int i = 0; i < nw; ++i) s += red[i];
     return s;
+}
+
+// ---- the sample formats of the I/O forms (cruse_stream_*_io): the boundary kernels are templates on the element type of `in` / `out`,
+// float or short (16-bit PCM), and decode on LIM (the per-slot attenuation limit).  <float> / <float, false> are what the plain entry
+// points launch; every form shares all arithmetic between the load of a sample and the store of one.
+__device__ __forceinline__ float ld_sample(const float* p, int i) { return p[i]; }
+__device__ __forceinline__ float ld_sample(const short* p, int i) { return (float)p[i] / 32768.0f; }      // exact
+
+// stores y; true where a PCM sample was clamped: clamp(rint(y * 32768), -32768, 32767), ties to even
+__device__ __forceinline__ bool st_sample(float* p, size_t i, float y) {
+    p[i] = y;
+    return false;
+}
+__device__ __forceinline__ bool st_sample(short* p, size_t i, float y) {
+    const float r = rintf(y * 32768.0f);
+    const float c = fminf(fmaxf(r, -32768.0f), 32767.0f);
+    p[i] = (short)__float2int_rn(c);
+    return c != r;
+}
+
+// clip[s] += the samples this launch clamped for slot s.  One workgroup per slot and launch, launches ordered: a plain store.
+__device__ __forceinline__ void count_clipped(int* __restrict__ clip, int s, int mine, float* red) {
+    if (clip == nullptr) return;                          // uniform over the workgroup
+    const float n = block_sum((float)mine, red);          // at most a few thousand: exact in f32
+    if (threadIdx.x == 0) clip[s] += (int)n;
 }
 
 // The convolutions run over the nf frames of a packet (nf = 1: the single hop); frame f's rows are fs floats apart.  Weight rows are ws
@@ -184,7 +210,8 @@ __device__ __forceinline__ float irdft320(const float* re, const float* im, cons
     return (re[0] + 2.0f * acc + ((n & 1) ? -re[F0] : re[F0])) * (1.0f / NFFT);
 }
 
-__global__ void __launch_bounds__(1024) stream_encode_kernel(const int* __restrict__ mode, Layout L, const float* __restrict__ in,
+template <typename IN>
+__global__ void __launch_bounds__(1024) stream_encode_kernel(const int* __restrict__ mode, Layout L, const IN* __restrict__ in,
                                                             const float* __restrict__ tab, const float* __restrict__ w,
                                                             float* __restrict__ state, float* __restrict__ work) {
     extern __shared__ float sm[];
@@ -192,10 +219,10 @@ __global__ void __launch_bounds__(1024) stream_encode_kernel(const int* __restri
     if (m == CRUSE_STREAM_MODE_SKIP) return;
     float* st = state + (size_t)s * L.st_stride;
     float* wk = work + (size_t)s * L.wk_stride;
-    const float* blk = in + (size_t)s * HOP;
+    const IN* blk = in + (size_t)s * HOP;
     const int tid = threadIdx.x;
     if (m == CRUSE_STREAM_MODE_STORE) {
-        for (int i = tid; i < HOP; i += blockDim.x) st[L.st_hist + 1 + i] = blk[i];
+        for (int i = tid; i < HOP; i += blockDim.x) st[L.st_hist + 1 + i] = ld_sample(blk, i);
         return;
     }
     // LDS: frame[320] | rows of levels 0..4 (current) | previous rows of levels 0..3 | re[161] | im[161]
@@ -212,14 +239,14 @@ __global__ void __launch_bounds__(1024) stream_encode_kernel(const int* __restri
     for (int i = tid; i < HOP; i += blockDim.x) {
         float a, bq;
         if (m == CRUSE_STREAM_MODE_FRAME0) {          // x[160], x[159], ..., x[1] | x[0..159]
-            a = i == 0 ? blk[0] : hist[161 - i];
+            a = i == 0 ? ld_sample(blk, 0) : hist[161 - i];
             bq = hist[1 + i];
         } else if (m == CRUSE_STREAM_MODE_END) {      // last block | x[L-2], ..., x[L-161]
             a = hist[1 + i];
             bq = hist[159 - i];
         } else {                                      // previous block | this block
             a = hist[1 + i];
-            bq = blk[i];
+            bq = ld_sample(blk, i);
         }
         fr[i] = a * tab[TB_WIN + i];
         fr[HOP + i] = bq * tab[TB_WIN + HOP + i];
@@ -231,7 +258,7 @@ __global__ void __launch_bounds__(1024) stream_encode_kernel(const int* __restri
         const float last = hist[HOP];
         __syncthreads();
         if (tid == 0) st[L.st_hist] = last;
-        for (int i = tid; i < HOP; i += blockDim.x) st[L.st_hist + 1 + i] = blk[i];
+        for (int i = tid; i < HOP; i += blockDim.x) st[L.st_hist + 1 + i] = ld_sample(blk, i);
     }
     // 320-point real DFT, bins 0..160; magnitude of bins 0..159
     for (int k = tid; k < NB; k += blockDim.x) {
@@ -383,9 +410,13 @@ __global__ void __launch_bounds__(256) stream_gru_f32_kernel(GruArgs a) {
     }
 }
 
+// lim[s] (LIM): the slot's attenuation limit as a gain, the output is lim * noisy + (1 - lim) * enhanced, mixed on the spectrum;
+// clip[s] (PCM out, may be null): the count of clamped samples
+template <typename OUT, bool LIM>
 __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restrict__ mode, Layout L, const float* __restrict__ tab,
                                                             const float* __restrict__ w, float ln_eps, float* __restrict__ state,
-                                                            float* __restrict__ work, float* __restrict__ out) {
+                                                            float* __restrict__ work, OUT* __restrict__ out,
+                                                            const float* __restrict__ lim, int* __restrict__ clip) {
     extern __shared__ float sm[];
     const int s = blockIdx.x, m = mode[s];
     if (!mode_computes_frame(m)) return;
@@ -423,21 +454,35 @@ __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restri
         __syncthreads();
     }
     // mask on bins 0..159 (bin 160 zero), 320-point inverse real DFT (imaginary parts of bins 0 and 160 ignored, as irfft)
-    for (int i = tid; i < F0; i += blockDim.x) {
-        wk[L.wk_mask + i] = row[0][i];
-        re[i] *= row[0][i];
-        im[i] *= row[0][i];
+    if constexpr (LIM) {                                  // gain = lim + (1 - lim) * mask; bin 160 keeps lim of the input
+        const float lm = lim[s];
+        for (int i = tid; i < F0; i += blockDim.x) {
+            wk[L.wk_mask + i] = row[0][i];
+            const float gain = fmaf(1.0f - lm, row[0][i], lm);
+            re[i] *= gain;
+            im[i] *= gain;
+        }
+        if (tid == 0) { re[F0] *= lm; im[F0] *= lm; }
+    } else {
+        for (int i = tid; i < F0; i += blockDim.x) {
+            wk[L.wk_mask + i] = row[0][i];
+            re[i] *= row[0][i];
+            im[i] *= row[0][i];
+        }
+        if (tid == 0) { re[F0] = 0.f; im[F0] = 0.f; }
     }
-    if (tid == 0) { re[F0] = 0.f; im[F0] = 0.f; }
     __syncthreads();
     for (int n = tid; n < NFFT; n += blockDim.x)
         y[n] = irdft320(re, im, tab + TB_COS, n) * tab[TB_WIN + n];
     __syncthreads();
     // overlap-add with the stored tail, divide by the window envelope: output block; the second half becomes the tail
+    int nclip = 0;
     for (int i = tid; i < HOP; i += blockDim.x) {
-        out[(size_t)s * HOP + i] = (st[L.st_tail + i] + y[i]) * tab[TB_IENV + i];
+        nclip += st_sample(out, (size_t)s * HOP + i, (st[L.st_tail + i] + y[i]) * tab[TB_IENV + i]);
         st[L.st_tail + i] = y[HOP + i];
     }
+    // the frame-0 chain's block lies in front of the clip (the main chain of the same push overwrites it): not counted
+    if constexpr (!std::is_same<OUT, float>::value) count_clipped(clip, s, m == CRUSE_STREAM_MODE_FRAME0 ? 0 : nclip, red);
 }
 
 template <int KIND, int KQ>
@@ -506,9 +551,10 @@ int packet_max_frames(const Layout& L) {
     return avail <= 0 ? 0 : avail / (2 * packet_row_max(L));
 }
 
+template <typename IN>
 __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __restrict__ pk, int S, int hops, int in_hops, int NFW,
                                                               Layout L, int WS, int e1, int e2, int e3, int rowmax, int wcap,
-                                                              const float* __restrict__ in, const float* __restrict__ tab, const float* __restrict__ w,
+                                                              const IN* __restrict__ in, const float* __restrict__ tab, const float* __restrict__ w,
                                                               float* __restrict__ state, float* __restrict__ work) {
     extern __shared__ float sm[];
     const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -517,10 +563,10 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
     float* st = state + (size_t)s * L.st_stride;
     float* wk = work + (size_t)s * NFW * WS;
     const int eoff[4] = {0, e1, e2, e3};
-    const float* blk = in + (size_t)s * in_hops * HOP;
+    const IN* blk = in + (size_t)s * in_hops * HOP;
     float* hist = st + L.st_hist;
     if (p.nf == 0) {                                      // block 0 of a clip alone: stored, no frame
-        for (int i = tid; i < HOP; i += nt) hist[1 + i] = blk[i];
+        for (int i = tid; i < HOP; i += nt) hist[1 + i] = ld_sample(blk, i);
         return;
     }
     const int nf = p.nf;
@@ -531,8 +577,8 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
     float* Wb = P + rowmax;
     // block v of the sequence (the stored block first where the slot holds one), sample i
     auto vget = [&](int v, int i) -> float {
-        if (p.hist) return v == 0 ? hist[1 + i] : blk[(v - 1) * HOP + i];
-        return blk[v * HOP + i];
+        if (p.hist) return v == 0 ? hist[1 + i] : ld_sample(blk, (v - 1) * HOP + i);
+        return ld_sample(blk, v * HOP + i);
     };
     const int nv = p.hist + p.c, off = p.f0 ? 0 : 1;
     for (int idx = tid; idx < nf * HOP; idx += nt) {
@@ -553,7 +599,7 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
     const float before = nv >= 2 ? vget(nv - 2, HOP - 1) : hist[0];        // the sample in front of the last block
     __syncthreads();
     if (tid == 0) hist[0] = before;
-    for (int i = tid; i < HOP; i += nt) hist[1 + i] = blk[(p.c - 1) * HOP + i];
+    for (int i = tid; i < HOP; i += nt) hist[1 + i] = ld_sample(blk, (p.c - 1) * HOP + i);
     // 320-point real DFT of every frame, bins 0..160; magnitude of bins 0..159
     for (int idx = tid; idx < nf * NB; idx += nt) {
         const int f = idx / NB, k = idx - f * NB;
@@ -591,10 +637,12 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
     }
 }
 
+template <typename OUT, bool LIM>
 __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __restrict__ pk, int S, int hops, int out_hops, int NFW,
                                                               Layout L, int WS, int rowmax, int wcap, const float* __restrict__ tab,
                                                               const float* __restrict__ w, float ln_eps, float* __restrict__ state,
-                                                              float* __restrict__ work, float* __restrict__ out) {
+                                                              float* __restrict__ work, OUT* __restrict__ out,
+                                                              const float* __restrict__ lim, int* __restrict__ clip) {
     extern __shared__ float sm[];
     const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const Pkt p = packet_of(pk, S, s, hops);
@@ -643,13 +691,26 @@ __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __rest
         float* t = src; src = dst; dst = t;
     }
     // src: the masks.  Masked spectrum re[161] | im[161] of every frame into dst (bin 160 zero), cos / sin tables into Wb
-    for (int idx = tid; idx < nf * NB; idx += nt) {
-        const int f = idx / NB, k = idx - f * NB;
-        float* row = wk + (size_t)f * WS;
-        const float m = k < F0 ? src[f * rowmax + k] : 0.f;
-        if (k < F0) row[L.wk_mask + k] = m;
-        dst[f * rowmax + k] = row[L.wk_re + k] * m;
-        dst[f * rowmax + NB + k] = row[L.wk_im + k] * m;
+    if constexpr (LIM) {                                  // gain = lim + (1 - lim) * mask; bin 160 keeps lim of the input
+        const float lm = lim[s];
+        for (int idx = tid; idx < nf * NB; idx += nt) {
+            const int f = idx / NB, k = idx - f * NB;
+            float* row = wk + (size_t)f * WS;
+            const float m = k < F0 ? src[f * rowmax + k] : 0.f;
+            if (k < F0) row[L.wk_mask + k] = m;
+            const float gain = k < F0 ? fmaf(1.0f - lm, m, lm) : lm;
+            dst[f * rowmax + k] = row[L.wk_re + k] * gain;
+            dst[f * rowmax + NB + k] = row[L.wk_im + k] * gain;
+        }
+    } else {
+        for (int idx = tid; idx < nf * NB; idx += nt) {
+            const int f = idx / NB, k = idx - f * NB;
+            float* row = wk + (size_t)f * WS;
+            const float m = k < F0 ? src[f * rowmax + k] : 0.f;
+            if (k < F0) row[L.wk_mask + k] = m;
+            dst[f * rowmax + k] = row[L.wk_re + k] * m;
+            dst[f * rowmax + NB + k] = row[L.wk_im + k] * m;
+        }
     }
     for (int i = tid; i < 2 * NFFT; i += nt) Wb[i] = tab[TB_COS + i];
     __syncthreads();
@@ -661,17 +722,19 @@ __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __rest
     }
     __syncthreads();
     // overlap-add: a chain over the packet's frames (tail -> block -> new tail), division by the window envelope
+    int nclip = 0;
     for (int i = tid; i < HOP; i += nt) {
         float tail = st[L.st_tail + i];
         const float ienv = tab[TB_IENV + i];
         for (int f = 0; f < nf; ++f) {
             const float o = (tail + src[f * rowmax + i]) * ienv;
             const int ob = f - p.f0;                                       // frame 0's block lies in front of the clip
-            if (ob >= 0) out[((size_t)s * out_hops + ob) * HOP + i] = o;
+            if (ob >= 0) nclip += st_sample(out, ((size_t)s * out_hops + ob) * HOP + i, o);
             tail = src[f * rowmax + HOP + i];
         }
         st[L.st_tail + i] = tail;
     }
+    if constexpr (!std::is_same<OUT, float>::value) count_clipped(clip, s, nclip, Wb);      // the tables in Wb are no longer read
 }
 
 // shared argument checks of the packet entry points
@@ -682,6 +745,140 @@ int packet_args(const char* who, int S, int hops, int NFW, const Layout& L) {
     CRUSE_REQUIRE(NFW <= maxf, CRUSE_E_SHAPE, "%s: %d frames per slot exceed the %d whose rows fit in LDS (max_hops %d for these channels)", who,
                   NFW, maxf, maxf - 1);
     return CRUSE_OK;
+}
+
+// ---- host side of the boundary kernels: the plain entry point and its _io form share one function (`who` names the entry point in
+// the messages); fmt 0 = f32, 1 = s16.  Plain: fmt 0, no limit, no counter -> the <float> / <float, false> kernels.
+enum { FMT_F32 = 0, FMT_S16 = 1 };
+
+int fmt_args(const char* who, int fmt) {
+    CRUSE_REQUIRE(fmt == FMT_F32 || fmt == FMT_S16, CRUSE_E_SHAPE, "%s: unknown sample format %d (0: f32, 1: s16)", who, fmt);
+    return CRUSE_OK;
+}
+
+template <typename IN>
+int launch_encode(const char* name, const int* mode, int S, const Layout& L, size_t lds, const void* in, const float* tab, const float* w,
+                  float* state, float* work, void* stream) {
+    const int rc = cruse_ensure_dyn_lds((const void*)stream_encode_kernel<IN>, lds, name);
+    if (rc) return rc;
+    hipLaunchKernelGGL(stream_encode_kernel<IN>, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, (const IN*)in, tab, w, state,
+                       work);
+    CRUSE_LAUNCH_CHECK(name);
+    return CRUSE_OK;
+}
+
+int encode_any(const char* who, const char* name, const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const void* in, int in_fmt,
+               const float* tab, const float* w, float* state, float* work, void* stream) {
+    Layout L;
+    int rc = make_layout(c0, c1, c2, c3, c4, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(S > 0 && mode && in && tab && w && state && work, CRUSE_E_SHAPE, "%s: S = %d or a null buffer", who, S);
+    rc = fmt_args(who, in_fmt);
+    if (rc) return rc;
+    int n = NFFT + 2 * NB;
+    for (int k = 0; k < 5; ++k) n += L.ch[k] * L.F[k];
+    for (int k = 0; k < 4; ++k) n += L.ch[k] * L.F[k];
+    const size_t lds = (size_t)n * sizeof(float);
+    return in_fmt == FMT_S16 ? launch_encode<short>(name, mode, S, L, lds, in, tab, w, state, work, stream)
+                             : launch_encode<float>(name, mode, S, L, lds, in, tab, w, state, work, stream);
+}
+
+template <typename OUT, bool LIM>
+int launch_decode(const char* name, const int* mode, int S, const Layout& L, size_t lds, const float* tab, const float* w, float ln_eps,
+                  float* state, float* work, void* out, const float* lim, int* clip, void* stream) {
+    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_kernel<OUT, LIM>, lds, name);
+    if (rc) return rc;
+    hipLaunchKernelGGL((stream_decode_kernel<OUT, LIM>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, tab, w, ln_eps, state,
+                       work, (OUT*)out, lim, clip);
+    CRUSE_LAUNCH_CHECK(name);
+    return CRUSE_OK;
+}
+
+// the clamp counter belongs to PCM output: f32 output is never clamped
+int out_args(const char* who, int out_fmt, const int* clip) {
+    const int rc = fmt_args(who, out_fmt);
+    if (rc) return rc;
+    CRUSE_REQUIRE(out_fmt == FMT_S16 || clip == nullptr, CRUSE_E_SHAPE, "%s: a clip counter needs s16 output (out_fmt 1), got out_fmt %d", who, out_fmt);
+    return CRUSE_OK;
+}
+
+int decode_any(const char* who, const char* name, const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab,
+               const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip, void* stream) {
+    Layout L;
+    int rc = make_layout(c0, c1, c2, c3, c4, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(S > 0 && mode && tab && w && state && work && out, CRUSE_E_SHAPE, "%s: S = %d or a null buffer", who, S);
+    rc = out_args(who, out_fmt, clip);
+    if (rc) return rc;
+    int n = 2 * NB + NFFT + FRAME_THREADS / 64;
+    for (int k = 0; k < 5; ++k) n += L.ch[k] * L.F[k];
+    const size_t lds = (size_t)n * sizeof(float);
+#define CRUSE_DECODE(OUT, LIM) launch_decode<OUT, LIM>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, stream)
+    if (out_fmt == FMT_S16) return lim ? CRUSE_DECODE(short, true) : CRUSE_DECODE(short, false);
+    return lim ? CRUSE_DECODE(float, true) : CRUSE_DECODE(float, false);
+#undef CRUSE_DECODE
+}
+
+template <typename IN>
+int launch_encode_n(const char* name, const int* pk, int S, int hops, int in_hops, int NFW, const Layout& L, const void* in, const float* tab,
+                    const float* w, float* state, float* work, void* stream) {
+    const int rowmax = packet_row_max(L), wcap = packet_wcap(L);
+    int eoff[4];
+    const int WS = packet_work_stride(L, eoff);
+    const size_t lds = (size_t)((2 * NFW + 1) * rowmax + wcap) * sizeof(float);
+    const int rc = cruse_ensure_dyn_lds((const void*)stream_encode_n_kernel<IN>, lds, name);
+    if (rc) return rc;
+    hipLaunchKernelGGL(stream_encode_n_kernel<IN>, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, in_hops, NFW, L, WS,
+                       eoff[1], eoff[2], eoff[3], rowmax, wcap, (const IN*)in, tab, w, state, work);
+    CRUSE_LAUNCH_CHECK(name);
+    return CRUSE_OK;
+}
+
+int encode_n_any(const char* who, const char* name, const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2,
+                 int c3, int c4, const void* in, int in_fmt, const float* tab, const float* w, float* state, float* work, void* stream) {
+    Layout L;
+    int rc = make_layout(c0, c1, c2, c3, c4, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(pk && in && tab && w && state && work, CRUSE_E_SHAPE, "%s: null buffer", who);
+    rc = packet_args(who, S, hops, work_frames, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(in_hops >= hops, CRUSE_E_SHAPE, "%s: in_hops = %d < hops = %d", who, in_hops, hops);
+    rc = fmt_args(who, in_fmt);
+    if (rc) return rc;
+    return in_fmt == FMT_S16 ? launch_encode_n<short>(name, pk, S, hops, in_hops, work_frames, L, in, tab, w, state, work, stream)
+                             : launch_encode_n<float>(name, pk, S, hops, in_hops, work_frames, L, in, tab, w, state, work, stream);
+}
+
+template <typename OUT, bool LIM>
+int launch_decode_n(const char* name, const int* pk, int S, int hops, int out_hops, int NFW, const Layout& L, const float* tab, const float* w,
+                    float ln_eps, float* state, float* work, void* out, const float* lim, int* clip, void* stream) {
+    const int rowmax = packet_row_max(L), wcap = packet_wcap(L), WS = packet_work_stride(L, nullptr);
+    const size_t lds = (size_t)(2 * NFW * rowmax + wcap + 2 * NFW) * sizeof(float);
+    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_n_kernel<OUT, LIM>, lds, name);
+    if (rc) return rc;
+    hipLaunchKernelGGL((stream_decode_n_kernel<OUT, LIM>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, out_hops, NFW, L,
+                       WS, rowmax, wcap, tab, w, ln_eps, state, work, (OUT*)out, lim, clip);
+    CRUSE_LAUNCH_CHECK(name);
+    return CRUSE_OK;
+}
+
+int decode_n_any(const char* who, const char* name, const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2,
+                 int c3, int c4, const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
+                 const float* lim, int* clip, void* stream) {
+    Layout L;
+    int rc = make_layout(c0, c1, c2, c3, c4, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(pk && tab && w && state && work && out, CRUSE_E_SHAPE, "%s: null buffer", who);
+    rc = packet_args(who, S, hops, work_frames, L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(out_hops >= hops, CRUSE_E_SHAPE, "%s: out_hops = %d < hops = %d", who, out_hops, hops);
+    rc = out_args(who, out_fmt, clip);
+    if (rc) return rc;
+#define CRUSE_DECODE_N(OUT, LIM) \
+    launch_decode_n<OUT, LIM>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, stream)
+    if (out_fmt == FMT_S16) return lim ? CRUSE_DECODE_N(short, true) : CRUSE_DECODE_N(short, false);
+    return lim ? CRUSE_DECODE_N(float, true) : CRUSE_DECODE_N(float, false);
+#undef CRUSE_DECODE_N
 }
 
 }  // namespace
@@ -719,19 +916,12 @@ extern "C" int cruse_stream_tables(float* tab, void* stream) {
 
 extern "C" int cruse_stream_encode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* in, const float* tab,
                                    const float* w, float* state, float* work, void* stream) {
-    Layout L;
-    int rc = make_layout(c0, c1, c2, c3, c4, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(S > 0 && mode && in && tab && w && state && work, CRUSE_E_SHAPE, "stream_encode: S = %d or a null buffer", S);
-    int n = NFFT + 2 * NB;
-    for (int k = 0; k < 5; ++k) n += L.ch[k] * L.F[k];
-    for (int k = 0; k < 4; ++k) n += L.ch[k] * L.F[k];
-    const size_t lds = (size_t)n * sizeof(float);
-    rc = cruse_ensure_dyn_lds((const void*)stream_encode_kernel, lds, "cruse_stream_encode");
-    if (rc) return rc;
-    hipLaunchKernelGGL(stream_encode_kernel, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, in, tab, w, state, work);
-    CRUSE_LAUNCH_CHECK("cruse_stream_encode");
-    return CRUSE_OK;
+    return encode_any("stream_encode", "cruse_stream_encode", mode, S, c0, c1, c2, c3, c4, in, FMT_F32, tab, w, state, work, stream);
+}
+
+extern "C" int cruse_stream_encode_io(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const void* in, int in_fmt,
+                                      const float* tab, const float* w, float* state, float* work, void* stream) {
+    return encode_any("stream_encode_io", "cruse_stream_encode_io", mode, S, c0, c1, c2, c3, c4, in, in_fmt, tab, w, state, work, stream);
 }
 
 extern "C" int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg, const float* x, int x_stride, int x_off,
@@ -745,18 +935,15 @@ extern "C" int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg
 
 extern "C" int cruse_stream_decode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
                                    float ln_eps, float* state, float* work, float* out, void* stream) {
-    Layout L;
-    int rc = make_layout(c0, c1, c2, c3, c4, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(S > 0 && mode && tab && w && state && work && out, CRUSE_E_SHAPE, "stream_decode: S = %d or a null buffer", S);
-    int n = 2 * NB + NFFT + FRAME_THREADS / 64;
-    for (int k = 0; k < 5; ++k) n += L.ch[k] * L.F[k];
-    const size_t lds = (size_t)n * sizeof(float);
-    rc = cruse_ensure_dyn_lds((const void*)stream_decode_kernel, lds, "cruse_stream_decode");
-    if (rc) return rc;
-    hipLaunchKernelGGL(stream_decode_kernel, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, tab, w, ln_eps, state, work, out);
-    CRUSE_LAUNCH_CHECK("cruse_stream_decode");
-    return CRUSE_OK;
+    return decode_any("stream_decode", "cruse_stream_decode", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out, FMT_F32, nullptr,
+                      nullptr, stream);
+}
+
+extern "C" int cruse_stream_decode_io(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
+                                      float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
+                                      void* stream) {
+    return decode_any("stream_decode_io", "cruse_stream_decode_io", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out, out_fmt,
+                      lim, clip, stream);
 }
 
 extern "C" int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4, int* out) {
@@ -773,23 +960,15 @@ extern "C" int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4
 
 extern "C" int cruse_stream_encode_n(const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                      const float* in, const float* tab, const float* w, float* state, float* work, void* stream) {
-    Layout L;
-    int rc = make_layout(c0, c1, c2, c3, c4, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(pk && in && tab && w && state && work, CRUSE_E_SHAPE, "stream_encode_n: null buffer");
-    rc = packet_args("stream_encode_n", S, hops, work_frames, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(in_hops >= hops, CRUSE_E_SHAPE, "stream_encode_n: in_hops = %d < hops = %d", in_hops, hops);
-    const int rowmax = packet_row_max(L), wcap = packet_wcap(L);
-    int eoff[4];
-    const int WS = packet_work_stride(L, eoff);
-    const size_t lds = (size_t)((2 * work_frames + 1) * rowmax + wcap) * sizeof(float);
-    rc = cruse_ensure_dyn_lds((const void*)stream_encode_n_kernel, lds, "cruse_stream_encode_n");
-    if (rc) return rc;
-    hipLaunchKernelGGL(stream_encode_n_kernel, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, in_hops, work_frames, L,
-                       WS, eoff[1], eoff[2], eoff[3], rowmax, wcap, in, tab, w, state, work);
-    CRUSE_LAUNCH_CHECK("cruse_stream_encode_n");
-    return CRUSE_OK;
+    return encode_n_any("stream_encode_n", "cruse_stream_encode_n", pk, S, hops, in_hops, work_frames, c0, c1, c2, c3, c4, in, FMT_F32, tab, w,
+                        state, work, stream);
+}
+
+extern "C" int cruse_stream_encode_n_io(const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                                        const void* in, int in_fmt, const float* tab, const float* w, float* state, float* work,
+                                        void* stream) {
+    return encode_n_any("stream_encode_n_io", "cruse_stream_encode_n_io", pk, S, hops, in_hops, work_frames, c0, c1, c2, c3, c4, in, in_fmt,
+                        tab, w, state, work, stream);
 }
 
 extern "C" int cruse_stream_gru_proj_n(const int* pk, int S, int hops, int work_frames, int layer, int g, int Hg, const float* work,
@@ -812,19 +991,13 @@ extern "C" int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_f
 
 extern "C" int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                      const float* tab, const float* w, float ln_eps, float* state, float* work, float* out, void* stream) {
-    Layout L;
-    int rc = make_layout(c0, c1, c2, c3, c4, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(pk && tab && w && state && work && out, CRUSE_E_SHAPE, "stream_decode_n: null buffer");
-    rc = packet_args("stream_decode_n", S, hops, work_frames, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(out_hops >= hops, CRUSE_E_SHAPE, "stream_decode_n: out_hops = %d < hops = %d", out_hops, hops);
-    const int rowmax = packet_row_max(L), wcap = packet_wcap(L), WS = packet_work_stride(L, nullptr);
-    const size_t lds = (size_t)(2 * work_frames * rowmax + wcap + 2 * work_frames) * sizeof(float);
-    rc = cruse_ensure_dyn_lds((const void*)stream_decode_n_kernel, lds, "cruse_stream_decode_n");
-    if (rc) return rc;
-    hipLaunchKernelGGL(stream_decode_n_kernel, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, out_hops, work_frames, L,
-                       WS, rowmax, wcap, tab, w, ln_eps, state, work, out);
-    CRUSE_LAUNCH_CHECK("cruse_stream_decode_n");
-    return CRUSE_OK;
+    return decode_n_any("stream_decode_n", "cruse_stream_decode_n", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w, ln_eps,
+                        state, work, out, FMT_F32, nullptr, nullptr, stream);
+}
+
+extern "C" int cruse_stream_decode_n_io(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                                        const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
+                                        const float* lim, int* clip, void* stream) {
+    return decode_n_any("stream_decode_n_io", "cruse_stream_decode_n_io", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w,
+                        ln_eps, state, work, out, out_fmt, lim, clip, stream);
 }

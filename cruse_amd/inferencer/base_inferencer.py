@@ -21,7 +21,9 @@ from ..loss import enhanced_spectrum
 
 class Inferencer:
     def __init__(self, model: torch.nn.Module, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
-                 sr: int = 16000, device="cuda"):
+                 sr: int = 16000, device="cuda", atten_lim_db=None):
+        from .. import ops
+        self.lim = ops.atten_lim_gain(atten_lim_db)       # DeepFilterNet's atten_lim_db as a gain; 0: no limit (the default)
         self.model = model.to(device).eval()
         self.n_fft, self.hop, self.win, self.sr = n_fft, hop_length, win_length, sr
         self.device = torch.device(device)
@@ -29,13 +31,16 @@ class Inferencer:
 
     @torch.no_grad()
     def mag_mask_to_wave(self, noisy: torch.Tensor) -> torch.Tensor:
-        """noisy [B,L] (device) -> enhanced [B,L] (device)."""
+        """noisy [B,L] (device) -> enhanced [B,L] (device); with atten_lim_db: lim * noisy + (1 - lim) * enhanced, lim = 10^(-dB/20)."""
         if noisy.dim() != 2:
             raise RuntimeError(f"Inferencer expects [B,L] waveforms, got {tuple(noisy.shape)}")
         spec = feature.pre_stft(noisy, self.n_fft, self.hop, self.win, f_net=self.f_net)
         mask = self.model(spec["mag_net"])                                   # [B,1,T,f_net]
         est = enhanced_spectrum(mask, spec["real"].squeeze(1), spec["imag"].squeeze(1))   # [B,T,F,2]
-        return feature.istft_ri(est[..., 0], est[..., 1], self.n_fft, self.hop, length=noisy.shape[-1])
+        wave = feature.istft_ri(est[..., 0], est[..., 1], self.n_fft, self.hop, length=noisy.shape[-1])
+        if self.lim == 0.0:
+            return wave
+        return self.lim * noisy + (1.0 - self.lim) * wave
 
     @staticmethod
     def to_int16(enhanced: np.ndarray) -> np.ndarray:

@@ -46,12 +46,21 @@ class StreamingInferencer:
     LayerNorm, the gates, the carried state and every row stage() shows stay f32, and encode / decode are the f32 kernels.  It is
     meant for servers with many slots.  The module's own `precision` is not consulted in either mode; BatchNorm uses
     the running statistics (eval mode).  Call refresh() after changing the module's weights.
+
+    atten_lim = True: every slot has an attenuation limit (DeepFilterNet's atten_lim_db), set_atten_lim(db, slots): the slot's output
+    is lim * noisy + (1 - lim) * enhanced with lim = 10^(-db / 20), mixed on the spectrum inside the decode kernels (bin 160 keeps lim of
+    the input).  The limits live in the device tensor `lim` [n_slots] (zeros: no limit, today's output) that the kernels read, so a
+    change is a copy into it and never re-captures a graph.  A limit belongs to the slot: reset() and flush() leave it alone.
+    pcm_in = True: push / push_packet / enhance take torch.int16 samples, read as v / 32768 by the encode kernels.  pcm_out = True:
+    they and flush return torch.int16, clamp(rint(y * 32768), -32768, 32767) written by the decode kernels, and clipped() counts the
+    clamped samples per slot.  The three are independent and work with either precision; with all three off nothing changes.
     """
 
     HOP = 160
 
     def __init__(self, model: torch.nn.Module, n_slots: int, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
-                 device="cuda", use_graph: bool = True, max_hops: int = 1, precision: str = "f32"):
+                 device="cuda", use_graph: bool = True, max_hops: int = 1, precision: str = "f32", atten_lim: bool = False,
+                 pcm_in: bool = False, pcm_out: bool = False):
         from ..model.cruse_net import unet_2
         if (n_fft, hop_length, win_length) != (320, 160, 320):
             raise ValueError(f"StreamingInferencer supports n_fft = win_length = 320, hop_length = 160 only "
@@ -84,8 +93,13 @@ class StreamingInferencer:
         S, dev = self.S, self.device
         self.state = torch.zeros(S, self.lay["st_stride"], device=dev)
         self.work = torch.zeros(S, self.lay["wk_stride"], device=dev)
-        self.blocks = torch.zeros(S, self.HOP, device=dev)
-        self.out = torch.zeros(S, self.HOP, device=dev)
+        self.atten_lim, self.pcm_in, self.pcm_out = bool(atten_lim), bool(pcm_in), bool(pcm_out)
+        self.in_dtype = torch.int16 if self.pcm_in else torch.float32
+        self.out_dtype = torch.int16 if self.pcm_out else torch.float32
+        self.blocks = torch.zeros(S, self.HOP, device=dev, dtype=self.in_dtype)
+        self.out = torch.zeros(S, self.HOP, device=dev, dtype=self.out_dtype)
+        self.lim = torch.zeros(S, device=dev) if self.atten_lim else None       # per-slot gains 10^(-dB/20); 0: no limit
+        self.clip = torch.zeros(S, device=dev, dtype=torch.int32) if self.pcm_out else None     # clamped samples per slot
         self.mode = torch.zeros(2, S, device=dev, dtype=torch.int32)            # row 0: the frame-0 chain, row 1: the main chain
         self._mode_host = torch.zeros(2, S, dtype=torch.int32).pin_memory()
         self._host_free = None                                                  # event: the last copy out of _mode_host is done
@@ -102,8 +116,8 @@ class StreamingInferencer:
                                  f"max_hops + 1 frames of a slot in LDS), got {max_hops}")
             K = self.max_hops
             self.play = play
-            self.pblocks = torch.zeros(S, K, self.HOP, device=dev)
-            self.pout = torch.zeros(S, K, self.HOP, device=dev)
+            self.pblocks = torch.zeros(S, K, self.HOP, device=dev, dtype=self.in_dtype)
+            self.pout = torch.zeros(S, K, self.HOP, device=dev, dtype=self.out_dtype)
             self.pwork = torch.zeros(S, K + 1, play["wk_stride"], device=dev)   # one work row per frame of a packet
             self.gi = torch.zeros(S, K + 1, 3 * self.H, device=dev)             # GRU input products of the layer in flight
             self.pk = torch.zeros(2, S, device=dev, dtype=torch.int32)          # row 0: min(blocks held, 2), row 1: counts
@@ -174,7 +188,7 @@ class StreamingInferencer:
         ops.stream_encode(mode, self.ch, self.blocks, self.tab, self.w, self.state, self.work)
         for layer, x_off, st_off, h_off, pack, pack16, ln1 in self._layers:
             ops.stream_gru(mode, layer, g, Hg, self.work, x_off, self.state, st_off, pack, self.work, h_off, pack16=pack16, **ln1)
-        ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out)
+        ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out, lim=self.lim, clip=self.clip)
 
     def _replay(self, key, fn) -> None:
         """run fn(): directly, or as the graph captured from it on the first call with this key"""
@@ -205,6 +219,14 @@ class StreamingInferencer:
         self._host_free = ev
         self._launch(2 if m0.any() else 1)
 
+    def _samples(self, t: torch.Tensor, who: str) -> torch.Tensor:
+        """the input samples in the instance's input format: float32 (converted, as always), or int16 and nothing else with pcm_in"""
+        if not self.pcm_in:
+            return t.to(torch.float32)
+        if t.dtype != torch.int16:
+            raise ValueError(f"{who}: this StreamingInferencer was built with pcm_in=True and takes torch.int16 samples, got {t.dtype}")
+        return t
+
     @torch.no_grad()
     def push(self, blocks: torch.Tensor, active=None):
         """blocks [n_slots, 160] (the next block of every active slot; rows of inactive slots are ignored); active: bool per slot
@@ -213,13 +235,14 @@ class StreamingInferencer:
         S = self.S
         if tuple(blocks.shape) != (S, self.HOP):
             raise ValueError(f"push expects blocks of shape ({S}, {self.HOP}), got {tuple(blocks.shape)}")
+        blocks = self._samples(blocks, "push")
         if active is None:
             act = np.ones(S, dtype=bool)
         else:
             act = (active.cpu().numpy() if torch.is_tensor(active) else np.asarray(active)).astype(bool).reshape(-1)
             if act.size != S:
                 raise ValueError(f"active must have {S} entries, got {act.size}")
-        self.blocks.copy_(blocks.to(torch.float32), non_blocking=True)
+        self.blocks.copy_(blocks, non_blocking=True)
         b = self.nblk
         m0 = np.where(act & (b == 1), ops.STREAM_FRAME0, ops.STREAM_SKIP).astype(np.int32)
         m1 = np.where(act, np.where(b == 0, ops.STREAM_STORE, ops.STREAM_FRAME), ops.STREAM_SKIP).astype(np.int32)
@@ -259,6 +282,48 @@ class StreamingInferencer:
         self.nblk[slots] = 0
         self._last_frames[slots] = 0
 
+    # -- attenuation limit, clip counters -----------------------------------------------------------------------------------
+    def _slot_list(self, slots):
+        if slots is None:
+            return list(range(self.S))
+        slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
+        for s in slots:
+            if not 0 <= s < self.S:
+                raise ValueError(f"slot {s} out of range [0, {self.S})")
+        return slots
+
+    @torch.no_grad()
+    def set_atten_lim(self, db, slots=None) -> None:
+        """Attenuation limit in dB of `slots` (None: all): a scalar or None for all of them, or one value per listed slot.  None or
+        inf: no limit (full suppression); 0: the input passes through, 20 ms late.  Takes effect with the next frame of the slot and
+        stays until it is set again (reset and flush keep it).  Needs atten_lim=True at construction."""
+        if not self.atten_lim:
+            raise ValueError("set_atten_lim: this StreamingInferencer was built without atten_lim=True (its kernels read no limits)")
+        slots = self._slot_list(slots)
+        if db is None or np.ndim(db) == 0:
+            vals = [db] * len(slots)
+        else:
+            vals = list(db.tolist() if torch.is_tensor(db) or isinstance(db, np.ndarray) else db)
+            if len(vals) != len(slots):
+                raise ValueError(f"set_atten_lim: {len(vals)} values for {len(slots)} slots")
+        gains = [ops.atten_lim_gain(v) for v in vals]                          # refuses negative and NaN before anything is copied
+        if slots:
+            idx = torch.tensor(slots, device=self.device, dtype=torch.long)
+            self.lim.index_copy_(0, idx, torch.tensor(gains, dtype=torch.float32).to(self.device))
+
+    @torch.no_grad()
+    def clipped(self, slots=None, reset: bool = False) -> np.ndarray:
+        """int64 host array: the output samples of each slot in `slots` (None: all) that were clamped to the int16 range since the
+        counter was last zeroed; reset=True zeroes the counters read.  Needs pcm_out=True (float output is never clamped)."""
+        if not self.pcm_out:
+            raise ValueError("clipped: this StreamingInferencer was built without pcm_out=True (float output is not clamped)")
+        slots = self._slot_list(slots)
+        idx = torch.tensor(slots, device=self.device, dtype=torch.long)
+        n = self.clip.index_select(0, idx).cpu().numpy().astype(np.int64)
+        if reset and slots:
+            self.clip.index_fill_(0, idx, 0)
+        return n
+
     # -- packets ----------------------------------------------------------------------------------------------------------
     def _packet_chain(self, hops: int, nf: int) -> None:
         """One linear chain for packets of up to `hops` blocks of which the longest slot computes `nf` frames."""
@@ -270,7 +335,7 @@ class StreamingInferencer:
             ops.stream_gru_proj_n(pk, hops, layer, g, Hg, wk, x_off, pack, self.gi, pack16=pack16, **ln1)
             for f in range(nf):
                 ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, st_off, pack, wk, h_off, pack16=pack16)
-        ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout)
+        ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout, lim=self.lim, clip=self.clip)
 
     @torch.no_grad()
     def push_packet(self, blocks: torch.Tensor, counts=None):
@@ -283,6 +348,7 @@ class StreamingInferencer:
             blocks = blocks.reshape(S, blocks.shape[1] // HOP, HOP)
         if blocks.dim() != 3 or blocks.shape[0] != S or blocks.shape[2] != HOP or blocks.shape[1] < 1:
             raise ValueError(f"push_packet expects blocks of shape ({S}, K, {HOP}) or ({S}, K*{HOP}), got {tuple(blocks.shape)}")
+        blocks = self._samples(blocks, "push_packet")
         K = int(blocks.shape[1])
         if K > self.max_hops:
             raise ValueError(f"push_packet: a packet of {K} blocks exceeds max_hops = {self.max_hops}")
@@ -305,8 +371,8 @@ class StreamingInferencer:
         frames = np.array([p.n_frames for p in plans], dtype=np.int64)
         hops = int(cnt.max())
         if hops == 0:
-            return torch.zeros(S, K, HOP, device=self.device), torch.from_numpy(n_out)
-        self.pblocks[:, :K].copy_(blocks.to(torch.float32), non_blocking=True)
+            return torch.zeros(S, K, HOP, device=self.device, dtype=self.out_dtype), torch.from_numpy(n_out)
+        self.pblocks[:, :K].copy_(blocks, non_blocking=True)
         if self._pk_free is not None:
             self._pk_free.synchronize()
         hp = self._pk_host.numpy()
@@ -332,6 +398,8 @@ class StreamingInferencer:
         device's work buffers at a time: memory beyond the input and output waveforms does not grow with L."""
         if waves.dim() != 2:
             raise ValueError(f"enhance expects waves of shape (n, L), got {tuple(waves.shape)}")
+        if self.pcm_in:
+            self._samples(waves, "enhance")
         n, L = int(waves.shape[0]), int(waves.shape[1])
         hops = self.max_hops if hops is None else int(hops)
         if not 1 <= n <= self.S:
@@ -344,8 +412,8 @@ class StreamingInferencer:
         nb = padded_blocks(L)
         slots = list(range(n))
         self.reset(slots)
-        res = torch.empty(n, nb * HOP, device=self.device)
-        pkt = torch.zeros(S, hops * HOP, device=self.device)
+        res = torch.empty(n, nb * HOP, device=self.device, dtype=self.out_dtype)
+        pkt = torch.zeros(S, hops * HOP, device=self.device, dtype=self.in_dtype)
         counts = np.zeros(S, dtype=np.int64)
         done = 0                                                                # output blocks written
         for b0 in range(0, nb, hops):

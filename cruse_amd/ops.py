@@ -1062,9 +1062,50 @@ def stream_tables(device) -> torch.Tensor:
     return tab
 
 
+# sample formats of the _io entry points (in_fmt / out_fmt of the header); the plain entry points are f32 on both sides
+STREAM_FMT_F32, STREAM_FMT_S16 = 0, 1
+
+
+def _stream_fmt(t: torch.Tensor, name: str) -> int:
+    if t.dtype == torch.float32:
+        return STREAM_FMT_F32
+    if t.dtype == torch.int16:
+        return STREAM_FMT_S16
+    raise RuntimeError(f"{name}: expected float32 or int16 samples, got {t.dtype}")
+
+
+def _stream_io(out: torch.Tensor, lim, clip, name: str):
+    """(out_fmt, lim, clip) of a decode call, or None where the plain entry point serves it"""
+    fmt = _stream_fmt(out, name)
+    if fmt == STREAM_FMT_F32 and lim is None and clip is None:
+        return None
+    if lim is not None and (lim.dtype != torch.float32 or lim.numel() != out.shape[0]):
+        raise RuntimeError(f"{name}: lim must be float32 with one entry per slot ({out.shape[0]}), got {lim.dtype} x {lim.numel()}")
+    if clip is not None and (clip.dtype != torch.int32 or clip.numel() != out.shape[0]):
+        raise RuntimeError(f"{name}: clip must be int32 with one entry per slot ({out.shape[0]}), got {clip.dtype} x {clip.numel()}")
+    return fmt, _p(lim), _p(clip)
+
+
+def atten_lim_gain(db) -> float:
+    """The linear gain of an attenuation limit of `db` dB (DeepFilterNet's atten_lim_db): 10^(-db / 20); None or inf -> 0 (no limit),
+    0 -> 1 (the input passes through).  The output of a limited slot is gain * noisy + (1 - gain) * enhanced."""
+    if db is None:
+        return 0.0
+    db = float(db)
+    if db != db or db < 0.0:
+        raise ValueError(f"attenuation limit must be a non-negative number of dB, inf or None, got {db}")
+    return 0.0 if db == float("inf") else 10.0 ** (-db / 20.0)
+
+
 def stream_encode(mode, ch, blocks, tab, w, state, work) -> None:
-    check(lib.cruse_stream_encode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(blocks), _p(tab), _p(w), _p(state), _p(work),
-                                  _stream()))
+    """blocks [S, 160]: float32, or int16 PCM (read as v / 32768, cruse_stream_encode_io)"""
+    fmt = _stream_fmt(blocks, "stream_encode")
+    if fmt == STREAM_FMT_F32:
+        check(lib.cruse_stream_encode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(blocks), _p(tab), _p(w), _p(state), _p(work),
+                                      _stream()))
+    else:
+        check(lib.cruse_stream_encode_io(_p(mode), mode.numel(), *[int(c) for c in ch], _p(blocks), fmt, _p(tab), _p(w), _p(state),
+                                         _p(work), _stream()))
 
 
 def _f16_args(name, pack16):
@@ -1081,9 +1122,16 @@ def stream_gru(mode, layer, groups, Hg, x, x_off, hprev, h_off, pack, hout, o_of
              hprev.shape[1], h_off, _p(pack), *p16, _p(hout), hout.shape[1], o_off, _stream()))
 
 
-def stream_decode(mode, ch, tab, w, ln_eps, state, work, out) -> None:
-    check(lib.cruse_stream_decode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state), _p(work),
-                                  _p(out), _stream()))
+def stream_decode(mode, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None) -> None:
+    """out [S, 160]: float32, or int16 PCM (clamp(rint(y * 32768))); lim [S] f32: per-slot attenuation-limit gains (atten_lim_gain);
+    clip [S] int32: += the clamped samples per slot (int16 out only).  Any of them selects cruse_stream_decode_io."""
+    io = _stream_io(out, lim, clip, "stream_decode")
+    if io is None:
+        check(lib.cruse_stream_decode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state), _p(work),
+                                      _p(out), _stream()))
+    else:
+        check(lib.cruse_stream_decode_io(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state),
+                                         _p(work), _p(out), *io, _stream()))
 
 
 # packets: up to `hops` blocks per slot in one chain (cruse_stream_*_n).  pk is the [2, S] int32 device tensor of the header
@@ -1097,8 +1145,14 @@ def stream_packet_layout(ch) -> Dict[str, int]:
 
 
 def stream_encode_n(pk, hops, ch, blocks, tab, w, state, work) -> None:
-    check(lib.cruse_stream_encode_n(_p(pk), pk.shape[1], int(hops), blocks.shape[1], work.shape[1], *[int(c) for c in ch], _p(blocks),
-                                    _p(tab), _p(w), _p(state), _p(work), _stream()))
+    """blocks [S, in_hops, 160]: float32, or int16 PCM (cruse_stream_encode_n_io)"""
+    fmt = _stream_fmt(blocks, "stream_encode_n")
+    if fmt == STREAM_FMT_F32:
+        check(lib.cruse_stream_encode_n(_p(pk), pk.shape[1], int(hops), blocks.shape[1], work.shape[1], *[int(c) for c in ch], _p(blocks),
+                                        _p(tab), _p(w), _p(state), _p(work), _stream()))
+    else:
+        check(lib.cruse_stream_encode_n_io(_p(pk), pk.shape[1], int(hops), blocks.shape[1], work.shape[1], *[int(c) for c in ch],
+                                           _p(blocks), fmt, _p(tab), _p(w), _p(state), _p(work), _stream()))
 
 
 def stream_gru_proj_n(pk, hops, layer, groups, Hg, work, x_off, pack, gi, ln_g=None, ln_b=None, ln_eps=1e-5, pack16=None) -> None:
@@ -1114,9 +1168,15 @@ def stream_gru_rec_n(pk, hops, frame, groups, Hg, gi, state, st_off, pack, work,
              *p16, _p(work), work.shape[2], h_off, _stream()))
 
 
-def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out) -> None:
-    check(lib.cruse_stream_decode_n(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab), _p(w),
-                                    float(ln_eps), _p(state), _p(work), _p(out), _stream()))
+def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None) -> None:
+    """out [S, out_hops, 160]: float32 or int16 PCM; lim / clip as stream_decode (cruse_stream_decode_n_io)"""
+    io = _stream_io(out, lim, clip, "stream_decode_n")
+    if io is None:
+        check(lib.cruse_stream_decode_n(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab), _p(w),
+                                        float(ln_eps), _p(state), _p(work), _p(out), _stream()))
+    else:
+        check(lib.cruse_stream_decode_n_io(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab),
+                                           _p(w), float(ln_eps), _p(state), _p(work), _p(out), *io, _stream()))
 
 
 # the layer's fragment-ordered f16 weights for the f16-operand MFMA GRU (the pack16 argument of stream_gru / _gru_proj_n / _gru_rec_n)

@@ -813,6 +813,28 @@ int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_frames, int 
 int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                           const float* tab, const float* w, float ln_eps, float* state, float* work, float* out, void* stream);
 
+/* ---- sample formats and the per-slot attenuation limit in the boundary kernels (additive; the entry points above are unchanged and
+ * launch the same kernels as before) ---------------------------------------------------------------------------------------------
+ * Each takes its sibling's arguments plus: in_fmt / out_fmt: 0 = f32, 1 = s16 (16-bit PCM) -- the element type of `in` / `out`.  An s16
+ * input sample v is read as v / 32768.0f (exact); an s16 output sample is clamp(rint(y * 32768), -32768, 32767), ties to even.
+ * lim[S] (device, may be NULL: no limit): the slot's attenuation limit as a linear gain, lim = 10^(-dB / 20) in [0, 1]; the output is
+ * lim * noisy + (1 - lim) * enhanced, mixed on the spectrum: bins 0..159 are scaled by fmaf(1 - lim, mask, lim) and bin 160 by lim
+ * (DeepFilterNet's atten_lim_db).  The mask row of the work buffer keeps the model's mask.  lim = 0 gives the sibling's output.
+ * clip[S] (device int, may be NULL: not counted; needs out_fmt 1): clip[s] += the s16 samples of slot s this launch clamped.
+ * Slots that compute no frame are neither written nor counted.  Refused with CRUSE_E_SHAPE before any launch: what the sibling
+ * refuses, an unknown format, a clip counter with f32 output. */
+int cruse_stream_encode_io(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const void* in, int in_fmt,
+                           const float* tab, const float* w, float* state, float* work, void* stream);
+int cruse_stream_decode_io(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
+                           float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
+                           void* stream);
+int cruse_stream_encode_n_io(const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                             const void* in, int in_fmt, const float* tab, const float* w, float* state, float* work,
+                             void* stream);
+int cruse_stream_decode_n_io(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                             const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
+                             const float* lim, int* clip, void* stream);
+
 /* ---- f16-operand MFMA GRU of the streaming chains (additive; rows, mode / pk semantics and the f32 pack are those above, so these
  * may replace their f32 counterparts call by call) ------------------------------------------------------------------------------
  * pack16 (device, f16): the layer's weights as MFMA A fragments, [W_ih | W_hh][g][gate r,z,n][UT][KS][64 lanes][8], UT =

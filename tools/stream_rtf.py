@@ -12,7 +12,12 @@ With --precision f32,f16 every cell is measured for both modes of StreamingInfer
 carries "precision", and f16 rows "vs_f32" = their wall time per hop over the f32 row's of the same cell (profiles/stream_f16_rtf.json).
 The default, f32 alone, prints what it always printed.
 
-    python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--precision f32,f16] [--out FILE]
+With --pcm the instances are built with pcm_in = pcm_out = True and fed int16 blocks; with --atten-lim DB they are built with
+atten_lim = True and every slot limited to DB dB.  Either adds "io" to the result; without them nothing changes (DESIGN 12c,
+profiles/stream_io_rtf.json).
+
+    python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--precision f32,f16] [--pcm]
+                               [--atten-lim DB] [--out FILE]
 """
 from __future__ import annotations
 
@@ -43,14 +48,30 @@ def closed_form(model):
             p.copy_(v.reshape(p.shape).to(p.dtype))
 
 
+IO = {"pcm": False, "atten_lim": None}       # --pcm / --atten-lim: the I/O mode of every instance measured
+
+
 def _inferencer(model, S: int, precision: str, **kw):
     from cruse_amd.inferencer import StreamingInferencer
-    return StreamingInferencer(model, S, **kw) if precision == "f32" else StreamingInferencer(model, S, precision=precision, **kw)
+    if IO["pcm"]:
+        kw.update(pcm_in=True, pcm_out=True)
+    if IO["atten_lim"] is not None:
+        kw.update(atten_lim=True)
+    inf = StreamingInferencer(model, S, **kw) if precision == "f32" else StreamingInferencer(model, S, precision=precision, **kw)
+    if IO["atten_lim"] is not None:
+        inf.set_atten_lim(IO["atten_lim"])
+    return inf
+
+
+def _blocks(*shape):
+    """0.1 * randn blocks, as int16 PCM with --pcm"""
+    x = 0.1 * torch.randn(*shape, device="cuda")
+    return (x * 32768.0).round().clamp(-32768, 32767).to(torch.int16) if IO["pcm"] else x
 
 
 def measure(model, S: int, seconds: float, precision: str = "f32"):
     inf = _inferencer(model, S, precision)
-    blocks = 0.1 * torch.randn(S, 160, device="cuda")
+    blocks = _blocks(S, 160)
     for _ in range(50):
         inf.push(blocks)
     torch.cuda.synchronize()
@@ -74,7 +95,7 @@ def measure(model, S: int, seconds: float, precision: str = "f32"):
 def measure_packets(model, S: int, hops: int, seconds: float, precision: str = "f32"):
     """one (n_slots, hops) cell; hops = 1 is the single-hop push chain"""
     inf = _inferencer(model, S, precision, max_hops=hops)
-    blocks = 0.1 * torch.randn(S, hops, 160, device="cuda")
+    blocks = _blocks(S, hops, 160)
     call = (lambda: inf.push(blocks[:, 0])) if hops == 1 else (lambda: inf.push_packet(blocks))
     for _ in range(50):
         call()
@@ -105,8 +126,11 @@ def main():
     ap.add_argument("--groups", type=int, default=4)
     ap.add_argument("--hops", default=None, help="comma-separated packet sizes, e.g. 1,2,4,8: measure every (slots, hops) cell")
     ap.add_argument("--precision", default="f32", help="f32 (default), f16 or f32,f16: the StreamingInferencer modes to measure")
+    ap.add_argument("--pcm", action="store_true", help="int16 PCM blocks in and out (pcm_in = pcm_out = True)")
+    ap.add_argument("--atten-lim", type=float, default=None, metavar="DB", help="every slot limited to DB dB of attenuation (atten_lim = True)")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()
+    IO.update(pcm=a.pcm, atten_lim=a.atten_lim)
     from cruse_amd.model.cruse_net import unet_2
     torch.manual_seed(0)
     m = unet_2(rnn_groups=a.groups, precision="f32")
@@ -136,6 +160,8 @@ def main():
             if r["precision"] == "f16":
                 r["vs_f32"] = round(per_hop(r) / f32[(r["n_slots"], r.get("hops", 1))], 3)
     res = {"model": f"unet_2 ch={m.ch} rnn_groups={a.groups}", "device": torch.cuda.get_device_name(0), "rows": rows}
+    if a.pcm or a.atten_lim is not None:
+        res["io"] = {"pcm": a.pcm, "atten_lim_db": a.atten_lim}
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
