@@ -27,7 +27,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from .packets import packet_plan, padded_blocks
+from . import resample
+from .packets import packet_plan
 
 
 def _bn_fold(bn):
@@ -54,14 +55,25 @@ class StreamingInferencer:
     pcm_in = True: push / push_packet / enhance take torch.int16 samples, read as v / 32768 by the encode kernels.  pcm_out = True:
     they and flush return torch.int16, clamp(rint(y * 32768), -32768, 32767) written by the decode kernels, and clipped() counts the
     clamped samples per slot.  The three are independent and work with either precision; with all three off nothing changes.
+
+    io_rate = 8000, 32000 or 48000 (default 16000, the model's rate: nothing changes): the server's samples are at io_rate.  A block is
+    io_block = io_rate / 100 samples (10 ms: 80, 320 or 480): push takes and returns [n_slots, io_block], push_packet [n_slots, K,
+    io_block], flush returns [len(slots), io_block], enhance pads to a multiple of io_block.  Two kernels per call convert between
+    io_rate and 16 kHz around the unchanged chains (cruse_stream_resample_*; the filters: inferencer/resample.py), with the per-slot
+    filter histories in `rs_state`, zeroed by reset() and flush() with the rest of the slot; pcm_in / pcm_out and clipped() then apply
+    to the io_rate samples, and stage() keeps showing the 16 kHz rows.  With In / Out the two converters (causal, zero history) and E
+    today's 16 kHz enhancement of a whole clip, pushes + flush, packets + flush and enhance return Out(E(In(u))) truncated to the
+    input's length: the converters delay the signal by io_delay samples at io_rate (64 / 96 at 32 / 48 kHz = 2 ms; 32 at 8 kHz = 4 ms)
+    on top of the chain's 20 ms, and the last io_delay samples of the filters' tail are dropped.
     """
 
     HOP = 160
 
     def __init__(self, model: torch.nn.Module, n_slots: int, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
                  device="cuda", use_graph: bool = True, max_hops: int = 1, precision: str = "f32", atten_lim: bool = False,
-                 pcm_in: bool = False, pcm_out: bool = False):
+                 pcm_in: bool = False, pcm_out: bool = False, io_rate: int = 16000):
         from ..model.cruse_net import unet_2
+        io_rate = resample.check_rate(io_rate)
         if (n_fft, hop_length, win_length) != (320, 160, 320):
             raise ValueError(f"StreamingInferencer supports n_fft = win_length = 320, hop_length = 160 only "
                              f"(got n_fft={n_fft}, hop_length={hop_length}, win_length={win_length})")
@@ -96,8 +108,17 @@ class StreamingInferencer:
         self.atten_lim, self.pcm_in, self.pcm_out = bool(atten_lim), bool(pcm_in), bool(pcm_out)
         self.in_dtype = torch.int16 if self.pcm_in else torch.float32
         self.out_dtype = torch.int16 if self.pcm_out else torch.float32
-        self.blocks = torch.zeros(S, self.HOP, device=dev, dtype=self.in_dtype)
-        self.out = torch.zeros(S, self.HOP, device=dev, dtype=self.out_dtype)
+        self._io_rate = io_rate
+        self._rs = io_rate != resample.MODEL_RATE
+        # the chains' own boundary tensors: the caller's formats, or f32 behind the converters
+        self.blocks = torch.zeros(S, self.HOP, device=dev, dtype=torch.float32 if self._rs else self.in_dtype)
+        self.out = torch.zeros(S, self.HOP, device=dev, dtype=torch.float32 if self._rs else self.out_dtype)
+        self.rs_state = self.rs_taps = None
+        if self._rs:
+            self.io_blocks = torch.zeros(S, self.io_block, device=dev, dtype=self.in_dtype)
+            self.io_out = torch.zeros(S, self.io_block, device=dev, dtype=self.out_dtype)
+            self.rs_taps = ops.stream_resample_taps(io_rate, dev)
+            self.rs_state = torch.zeros(S, sum(resample.history(io_rate)), device=dev)      # [in-side history | out-side history]
         self.lim = torch.zeros(S, device=dev) if self.atten_lim else None       # per-slot gains 10^(-dB/20); 0: no limit
         self.clip = torch.zeros(S, device=dev, dtype=torch.int32) if self.pcm_out else None     # clamped samples per slot
         self.mode = torch.zeros(2, S, device=dev, dtype=torch.int32)            # row 0: the frame-0 chain, row 1: the main chain
@@ -116,14 +137,31 @@ class StreamingInferencer:
                                  f"max_hops + 1 frames of a slot in LDS), got {max_hops}")
             K = self.max_hops
             self.play = play
-            self.pblocks = torch.zeros(S, K, self.HOP, device=dev, dtype=self.in_dtype)
-            self.pout = torch.zeros(S, K, self.HOP, device=dev, dtype=self.out_dtype)
+            self.pblocks = torch.zeros(S, K, self.HOP, device=dev, dtype=self.blocks.dtype)
+            self.pout = torch.zeros(S, K, self.HOP, device=dev, dtype=self.out.dtype)
+            if self._rs:
+                self.io_pblocks = torch.zeros(S, K, self.io_block, device=dev, dtype=self.in_dtype)
+                self.io_pout = torch.zeros(S, K, self.io_block, device=dev, dtype=self.out_dtype)
             self.pwork = torch.zeros(S, K + 1, play["wk_stride"], device=dev)   # one work row per frame of a packet
             self.gi = torch.zeros(S, K + 1, 3 * self.H, device=dev)             # GRU input products of the layer in flight
             self.pk = torch.zeros(2, S, device=dev, dtype=torch.int32)          # row 0: min(blocks held, 2), row 1: counts
             self._pk_host = torch.zeros(2, S, dtype=torch.int32).pin_memory()
             self._pk_free = None
         self.refresh()
+
+    @property
+    def io_rate(self) -> int:
+        return self._io_rate
+
+    @property
+    def io_block(self) -> int:
+        """samples of a block (10 ms) at io_rate"""
+        return resample.io_block(self._io_rate)
+
+    @property
+    def io_delay(self) -> int:
+        """samples at io_rate by which the two rate converters delay the output (0 at 16 kHz), beside the chain's own 20 ms"""
+        return resample.io_delay(self._io_rate)
 
     # -- weights ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -188,7 +226,8 @@ class StreamingInferencer:
         ops.stream_encode(mode, self.ch, self.blocks, self.tab, self.w, self.state, self.work)
         for layer, x_off, st_off, h_off, pack, pack16, ln1 in self._layers:
             ops.stream_gru(mode, layer, g, Hg, self.work, x_off, self.state, st_off, pack, self.work, h_off, pack16=pack16, **ln1)
-        ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out, lim=self.lim, clip=self.clip)
+        ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out, lim=self.lim,
+                          clip=None if self._rs else self.clip)             # behind the converters, resample_out counts
 
     def _replay(self, key, fn) -> None:
         """run fn(): directly, or as the graph captured from it on the first call with this key"""
@@ -206,7 +245,16 @@ class StreamingInferencer:
 
     def _launch(self, passes: int) -> None:
         rows = (0, 1) if passes == 2 else (1,)
-        self._replay(passes, lambda: [self._chain(r) for r in rows])
+
+        def hop():
+            if self._rs:                                                        # once, on the main chain's modes
+                ops.stream_resample_in(self.mode[1], self.io_rate, self.io_blocks, self.rs_taps, self.rs_state, self.blocks)
+            for r in rows:
+                self._chain(r)
+            if self._rs:
+                ops.stream_resample_out(self.mode[1], self.io_rate, self.out, self.rs_taps, self.rs_state, self.io_out, clip=self.clip)
+
+        self._replay(passes, hop)
 
     def _run(self, m0: np.ndarray, m1: np.ndarray) -> None:
         if self._host_free is not None:
@@ -231,10 +279,10 @@ class StreamingInferencer:
     def push(self, blocks: torch.Tensor, active=None):
         """blocks [n_slots, 160] (the next block of every active slot; rows of inactive slots are ignored); active: bool per slot
         (None: all).  Returns (out [n_slots, 160] on the device, valid [n_slots] bool on the host): out[s] is the next enhanced
-        block of slot s where valid[s]; inactive slots keep their state untouched."""
-        S = self.S
-        if tuple(blocks.shape) != (S, self.HOP):
-            raise ValueError(f"push expects blocks of shape ({S}, {self.HOP}), got {tuple(blocks.shape)}")
+        block of slot s where valid[s]; inactive slots keep their state untouched.  160: io_block at another io_rate."""
+        S, B = self.S, self.io_block
+        if tuple(blocks.shape) != (S, B):
+            raise ValueError(f"push expects blocks of shape ({S}, {B}), got {tuple(blocks.shape)}")
         blocks = self._samples(blocks, "push")
         if active is None:
             act = np.ones(S, dtype=bool)
@@ -242,7 +290,7 @@ class StreamingInferencer:
             act = (active.cpu().numpy() if torch.is_tensor(active) else np.asarray(active)).astype(bool).reshape(-1)
             if act.size != S:
                 raise ValueError(f"active must have {S} entries, got {act.size}")
-        self.blocks.copy_(blocks, non_blocking=True)
+        (self.io_blocks if self._rs else self.blocks).copy_(blocks, non_blocking=True)
         b = self.nblk
         m0 = np.where(act & (b == 1), ops.STREAM_FRAME0, ops.STREAM_SKIP).astype(np.int32)
         m1 = np.where(act, np.where(b == 0, ops.STREAM_STORE, ops.STREAM_FRAME), ops.STREAM_SKIP).astype(np.int32)
@@ -250,7 +298,7 @@ class StreamingInferencer:
         self.nblk += act
         self._last_frames[act] = 0
         self._run(m0, m1)
-        return self.out.clone(), torch.from_numpy(valid)
+        return (self.io_out if self._rs else self.out).clone(), torch.from_numpy(valid)
 
     @torch.no_grad()
     def flush(self, slots) -> torch.Tensor:
@@ -267,7 +315,7 @@ class StreamingInferencer:
         self._last_frames[slots] = 0
         self._run(np.zeros(self.S, dtype=np.int32), m1)
         idx = torch.tensor(slots, device=self.device, dtype=torch.long)
-        last = self.out.index_select(0, idx)
+        last = (self.io_out if self._rs else self.out).index_select(0, idx)
         self.reset(slots)
         return last
 
@@ -278,7 +326,10 @@ class StreamingInferencer:
             slots = list(range(self.S))
         slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
         if slots:
-            self.state.index_fill_(0, torch.tensor(slots, device=self.device, dtype=torch.long), 0.0)
+            idx = torch.tensor(slots, device=self.device, dtype=torch.long)
+            self.state.index_fill_(0, idx, 0.0)
+            if self._rs:
+                self.rs_state.index_fill_(0, idx, 0.0)
         self.nblk[slots] = 0
         self._last_frames[slots] = 0
 
@@ -328,6 +379,8 @@ class StreamingInferencer:
     def _packet_chain(self, hops: int, nf: int) -> None:
         """One linear chain for packets of up to `hops` blocks of which the longest slot computes `nf` frames."""
         pk, g, Hg, wk = self.pk, self.g, self.Hg, self.pwork
+        if self._rs:
+            ops.stream_resample_in_n(pk, hops, self.io_rate, self.io_pblocks, self.rs_taps, self.rs_state, self.pblocks)
         ops.stream_encode_n(pk, hops, self.ch, self.pblocks, self.tab, self.w, self.state, wk)
         if nf == 0:                                                             # nothing but first blocks to store
             return
@@ -335,15 +388,19 @@ class StreamingInferencer:
             ops.stream_gru_proj_n(pk, hops, layer, g, Hg, wk, x_off, pack, self.gi, pack16=pack16, **ln1)
             for f in range(nf):
                 ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, st_off, pack, wk, h_off, pack16=pack16)
-        ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout, lim=self.lim, clip=self.clip)
+        ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout, lim=self.lim,
+                            clip=None if self._rs else self.clip)
+        if self._rs:
+            ops.stream_resample_out_n(pk, hops, self.io_rate, self.pout, self.rs_taps, self.rs_state, self.io_pout, clip=self.clip)
 
     @torch.no_grad()
     def push_packet(self, blocks: torch.Tensor, counts=None):
         """blocks [n_slots, K, 160] or [n_slots, K*160], 1 <= K <= max_hops; counts: an int per slot in [0, K] (None: K for every
         slot; 0: the slot is inactive and its state untouched).  Slot s consumes its first counts[s] blocks.  Returns
         (out [n_slots, K, 160] on the device, n_out [n_slots] int64 on the host): out[s, :n_out[s]] are the next enhanced blocks
-        of slot s, in order.  n_out[s] = counts[s] where the slot already held a block, else max(counts[s] - 1, 0)."""
-        S, HOP = self.S, self.HOP
+        of slot s, in order.  n_out[s] = counts[s] where the slot already held a block, else max(counts[s] - 1, 0).
+        160: io_block at another io_rate."""
+        S, HOP = self.S, self.io_block
         if blocks.dim() == 2 and blocks.shape[0] == S and blocks.shape[1] % HOP == 0 and blocks.shape[1] > 0:
             blocks = blocks.reshape(S, blocks.shape[1] // HOP, HOP)
         if blocks.dim() != 3 or blocks.shape[0] != S or blocks.shape[2] != HOP or blocks.shape[1] < 1:
@@ -372,7 +429,7 @@ class StreamingInferencer:
         hops = int(cnt.max())
         if hops == 0:
             return torch.zeros(S, K, HOP, device=self.device, dtype=self.out_dtype), torch.from_numpy(n_out)
-        self.pblocks[:, :K].copy_(blocks, non_blocking=True)
+        (self.io_pblocks if self._rs else self.pblocks)[:, :K].copy_(blocks, non_blocking=True)
         if self._pk_free is not None:
             self._pk_free.synchronize()
         hp = self._pk_host.numpy()
@@ -387,7 +444,7 @@ class StreamingInferencer:
         self._last_f0[act] = np.array([p.first_frame == 0 for p in plans])[act]
         nf = int(frames.max())
         self._replay(("packet", hops, nf), lambda: self._packet_chain(hops, nf))
-        return self.pout[:, :K].clone(), torch.from_numpy(n_out)
+        return (self.io_pout if self._rs else self.pout)[:, :K].clone(), torch.from_numpy(n_out)
 
     @torch.no_grad()
     def enhance(self, waves: torch.Tensor, hops=None) -> torch.Tensor:
@@ -395,7 +452,8 @@ class StreamingInferencer:
         blocks per call, then flush; -> [n, L] on the device.  Uses slots 0..n-1: resets them first and leaves them reset.  When L
         is not a multiple of 160 the clip is zero-padded to the next multiple and the result trimmed to L, so it equals the
         offline result OF THE PADDED CLIP (the end reflection then mirrors the padding).  Only one packet of the clip is on the
-        device's work buffers at a time: memory beyond the input and output waveforms does not grow with L."""
+        device's work buffers at a time: memory beyond the input and output waveforms does not grow with L.  At another io_rate
+        320 and 160 read 2 * io_block and io_block."""
         if waves.dim() != 2:
             raise ValueError(f"enhance expects waves of shape (n, L), got {tuple(waves.shape)}")
         if self.pcm_in:
@@ -404,12 +462,12 @@ class StreamingInferencer:
         hops = self.max_hops if hops is None else int(hops)
         if not 1 <= n <= self.S:
             raise ValueError(f"enhance: {n} clips for {self.S} slots")
-        if L < 2 * self.HOP:
-            raise ValueError(f"enhance: clips of {L} samples are shorter than 320")
+        if L < 2 * self.io_block:
+            raise ValueError(f"enhance: clips of {L} samples are shorter than {2 * self.io_block}")
         if not 1 <= hops <= self.max_hops:
             raise ValueError(f"enhance: hops = {hops} outside [1, max_hops = {self.max_hops}]")
-        S, HOP = self.S, self.HOP
-        nb = padded_blocks(L)
+        S, HOP = self.S, self.io_block
+        nb = (L + HOP - 1) // HOP                                               # the last block zero-padded (packets.padded_blocks at 160)
         slots = list(range(n))
         self.reset(slots)
         res = torch.empty(n, nb * HOP, device=self.device, dtype=self.out_dtype)

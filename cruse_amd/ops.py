@@ -1179,6 +1179,53 @@ def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out, lim=None, cl
                                            _p(w), float(ln_eps), _p(state), _p(work), _p(out), *io, _stream()))
 
 
+# 8 / 32 / 48 kHz I/O around the 16 kHz chains (cruse_stream_resample_*).  taps: stream_resample_taps(io_rate); rs_state [S, >= the two
+# history sizes of inferencer.resample.history(io_rate)] f32: the slots' converter histories, zero at the start of a clip.
+def stream_resample_taps(io_rate: int, device) -> torch.Tensor:
+    """the f32 device table of the converters' low-pass (inferencer.resample.design, float64 rounded once)"""
+    from .inferencer.resample import design
+    return torch.from_numpy(design(io_rate)[1]).to(torch.float32).to(device)
+
+
+def _rs_rows(lo: torch.Tensor, io: torch.Tensor, S: int, io_rate: int, name: str) -> None:
+    """lo: the 16 kHz tensor [S, (hops,) 160], io: the io_rate tensor [S, (hops,) io_rate / 100] -- the kernels take the widths on trust"""
+    B = int(io_rate) // 100
+    if (lo.shape[0] != S or io.shape[0] != S or lo.dim() != io.dim() or lo.shape[-1] != 160 or io.shape[-1] != B
+            or (lo.dim() == 3 and lo.shape[1] != io.shape[1])):
+        raise RuntimeError(f"{name}: expected [{S}, (hops,) 160] and [{S}, (hops,) {B}] samples at io_rate {io_rate}, got "
+                           f"{tuple(lo.shape)} and {tuple(io.shape)}")
+
+
+def stream_resample_in(mode, io_rate, x, taps, rs_state, blocks) -> None:
+    """x [S, io_rate / 100] (float32 or int16 PCM) -> blocks [S, 160] f32 for every slot whose mode is STORE or FRAME"""
+    _rs_rows(blocks, x, mode.numel(), io_rate, "stream_resample_in")
+    check(lib.cruse_stream_resample_in(_p(mode), mode.numel(), int(io_rate), _p(x), _stream_fmt(x, "stream_resample_in"), _p(taps),
+                                       _p(_f32(rs_state, "rs_state")), rs_state.shape[1], _p(_f32(blocks, "blocks")), _stream()))
+
+
+def stream_resample_out(mode, io_rate, out16, taps, rs_state, y, clip=None) -> None:
+    """out16 [S, 160] f32 -> y [S, io_rate / 100] (float32 or int16 PCM, clip [S] int32 += the clamped samples) for every slot whose
+    mode is FRAME or END"""
+    _rs_rows(out16, y, mode.numel(), io_rate, "stream_resample_out")
+    check(lib.cruse_stream_resample_out(_p(mode), mode.numel(), int(io_rate), _p(_f32(out16, "out16")), _p(taps), _p(_f32(rs_state, "rs_state")),
+                                        rs_state.shape[1], _p(y), _stream_fmt(y, "stream_resample_out"), _p(clip), _stream()))
+
+
+def stream_resample_in_n(pk, hops, io_rate, x, taps, rs_state, blocks) -> None:
+    """x [S, in_hops, io_rate / 100] -> blocks [S, in_hops, 160] f32: the pk[1, s] blocks each slot consumes"""
+    _rs_rows(blocks, x, pk.shape[1], io_rate, "stream_resample_in_n")
+    check(lib.cruse_stream_resample_in_n(_p(pk), pk.shape[1], int(hops), x.shape[1], int(io_rate), _p(x), _stream_fmt(x, "stream_resample_in_n"),
+                                         _p(taps), _p(_f32(rs_state, "rs_state")), rs_state.shape[1], _p(_f32(blocks, "blocks")), _stream()))
+
+
+def stream_resample_out_n(pk, hops, io_rate, out16, taps, rs_state, y, clip=None) -> None:
+    """out16 [S, out_hops, 160] f32 -> y [S, out_hops, io_rate / 100]: the output blocks each slot's packet yields"""
+    _rs_rows(out16, y, pk.shape[1], io_rate, "stream_resample_out_n")
+    check(lib.cruse_stream_resample_out_n(_p(pk), pk.shape[1], int(hops), y.shape[1], int(io_rate), _p(_f32(out16, "out16")), _p(taps),
+                                          _p(_f32(rs_state, "rs_state")), rs_state.shape[1], _p(y), _stream_fmt(y, "stream_resample_out_n"),
+                                          _p(clip), _stream()))
+
+
 # the layer's fragment-ordered f16 weights for the f16-operand MFMA GRU (the pack16 argument of stream_gru / _gru_proj_n / _gru_rec_n)
 def stream_pack_f16(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
     """W_ih, W_hh [g, 3*Hg, Hg] (any float dtype / device) -> the flat f16 pack16 of the header, on the inputs' device:

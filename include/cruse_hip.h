@@ -855,6 +855,33 @@ int cruse_stream_gru_rec_n_f16(const int* pk, int S, int hops, int work_frames, 
                                const float* state, int st_stride, int st_off, const float* pack, const void* pack16, float* work,
                                int wk_stride, int h_off, void* stream);
 
+/* ---- 8 / 32 / 48 kHz I/O: sample-rate conversion around the 16 kHz chains (additive; nothing above changes) ----------------------
+ * io_rate: 8000, 32000 or 48000.  q = 3 for 48000, else 2; N = 32 q + 1 taps; a block is B = io_rate / 100 samples (10 ms).
+ * taps[N] (device, f32): the low-pass h, designed by the host (cruse_amd/inferencer/resample.py: Kaiser-windowed sinc, unit DC gain).
+ *   decimate by q, phase 0:  D_q(u)[n] = sum_{k=0}^{N-1} h[k] u[q n - k]
+ *   interpolate by q:        I_q(x)[m] = q sum_i h[m - q i] x[i] over 0 <= m - q i <= N - 1
+ * both causal from a zero history, summed over k (i) ascending with fmaf in f32.  32000 / 48000: the input side is D_q, the output side
+ * I_q; 8000: the input side is I_2, the output side D_2.  rs_state[S][rs_stride] (device, f32) carries the slot's last input samples
+ * of each side: [in-side history | out-side history], N - 1 | (N - 1) / q samples at 32000 / 48000 and (N - 1) / 2 | N - 1 at 8000;
+ * rs_stride >= their sum.  Zero it where the slot's state row is zeroed.  One workgroup per slot; a slot that converts nothing
+ * leaves its history, its output row and its counter untouched.  in_fmt / out_fmt, the s16 conversions and clip[S] are those of
+ * the _io entry points.  Refused with CRUSE_E_SHAPE before any launch: S < 1, a null buffer, an unknown io_rate (16000 included) or
+ * format, a clip counter with f32 output, rs_stride too small, hops < 1, in_hops / out_hops < hops. */
+/* before cruse_stream_encode: a slot whose mode (the MAIN chain's row) is STORE or FRAME reads its block in[s][B] and writes the 160
+ * samples blocks[s][160] that cruse_stream_encode reads */
+int cruse_stream_resample_in(const int* mode, int S, int io_rate, const void* in, int in_fmt, const float* taps, float* rs_state,
+                             int rs_stride, float* blocks, void* stream);
+/* after cruse_stream_decode of the main chain: a slot whose mode is FRAME or END reads out16[s][160] and writes out[s][B] */
+int cruse_stream_resample_out(const int* mode, int S, int io_rate, const float* out16, const float* taps, float* rs_state,
+                              int rs_stride, void* out, int out_fmt, int* clip, void* stream);
+/* before cruse_stream_encode_n: slot s converts its pk[S + s] blocks in[s][0..][B] -> blocks[s][0..][160], both [S][in_hops][.] */
+int cruse_stream_resample_in_n(const int* pk, int S, int hops, int in_hops, int io_rate, const void* in, int in_fmt, const float* taps,
+                               float* rs_state, int rs_stride, float* blocks, void* stream);
+/* after cruse_stream_decode_n: slot s converts the output blocks its packet yields (its frames, less frame 0 of a clip; the count
+ * follows from pk alone) out16[s][0..][160] -> out[s][0..][B], both [S][out_hops][.] */
+int cruse_stream_resample_out_n(const int* pk, int S, int hops, int out_hops, int io_rate, const float* out16, const float* taps,
+                                float* rs_state, int rs_stride, void* out, int out_fmt, int* clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,8 +16,12 @@ With --pcm the instances are built with pcm_in = pcm_out = True and fed int16 bl
 atten_lim = True and every slot limited to DB dB.  Either adds "io" to the result; without them nothing changes (DESIGN 12c,
 profiles/stream_io_rtf.json).
 
+With --io-rate 16000,48000,... every cell is measured once per rate (StreamingInferencer(io_rate=...): blocks of rate / 100 samples
+through the rate-conversion kernels; a hop is still 10 ms) and every row carries "io_rate"; without it nothing changes (DESIGN 12d,
+profiles/stream_rs_rtf.json).
+
     python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--precision f32,f16] [--pcm]
-                               [--atten-lim DB] [--out FILE]
+                               [--atten-lim DB] [--io-rate 16000,8000,48000] [--out FILE]
 """
 from __future__ import annotations
 
@@ -48,7 +52,7 @@ def closed_form(model):
             p.copy_(v.reshape(p.shape).to(p.dtype))
 
 
-IO = {"pcm": False, "atten_lim": None}       # --pcm / --atten-lim: the I/O mode of every instance measured
+IO = {"pcm": False, "atten_lim": None, "io_rate": None}      # --pcm / --atten-lim / --io-rate: the I/O mode of every instance measured
 
 
 def _inferencer(model, S: int, precision: str, **kw):
@@ -57,6 +61,8 @@ def _inferencer(model, S: int, precision: str, **kw):
         kw.update(pcm_in=True, pcm_out=True)
     if IO["atten_lim"] is not None:
         kw.update(atten_lim=True)
+    if IO["io_rate"] is not None:
+        kw.update(io_rate=IO["io_rate"])
     inf = StreamingInferencer(model, S, **kw) if precision == "f32" else StreamingInferencer(model, S, precision=precision, **kw)
     if IO["atten_lim"] is not None:
         inf.set_atten_lim(IO["atten_lim"])
@@ -64,7 +70,9 @@ def _inferencer(model, S: int, precision: str, **kw):
 
 
 def _blocks(*shape):
-    """0.1 * randn blocks, as int16 PCM with --pcm"""
+    """0.1 * randn blocks (`shape` ends in 160: a block, io_rate / 100 samples with --io-rate), as int16 PCM with --pcm"""
+    if IO["io_rate"] is not None:
+        shape = shape[:-1] + (IO["io_rate"] // 100,)
     x = 0.1 * torch.randn(*shape, device="cuda")
     return (x * 32768.0).round().clamp(-32768, 32767).to(torch.int16) if IO["pcm"] else x
 
@@ -128,9 +136,11 @@ def main():
     ap.add_argument("--precision", default="f32", help="f32 (default), f16 or f32,f16: the StreamingInferencer modes to measure")
     ap.add_argument("--pcm", action="store_true", help="int16 PCM blocks in and out (pcm_in = pcm_out = True)")
     ap.add_argument("--atten-lim", type=float, default=None, metavar="DB", help="every slot limited to DB dB of attenuation (atten_lim = True)")
+    ap.add_argument("--io-rate", default=None, help="comma-separated I/O sample rates (8000, 16000, 32000, 48000): measure every cell at each")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()
     IO.update(pcm=a.pcm, atten_lim=a.atten_lim)
+    rates = [None] if a.io_rate is None else [int(r) for r in a.io_rate.split(",")]
     from cruse_amd.model.cruse_net import unet_2
     torch.manual_seed(0)
     m = unet_2(rnn_groups=a.groups, precision="f32")
@@ -140,25 +150,30 @@ def main():
     if any(p not in ("f32", "f16") for p in precs):
         ap.error(f"--precision takes f32, f16 or f32,f16, got {a.precision}")
     rows = []
-    for prec in precs:
-        if a.hops is None:
-            part = [measure(m, int(s), a.seconds, prec) for s in a.slots.split(",")]
-        else:
-            part = [measure_packets(m, int(s), int(h), a.seconds, prec) for s in a.slots.split(",") for h in a.hops.split(",")]
-            base = {r["n_slots"]: r["wall_us_per_hop"]["mean"] for r in part if r["hops"] == 1}
-            for r in part:                                          # per hop against the push path of the same mode and run
-                if r["n_slots"] in base:
-                    r["per_hop_vs_push"] = round(r["wall_us_per_hop"]["mean"] / base[r["n_slots"]], 3)
-        if precs != ["f32"]:
+    for rate in rates:
+        IO.update(io_rate=rate)
+        for prec in precs:
+            if a.hops is None:
+                part = [measure(m, int(s), a.seconds, prec) for s in a.slots.split(",")]
+            else:
+                part = [measure_packets(m, int(s), int(h), a.seconds, prec) for s in a.slots.split(",") for h in a.hops.split(",")]
+                base = {r["n_slots"]: r["wall_us_per_hop"]["mean"] for r in part if r["hops"] == 1}
+                for r in part:                                      # per hop against the push path of the same mode and run
+                    if r["n_slots"] in base:
+                        r["per_hop_vs_push"] = round(r["wall_us_per_hop"]["mean"] / base[r["n_slots"]], 3)
             for r in part:
-                r["precision"] = prec
-        rows += part
+                if precs != ["f32"]:
+                    r["precision"] = prec
+                if rate is not None:
+                    r["io_rate"] = rate
+            rows += part
     if "f32" in precs and "f16" in precs:
         per_hop = lambda r: r["wall_us_per_hop"]["mean"] if "wall_us_per_hop" in r else r["push_wall_us"]["mean"]
-        f32 = {(r["n_slots"], r.get("hops", 1)): per_hop(r) for r in rows if r["precision"] == "f32"}
+        cell = lambda r: (r["n_slots"], r.get("hops", 1), r.get("io_rate"))
+        f32 = {cell(r): per_hop(r) for r in rows if r["precision"] == "f32"}
         for r in rows:
             if r["precision"] == "f16":
-                r["vs_f32"] = round(per_hop(r) / f32[(r["n_slots"], r.get("hops", 1))], 3)
+                r["vs_f32"] = round(per_hop(r) / f32[cell(r)], 3)
     res = {"model": f"unet_2 ch={m.ch} rnn_groups={a.groups}", "device": torch.cuda.get_device_name(0), "rows": rows}
     if a.pcm or a.atten_lim is not None:
         res["io"] = {"pcm": a.pcm, "atten_lim_db": a.atten_lim}
