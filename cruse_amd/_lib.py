@@ -153,6 +153,11 @@ SIGNATURES = {
     "cruse_stream_resample_out": ("piipppipipp", "i"),
     "cruse_stream_resample_in_n": ("piiiipippipp", "i"),
     "cruse_stream_resample_out_n": ("piiiipppipipp", "i"),
+    "cruse_si_sdr": ("ppiipp", "i"),
+    "cruse_stoi_layout": ("iip", "i"),
+    "cruse_stoi_ws_bytes": ("ii", "z"),
+    "cruse_stoi_tables": ("pp", "i"),
+    "cruse_stoi": ("ppiippzpp", "i"),
 }
 
 

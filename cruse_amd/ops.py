@@ -1239,3 +1239,53 @@ def stream_pack_f16(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
     # unit = ut*16 + r, k = ks*32 + q*8 + j, lane = q*16 + r
     p = p.reshape(2, g, 3, UT, 16, KS, 4, 8).permute(0, 1, 2, 3, 5, 6, 4, 7)
     return p.contiguous().reshape(-1).to(torch.float16)
+
+
+# ======================================================================================================================
+# validation metrics (cruse_si_sdr, cruse_stoi*; cruse_amd/metrics.py caches the tables and the workspace)
+# ======================================================================================================================
+STOI_LAYOUT_NAMES = ("L10", "nF", "nGs", "nSB", "x10", "e", "nk", "kept", "tob", "part", "total")
+STOI_TABLE_FLOATS = 1540
+
+
+def _clip_pair(ref: torch.Tensor, est: torch.Tensor, name: str):
+    if ref.dim() != 2 or ref.shape != est.shape:
+        raise RuntimeError(f"{name}: expected two [B, L] tensors of one shape, got {tuple(ref.shape)} and {tuple(est.shape)}")
+    return _p(_f32(ref, name)), _p(_f32(est, name)), ref.shape[0], ref.shape[1]
+
+
+def si_sdr(ref: torch.Tensor, est: torch.Tensor) -> torch.Tensor:
+    """SI-SDR in dB of every clip of est [B, L] against ref [B, L] -> [B] f32"""
+    r, e, B, L = _clip_pair(ref, est, "si_sdr")
+    out = torch.empty(B, device=ref.device, dtype=torch.float32)
+    check(lib.cruse_si_sdr(r, e, B, L, _p(out), _stream()))
+    return out
+
+
+def stoi_layout(B: int, L: int) -> Dict[str, int]:
+    """Sizes of the STOI stages and the offsets (4-byte units) of the stage arrays in the workspace of cruse_stoi(B, L)."""
+    arr = (ctypes.c_int * len(STOI_LAYOUT_NAMES))()
+    check(lib.cruse_stoi_layout(int(B), int(L), arr))
+    return dict(zip(STOI_LAYOUT_NAMES, list(arr)))
+
+
+def stoi_tables(device) -> torch.Tensor:
+    tab = torch.empty(STOI_TABLE_FLOATS, device=device, dtype=torch.float32)
+    check(lib.cruse_stoi_tables(_p(tab), _stream()))
+    return tab
+
+
+def stoi_workspace(B: int, L: int, device) -> torch.Tensor:
+    """an f32 tensor of cruse_stoi_ws_bytes(B, L) bytes (raises where the shape is refused)"""
+    n = stoi_layout(B, L)["total"]
+    assert 4 * n == lib.cruse_stoi_ws_bytes(int(B), int(L))
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def stoi(ref: torch.Tensor, est: torch.Tensor, tab: torch.Tensor, ws: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """classic STOI of every clip of est [B, L] against ref [B, L], both at 16 kHz -> [B] f32; the stages stay in ws (stoi_layout)"""
+    r, e, B, L = _clip_pair(ref, est, "stoi")
+    if out is None:
+        out = torch.empty(B, device=ref.device, dtype=torch.float32)
+    check(lib.cruse_stoi(r, e, B, L, _p(_f32(tab, "stoi")), _p(ws), ws.numel() * ws.element_size(), _p(_f32(out, "stoi")), _stream()))
+    return out

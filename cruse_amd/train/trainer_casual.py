@@ -17,8 +17,12 @@ What the reference's knobs do here:
   meta.hip_graph (this repo)  -> true: replay the step from HIP graphs, false: launch eagerly, "auto" (default): time both
                                  on the first eight real steps and keep the faster
   save_checkpoint_interval, validation_interval, save_max_metric_score -> as base_trainer.py:72-86,395-418
-The validation score is the configured loss on the validation set (the reference's STOI / PESQ metrics are host-side
-libraries outside this path), so `save_max_metric_score = false` is the meaningful setting.
+  validation.metrics (this repo) -> names from cruse_amd.metrics.REGISTERED_METRICS ("SI_SDR", "STOI"), scored on the device for
+                                 (clean, noisy) and (clean, enhanced) as base_trainer.py:328-376 does; validation.score_metric
+                                 (default: the first name) is the one whose enhanced mean scores the epoch
+Without validation.metrics the validation score is the configured loss on the validation set, and `save_max_metric_score = false`
+is the meaningful setting.  With it and `save_max_metric_score = true` the score is the enhanced mean of score_metric, higher is
+better.  The reference's combined score (STOI + (WB_PESQ + 0.5) / 5) / 2 needs PESQ, which is not built (cruse_amd/metrics.py).
 """
 from __future__ import annotations
 
@@ -285,6 +289,26 @@ class _Prefetcher:
         return noisy, clean
 
 
+def validation_metrics(va):
+    """[trainer.validation] metrics / score_metric -> (tuple of metric names, score metric); ((), None) without the `metrics` key.
+    An unknown name raises and names the registered metrics."""
+    names = va.get("metrics", None)
+    if names is None:
+        if "score_metric" in va:
+            raise ValueError("[trainer.validation] score_metric needs the `metrics` key")
+        return (), None
+    from ..metrics import REGISTERED_METRICS
+    if isinstance(names, str) or len(names) == 0:
+        raise ValueError(f"[trainer.validation] metrics must be a non-empty list of names, got {names!r}")
+    names = tuple(names)
+    score = va.get("score_metric", names[0])
+    for n in names + (score,):
+        REGISTERED_METRICS[n]                                            # KeyError: names the registered metrics
+    if score not in names:
+        raise ValueError(f"[trainer.validation] score_metric {score!r} is not in metrics {list(names)}")
+    return names, score
+
+
 def _graph_mode(v):
     """meta.hip_graph: true / false / "auto"."""
     if isinstance(v, str):
@@ -317,6 +341,8 @@ class Trainer:
             "Check the 'save_checkpoint_interval' parameter in the config. It should be large than one."   # base_trainer.py:76
         self.validation_interval = va.get("validation_interval", 1)
         self.save_max_metric_score = va.get("save_max_metric_score", False)
+        self.metric_names, self.score_metric = validation_metrics(va)
+        self.acoustics = dict(ac)
         assert self.validation_interval >= 1, \
             "Check the 'validation_interval' parameter in the config. It should be large than one."       # base_trainer.py:84
         self.save_dir = os.path.join(config["meta"]["save_dir"], config["meta"].get("experiment_name", "exp"))
@@ -435,20 +461,48 @@ class Trainer:
 
     @torch.no_grad()
     def _validation_epoch(self, epoch):
+        self.score_label = "validation loss"
         total, nb = 0.0, 0
+        sums, clips, enhance = None, 0, None
+        if self.metric_names:
+            from ..inferencer import Inferencer
+            from ..metrics import REGISTERED_METRICS
+            was_training = self.model.training
+            ac = self.acoustics
+            enhance = Inferencer(self.model, n_fft=ac["n_fft"], hop_length=ac["hop_length"], win_length=ac.get("win_length", ac["n_fft"]),
+                                 sr=ac.get("sr", 16000), device=self.device)            # puts the model in eval mode
+            sums = torch.zeros(len(self.metric_names), 2, dtype=torch.float64, device=self.device)      # per metric: noisy, enhanced
         for noisy, clean in self.validation_dataloader:
             noisy = noisy.to(self.device).float().contiguous()
             clean = clean.to(self.device).float().contiguous()
             total += self.engine.eval_loss(noisy, clean)
             nb += 1
-        return total / max(nb, 1)
+            if enhance is not None:
+                enhanced = enhance.mag_mask_to_wave(noisy)
+                for k, name in enumerate(self.metric_names):
+                    fn = REGISTERED_METRICS[name]
+                    sums[k, 0] += fn(clean, noisy).double().sum()
+                    sums[k, 1] += fn(clean, enhanced).double().sum()
+                clips += noisy.shape[0]
+        loss = total / max(nb, 1)
+        if enhance is None:
+            return loss
+        self.model.train(was_training)
+        means = (sums / max(clips, 1)).tolist()                          # one synchronisation per validation epoch
+        self.last_metric_means = {name: {"Noisy": m[0], "Enhanced": m[1]} for name, m in zip(self.metric_names, means)}
+        for name, m in self.last_metric_means.items():
+            print(f"[epoch {epoch}] validation {name}: Noisy {m['Noisy']:.6f}  Enhanced {m['Enhanced']:.6f}")
+        if not self.save_max_metric_score:
+            return loss
+        self.score_label = f"validation score ({self.score_metric}, enhanced)"
+        return self.last_metric_means[self.score_metric]["Enhanced"]
 
     def train(self):
         for epoch in range(self.start_epoch, self.epochs + 1):
             if self.only_validation and self.rank == 0:                  # base_trainer.py:386-396
                 self.model.eval()
                 score = self._validation_epoch(epoch)
-                print(f"[epoch {epoch}] validation loss {score:.6f}")
+                print(f"[epoch {epoch}] {self.score_label} {score:.6f}")
                 if self._is_best_epoch(score, save_max_metric_score=self.save_max_metric_score):
                     self._save_checkpoint(epoch, is_best_epoch=True)
                 continue
@@ -466,7 +520,7 @@ class Trainer:
             if self.rank == 0 and epoch % self.validation_interval == 0 and self.validation_dataloader is not None:
                 self.model.eval()
                 score = self._validation_epoch(epoch)
-                print(f"[epoch {epoch}] validation loss {score:.6f}")
+                print(f"[epoch {epoch}] {self.score_label} {score:.6f}")
                 if self._is_best_epoch(score, save_max_metric_score=self.save_max_metric_score):
                     self._save_checkpoint(epoch, is_best_epoch=True)     # rewrites latest_model.tar with the new best_score
                 self.model.train()

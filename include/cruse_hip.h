@@ -882,6 +882,33 @@ int cruse_stream_resample_in_n(const int* pk, int S, int hops, int in_hops, int 
 int cruse_stream_resample_out_n(const int* pk, int S, int hops, int out_hops, int io_rate, const float* out16, const float* taps,
                                 float* rs_state, int rs_stride, void* out, int out_fmt, int* clip, void* stream);
 
+/* ---- validation metrics on the device (ABI 13, additive; csrc/metrics.hip) -------------------------------------------------------
+ * The two closed-form metrics of train_base/metrics.py, scored per clip of a batch ref[B][L], est[B][L] (f32) into out[B] (f32).
+ * Every sum runs in a fixed order and there are no atomics: a result is bit-identical from run to run, and a clip scores the same
+ * alone and inside a batch.  Refused with CRUSE_E_SHAPE before any HIP call: a null buffer, B < 1, L < 1, L > 2^28. */
+/* SI_SDR (train_base/metrics.py:60-82): alpha = <ref, est> / <ref, ref>, p = alpha ref, 10 log10(sum p^2 / sum (est - p)^2), the
+ * three sums in f64.  One launch, one workgroup per clip, so no clip spans several workgroups and there is no second launch. */
+int cruse_si_sdr(const float* ref, const float* est, int B, int L, float* out, void* stream);
+/* Classic (non-extended) STOI of 16 kHz clips, as DESIGN.md section 13 defines it stage by stage (Taal et al. 2011; STOI of
+ * train_base/metrics.py:85-86): 16 -> 10 kHz by a zero-phase 257-tap polyphase FIR, removal of the frames of ref more than 40 dB under
+ * its loudest, 512-point spectra of 256-sample Hann frames in 15 third-octave bands, clipped and normalised correlation over all
+ * 30-frame segments.  A clip that keeps fewer than 31 frames scores 1e-5.  Bounds: B <= 65535, L <= 2^28 and a workspace below 8 GiB
+ * (CRUSE_E_SHAPE beyond).  Six launches at most, none waited for by the host: the call captures into a HIP graph.
+ * cruse_stoi_layout: out[CRUSE_STOI_LAYOUT_INTS] (HOST array) = L10 (10 kHz samples per clip), nF (frames before removal), nGs (row
+ * stride of tob, max(nF - 1, 1)), nSB (segment blocks per band), then the workspace offsets in 4-byte units of the stage arrays
+ * x10 [B][2][L10] f32 (ref, est at 10 kHz), e [B][max(nF,1)] f32 (frame energies of ref in dB), nk [B] int (kept frames), kept
+ * [B][max(nF,1)] int (their indices, ascending; nk[b] valid), tob [B][2][15][nGs] f32 (band magnitudes; nk[b] - 1 valid per row),
+ * part [B][15][nSB] f64 (block partial sums), and the workspace size in the same units. */
+#define CRUSE_STOI_LAYOUT_INTS 11
+int cruse_stoi_layout(int B, int L, int* out);
+/* bytes of device workspace of cruse_stoi(B, L); 0 where cruse_stoi_layout refuses the shape */
+size_t cruse_stoi_ws_bytes(int B, int L);
+/* tab[1540] (device) <- prototype taps h[257] at 0, window hanning(258)[1:-1] at 260, cos / sin(2 pi j / 512) at 516 / 1028, built in
+ * double on the host and rounded once; synchronises `stream` */
+int cruse_stoi_tables(float* tab, void* stream);
+/* ws: 8-byte aligned (CRUSE_E_ALIGN), ws_bytes >= cruse_stoi_ws_bytes(B, L) (CRUSE_E_SHAPE); its contents need no initialisation */
+int cruse_stoi(const float* ref, const float* est, int B, int L, const float* tab, void* ws, size_t ws_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
