@@ -158,6 +158,8 @@ SIGNATURES = {
     "cruse_stoi_ws_bytes": ("ii", "z"),
     "cruse_stoi_tables": ("pp", "i"),
     "cruse_stoi": ("ppiippzpp", "i"),
+    "cruse_biquad_ws_bytes": ("iii", "z"),
+    "cruse_biquad_cascade": ("ppiiiiippp", "i"),
 }
 
 

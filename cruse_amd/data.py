@@ -138,14 +138,83 @@ class DevicePairs(Dataset):
     The trainer recognises `device_resident` and asks for whole batches (device_batch) with the indices of the DataLoader's own
     sampler; the DataLoader object the reference flow builds around the dataset is never iterated.  __getitem__ still works (host
     copies of one pair) for anything that wants to look at an item.
-    path = "cruse_amd.data.DevicePairs", args = {num, length, seed, pool, snr_low, snr_high}."""
+    path = "cruse_amd.data.DevicePairs", args = {num, length, seed, pool, snr_low, snr_high, eq_prob, eq_filters, hp_prob}.
+
+    EQ augmentation (train_base/acoustics/audioAug.py: compositeSecFilt, hp_filter), off by default: with
+    eq_prob / hp_prob > 0 every clean clip and every noise clip of a batch independently gets a cascade of `eq_filters` random
+    sections with probability eq_prob and the 150 Hz high-pass with probability hp_prob, BEFORE snr_mix and without clipping (the
+    pools are not normalised to +-1; snr_mix peak-normalises afterwards).  The returned clean is the filtered, normalised speech: the
+    target follows the augmentation.  A clip that is not selected gets identity sections, so one cruse_biquad_cascade launch of
+    S = eq_filters + 1 sections per tensor covers the batch.  The draws come from a numpy Generator the dataset owns (seeded from
+    `seed`), the sections are designed on the host in float64 and reach the device by one non-blocking copy per tensor from a ring
+    of pinned buffers; a buffer is rewritten only after the event behind its last copy has completed, and the stream is never
+    synchronised with the host.  `aug_coefs` holds the last batch's (clean, noise) coefficient arrays [B, S, 6]."""
 
     device_resident = True
+    NPIN = 4                   # pinned coefficient buffers per tensor: a slot is reused four batches later
+    AUG_SR = 16000             # the filters are designed for the rate of the pools (synth_batch: 16 kHz), whatever [acoustics] sr says
 
-    def __init__(self, num: int = 2048, length: int = 64000, seed: int = 0, pool: int = 128, snr_low: float = 0.0, snr_high: float = 20.0):
+    def __init__(self, num: int = 2048, length: int = 64000, seed: int = 0, pool: int = 128, snr_low: float = 0.0, snr_high: float = 20.0,
+                 eq_prob: float = 0.0, eq_filters: int = 3, hp_prob: float = 0.0):
         self.num, self.length, self.seed, self.pool = num, length, seed, max(1, min(pool, num))
         self.snr_low, self.snr_high = float(snr_low), float(snr_high)
+        self.eq_prob, self.eq_filters, self.hp_prob = float(eq_prob), int(eq_filters), float(hp_prob)
+        if not (0.0 <= self.eq_prob <= 1.0 and 0.0 <= self.hp_prob <= 1.0):
+            raise ValueError(f"DevicePairs: eq_prob = {eq_prob} and hp_prob = {hp_prob} are probabilities")
+        if self.augments and not 0 < self.eq_filters < 6:
+            raise ValueError(f"DevicePairs: eq_filters = {eq_filters} must lie in 1..5 (six filter types, distinct per clip)")
+        self.aug_coefs = None
+        self._aug_rng = None
+        self._pin = {}             # (device, B) -> [NPIN][2] pinned [B, S, 6] f64
+        self._pin_ev = {}          # (device, B) -> [NPIN] event behind the slot's last copies
+        self._aug_k = 0
         self._pools = {}
+
+    @property
+    def augments(self) -> bool:
+        return self.eq_prob > 0.0 or self.hp_prob > 0.0
+
+    def draw_aug_coefs(self, n: int):
+        """[n, eq_filters + 1, 6] float64: per clip the EQ cascade with probability eq_prob, then the high-pass with probability hp_prob;
+        identity sections where not selected.  Consumes the dataset's own generator."""
+        import numpy as np
+        from .acoustics import audio_aug as A
+        if self._aug_rng is None:
+            self._aug_rng = np.random.default_rng(self.seed * 100003 + 41)
+        rng = self._aug_rng
+        coef = np.empty((n, self.eq_filters + 1, 6), dtype=np.float64)
+        coef[:] = A.IDENTITY_SECTION
+        eq = rng.random(n) < self.eq_prob
+        hp = rng.random(n) < self.hp_prob
+        if eq.any():
+            coef[eq, :self.eq_filters] = A.draw_sec_filters(int(eq.sum()), self.eq_filters, self.AUG_SR, rng)
+        if hp.any():
+            coef[hp, self.eq_filters] = A.draw_hp_filters(int(hp.sum()), 1, self.AUG_SR, rng)[:, 0]
+        return coef
+
+    def _augment(self, c, n, device):
+        from . import ops
+        B = c.shape[0]
+        key = (device, B)
+        if key not in self._pin:
+            S = self.eq_filters + 1
+            self._pin[key] = [[torch.empty(B, S, 6, dtype=torch.float64).pin_memory() for _ in range(2)] for _ in range(self.NPIN)]
+            self._pin_ev[key] = [None] * self.NPIN
+        slot = self._aug_k % self.NPIN
+        self._aug_k += 1
+        ev = self._pin_ev[key][slot]
+        if ev is not None:
+            ev.synchronize()                       # the copies issued NPIN batches ago: a wait on that event, not on the stream
+        host = (self.draw_aug_coefs(B), self.draw_aug_coefs(B))
+        dev = []
+        for buf, h in zip(self._pin[key][slot], host):
+            buf.numpy()[...] = h
+            dev.append(buf.to(device, non_blocking=True))
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(device))
+        self._pin_ev[key][slot] = ev
+        self.aug_coefs = host
+        return ops.biquad_cascade(c, dev[0], clamp=False), ops.biquad_cascade(n, dev[1], clamp=False)
 
     def __len__(self):
         return self.num
@@ -166,6 +235,8 @@ class DevicePairs(Dataset):
         idx = idx.to(device, non_blocking=True)
         c = clean_p.index_select(0, idx % self.pool)
         n = noise_p.index_select(0, (idx * 7 + 3) % self.pool)
+        if self.augments:
+            c, n = self._augment(c, n, torch.device(device))
         noisy, clean, _ = snr_mix(c, n, snr.index_select(0, idx % self.num), return_parts=True)
         return noisy, clean
 

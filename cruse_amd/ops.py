@@ -1289,3 +1289,44 @@ def stoi(ref: torch.Tensor, est: torch.Tensor, tab: torch.Tensor, ws: torch.Tens
         out = torch.empty(B, device=ref.device, dtype=torch.float32)
     check(lib.cruse_stoi(r, e, B, L, _p(_f32(tab, "stoi")), _p(ws), ws.numel() * ws.element_size(), _p(_f32(out, "stoi")), _stream()))
     return out
+
+
+# ======================================================================================================================
+# biquad cascade (cruse_biquad_cascade; cruse_amd/acoustics/audio_aug.py designs the sections, data.DevicePairs applies them)
+# ======================================================================================================================
+BIQUAD_CHUNK = 32           # CRUSE_BIQUAD_CHUNK (include/cruse_hip.h): consecutive samples a lane holds
+BIQUAD_TILE = 32768         # CRUSE_BIQUAD_TILE: samples a workgroup holds; a longer clip goes through tiles in order
+BIQUAD_MAX_SECTIONS = 8
+
+
+def biquad_cascade(x: torch.Tensor, coef: torch.Tensor, clamp: bool = True, out: Optional[torch.Tensor] = None,
+                   ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """S biquad sections in order over every clip of x [B, L] f32 -> [B, L] f32: scipy.signal.lfilter in float64 from rest, with
+    clamp the output of every section clipped to [-1, 1].  coef: float64 on the device, [S, 6] (shared) or [B, S, 6], rows
+    (b0 b1 b2 a0 a1 a2).  ws: a workspace of cruse_biquad_ws_bytes(B, L, S) bytes, taken here when None (0 bytes for every shape today;
+    the parameter lets a caller that captures the call into a graph own the buffer, and the tests guard it with sentinels)."""
+    if x.dim() != 2:
+        raise RuntimeError(f"biquad_cascade: x must be [B, L], got {tuple(x.shape)}")
+    B, L = x.shape
+    if coef.dtype != torch.float64:
+        raise RuntimeError(f"biquad_cascade: coefficients must be float64 (DESIGN section 14), got {coef.dtype}")
+    if coef.dim() == 2 and coef.shape[1] == 6:
+        S, stride = coef.shape[0], 0
+    elif coef.dim() == 3 and coef.shape[0] == B and coef.shape[2] == 6:
+        S, stride = coef.shape[1], 6 * coef.shape[1]
+    else:
+        raise RuntimeError(f"biquad_cascade: coefficients {tuple(coef.shape)} must be [S, 6] or [{B}, S, 6]")
+    if coef.device != x.device:
+        raise RuntimeError(f"biquad_cascade: coefficients on {coef.device}, samples on {x.device}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape:
+        raise RuntimeError(f"biquad_cascade: out {tuple(out.shape)} != x {tuple(x.shape)}")
+    need = lib.cruse_biquad_ws_bytes(int(B), int(L), int(S))
+    if ws is None and need:
+        ws = torch.empty(need, device=x.device, dtype=torch.uint8)
+    if ws is not None and ws.numel() * ws.element_size() < need:
+        raise RuntimeError(f"biquad_cascade: workspace of {ws.numel() * ws.element_size()} bytes, {need} needed")
+    check(lib.cruse_biquad_cascade(_p(_f32(x, "biquad_cascade")), _p(coef), stride, B, L, S, 1 if clamp else 0, _p(ws),
+                                   _p(_f32(out, "biquad_cascade")), _stream()))
+    return out

@@ -909,6 +909,24 @@ int cruse_stoi_tables(float* tab, void* stream);
 /* ws: 8-byte aligned (CRUSE_E_ALIGN), ws_bytes >= cruse_stoi_ws_bytes(B, L) (CRUSE_E_SHAPE); its contents need no initialisation */
 int cruse_stoi(const float* ref, const float* est, int B, int L, const float* tab, void* ws, size_t ws_bytes, float* out, void* stream);
 
+/* ---- biquad cascade over whole clips (ABI 13, additive; csrc/biquad.hip) -----------------------------------
+ * The lfilter under the reference's EQ augmentation (train_base/acoustics/audioAug.py:149-178; torchaudio.functional.lfilter there).
+ * x, y [B][L] f32, contiguous.  coef: S sections of (b0, b1, b2, a0, a1, a2) in FLOAT64 (device), [B][S][6] with coef_stride = 6 S or
+ * one shared [S][6] with coef_stride = 0 (cruse_fir_causal's hs convention); 8-byte aligned (CRUSE_E_ALIGN).  One section is
+ * scipy.signal.lfilter(b / a0, [1, a1 / a0, a2 / a0], x) from a zero state, evaluated in float64; with clamp != 0 its output is then
+ * clipped to [-1, 1] (lfilter's clamp=True) before it enters the next section -- never inside a section's feedback.  What one
+ * section hands the next stays float64; the last output is rounded once to f32.
+ * One launch, one workgroup per clip; a lane holds CRUSE_BIQUAD_CHUNK consecutive samples, a workgroup CRUSE_BIQUAD_TILE, and a longer
+ * clip goes through tiles in order inside its workgroup.  No allocation, no host synchronisation, no host read of coef (the call
+ * captures into a HIP graph); results are bit-identical from run to run.  Refused with CRUSE_E_SHAPE before any HIP call: B < 1,
+ * L < 1, L > 2^30, S < 1, S > 8, a null x / coef / y, a coef_stride other than 0 or 6 S. */
+#define CRUSE_BIQUAD_CHUNK 32
+#define CRUSE_BIQUAD_TILE 32768
+/* bytes of device workspace of cruse_biquad_cascade(B, L, S): 0, no clip leaves its workgroup (ws may then be null).  Host only. */
+size_t cruse_biquad_ws_bytes(int B, int L, int S);
+int cruse_biquad_cascade(const float* x, const double* coef, int coef_stride, int B, int L, int S, int clamp, void* ws, float* y,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
