@@ -160,6 +160,11 @@ SIGNATURES = {
     "cruse_stoi": ("ppiippzpp", "i"),
     "cruse_biquad_ws_bytes": ("iii", "z"),
     "cruse_biquad_cascade": ("ppiiiiippp", "i"),
+    "cruse_fftconv_spec_bytes": ("iii", "z"),
+    "cruse_fftconv_ws_bytes": ("ii", "z"),
+    "cruse_fftconv_prepare": ("piippzp", "i"),
+    "cruse_fftconv_apply": ("piipziippzppp", "i"),
+    "cruse_peak_scale": ("ppiifpp", "i"),
 }
 
 

@@ -90,6 +90,51 @@ def snr_mix(clean_y: torch.Tensor, noise_y: torch.Tensor, snr, target_dB_FS=None
     return (noisy, co, no) if return_parts else noisy
 
 
+def synth_rirs(n: int, rir_len: int, rt60_low: float, rt60_high: float, sr: int, device, generator):
+    """[n, rir_len] f32 synthetic room impulse responses in the manner of fixture G20's: a unit direct path after a delay of 0-15 ms,
+    zeros before it, and after it 0.3 N(0,1) 10^(-3 k / (rt60 sr)) at tap k (-60 dB at k = rt60 sr), one rt60 per response drawn
+    uniformly from [rt60_low, rt60_high] seconds.  Drawn on `device` from `generator` (delay, rt60, tail, in this order)."""
+    delay = torch.randint(0, 15 * sr // 1000 + 1, (n,), device=device, generator=generator).clamp_(max=rir_len - 1)
+    rt60 = rt60_low + (rt60_high - rt60_low) * torch.rand(n, device=device, generator=generator)
+    k = torch.arange(rir_len, device=device, dtype=torch.float32)
+    h = 0.3 * torch.randn(n, rir_len, device=device, generator=generator) * torch.pow(10.0, -3.0 * k[None, :] / (rt60[:, None] * sr))
+    h = torch.where(k[None, :] < delay[:, None], torch.zeros_like(h), h)
+    h.scatter_(1, delay[:, None], 1.0)
+    return h.contiguous()
+
+
+def rir_early_len(rir: torch.Tensor, predelay: int = 50, sr: int = 16000) -> torch.Tensor:
+    """int32 [NR]: add_reverb's `et` of every row of rir [NR, R] -- the index of the largest VALUE (not magnitude, dataset.py:219)
+    plus predelay ms.  Not clamped to R: cruse_fftconv_prepare clamps, as the reference's slice rir[:et] saturates."""
+    return (torch.argmax(rir, dim=1) + (predelay * sr) // 1000).to(torch.int32)
+
+
+def add_reverb(cln_wav: torch.Tensor, rir_wav: torch.Tensor, channels: int = 1, predelay: int = 50, sr: int = 16000):
+    """SynDataset.add_reverb (dataset/dataset.py:215-233) for one clip or a batch ON THE GPU: the reverberant speech
+    fftconvolve(cln, rir)[:L] and the early-reflection target fftconvolve(cln, rir[:et])[:L], et = argmax(rir) + predelay ms, both from
+    one cruse_fftconv_apply on the same input spectra.  cln_wav [L] or [B, L]; rir_wav [R] (one response for all clips) or [B, R].
+    Returns (wav_tgt, wav_early_tgt) in the shape of cln_wav, f32.
+    Repairs, stated: (1) the reference returns [L, channels] float64 arrays; here the mono pair comes back in the shape of cln_wav in
+    f32 (dataset.SynDataset.add_reverb keeps the reference's [L, 1]).  (2) channels > 1 is refused: the reference's multi-microphone
+    branch also picks a random row of a 2-D cln_wav (:224) -- multi-channel paths are out of scope.  (3) rir[:et]
+    with et > R is the whole response there (a slice saturates) and is here by the kernel's clamp; et is never read by the host.
+    (4) argmax is taken over the values, as :219 does: a negative tap of larger magnitude than the direct path does not move et."""
+    from . import ops
+    if channels != 1:
+        raise NotImplementedError("add_reverb: channels > 1 (multi-microphone responses) is not built (SURVEY section 2)")
+    one = cln_wav.dim() == 1
+    x = (cln_wav.reshape(1, -1) if one else cln_wav).contiguous().float()
+    if x.dim() != 2:
+        raise RuntimeError(f"add_reverb: cln_wav {tuple(cln_wav.shape)} must be [L] or [B, L]")
+    h = torch.as_tensor(rir_wav).to(x.device).float()
+    h = (h.reshape(1, -1) if h.dim() == 1 else h).contiguous()
+    if h.dim() != 2 or h.shape[0] not in (1, x.shape[0]):
+        raise RuntimeError(f"add_reverb: rir_wav {tuple(rir_wav.shape)} must be [R] or [{x.shape[0]}, R]")
+    bank = ops.fft_conv_prepare(h, rir_early_len(h, predelay, sr))
+    full, early = ops.fft_conv_apply(x, bank, want_early=True)
+    return (full[0], early[0]) if one else (full, early)
+
+
 class SyntheticPairs(Dataset):
     """[train_dataset] plug-in: path = "cruse_amd.data.SyntheticPairs", args = {num, length, seed}."""
 
@@ -138,7 +183,8 @@ class DevicePairs(Dataset):
     The trainer recognises `device_resident` and asks for whole batches (device_batch) with the indices of the DataLoader's own
     sampler; the DataLoader object the reference flow builds around the dataset is never iterated.  __getitem__ still works (host
     copies of one pair) for anything that wants to look at an item.
-    path = "cruse_amd.data.DevicePairs", args = {num, length, seed, pool, snr_low, snr_high, eq_prob, eq_filters, hp_prob}.
+    path = "cruse_amd.data.DevicePairs", args = {num, length, seed, pool, snr_low, snr_high, eq_prob, eq_filters, hp_prob,
+    reverb_proportion, reverb_noise_proportion, reverb_target, rir_pool, rir_len, rt60_low, rt60_high, predelay}.
 
     EQ augmentation (train_base/acoustics/audioAug.py: compositeSecFilt, hp_filter), off by default: with
     eq_prob / hp_prob > 0 every clean clip and every noise clip of a batch independently gets a cascade of `eq_filters` random
@@ -148,14 +194,28 @@ class DevicePairs(Dataset):
     S = eq_filters + 1 sections per tensor covers the batch.  The draws come from a numpy Generator the dataset owns (seeded from
     `seed`), the sections are designed on the host in float64 and reach the device by one non-blocking copy per tensor from a ring
     of pinned buffers; a buffer is rewritten only after the event behind its last copy has completed, and the stream is never
-    synchronised with the host.  `aug_coefs` holds the last batch's (clean, noise) coefficient arrays [B, S, 6]."""
+    synchronised with the host.  `aug_coefs` holds the last batch's (clean, noise) coefficient arrays [B, S, 6].
+
+    Reverberation (SynDataset._select_rir / snr_mix(rir=, rir_noise=) / add_reverb, dataset/dataset.py:205-247), off
+    by default: every clean clip is convolved with a room impulse response with probability reverb_proportion and every noise clip
+    with probability reverb_noise_proportion, each with an independently drawn row of a pool of `rir_pool` synthetic responses of
+    `rir_len` taps (synth_rirs: there are no RIR files, as there are no speech files), FIRST -- then the EQ, then snr_mix, the order
+    the reference marks (:249).  One cruse_fftconv_apply per tensor covers the batch: a clip that is not selected carries index -1 and
+    passes through bit for bit.  The rows come from a numpy Generator of their own (seed * 100003 + 43: the EQ draws are the same
+    with reverb on or off) and reach the device as int32 [B] through a pinned ring under the same event discipline as the
+    coefficients.  `reverb_index` holds the last batch's (clean, noise) index arrays.  reverb_target "full": the returned clean is
+    the reverberant, normalised speech (what the reference's snr_mix returns); "early": the speech through the first
+    argmax(rir) + predelay ms of its response (add_reverb's wav_early_tgt), through the same EQ coefficients, at the scale
+    1 / (max |full| + eps) snr_mix gave the speech inside `noisy` -- the target of a dereverberating enhancer."""
 
     device_resident = True
     NPIN = 4                   # pinned coefficient buffers per tensor: a slot is reused four batches later
     AUG_SR = 16000             # the filters are designed for the rate of the pools (synth_batch: 16 kHz), whatever [acoustics] sr says
 
     def __init__(self, num: int = 2048, length: int = 64000, seed: int = 0, pool: int = 128, snr_low: float = 0.0, snr_high: float = 20.0,
-                 eq_prob: float = 0.0, eq_filters: int = 3, hp_prob: float = 0.0):
+                 eq_prob: float = 0.0, eq_filters: int = 3, hp_prob: float = 0.0, reverb_proportion: float = 0.0,
+                 reverb_noise_proportion: float = 0.0, reverb_target: str = "full", rir_pool: int = 32, rir_len: int = 8000,
+                 rt60_low: float = 0.2, rt60_high: float = 0.8, predelay: int = 50):
         self.num, self.length, self.seed, self.pool = num, length, seed, max(1, min(pool, num))
         self.snr_low, self.snr_high = float(snr_low), float(snr_high)
         self.eq_prob, self.eq_filters, self.hp_prob = float(eq_prob), int(eq_filters), float(hp_prob)
@@ -169,10 +229,80 @@ class DevicePairs(Dataset):
         self._pin_ev = {}          # (device, B) -> [NPIN] event behind the slot's last copies
         self._aug_k = 0
         self._pools = {}
+        self.reverb_proportion, self.reverb_noise_proportion = float(reverb_proportion), float(reverb_noise_proportion)
+        self.reverb_target, self.rir_pool, self.rir_len = reverb_target, int(rir_pool), int(rir_len)
+        self.rt60_low, self.rt60_high, self.predelay = float(rt60_low), float(rt60_high), int(predelay)
+        if not (0.0 <= self.reverb_proportion <= 1.0 and 0.0 <= self.reverb_noise_proportion <= 1.0):
+            raise ValueError(f"DevicePairs: reverb_proportion = {reverb_proportion} and reverb_noise_proportion = {reverb_noise_proportion} "
+                             "are probabilities")
+        if reverb_target not in ("full", "early"):
+            raise ValueError(f"DevicePairs: reverb_target = {reverb_target!r} must be 'full' or 'early'")
+        if self.rir_len < 1 or self.rir_pool < 1 or self.rt60_low > self.rt60_high or self.rt60_low <= 0.0:
+            raise ValueError(f"DevicePairs: rir_len = {rir_len}, rir_pool = {rir_pool} must be >= 1 and 0 < rt60_low = {rt60_low} <= rt60_high = {rt60_high}")
+        self.reverb_index = None
+        self._rev_rng = None
+        self._rpin = {}            # (device, B) -> [NPIN] pinned [2, B] int32
+        self._rpin_ev = {}
+        self._rev_k = 0
+        self._rirs = {}            # device -> (rir pool [rir_pool, rir_len], early_len int32 [rir_pool], prepared bank)
 
     @property
     def augments(self) -> bool:
         return self.eq_prob > 0.0 or self.hp_prob > 0.0
+
+    @property
+    def reverberates(self) -> bool:
+        return self.reverb_proportion > 0.0 or self.reverb_noise_proportion > 0.0
+
+    def draw_reverb_index(self, n: int, proportion: float):
+        """int32 [n]: per clip a row of the RIR pool with probability `proportion`, -1 otherwise.  Consumes the dataset's reverb generator."""
+        import numpy as np
+        if self._rev_rng is None:
+            self._rev_rng = np.random.default_rng(self.seed * 100003 + 43)
+        sel = self._rev_rng.random(n) < proportion
+        rows = self._rev_rng.integers(0, self.rir_pool, size=n)
+        return np.where(sel, rows, -1).astype(np.int32)
+
+    def _ensure_rirs(self, device):
+        from . import ops
+        device = torch.device(device)
+        if device not in self._rirs:
+            g = torch.Generator(device=device).manual_seed(self.seed * 100003 + 31)
+            rirs = synth_rirs(self.rir_pool, self.rir_len, self.rt60_low, self.rt60_high, self.AUG_SR, device, g)
+            early = rir_early_len(rirs, self.predelay, self.AUG_SR)
+            self._rirs[device] = (rirs, early, ops.fft_conv_prepare(rirs, early))
+        return self._rirs[device]
+
+    def _reverb(self, c, n, device):
+        """-> (clean, noise, early clean or None): the two tensors through their drawn responses"""
+        from . import ops
+        B = c.shape[0]
+        key = (device, B)
+        if key not in self._rpin:
+            self._rpin[key] = [torch.empty(2, B, dtype=torch.int32).pin_memory() for _ in range(self.NPIN)]
+            self._rpin_ev[key] = [None] * self.NPIN
+        slot = self._rev_k % self.NPIN
+        self._rev_k += 1
+        ev = self._rpin_ev[key][slot]
+        if ev is not None:
+            ev.synchronize()                       # the copy issued NPIN batches ago: a wait on that event, not on the stream
+        host = (self.draw_reverb_index(B, self.reverb_proportion), self.draw_reverb_index(B, self.reverb_noise_proportion))
+        buf = self._rpin[key][slot]
+        buf.numpy()[0], buf.numpy()[1] = host
+        idx = buf.to(device, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(device))
+        self._rpin_ev[key][slot] = ev
+        self.reverb_index = host
+        bank = self._ensure_rirs(device)[2]
+        early = None
+        if self.reverb_proportion > 0.0 and self.reverb_target == "early":
+            c, early = ops.fft_conv_apply(c, bank, h_index=idx[0], want_early=True)
+        elif self.reverb_proportion > 0.0:
+            c = ops.fft_conv_apply(c, bank, h_index=idx[0])
+        if self.reverb_noise_proportion > 0.0:
+            n = ops.fft_conv_apply(n, bank, h_index=idx[1])
+        return c, n, early
 
     def draw_aug_coefs(self, n: int):
         """[n, eq_filters + 1, 6] float64: per clip the EQ cascade with probability eq_prob, then the high-pass with probability hp_prob;
@@ -192,7 +322,7 @@ class DevicePairs(Dataset):
             coef[hp, self.eq_filters] = A.draw_hp_filters(int(hp.sum()), 1, self.AUG_SR, rng)[:, 0]
         return coef
 
-    def _augment(self, c, n, device):
+    def _augment(self, c, n, device, early=None):
         from . import ops
         B = c.shape[0]
         key = (device, B)
@@ -214,7 +344,9 @@ class DevicePairs(Dataset):
         ev.record(torch.cuda.current_stream(device))
         self._pin_ev[key][slot] = ev
         self.aug_coefs = host
-        return ops.biquad_cascade(c, dev[0], clamp=False), ops.biquad_cascade(n, dev[1], clamp=False)
+        if early is not None:                      # the early target follows the speech: the same sections
+            early = ops.biquad_cascade(early, dev[0], clamp=False)
+        return ops.biquad_cascade(c, dev[0], clamp=False), ops.biquad_cascade(n, dev[1], clamp=False), early
 
     def __len__(self):
         return self.num
@@ -235,9 +367,15 @@ class DevicePairs(Dataset):
         idx = idx.to(device, non_blocking=True)
         c = clean_p.index_select(0, idx % self.pool)
         n = noise_p.index_select(0, (idx * 7 + 3) % self.pool)
+        early = None
+        if self.reverberates:
+            c, n, early = self._reverb(c, n, torch.device(device))
         if self.augments:
-            c, n = self._augment(c, n, torch.device(device))
+            c, n, early = self._augment(c, n, torch.device(device), early)
         noisy, clean, _ = snr_mix(c, n, snr.index_select(0, idx % self.num), return_parts=True)
+        if early is not None:
+            from . import ops
+            clean = ops.peak_scale(early, c)        # 1 / (max |full| + eps): the scale of the speech inside `noisy`
         return noisy, clean
 
     def __getitem__(self, i):

@@ -1330,3 +1330,91 @@ def biquad_cascade(x: torch.Tensor, coef: torch.Tensor, clamp: bool = True, out:
     check(lib.cruse_biquad_cascade(_p(_f32(x, "biquad_cascade")), _p(coef), stride, B, L, S, 1 if clamp else 0, _p(ws),
                                    _p(_f32(out, "biquad_cascade")), _stream()))
     return out
+
+
+# ======================================================================================================================
+# FFT convolution with a bank of filters (cruse_fftconv_*; data.add_reverb and data.DevicePairs apply room impulse responses with it)
+# ======================================================================================================================
+FFTCONV_PART = 2048         # CRUSE_FFTCONV_PART (include/cruse_hip.h): samples per partition; one spectrum is 8 * FFTCONV_PART bytes
+
+
+class FftConvFilters:
+    """A prepared filter bank: `spec` (uint8, cruse_fftconv_spec_bytes), the NR filters of R taps it came from, and whether it holds
+    the early spectra."""
+
+    def __init__(self, spec: torch.Tensor, NR: int, R: int, early: bool):
+        self.spec, self.NR, self.R, self.early = spec, NR, R, early
+
+
+_FFTCONV_WS: Dict[tuple, torch.Tensor] = {}
+
+
+def _i32(t: torch.Tensor, n: int, device, name: str) -> torch.Tensor:
+    if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != n or t.device != device:
+        raise RuntimeError(f"{name}: expected int32 [{n}] on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def fft_conv_prepare(h: torch.Tensor, early_len: Optional[torch.Tensor] = None, spec: Optional[torch.Tensor] = None) -> FftConvFilters:
+    """h [R] or [NR, R] f32 on the device -> the spectra cruse_fftconv_apply reads.  early_len: int32 [NR] on the device; the bank then
+    also holds every filter cut to its first clamp(early_len, 0, R) taps.  spec: a caller's uint8 buffer (taken here when None)."""
+    if h.dim() not in (1, 2) or h.numel() == 0:
+        raise RuntimeError(f"fft_conv_prepare: filters must be [R] or [NR, R], got {tuple(h.shape)}")
+    h2 = h.reshape(1, -1) if h.dim() == 1 else h
+    NR, R = h2.shape
+    if early_len is not None:
+        _i32(early_len, NR, h.device, "fft_conv_prepare: early_len")
+    need = lib.cruse_fftconv_spec_bytes(int(NR), int(R), 0 if early_len is None else 1)
+    if spec is None:
+        spec = torch.empty(need, device=h.device, dtype=torch.uint8)
+    nbytes = spec.numel() * spec.element_size()
+    check(lib.cruse_fftconv_prepare(_p(_f32(h2, "fft_conv_prepare")), NR, R, _p(early_len), _p(spec), nbytes, _stream()))
+    return FftConvFilters(spec, NR, R, early_len is not None)
+
+
+def fft_conv_apply(x: torch.Tensor, bank: FftConvFilters, h_index: Optional[torch.Tensor] = None, want_early: bool = False,
+                   out: Optional[torch.Tensor] = None, out_early: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """x [B, L] f32 -> fftconvolve(x[b], h[f(b)])[:L] per clip (and, with want_early, the same through the early filters: a pair).
+    f(b) = h_index[b] (int32 [B] on the device; negative or >= NR: the clip passes through unchanged); without h_index the bank holds
+    one filter for all clips or one per clip.  The input-spectrum workspace is cached per (device, B, L) unless `ws` is given."""
+    if x.dim() != 2:
+        raise RuntimeError(f"fft_conv_apply: x must be [B, L], got {tuple(x.shape)}")
+    B, L = x.shape
+    if want_early and not bank.early:
+        raise RuntimeError("fft_conv_apply: the bank was prepared without early_len")
+    if bank.spec.device != x.device:
+        raise RuntimeError(f"fft_conv_apply: filters on {bank.spec.device}, samples on {x.device}")
+    if h_index is not None:
+        _i32(h_index, B, x.device, "fft_conv_apply: h_index")
+    need = lib.cruse_fftconv_ws_bytes(int(B), int(L))
+    if ws is None:
+        key = (x.device, int(B), int(L))
+        ws = _FFTCONV_WS.get(key)
+        if ws is None:
+            ws = _FFTCONV_WS[key] = torch.empty(need, device=x.device, dtype=torch.uint8)
+    outs = []
+    for o in (out, out_early if want_early else None):
+        if o is not None and o.shape != x.shape:
+            raise RuntimeError(f"fft_conv_apply: out {tuple(o.shape)} != x {tuple(x.shape)}")
+        outs.append(torch.empty_like(x) if o is None else _f32(o, "fft_conv_apply"))
+    y, ye = outs[0], outs[1] if want_early else None
+    check(lib.cruse_fftconv_apply(_p(_f32(x, "fft_conv_apply")), B, L, _p(bank.spec), bank.spec.numel() * bank.spec.element_size(), bank.NR, bank.R,
+                                  _p(h_index), _p(ws), ws.numel() * ws.element_size(), _p(y), _p(ye), _stream()))
+    return (y, ye) if want_early else y
+
+
+def fft_conv_causal(x: torch.Tensor, h: torch.Tensor, early_len: Optional[torch.Tensor] = None):
+    """scipy.signal.fftconvolve(x, h)[:L] per clip in one call: x [B, L], h [R] (shared) or [B, R]; with early_len (int32 [1] or [B])
+    a pair (y, y_early)."""
+    if h.dim() == 2 and h.shape[0] != x.shape[0]:
+        raise RuntimeError(f"fft_conv_causal: filters {tuple(h.shape)} must be [R] or [{x.shape[0]}, R]")
+    return fft_conv_apply(x, fft_conv_prepare(h, early_len), want_early=early_len is not None)
+
+
+def peak_scale(x: torch.Tensor, ref: torch.Tensor, eps: float = 1e-7) -> torch.Tensor:
+    """x[b] / (max |ref[b]| + eps) per clip, x and ref [B, L] f32: snr_mix's peak normalisation of `ref` applied to `x`"""
+    if x.dim() != 2 or x.shape != ref.shape:
+        raise RuntimeError(f"peak_scale: expected two [B, L] tensors of one shape, got {tuple(x.shape)} and {tuple(ref.shape)}")
+    y = torch.empty_like(x)
+    check(lib.cruse_peak_scale(_p(_f32(x, "peak_scale")), _p(_f32(ref, "peak_scale")), x.shape[0], x.shape[1], float(eps), _p(y), _stream()))
+    return y

@@ -927,6 +927,36 @@ size_t cruse_biquad_ws_bytes(int B, int L, int S);
 int cruse_biquad_cascade(const float* x, const double* coef, int coef_stride, int B, int L, int S, int clamp, void* ws, float* y,
                          void* stream);
 
+/* ---- FFT convolution with a bank of filters (ABI 13, additive; csrc/fftconv.hip) ---------------------------
+ * y[b][n] = sum_{k < R, k <= n} h[f(b)][k] x[b][n - k], n < L: scipy.signal.fftconvolve(x, h)[:L], the room-impulse-response step of
+ * SynDataset.snr_mix (dataset/dataset.py:244-247) and both convolutions of SynDataset.add_reverb (:226-228), by uniformly partitioned
+ * overlap-save convolution in f32.  Optionally y_early[b][n] = the same sum over k < early_len[f(b)]: add_reverb's
+ * fftconvolve(cln_wav, rir[:et]) (:221, :228), from the same input spectra.
+ * Partitions of CRUSE_FFTCONV_PART samples, transforms of twice that.  One spectrum is CRUSE_FFTCONV_PART complex f32 values (bins
+ * 1 .. PART - 1, and the real bins 0 and PART together in bin 0) = 8 PART bytes.
+ *   spec: [1 or 2][NR][npart] spectra, npart = ceil(R / PART); the second half holds the early filters.
+ *   ws:   [B][nblk] spectra, nblk = ceil(L / PART); needs no initialisation, holds the input spectra after the call.
+ * x, y, y_early [B][L] f32 and h [NR][R] f32, contiguous; spec and ws 8-byte aligned (CRUSE_E_ALIGN).  No atomics and one summation
+ * order: results are bit-identical from run to run and a clip convolves the same alone and inside a batch.  No allocation, no host
+ * synchronisation, no host read of a device buffer: the calls capture into a HIP graph.  Refused with CRUSE_E_SHAPE before any HIP
+ * call, cruse_last_error naming the argument: a null x / h / spec / ws / y, B, L, NR or R < 1, L or R > 2^30, NR > 65535 (prepare),
+ * B * nblk > 2^31 - 1, NR neither 1 nor B with a null h_index, spec_bytes or ws_bytes too small. */
+#define CRUSE_FFTCONV_PART 2048
+/* bytes of a prepared bank (early != 0: with the early spectra) and of the input-spectrum workspace; 0 for a size < 1.  Host only. */
+size_t cruse_fftconv_spec_bytes(int NR, int R, int early);
+size_t cruse_fftconv_ws_bytes(int B, int L);
+/* spec <- the spectra of the zero-padded partitions of h[NR][R]; with early_len (int32 [NR] on the device, may be NULL) also those of
+ * every filter cut to its first clamp(early_len[r], 0, R) taps (0: a silent early output).  One launch. */
+int cruse_fftconv_prepare(const float* h, int NR, int R, const int* early_len, void* spec, size_t spec_bytes, void* stream);
+/* f(b) = h_index[b] (int32 [B] on the device); with h_index NULL, b if NR == B and 0 if NR == 1 (cruse_fir_causal's two cases).  A
+ * clip whose index is negative -- or >= NR, which the host cannot know -- passes through: y[b] (and y_early[b]) are x[b] bit for bit
+ * and its transforms are skipped.  y_early may be NULL; not NULL, spec must hold the early spectra.  Out of place.  Two launches. */
+int cruse_fftconv_apply(const float* x, int B, int L, const void* spec, size_t spec_bytes, int NR, int R, const int* h_index, void* ws,
+                        size_t ws_bytes, float* y, float* y_early, void* stream);
+/* y[b] = x[b] * (1 / (max |ref[b]| + eps)): the scale SynDataset.snr_mix gives the speech (dataset/dataset.py:251), applied to
+ * another tensor -- the early-reflection target beside the reverberant speech that sets the peak.  x, ref, y [B][L], out of place. */
+int cruse_peak_scale(const float* x, const float* ref, int B, int L, float eps, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

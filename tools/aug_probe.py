@@ -4,7 +4,14 @@
   epoch         Trainer._train_epoch as bench.py's trainer_path row drives it, on the [train_dataset] sections of
                 configs/cruse_augment.toml and configs/cruse_device_dataset.toml in one process: frames/s (the better of epochs 2-3) and
                 the ratio augmented / plain
-usage: python tools/aug_probe.py [--batches 120] [--out profiles/aug_probe.json]"""
+usage: python tools/aug_probe.py [--batches 120] [--out profiles/aug_probe.json]
+With --reverb the same three rows for the reverberation -> profiles/aug_probe_reverb.json:
+  kernel        cruse_fftconv_apply (with and without y_early) and cruse_fftconv_prepare at B = 64, L = 64000, R = 8000, with a bank of 32
+                filters behind an index and with a filter per clip, and cruse_fir_causal on the same tensors in the same run
+  device_batch  plain, reverb only, reverb + EQ
+  epoch         configs/cruse_reverb.toml against configs/cruse_device_dataset.toml
+Each row is its own process under its own time limit (--row kernel | device_batch | epoch, merged into --out); without --row the
+rows run as child processes, one after the other, and the first that fails ends the run."""
 from __future__ import annotations
 
 import argparse
@@ -48,6 +55,44 @@ def kernel_row(dev, B=64, L=64000, S=4):
     for clamp in (False, True):
         med, best = timed_us(lambda: ops.biquad_cascade(x, coef, clamp=clamp, out=y))
         out["clamp" if clamp else "no_clamp"] = {"median_us": round(med, 2), "min_us": round(best, 2), "GB_per_s": round(out["bytes"] / med / 1e3, 1)}
+    return out
+
+
+def reverb_kernel_row(dev, B=64, L=64000, R=8000, NR=32):
+    from cruse_amd import ops
+    from cruse_amd.data import fir_causal, rir_early_len, synth_batch, synth_rirs
+    g = torch.Generator(device=dev).manual_seed(1)
+    _, x = synth_batch(B, L, dev, 3)
+    y, ye = torch.empty_like(x), torch.empty_like(x)
+    out = {"B": B, "L": L, "R": R, "partition": ops.FFTCONV_PART}
+    row = lambda t: {"median_us": round(t[0], 1), "min_us": round(t[1], 1)}
+    for name, n in (("pool_indexed", NR), ("per_clip", B)):
+        h = synth_rirs(n, R, 0.2, 0.8, 16000, dev, g)
+        early = rir_early_len(h)
+        idx = (torch.arange(B, device=dev) % n).to(torch.int32) if n != B else None
+        bank = ops.fft_conv_prepare(h, early)
+        spec = bank.spec
+        r = {"NR": n, "prepare_with_early": row(timed_us(lambda: ops.fft_conv_prepare(h, early, spec=spec), n=20)),
+             "apply": row(timed_us(lambda: ops.fft_conv_apply(x, bank, h_index=idx, out=y), n=30)),
+             "apply_with_early": row(timed_us(lambda: ops.fft_conv_apply(x, bank, h_index=idx, want_early=True, out=y, out_early=ye), n=30))}
+        hb = h if n == B else h.index_select(0, idx.long()).contiguous()
+        r["fir_causal"] = row(timed_us(lambda: fir_causal(x, hb), warm=2, n=8))
+        r["fir_over_fft"] = round(r["fir_causal"]["median_us"] / r["apply"]["median_us"], 1)
+        r["rel_l2_fft_vs_fir"] = float((y - fir_causal(x, hb)).double().norm() / fir_causal(x, hb).double().norm())
+        out[name] = r
+    return out
+
+
+def reverb_device_batch_row(dev, args, B):
+    from cruse_amd.data import DevicePairs
+    rev = {k: args[k] for k in ("reverb_proportion", "reverb_noise_proportion", "reverb_target")}
+    base = {k: v for k, v in args.items() if k not in rev}
+    out = {}
+    for name, extra in (("plain", {}), ("reverb", rev), ("reverb_eq", dict(rev, eq_prob=0.5, eq_filters=3, hp_prob=0.5))):
+        ds = DevicePairs(**base, **extra)
+        idx = torch.arange(B)
+        med, best = timed_us(lambda: ds.device_batch(idx, dev), warm=8, n=40)
+        out[name] = {"median_us": round(med, 1), "min_us": round(best, 1)}
     return out
 
 
@@ -95,7 +140,11 @@ def main():
     ap.add_argument("--batches", type=int, default=120)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "aug_probe.json"))
     ap.add_argument("--skip-epoch", action="store_true")
+    ap.add_argument("--reverb", action="store_true")
+    ap.add_argument("--row", choices=("kernel", "device_batch", "epoch"))
     a = ap.parse_args()
+    if a.reverb:
+        return reverb_main(a)
     from tools.train_stand import load_toml
     assert torch.cuda.is_available(), "aug_probe needs a HIP device"
     dev = torch.device("cuda", 0)
@@ -118,6 +167,50 @@ def main():
         json.dump(res, f, indent=1)
         f.write("\n")
     print("wrote", a.out)
+
+
+ROW_LIMIT_S = {"kernel": 240, "device_batch": 180, "epoch": 900}
+
+
+def reverb_main(a):
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "aug_probe.json") else os.path.join(ROOT, "profiles", "aug_probe_reverb.json")
+    if a.row is None:                             # every row a fresh process under its own limit; a failure ends the run
+        import subprocess
+        rows = ("kernel", "device_batch") + (() if a.skip_epoch else ("epoch",))
+        for row in rows:
+            cmd = ["timeout", "-k", "10", str(ROW_LIMIT_S[row]), sys.executable, os.path.abspath(__file__), "--reverb", "--row", row, "--batches",
+                   str(a.batches), "--out", out]
+            rc = subprocess.call(cmd)
+            if rc != 0:
+                sys.exit(f"aug_probe --reverb: row {row} ended with status {rc}; nothing more is started")
+        return
+    from tools.train_stand import load_toml
+    assert torch.cuda.is_available(), "aug_probe needs a HIP device"
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    rev = load_toml(os.path.join(ROOT, "configs", "cruse_reverb.toml"))
+    plain = load_toml(os.path.join(ROOT, "configs", "cruse_device_dataset.toml"))
+    if a.row == "kernel":
+        val = reverb_kernel_row(dev)
+    elif a.row == "device_batch":
+        val = reverb_device_batch_row(dev, rev["train_dataset"]["args"], rev["train_dataset"]["dataloader"]["batch_size"])
+    else:
+        import tempfile
+        with tempfile.TemporaryDirectory(prefix="cruse_aug_probe_") as tmp:
+            val = {"plain": epoch_row(dev, plain, a.batches, tmp), "reverb": epoch_row(dev, rev, a.batches, tmp)}
+        val["ratio_reverb_to_plain"] = round(val["reverb"]["frames_per_s"] / val["plain"]["frames_per_s"], 4)
+    print(json.dumps({a.row: val}), flush=True)
+    res = {}
+    if os.path.exists(out):
+        with open(out) as f:
+            res = json.load(f)
+    res["device"] = torch.cuda.get_device_name(0)
+    res[a.row] = val
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
 
 
 if __name__ == "__main__":
