@@ -165,6 +165,8 @@ SIGNATURES = {
     "cruse_fftconv_prepare": ("piippzp", "i"),
     "cruse_fftconv_apply": ("piipziippzppp", "i"),
     "cruse_peak_scale": ("ppiifpp", "i"),
+    "cruse_resample_poly": ("piiippppiiipiipp", "i"),
+    "cruse_assemble_clips": ("pppiiipp", "i"),
 }
 
 

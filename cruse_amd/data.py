@@ -199,7 +199,7 @@ class DevicePairs(Dataset):
     Reverberation (SynDataset._select_rir / snr_mix(rir=, rir_noise=) / add_reverb, dataset/dataset.py:205-247), off
     by default: every clean clip is convolved with a room impulse response with probability reverb_proportion and every noise clip
     with probability reverb_noise_proportion, each with an independently drawn row of a pool of `rir_pool` synthetic responses of
-    `rir_len` taps (synth_rirs: there are no RIR files, as there are no speech files), FIRST -- then the EQ, then snr_mix, the order
+    `rir_len` taps (synth_rirs; filepairs.DeviceFilePairs is the subclass that fills all the pools from WAV files), FIRST -- then the EQ, then snr_mix, the order
     the reference marks (:249).  One cruse_fftconv_apply per tensor covers the batch: a clip that is not selected carries index -1 and
     passes through bit for bit.  The rows come from a numpy Generator of their own (seed * 100003 + 43: the EQ draws are the same
     with reverb on or off) and reach the device as int32 [B] through a pinned ring under the same event discipline as the
@@ -254,14 +254,23 @@ class DevicePairs(Dataset):
     def reverberates(self) -> bool:
         return self.reverb_proportion > 0.0 or self.reverb_noise_proportion > 0.0
 
-    def draw_reverb_index(self, n: int, proportion: float):
-        """int32 [n]: per clip a row of the RIR pool with probability `proportion`, -1 otherwise.  Consumes the dataset's reverb generator."""
+    def draw_reverb_index(self, n: int, proportion: float, rows=None):
+        """int32 [n]: per clip a row of the RIR pool (of `rows` responses, rir_pool by default) with probability `proportion`, -1
+        otherwise.  Consumes the dataset's reverb generator."""
         import numpy as np
         if self._rev_rng is None:
             self._rev_rng = np.random.default_rng(self.seed * 100003 + 43)
         sel = self._rev_rng.random(n) < proportion
-        rows = self._rev_rng.integers(0, self.rir_pool, size=n)
+        rows = self._rev_rng.integers(0, self.rir_pool if rows is None else rows, size=n)
         return np.where(sel, rows, -1).astype(np.int32)
+
+    def _draw_reverb_rows(self, B: int):
+        """(clean, noise) int32 [B] rows of this batch; a subclass with other pools or other draws overrides it"""
+        return self.draw_reverb_index(B, self.reverb_proportion), self.draw_reverb_index(B, self.reverb_noise_proportion)
+
+    def _noise_rir_bank(self, device):
+        """the prepared bank the NOISE clips are convolved with: the speech's own here"""
+        return self._ensure_rirs(device)[2]
 
     def _ensure_rirs(self, device):
         from . import ops
@@ -286,7 +295,7 @@ class DevicePairs(Dataset):
         ev = self._rpin_ev[key][slot]
         if ev is not None:
             ev.synchronize()                       # the copy issued NPIN batches ago: a wait on that event, not on the stream
-        host = (self.draw_reverb_index(B, self.reverb_proportion), self.draw_reverb_index(B, self.reverb_noise_proportion))
+        host = self._draw_reverb_rows(B)
         buf = self._rpin[key][slot]
         buf.numpy()[0], buf.numpy()[1] = host
         idx = buf.to(device, non_blocking=True)
@@ -301,7 +310,7 @@ class DevicePairs(Dataset):
         elif self.reverb_proportion > 0.0:
             c = ops.fft_conv_apply(c, bank, h_index=idx[0])
         if self.reverb_noise_proportion > 0.0:
-            n = ops.fft_conv_apply(n, bank, h_index=idx[1])
+            n = ops.fft_conv_apply(n, self._noise_rir_bank(device), h_index=idx[1])
         return c, n, early
 
     def draw_aug_coefs(self, n: int):
@@ -361,18 +370,22 @@ class DevicePairs(Dataset):
             self._pools[device] = (clean, noise, snr)
         return self._pools[device]
 
-    def device_batch(self, idx: torch.Tensor, device):
-        """idx [B] int64 (host or device): -> (noisy, clean) [B, length] f32 on `device`, issued on the current stream"""
+    def _gather(self, idx: torch.Tensor, device):
+        """-> (clean clips [B, length], noise clips [B, length], snr [B] in dB) of a batch before any filtering; a subclass that fills
+        its batches from other pools (filepairs.DeviceFilePairs) overrides this and inherits the rest of device_batch"""
         clean_p, noise_p, snr = self._ensure(device)
         idx = idx.to(device, non_blocking=True)
-        c = clean_p.index_select(0, idx % self.pool)
-        n = noise_p.index_select(0, (idx * 7 + 3) % self.pool)
+        return clean_p.index_select(0, idx % self.pool), noise_p.index_select(0, (idx * 7 + 3) % self.pool), snr.index_select(0, idx % self.num)
+
+    def device_batch(self, idx: torch.Tensor, device):
+        """idx [B] int64 (host or device): -> (noisy, clean) [B, length] f32 on `device`, issued on the current stream"""
+        c, n, snr = self._gather(idx, device)
         early = None
         if self.reverberates:
             c, n, early = self._reverb(c, n, torch.device(device))
         if self.augments:
             c, n, early = self._augment(c, n, torch.device(device), early)
-        noisy, clean, _ = snr_mix(c, n, snr.index_select(0, idx % self.num), return_parts=True)
+        noisy, clean, _ = snr_mix(c, n, snr, return_parts=True)
         if early is not None:
             from . import ops
             clean = ops.peak_scale(early, c)        # 1 / (max |full| + eps): the scale of the speech inside `noisy`

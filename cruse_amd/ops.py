@@ -1418,3 +1418,120 @@ def peak_scale(x: torch.Tensor, ref: torch.Tensor, eps: float = 1e-7) -> torch.T
     y = torch.empty_like(x)
     check(lib.cruse_peak_scale(_p(_f32(x, "peak_scale")), _p(_f32(ref, "peak_scale")), x.shape[0], x.shape[1], float(eps), _p(y), _stream()))
     return y
+
+
+# ======================================================================================================================
+# recordings -> training clips (cruse_resample_poly, cruse_assemble_clips; filepairs.DeviceFilePairs preloads and batches with them)
+# ======================================================================================================================
+RESAMPLE_TILE = 1024        # CRUSE_RESAMPLE_TILE (include/cruse_hip.h): consecutive outputs of one clip a workgroup owns
+_RESAMPLE_TAPS: Dict[tuple, torch.Tensor] = {}
+
+
+def resample_taps(up: int, down: int, device) -> torch.Tensor:
+    """the phase-major f32 table [up, stride] of the reduced ratio up / down on `device` (resample_design), built once"""
+    key = (torch.device(device), int(up), int(down))
+    if key not in _RESAMPLE_TAPS:
+        from . import resample_design as D
+        table = D.phase_table(D.design(up, down).astype("float32"), up)
+        _RESAMPLE_TAPS[key] = torch.from_numpy(table).to(device)
+    return _RESAMPLE_TAPS[key]
+
+
+def _host_i64(a, name: str):
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+    if a.ndim != 1 or a.shape[0] < 2:
+        raise RuntimeError(f"{name}: expected int64 [B + 1] offsets on the host, got shape {a.shape}")
+    return a
+
+
+def resample_poly(src: torch.Tensor, off_in, off_out, up: int, down: int, out: torch.Tensor, channels: int = 1, channel: int = 0,
+                  off_in_dev: Optional[torch.Tensor] = None, off_out_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.signal.resample_poly(clip, up, down, window=resample_design.design(up, down)) for every clip of a ragged batch, in one
+    launch.  src: flat f32 (mono) or int16 PCM interleaved over `channels`, of which `channel` is read (x / 32768); clip b is the
+    frames [off_in[b], off_in[b + 1]) and fills out[off_out[b] : off_out[b + 1]], ceil(L up / down) samples.  off_in / off_out: int64
+    [B + 1] HOST arrays (the library judges them and sizes the grid from them); their device copies are made here unless given.
+    up / down are reduced here; up = down = 1 is the conversion alone (bit-exact)."""
+    import math
+    import numpy as np
+    hi, ho = _host_i64(off_in, "resample_poly: off_in"), _host_i64(off_out, "resample_poly: off_out")
+    if hi.shape != ho.shape:
+        raise RuntimeError(f"resample_poly: off_in {hi.shape} and off_out {ho.shape} differ")
+    B = hi.shape[0] - 1
+    if src.dim() != 1 or src.dtype not in (torch.float32, torch.int16):
+        raise RuntimeError(f"resample_poly: src must be flat float32 or int16, got {src.dtype} {tuple(src.shape)}")
+    if out.dim() != 1 or out.device != src.device:
+        raise RuntimeError(f"resample_poly: out must be flat float32 on {src.device}, got {tuple(out.shape)} on {out.device}")
+    up, down = int(up), int(down)
+    g = math.gcd(up, down) if up > 0 and down > 0 else 1
+    up, down = up // g, down // g
+    if np.any(np.diff(hi) < 0) or np.any(np.diff(ho) < 0) or hi[0] < 0 or ho[0] < 0:
+        pass                                                   # the library refuses these by name (CRUSE_E_SHAPE)
+    elif int(hi[-1]) * max(int(channels), 1) > src.numel() or int(ho[-1]) > out.numel():
+        raise RuntimeError(f"resample_poly: offsets end at {int(hi[-1])} frames / {int(ho[-1])} outputs, beyond src ({src.numel()} values, "
+                           f"{channels} channels) or out ({out.numel()})")
+    di = torch.from_numpy(hi).to(src.device) if off_in_dev is None else off_in_dev
+    do = torch.from_numpy(ho).to(src.device) if off_out_dev is None else off_out_dev
+    for d in (di, do):
+        if d.dtype != torch.int64 or d.shape != (B + 1,) or d.device != src.device:
+            raise RuntimeError(f"resample_poly: device offsets must be int64 [{B + 1}] on {src.device}")
+    taps, ntap, stride = None, 0, 0
+    if (up, down) != (1, 1) and 1 <= up <= 1024 and 1 <= down <= 1024:
+        taps = resample_taps(up, down, src.device)
+        ntap, stride = 32 * max(up, down) + 1, taps.shape[1]
+    check(lib.cruse_resample_poly(_p(src), 0 if src.dtype == torch.float32 else 1, int(channels), int(channel), hi.ctypes.data, ho.ctypes.data,
+                                  _p(di), _p(do), B, up, down, _p(taps), ntap, stride, _p(_f32(out, "resample_poly")), _stream()))
+    return out
+
+
+def check_clip_plan(seg, seg_first, B: int, L: int, pool_len: int) -> None:
+    """Refuse a malformed plan of assemble_clips from the HOST arrays it was built from (the device never validates): seg int64
+    [nseg, 3] rows (src, dst, len), seg_first [B + 1] ascending from 0 to nseg; per clip len >= 1, dst ascending without overlap inside
+    [0, L), and [src, src + len) inside the pool."""
+    import numpy as np
+    seg, first = np.asarray(seg), np.asarray(seg_first)
+    if seg.ndim != 2 or seg.shape[1] != 3 or seg.dtype != np.int64:
+        raise ValueError(f"clip plan: seg must be int64 [nseg, 3], got {seg.dtype} {seg.shape}")
+    if first.shape != (B + 1,) or first[0] != 0 or first[-1] != seg.shape[0] or np.any(np.diff(first) < 0):
+        raise ValueError(f"clip plan: seg_first must rise from 0 to {seg.shape[0]} over {B + 1} entries, got {first.tolist()}")
+    if seg.shape[0] == 0:
+        return
+    src, dst, ln = seg[:, 0], seg[:, 1], seg[:, 2]
+    if np.any(ln < 1) or np.any(dst < 0) or np.any(dst + ln > L):
+        raise ValueError(f"clip plan: a segment is empty or leaves the clip [0, {L})")
+    if np.any(src < 0) or np.any(src + ln > pool_len):
+        raise ValueError(f"clip plan: a segment leaves the pool [0, {pool_len})")
+    inner = np.ones(seg.shape[0], dtype=bool)
+    inner[first[:-1][np.diff(first) > 0]] = False              # the first segment of every clip has no predecessor
+    if np.any((dst[1:] < (dst + ln)[:-1]) & inner[1:]):
+        raise ValueError("clip plan: the segments of a clip overlap or are not ascending in dst")
+
+
+def assemble_clips(pool: torch.Tensor, seg, seg_first, L: int, out: Optional[torch.Tensor] = None, seg_dev: Optional[torch.Tensor] = None,
+                   first_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b, dst + j] = pool[src + j] over the segments of clip b, 0.0 elsewhere -> [B, L] f32: utterances stitched with silence gaps
+    and cropped (filepairs.plan_clip).  pool: flat f32 on the device.  seg / seg_first: the plan on the HOST (numpy int64 [nseg, 3] and
+    int [B + 1]), judged here by check_clip_plan; seg_dev (int64 [nseg, 3]) / first_dev (int32 [B + 1]) are its device copies where the
+    caller has staged them already (a pinned ring), made here otherwise."""
+    import numpy as np
+    seg = np.ascontiguousarray(seg)
+    first = np.ascontiguousarray(np.asarray(seg_first, dtype=np.int32))
+    B, L = first.shape[0] - 1, int(L)
+    if pool.dim() != 1:
+        raise RuntimeError(f"assemble_clips: the pool must be flat, got {tuple(pool.shape)}")
+    check_clip_plan(seg, first, B, L, pool.numel())
+    nseg = seg.shape[0]
+    if seg_dev is None:
+        seg_dev = torch.from_numpy(seg).to(pool.device)
+    if first_dev is None:
+        first_dev = torch.from_numpy(first).to(pool.device)
+    if seg_dev.dtype != torch.int64 or seg_dev.numel() != 3 * nseg or seg_dev.device != pool.device:
+        raise RuntimeError(f"assemble_clips: seg_dev must be int64 [{nseg}, 3] on {pool.device}")
+    _i32(first_dev, B + 1, pool.device, "assemble_clips: first_dev")
+    if out is None:
+        out = torch.empty(B, L, device=pool.device, dtype=torch.float32)
+    elif out.shape != (B, L) or out.device != pool.device:
+        raise RuntimeError(f"assemble_clips: out {tuple(out.shape)} on {out.device}, expected {(B, L)} on {pool.device}")
+    check(lib.cruse_assemble_clips(_p(_f32(pool, "assemble_clips")), _p(seg_dev) if nseg else None, _p(first_dev), nseg, B, L,
+                                   _p(_f32(out, "assemble_clips")), _stream()))
+    return out

@@ -1,5 +1,7 @@
-"""Re-export of the on-GPU `SynDataset.snr_mix` (dataset/dataset.py:236-264) and `SynDataset.add_reverb` (:215-233)."""
+"""Re-export of the on-GPU `SynDataset.snr_mix` (dataset/dataset.py:236-264) and `SynDataset.add_reverb` (:215-233), and of the
+device-resident file-list dataset that stands for the class itself (cruse_amd.filepairs.DeviceFilePairs)."""
 from cruse_amd.data import add_reverb as _add_reverb
+from cruse_amd.filepairs import DeviceFilePairs  # noqa: F401
 from cruse_amd.data import snr_mix  # noqa: F401
 
 

@@ -957,6 +957,36 @@ int cruse_fftconv_apply(const float* x, int B, int L, const void* spec, size_t s
  * another tensor -- the early-reflection target beside the reverberant speech that sets the peak.  x, ref, y [B][L], out of place. */
 int cruse_peak_scale(const float* x, const float* ref, int B, int L, float eps, float* y, void* stream);
 
+/* ---- recordings -> training clips (ABI 13, additive; csrc/resample.hip) ------------------------------------
+ * cruse_resample_poly: one launch converts a ragged batch of B recordings at one source rate to the rate of the pools.  (up, down) is
+ * (dst_rate, src_rate) REDUCED, q = max(up, down), taps: the N = 32 q + 1 low-pass taps h (cruse_amd/resample_design.py: the Kaiser
+ * design of cruse_stream_resample_*, unit DC gain) laid out phase-major, table[p][j] = h[p + up j] (0 beyond N), up rows of tap_stride
+ * floats, tap_stride a multiple of 4 >= ceil(N / up), 16-byte aligned (CRUSE_E_ALIGN).  With v[up i] = x[i], zero elsewhere and
+ * outside the clip,
+ *     y[n] = up * sum_k h[k] v[n down + 16 q - k],   0 <= n < Lout = ceil(L up / down)
+ * = scipy.signal.resample_poly(x, up, down, window=h): zero-phase, zero-padded edges.  f32 fmaf over k ascending from 0, no atomics:
+ * bit-identical from run to run, and a clip gives the same samples alone and inside a batch.
+ * src: fmt 0 = f32 mono (channels = 1) or fmt 1 = int16 PCM interleaved; clip b is the frames [off_in[b], off_in[b + 1]) and sample i
+ * of it is src[(off_in[b] + i) * channels + chan] (/ 32768.0f for PCM, exact).  out: f32; clip b fills [off_out[b], off_out[b + 1])
+ * and every sample of [off_out[0], off_out[B]) is written exactly once.  off_in / off_out: int64 [B + 1] on the DEVICE; the same
+ * arrays on the HOST as off_in_host / off_out_host, which size the grid and are judged here -- the kernel trusts the device copies.
+ * up = down = 1: the conversion / de-interleave alone, y = x bit for bit; taps may be NULL.
+ * One launch, no allocation, no host synchronisation (the call captures into a HIP graph).  Refused with CRUSE_E_SHAPE before any
+ * HIP call: a null buffer, B < 1, up or down outside 1..1024 or not reduced, an unknown fmt, channels outside 1..1024, chan outside
+ * 0..channels-1, f32 with channels != 1, ntap != 32 q + 1, a tap_stride too small or no multiple of 4, a negative first offset, a clip
+ * with L < 1 or L, Lout > 2^31 - 1025, Lout != ceil(L up / down) (non-monotone offsets included), offsets beyond 2^50. */
+#define CRUSE_RESAMPLE_TILE 1024
+int cruse_resample_poly(const void* src, int fmt, int channels, int chan, const long long* off_in_host, const long long* off_out_host,
+                        const long long* off_in, const long long* off_out, int B, int up, int down, const float* taps, int ntap,
+                        int tap_stride, float* out, void* stream);
+/* cruse_assemble_clips: out[b][dst + j] = pool[src + j] for j < len over the segments seg_first[b] .. seg_first[b + 1] - 1 of clip b, and
+ * 0.0f everywhere else (silence gaps): SynDataset._select_clean_y / _select_noise_y (dataset/dataset.py:147-203) as a gather.  pool: flat
+ * f32; out [B][L] f32, every sample written exactly once; seg: int64 [nseg][3] rows (src, dst, len), per clip ascending in dst and
+ * non-overlapping inside [0, L); seg_first: int32 [B + 1]; both on the device.  The device validates nothing: the plan is judged on
+ * the host from the arrays it was built from (cruse_amd.ops.check_clip_plan).  One launch, capturable.  Refused with CRUSE_E_SHAPE
+ * before any HIP call: a null pool / seg_first / out, a null seg with nseg > 0, B < 1, L < 1, L > 2^31 - 1025, nseg < 0. */
+int cruse_assemble_clips(const float* pool, const long long* seg, const int* seg_first, int nseg, int B, int L, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

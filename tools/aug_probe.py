@@ -10,6 +10,12 @@ With --reverb the same three rows for the reverberation -> p
                 filters behind an index and with a filter per clip, and cruse_fir_causal on the same tensors in the same run
   device_batch  plain, reverb only, reverb + EQ
   epoch         configs/cruse_reverb.toml against configs/cruse_device_dataset.toml
+With --files DIR the file-list dataset -> profiles/aug_probe_files.json: a small synthetic corpus of WAVs at mixed
+rates is written into DIR, then
+  kernel        cruse_resample_poly alone, 64 clips x 10 s of int16 mono from 44.1 kHz and from 48 kHz
+  preload       DeviceFilePairs' first _ensure: wall time, and per (rate, channels) group the seconds of file reading and of device work
+  device_batch  DeviceFilePairs.device_batch beside DevicePairs.device_batch at the same B x length (64 x 4 s), in windows interleaved
+                P, N, P, N
 Each row is its own process under its own time limit (--row kernel | device_batch | epoch, merged into --out); without --row the
 rows run as child processes, one after the other, and the first that fails ends the run."""
 from __future__ import annotations
@@ -135,6 +141,103 @@ def epoch_row(dev, conf, nb, save_dir):
             "nonfinite_steps": int(tr.engine.nonfinite_steps())}
 
 
+def write_probe_corpus(root, seed=0):
+    """48 speech-like, 16 noise and 4 RIR files of 16-bit PCM at mixed rates (one group stereo) -> the three list files"""
+    import wave
+    os.makedirs(root, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    lists = {}
+    for name, n, (lo, hi) in (("clean", 48, (2.0, 6.0)), ("noise", 16, (3.0, 8.0)), ("rir", 4, (0.4, 0.5))):
+        paths = []
+        for k in range(n):
+            rate, ch = ((16000, 1), (8000, 1), (44100, 1), (48000, 2), (22050, 1))[k % 5]
+            m = int(rng.uniform(lo, hi) * rate)
+            t = np.arange(m) / rate
+            if name == "rir":
+                x = 0.2 * rng.standard_normal(m) * np.exp(-t / 0.08)
+                x[0] = 0.9
+            else:
+                f0 = rng.uniform(90, 280)
+                x = sum(np.sin(2 * np.pi * f0 * (j + 1) * t + rng.uniform(0, 6.28)) / (j + 1) for j in range(8)) * (name == "clean") + 0.3 * rng.standard_normal(m)
+            pcm = np.clip(np.rint(0.8 * x / np.abs(x).max() * 32767), -32768, 32767).astype(np.int16)
+            path = os.path.join(root, f"{name}_{k:03d}.wav")
+            with wave.open(path, "wb") as w:
+                w.setnchannels(ch)
+                w.setsampwidth(2)
+                w.setframerate(rate)
+                w.writeframes(np.repeat(pcm, ch).tobytes())
+            paths.append(path)
+        lists[name] = os.path.join(root, name + ".lst")
+        with open(lists[name], "w") as f:
+            f.write("\n".join(paths) + "\n")
+    return lists
+
+
+def files_main(a):
+    import time
+    from cruse_amd import ops
+    from cruse_amd import resample_design as D
+    from cruse_amd.data import DevicePairs
+    from cruse_amd.filepairs import DeviceFilePairs
+    assert torch.cuda.is_available(), "aug_probe needs a HIP device"
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    out = a.out if a.out != os.path.join(ROOT, "profiles", "aug_probe.json") else os.path.join(ROOT, "profiles", "aug_probe_files.json")
+    res = {"device": torch.cuda.get_device_name(0)}
+    kern = {}
+    for rate in (44100, 48000):                    # 64 clips x 10 s
+        up, down = D.ratio(16000, rate)
+        B, L = 64, 10 * rate
+        src = torch.randint(-20000, 20000, (B * L,), device=dev, dtype=torch.int16)
+        off_in = np.arange(B + 1, dtype=np.int64) * L
+        off_out = np.arange(B + 1, dtype=np.int64) * D.out_len(L, up, down)
+        y = torch.empty(int(off_out[-1]), device=dev)
+        di, do = torch.from_numpy(off_in).to(dev), torch.from_numpy(off_out).to(dev)
+        med, best = timed_us(lambda: ops.resample_poly(src, off_in, off_out, up, down, y, off_in_dev=di, off_out_dev=do), n=30)
+        T = D.taps_per_phase(up, down)
+        kern[str(rate)] = {"B": B, "seconds_per_clip": 10, "up": up, "down": down, "taps_per_output": T, "median_us": round(med, 1), "min_us": round(best, 1),
+                           "outputs": int(off_out[-1]), "GFMA_per_s": round(int(off_out[-1]) * T / med / 1e3, 1),
+                           "bytes": int(B * L * 2 + off_out[-1] * 4), "GB_per_s": round((B * L * 2 + int(off_out[-1]) * 4) / med / 1e3, 1)}
+    res["kernel"] = kern
+    print(json.dumps({"kernel": kern}), flush=True)
+    lists = write_probe_corpus(a.files)
+    B, sec = 64, 4.0
+    ds = DeviceFilePairs(clean_dataset=lists["clean"], noise_dataset=lists["noise"], rir_dataset=lists["rir"], snr_range=[0, 20], silence_length=0.2,
+                         sub_sample_length=sec, dataset_length=2048, seed=1)
+    t0 = time.perf_counter()
+    ds._ensure(dev)
+    torch.cuda.synchronize()
+    res["preload"] = {"wall_s": round(time.perf_counter() - t0, 4),
+                      "groups": [dict(r, read_s=round(r["read_s"], 5), device_s=round(r["device_s"], 5)) for r in ds.preload_stats]}
+    print(json.dumps({"preload": res["preload"]}), flush=True)
+    parent = DevicePairs(num=2048, length=int(sec * 16000), seed=1, pool=128)
+    idx = torch.arange(B)
+
+    def window(d, k=30):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for j in range(k):
+            d.device_batch((idx + j * B) % 2048, dev)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / k * 1e6
+
+    for d in (parent, ds):
+        window(d, 8)                               # warm: pools, pinned slots, code objects
+    wins = {"P": [], "N": []}
+    for _ in range(4):                             # P, N, P, N ...
+        wins["P"].append(window(parent))
+        wins["N"].append(window(ds))
+    res["device_batch"] = {"B": B, "length": int(sec * 16000), "parent_us": [round(v, 1) for v in wins["P"]], "files_us": [round(v, 1) for v in wins["N"]],
+                           "parent_median_us": round(float(np.median(wins["P"])), 1), "files_median_us": round(float(np.median(wins["N"])), 1),
+                           "segments_last_batch": [int(ds.last_plan[0].shape[0]), int(ds.last_plan[2].shape[0])]}
+    print(json.dumps({"device_batch": res["device_batch"]}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=120)
@@ -142,7 +245,10 @@ def main():
     ap.add_argument("--skip-epoch", action="store_true")
     ap.add_argument("--reverb", action="store_true")
     ap.add_argument("--row", choices=("kernel", "device_batch", "epoch"))
+    ap.add_argument("--files", metavar="DIR", help="probe the file-list dataset on a synthetic corpus written into DIR")
     a = ap.parse_args()
+    if a.files:
+        return files_main(a)
     if a.reverb:
         return reverb_main(a)
     from tools.train_stand import load_toml
