@@ -24,7 +24,7 @@ extern "C" int cruse_abi_version(void) { return CRUSE_ABI_VERSION; }
 #include <limits.h>
 #include <string.h>
 namespace {
-const char* const OPT_NAMES[] = {"gru_bwd_rs", "gru_fwd_lean", "gru_tf", "gru_poll_fwd", "gru_poll_bwd", "gru_wlo", "gru_dbg", "cm_dbg", "cm_nw", "cm_kint", "cm_swap",
+const char* const OPT_NAMES[] = {"gru_bwd_rs", "gru_fwd_lean", "gru_tf", "gru_poll_fwd", "gru_poll_bwd", "gru_wlo", "gru_dbg", "cm_dbg", "cm_nw", "cm_grid", "cm_kint", "cm_swap",
                                  "pw_valu", "wg_dbg", "wg_rd", "wg_grid"};
 constexpr int N_OPT = sizeof(OPT_NAMES) / sizeof(OPT_NAMES[0]);
 std::atomic<int> g_opt[N_OPT];

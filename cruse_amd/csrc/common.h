@@ -21,6 +21,23 @@ struct CruseBnIn { const double* sums; int nrep; long long count; float eps, mom
 struct CruseBnBwdIn { const float* y; const double* sums; int nrep; long long count; const float* mean; const float* rstd; const float* gamma;
                       const float* beta; int relu, training; void* copy_bf16; float* dgamma; float* dbeta; float* dbias; };
 
+// one frame-major convolution call, whichever of the ten cruse_conv_* entry points it came through.  scatter: 0 the gather form
+// (nn.Conv2d, S = 1 or 2), 1 the stride-2 transposed form (S = 2, w_layout = 0, Fout = 2 * Fin); x / y hold x_dtype / y_dtype
+// elements (CRUSE_DT_F32 or CRUSE_DT_BF16); sums, bnb, bni, bbi: null where the call does not carry that form
+struct CruseConvCall {
+    int scatter;
+    const void* x; const float* w; const float* bias; void* y;
+    int B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, act, accum, prec, x_dtype, y_dtype;
+    double* sums;
+    hipStream_t stream;
+    const CruseBnBwd* bnb; const CruseBnIn* bni; const CruseBnBwdIn* bbi;        // (last: the entry points that carry none leave them out)
+};
+// what a call would launch, as cruse_conv_plan reports it
+enum { CRUSE_CP_ROUTE, CRUSE_CP_FUSED, CRUSE_CP_MT, CRUSE_CP_NW, CRUSE_CP_GRID, CRUSE_CP_LDS, CRUSE_CP_CO_T, CRUSE_CP_N };
+// 1: the MFMA kernel took the call, 0: the shape / mode is not eligible (the caller goes on to the VALU kernel), < 0: error.
+// plan != null: nothing is launched, plan[CRUSE_CP_MT .. CRUSE_CP_LDS] receive what would have been (conv_mfma.hip)
+int cruse_conv_mfma_try(const CruseConvCall& c, int* plan);
+
 extern "C" void cruse_set_error(const char* fmt, ...);
 
 #define CRUSE_REQUIRE(cond, code, ...)                                   \

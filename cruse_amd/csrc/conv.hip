@@ -446,10 +446,6 @@ int set_smem(K kern, size_t bytes, const char* name) {
 
 }  // namespace
 
-int cruse_conv_mfma_try(int scatter, const float* x, const float* w, const float* bias, float* y,
-                        int B, int T, int Cin, int Fin, int Cout, int Fout, int KT, int S, int pad,
-                        int w_layout, int act, int accum, int prec, double* bn_sums, const CruseBnBwd* bnb, int x_bf16, int y_bf16,
-                        const CruseBnIn* bni, hipStream_t stream, const CruseBnBwdIn* bbi = nullptr);
 extern "C" int cruse_bn_act_bwd_apply(const float* dout, const float* y, const float* mean, const float* rstd, const float* gamma, const float* beta,
                                       const double* sums, int sum_replicas, long long rows, int C, int F, int relu, int training, int dout_dtype,
                                       void* dy, int dy_dtype, float* dgamma, float* dbeta, float* dbias, void* stream);
@@ -459,151 +455,165 @@ extern "C" int cruse_bn_act_bwd_reduce(const float* dout, const float* y, const 
 
 namespace {
 
-int conv_gather_impl(const float* x, const float* w, const float* bias, float* y,
-                     int B, int T, int Cin, int Fin, int Cout, int Fout,
-                     int KT, int S, int pad, int w_layout, int act, int accum, int prec, double* bn_sums, void* stream,
-                     const CruseBnBwd* bnb = nullptr, int x_dtype = CRUSE_DT_F32, int y_dtype = CRUSE_DT_F32, const CruseBnIn* bni = nullptr,
-                     const CruseBnBwdIn* bbi = nullptr) {
-    CRUSE_REQUIRE((x_dtype == CRUSE_DT_F32 || x_dtype == CRUSE_DT_BF16) && (y_dtype == CRUSE_DT_F32 || y_dtype == CRUSE_DT_BF16), CRUSE_E_DTYPE,
-                  "conv_gather: x_dtype %d / y_dtype %d (f32 or bf16)", x_dtype, y_dtype);
-    CRUSE_REQUIRE(B > 0 && T > 0 && Cin > 0 && Cout > 0 && Fin > 0 && Fout > 0, CRUSE_E_SHAPE,
-                  "conv_gather: empty shape B=%d T=%d Cin=%d Cout=%d Fin=%d Fout=%d", B, T, Cin, Cout, Fin, Fout);
-    CRUSE_REQUIRE((KT == 1 || KT == 2) && (S == 1 || S == 2) && (pad == 0 || pad == 1), CRUSE_E_SHAPE,
-                  "conv_gather: unsupported KT=%d S=%d pad=%d", KT, S, pad);
-    CRUSE_REQUIRE((Fout - 1) * S - pad + 2 <= Fin, CRUSE_E_SHAPE,
-                  "conv_gather: Fout=%d reads past Fin=%d (+1 zero column)", Fout, Fin);
-    CRUSE_REQUIRE(w_layout == 0 || (KT == 1 && S == 1), CRUSE_E_SHAPE, "conv_gather: w_layout 1 needs KT=1,S=1");
-    CRUSE_REQUIRE(!(accum && act), CRUSE_E_SHAPE, "conv_gather: accum with activation");
-    if (prec >= 0) {
-        const int r = cruse_conv_mfma_try(0, x, w, bias, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, act, accum,
-                                          prec, bn_sums, bnb, x_dtype == CRUSE_DT_BF16, y_dtype == CRUSE_DT_BF16, bni, (hipStream_t)stream, bbi);
+// conv_run's "the fused BatchNorm-backward input was not taken": the caller runs the separate pass (conv_bnbwd_in)
+constexpr int CONV_NOT_FUSED = 1;
+
+// The one host path of the ten entry points: validate, try the MFMA kernel, else the VALU kernel and the statistics pass it lacks.
+// plan != null (cruse_conv_plan): decide the same way, write what would be launched and launch nothing.
+// Where the two forms differ they branch on c.scatter; every such branch is behaviour, not an oversight.
+int conv_run(const CruseConvCall& c, int* plan = nullptr) {
+    const char* who = c.scatter ? "conv_scatter2" : "conv_gather";
+    const char* cin = c.scatter ? "Cs" : "Cin";
+    CRUSE_REQUIRE((c.x_dtype == CRUSE_DT_F32 || c.x_dtype == CRUSE_DT_BF16) && (c.y_dtype == CRUSE_DT_F32 || c.y_dtype == CRUSE_DT_BF16), CRUSE_E_DTYPE,
+                  "%s: x_dtype %d / y_dtype %d (f32 or bf16)", who, c.x_dtype, c.y_dtype);
+    if (c.scatter) {
+        CRUSE_REQUIRE(c.B > 0 && c.T > 0 && c.Cin > 0 && c.Cout > 0 && c.Fin > 0, CRUSE_E_SHAPE, "conv_scatter2: empty shape");
+        CRUSE_REQUIRE(c.Fout == 2 * c.Fin, CRUSE_E_SHAPE, "conv_scatter2: Fout=%d must be 2*Fg=%d", c.Fout, 2 * c.Fin);
+        CRUSE_REQUIRE((c.KT == 1 || c.KT == 2) && (c.pad == 0 || c.pad == 1), CRUSE_E_SHAPE, "conv_scatter2: unsupported KT=%d pad=%d", c.KT, c.pad);
+    } else {
+        CRUSE_REQUIRE(c.B > 0 && c.T > 0 && c.Cin > 0 && c.Cout > 0 && c.Fin > 0 && c.Fout > 0, CRUSE_E_SHAPE,
+                      "conv_gather: empty shape B=%d T=%d Cin=%d Cout=%d Fin=%d Fout=%d", c.B, c.T, c.Cin, c.Cout, c.Fin, c.Fout);
+        CRUSE_REQUIRE((c.KT == 1 || c.KT == 2) && (c.S == 1 || c.S == 2) && (c.pad == 0 || c.pad == 1), CRUSE_E_SHAPE,
+                      "conv_gather: unsupported KT=%d S=%d pad=%d", c.KT, c.S, c.pad);
+        CRUSE_REQUIRE((c.Fout - 1) * c.S - c.pad + 2 <= c.Fin, CRUSE_E_SHAPE, "conv_gather: Fout=%d reads past Fin=%d (+1 zero column)", c.Fout, c.Fin);
+        CRUSE_REQUIRE(c.w_layout == 0 || (c.KT == 1 && c.S == 1), CRUSE_E_SHAPE, "conv_gather: w_layout 1 needs KT=1,S=1");
+    }
+    CRUSE_REQUIRE(!(c.accum && c.act), CRUSE_E_SHAPE, "%s: accum with activation", who);
+    if (plan) plan[CRUSE_CP_FUSED] = c.bbi != nullptr;
+    if (c.prec >= 0) {
+        const int r = cruse_conv_mfma_try(c, plan);
+        if (r > 0 && plan) { plan[CRUSE_CP_ROUTE] = 1; plan[CRUSE_CP_CO_T] = 0; }
         if (r != 0) return r < 0 ? r : CRUSE_OK;
     }
-    if (bbi != nullptr) return 1;                    // (not handled: the caller runs the separate BatchNorm-backward pass)
-    CRUSE_REQUIRE(bni == nullptr, CRUSE_E_SHAPE, "conv_gather_bnin: the fused input BatchNorm needs the MFMA kernel in the bf16 mode (Cin %d, Cout %d, prec %d)", Cin, Cout, prec);
-    CRUSE_REQUIRE(x_dtype == CRUSE_DT_F32 && y_dtype == CRUSE_DT_F32, CRUSE_E_DTYPE,
-                  "conv_gather: a bf16 input / output needs the MFMA kernel in the bf16 data-gradient mode (Cin %d, Cout %d, prec %d)", Cin, Cout, prec);
-    const bool fuse = bn_sums && Cout <= 64 && bnb == nullptr;
-    ConvArgs a{x, w, bias, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, act, accum, fuse ? bn_sums : nullptr};
-    const size_t lds = (((size_t)Cin * KT * 3 * Cout + 3) & ~(size_t)3) * 4 +
-                       (size_t)(TF + KT - 1) * Cin * (Fin + 2) * 4;
-    CRUSE_REQUIRE(lds <= 160 * 1024, CRUSE_E_SHAPE, "conv_gather: tile needs %zu B of LDS", lds);
-    const int grid = B * cdiv(T, TF);
-    int rc;
-    if (Cout % 4 == 0) {
-        if ((rc = set_smem(conv_gather_kernel<4>, lds, "conv_gather"))) return rc;
-        hipLaunchKernelGGL(conv_gather_kernel<4>, dim3(grid), dim3(CONV_THREADS), lds, (hipStream_t)stream, a);
-    } else {
-        if ((rc = set_smem(conv_gather_kernel<1>, lds, "conv_gather"))) return rc;
-        hipLaunchKernelGGL(conv_gather_kernel<1>, dim3(grid), dim3(CONV_THREADS), lds, (hipStream_t)stream, a);
+    if (c.bbi != nullptr) return CONV_NOT_FUSED;
+    CRUSE_REQUIRE(c.bni == nullptr, CRUSE_E_SHAPE, "%s_bnin: the fused input BatchNorm needs the MFMA kernel in the bf16 mode (%s %d, Cout %d, prec %d)",
+                  who, cin, c.Cin, c.Cout, c.prec);
+    CRUSE_REQUIRE(c.x_dtype == CRUSE_DT_F32 && c.y_dtype == CRUSE_DT_F32, CRUSE_E_DTYPE,
+                  "%s: a bf16 input / output needs the MFMA kernel in the bf16 data-gradient mode (%s %d, Cout %d, prec %d)", who, cin, c.Cin, c.Cout, c.prec);
+    // the VALU gather kernel has a statistics epilogue for up to 64 channels, the VALU scatter kernel has none
+    const bool fuse = !c.scatter && c.sums && c.Cout <= 64 && c.bnb == nullptr;
+    const float* x = static_cast<const float*>(c.x);
+    float* y = static_cast<float*>(c.y);
+    ConvArgs a{x, c.w, c.bias, y, c.B, c.T, c.Cin, c.Fin, c.Cout, c.Fout, c.KT, c.S, c.pad, c.w_layout, c.act, c.accum, fuse ? c.sums : nullptr};
+    const size_t lds = (((size_t)c.Cin * c.KT * 3 * c.Cout + 3) & ~(size_t)3) * 4 + (size_t)(TF + c.KT - 1) * c.Cin * (c.Fin + 2) * 4;
+    CRUSE_REQUIRE(lds <= 160 * 1024, CRUSE_E_SHAPE, "%s: tile needs %zu B of LDS", who, lds);
+    const int grid = c.B * cdiv(c.T, TF);
+    const int co_t = c.scatter ? (c.Cout % 2 == 0 ? 2 : 1) : (c.Cout % 4 == 0 ? 4 : 1);      // outputs per thread: <4>/<1> gather, <2>/<1> scatter
+    if (plan) {
+        plan[CRUSE_CP_ROUTE] = 0; plan[CRUSE_CP_MT] = 0; plan[CRUSE_CP_NW] = 0; plan[CRUSE_CP_GRID] = grid; plan[CRUSE_CP_LDS] = (int)lds;
+        plan[CRUSE_CP_CO_T] = co_t;
+        return CRUSE_OK;
     }
-    CRUSE_LAUNCH_CHECK("conv_gather");
-    // no statistics epilogue on this path: one more pass (the backward sums go to replica 0, the others stay zero)
-    if (bnb) return cruse_bn_act_bwd_reduce(y, bnb->y, bnb->mean, bnb->rstd, bnb->gamma, bnb->beta, (long long)B * T, Cout, Fout,
-                                            bnb->relu, bn_sums, 1, stream);
-    if (bn_sums && !fuse) return cruse_bn_stats(y, (long long)B * T, Cout, Fout, bn_sums, 1, stream);
+    void (*kern)(ConvArgs) = !c.scatter ? (co_t == 4 ? conv_gather_kernel<4> : conv_gather_kernel<1>)
+                                        : (co_t == 2 ? conv_scatter2_kernel<2> : conv_scatter2_kernel<1>);
+    int rc;
+    if ((rc = set_smem(kern, lds, who))) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(CONV_THREADS), lds, c.stream, a);
+    CRUSE_LAUNCH_CHECK(who);
+    // no (or no such) statistics epilogue on this path: one more pass over y (the backward sums go to replica 0, the others stay zero)
+    const long long rows = (long long)c.B * c.T;
+    if (c.bnb) return cruse_bn_act_bwd_reduce(y, c.bnb->y, c.bnb->mean, c.bnb->rstd, c.bnb->gamma, c.bnb->beta, rows, c.Cout, c.Fout,
+                                              c.bnb->relu, c.sums, 1, c.stream);
+    if (c.sums && !fuse) return cruse_bn_stats(y, rows, c.Cout, c.Fout, c.sums, 1, c.stream);
     return CRUSE_OK;
 }
 
-int conv_scatter2_impl(const float* g, const float* w, const float* bias, float* y,
-                       int B, int T, int Cs, int Fg, int Cout, int Fout,
-                       int KT, int pad, int act, int accum, int prec, double* bn_sums, void* stream,
-                       const CruseBnBwd* bnb = nullptr, int x_dtype = CRUSE_DT_F32, int y_dtype = CRUSE_DT_F32, const CruseBnIn* bni = nullptr,
-                       const CruseBnBwdIn* bbi = nullptr) {
-    CRUSE_REQUIRE((x_dtype == CRUSE_DT_F32 || x_dtype == CRUSE_DT_BF16) && (y_dtype == CRUSE_DT_F32 || y_dtype == CRUSE_DT_BF16), CRUSE_E_DTYPE,
-                  "conv_scatter2: x_dtype %d / y_dtype %d (f32 or bf16)", x_dtype, y_dtype);
-    CRUSE_REQUIRE(B > 0 && T > 0 && Cs > 0 && Cout > 0 && Fg > 0, CRUSE_E_SHAPE, "conv_scatter2: empty shape");
-    CRUSE_REQUIRE(Fout == 2 * Fg, CRUSE_E_SHAPE, "conv_scatter2: Fout=%d must be 2*Fg=%d", Fout, 2 * Fg);
-    CRUSE_REQUIRE((KT == 1 || KT == 2) && (pad == 0 || pad == 1), CRUSE_E_SHAPE,
-                  "conv_scatter2: unsupported KT=%d pad=%d", KT, pad);
-    CRUSE_REQUIRE(!(accum && act), CRUSE_E_SHAPE, "conv_scatter2: accum with activation");
-    if (prec >= 0) {
-        const int r = cruse_conv_mfma_try(1, g, w, bias, y, B, T, Cs, Fg, Cout, Fout, KT, 2, pad, 0, act, accum, prec,
-                                          bn_sums, bnb, x_dtype == CRUSE_DT_BF16, y_dtype == CRUSE_DT_BF16, bni, (hipStream_t)stream, bbi);
-        if (r != 0) return r < 0 ? r : CRUSE_OK;
-    }
-    if (bbi != nullptr) return 1;                    // (not handled: the caller runs the separate BatchNorm-backward pass)
-    CRUSE_REQUIRE(bni == nullptr, CRUSE_E_SHAPE, "conv_scatter2_bnin: the fused input BatchNorm needs the MFMA kernel in the bf16 mode (Cs %d, Cout %d, prec %d)", Cs, Cout, prec);
-    CRUSE_REQUIRE(x_dtype == CRUSE_DT_F32 && y_dtype == CRUSE_DT_F32, CRUSE_E_DTYPE,
-                  "conv_scatter2: a bf16 input / output needs the MFMA kernel in the bf16 data-gradient mode (Cs %d, Cout %d, prec %d)", Cs, Cout, prec);
-    ConvArgs a{g, w, bias, y, B, T, Cs, Fg, Cout, Fout, KT, 2, pad, 0, act, accum, nullptr};
-    const size_t lds = (((size_t)Cs * KT * 3 * Cout + 3) & ~(size_t)3) * 4 +
-                       (size_t)(TF + KT - 1) * Cs * (Fg + 2) * 4;
-    CRUSE_REQUIRE(lds <= 160 * 1024, CRUSE_E_SHAPE, "conv_scatter2: tile needs %zu B of LDS", lds);
-    const int grid = B * cdiv(T, TF);
-    int rc;
-    if (Cout % 2 == 0) {
-        if ((rc = set_smem(conv_scatter2_kernel<2>, lds, "conv_scatter2"))) return rc;
-        hipLaunchKernelGGL(conv_scatter2_kernel<2>, dim3(grid), dim3(CONV_THREADS), lds, (hipStream_t)stream, a);
-    } else {
-        if ((rc = set_smem(conv_scatter2_kernel<1>, lds, "conv_scatter2"))) return rc;
-        hipLaunchKernelGGL(conv_scatter2_kernel<1>, dim3(grid), dim3(CONV_THREADS), lds, (hipStream_t)stream, a);
-    }
-    CRUSE_LAUNCH_CHECK("conv_scatter2");
-    // the VALU scatter kernel has no statistics epilogue: one more pass over y
-    if (bnb) return cruse_bn_act_bwd_reduce(y, bnb->y, bnb->mean, bnb->rstd, bnb->gamma, bnb->beta, (long long)B * T, Cout, Fout,
-                                            bnb->relu, bn_sums, 1, stream);
-    if (bn_sums) return cruse_bn_stats(y, (long long)B * T, Cout, Fout, bn_sums, 1, stream);
+// the forms: what each pair of entry points checks and adds before conv_run.  `who` is the entry point's name in messages.
+int prep_sums(const char* who, const CruseConvCall& c, int zeroed) {
+    CRUSE_REQUIRE(c.sums != nullptr, CRUSE_E_SHAPE, "%s: sums is NULL", who);
+    if (!zeroed) return cruse_zero_async(c.sums, 2 * (size_t)c.Cout * CRUSE_BN_STAT_REPLICAS * sizeof(double), c.stream, who);
     return CRUSE_OK;
 }
 
-int prep_sums(double* sums, int Cout, int zeroed, void* stream, const char* who) {
-    CRUSE_REQUIRE(sums != nullptr, CRUSE_E_SHAPE, "%s: sums is NULL", who);
-    if (!zeroed) return cruse_zero_async(sums, 2 * (size_t)Cout * CRUSE_BN_STAT_REPLICAS * sizeof(double), (hipStream_t)stream, who);
-    return CRUSE_OK;
+int conv_bnstats(const char* who, const CruseConvCall& c, int zeroed) {
+    const int rc = prep_sums(who, c, zeroed);
+    return rc ? rc : conv_run(c);
+}
+
+int conv_bnbwd(const char* who, CruseConvCall c, const CruseBnBwd& bnb, int zeroed) {
+    CRUSE_REQUIRE(bnb.y && bnb.mean && bnb.rstd && bnb.gamma && bnb.beta, CRUSE_E_SHAPE, "%s: BatchNorm tensors missing", who);
+    const int rc = prep_sums(who, c, zeroed);
+    if (rc) return rc;
+    c.bnb = &bnb;
+    return conv_run(c);
+}
+
+int conv_bnin(const char* who, CruseConvCall c, const CruseBnIn& bni, int zeroed) {
+    CRUSE_REQUIRE(c.x && bni.sums && bni.gamma && bni.beta && bni.nrep >= 1 && bni.count > 0, CRUSE_E_SHAPE, "%s: input BatchNorm tensors missing", who);
+    CRUSE_REQUIRE((bni.mean_o == nullptr) == (bni.rstd_o == nullptr) && (bni.rmean == nullptr) == (bni.rvar == nullptr), CRUSE_E_SHAPE,
+                  "%s: mean / rstd and the running statistics come in pairs", who);
+    if (c.sums) { const int rc = prep_sums(who, c, zeroed); if (rc) return rc; }
+    c.bni = &bni;
+    return conv_run(c);
+}
+
+// Data-gradient convolutions with the BatchNorm(+ReLU) BACKWARD of their input applied while staging (see CruseBnBwdIn): one entry point =
+// cruse_bn_act_bwd_apply(dout -> dy_bf16, parameter gradients) + cruse_conv_*[_bnbwd](dy_bf16 -> y).  Shapes / modes the MFMA kernel does not
+// take run exactly those two calls.  c.x / c.x_dtype: dout; bnb.y null: no output-side sums.
+int conv_bnbwd_in(const char* who, CruseConvCall c, CruseBnBwdIn bb, const CruseBnBwd& bnb, int zeroed, int* plan = nullptr) {
+    CRUSE_REQUIRE(c.x && bb.y && bb.mean && bb.rstd && bb.gamma && bb.beta && bb.sums && bb.nrep >= 1, CRUSE_E_SHAPE,
+                  "%s: input BatchNorm tensors missing", who);
+    CRUSE_REQUIRE((bnb.y == nullptr) == (c.sums == nullptr), CRUSE_E_SHAPE, "%s: bn_y and sums come together", who);
+    if (c.sums) { const int rc = prep_sums(who, c, zeroed); if (rc) return rc; }
+    bb.count = (long long)c.B * c.T * c.Fin;
+    c.bnb = bnb.y ? &bnb : nullptr;
+    const int dout_dtype = c.x_dtype;
+    if (dout_dtype == CRUSE_DT_BF16) {
+        c.bbi = &bb;
+        const int rc = conv_run(c, plan);
+        if (rc != CONV_NOT_FUSED) return rc;
+        c.bbi = nullptr;
+    }
+    CRUSE_REQUIRE(bb.copy_bf16 != nullptr, CRUSE_E_SHAPE, "conv_*_bnbwd_in: dy_bf16 is required");
+    if (!plan) {
+        const int rc = cruse_bn_act_bwd_apply(static_cast<const float*>(c.x), bb.y, bb.mean, bb.rstd, bb.gamma, bb.beta, bb.sums, bb.nrep, (long long)c.B * c.T,
+                                              c.Cin, c.Fin, bb.relu, bb.training, dout_dtype, bb.copy_bf16, CRUSE_DT_BF16, bb.dgamma, bb.dbeta, bb.dbias,
+                                              c.stream);
+        if (rc) return rc;
+    }
+    c.x = bb.copy_bf16; c.x_dtype = CRUSE_DT_BF16;
+    return conv_run(c, plan);
 }
 
 }  // namespace
 
+// The ten entry points: each fills the descriptor from its own argument list (the scatter2 lists have no S / w_layout) and hands it to its form.
 extern "C" int cruse_conv_gather(const float* x, const float* w, const float* bias, float* y,
                                  int B, int T, int Cin, int Fin, int Cout, int Fout,
                                  int KT, int S, int pad, int w_layout, int act, int accum, int prec, int x_dtype, int y_dtype, void* stream) {
-    return conv_gather_impl(x, w, bias, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, act, accum, prec, nullptr, stream, nullptr,
-                            x_dtype, y_dtype);
+    return conv_run({0, x, w, bias, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, act, accum, prec, x_dtype, y_dtype, nullptr, (hipStream_t)stream});
 }
 
 extern "C" int cruse_conv_scatter2(const float* g, const float* w, const float* bias, float* y,
                                    int B, int T, int Cs, int Fg, int Cout, int Fout,
                                    int KT, int pad, int act, int accum, int prec, int x_dtype, int y_dtype, void* stream) {
-    return conv_scatter2_impl(g, w, bias, y, B, T, Cs, Fg, Cout, Fout, KT, pad, act, accum, prec, nullptr, stream, nullptr, x_dtype, y_dtype);
+    return conv_run({1, g, w, bias, y, B, T, Cs, Fg, Cout, Fout, KT, 2, pad, 0, act, accum, prec, x_dtype, y_dtype, nullptr, (hipStream_t)stream});
 }
 
 extern "C" int cruse_conv_gather_bnstats(const float* x, const float* w, const float* bias, float* y,
                                          int B, int T, int Cin, int Fin, int Cout, int Fout,
                                          int KT, int S, int pad, int prec, double* sums, int zeroed, void* stream) {
-    int rc = prep_sums(sums, Cout, zeroed, stream, "conv_gather_bnstats");
-    if (rc) return rc;
-    return conv_gather_impl(x, w, bias, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, 0, 0, 0, prec, sums, stream);
+    return conv_bnstats("conv_gather_bnstats", {0, x, w, bias, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, 0, 0, 0, prec, CRUSE_DT_F32, CRUSE_DT_F32, sums, (hipStream_t)stream}, zeroed);
 }
 
 extern "C" int cruse_conv_scatter2_bnstats(const float* g, const float* w, const float* bias, float* y,
                                            int B, int T, int Cs, int Fg, int Cout, int Fout,
                                            int KT, int pad, int prec, double* sums, int zeroed, void* stream) {
-    int rc = prep_sums(sums, Cout, zeroed, stream, "conv_scatter2_bnstats");
-    if (rc) return rc;
-    return conv_scatter2_impl(g, w, bias, y, B, T, Cs, Fg, Cout, Fout, KT, pad, 0, 0, prec, sums, stream);
+    return conv_bnstats("conv_scatter2_bnstats", {1, g, w, bias, y, B, T, Cs, Fg, Cout, Fout, KT, 2, pad, 0, 0, 0, prec, CRUSE_DT_F32, CRUSE_DT_F32, sums, (hipStream_t)stream}, zeroed);
 }
 
 extern "C" int cruse_conv_gather_bnbwd(const float* x, const float* w, float* y, int B, int T, int Cin, int Fin, int Cout, int Fout,
                                        int KT, int S, int pad, int w_layout, int accum, int prec,
                                        const float* bn_y, const float* mean, const float* rstd, const float* gamma, const float* beta,
                                        int relu, double* sums, int zeroed, int x_dtype, int y_dtype, void* stream) {
-    CRUSE_REQUIRE(bn_y && mean && rstd && gamma && beta, CRUSE_E_SHAPE, "conv_gather_bnbwd: BatchNorm tensors missing");
-    int rc = prep_sums(sums, Cout, zeroed, stream, "conv_gather_bnbwd");
-    if (rc) return rc;
-    const CruseBnBwd bnb = {bn_y, mean, rstd, gamma, beta, relu};
-    return conv_gather_impl(x, w, nullptr, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, 0, accum, prec, sums, stream, &bnb, x_dtype, y_dtype);
+    return conv_bnbwd("conv_gather_bnbwd", {0, x, w, nullptr, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, 0, accum, prec, x_dtype, y_dtype, sums, (hipStream_t)stream}, {bn_y, mean, rstd, gamma, beta, relu}, zeroed);
 }
 
 extern "C" int cruse_conv_scatter2_bnbwd(const float* g, const float* w, float* y, int B, int T, int Cs, int Fg, int Cout, int Fout,
                                          int KT, int pad, int accum, int prec,
                                          const float* bn_y, const float* mean, const float* rstd, const float* gamma, const float* beta,
                                          int relu, double* sums, int zeroed, int x_dtype, int y_dtype, void* stream) {
-    CRUSE_REQUIRE(bn_y && mean && rstd && gamma && beta, CRUSE_E_SHAPE, "conv_scatter2_bnbwd: BatchNorm tensors missing");
-    int rc = prep_sums(sums, Cout, zeroed, stream, "conv_scatter2_bnbwd");
-    if (rc) return rc;
-    const CruseBnBwd bnb = {bn_y, mean, rstd, gamma, beta, relu};
-    return conv_scatter2_impl(g, w, nullptr, y, B, T, Cs, Fg, Cout, Fout, KT, pad, 0, accum, prec, sums, stream, &bnb, x_dtype, y_dtype);
+    return conv_bnbwd("conv_scatter2_bnbwd", {1, g, w, nullptr, y, B, T, Cs, Fg, Cout, Fout, KT, 2, pad, 0, 0, accum, prec, x_dtype, y_dtype, sums, (hipStream_t)stream}, {bn_y, mean, rstd, gamma, beta, relu}, zeroed);
 }
 
 extern "C" int cruse_conv_gather_bnin(const float* x_pre, const double* in_sums, int in_replicas, long long in_count, float eps, float momentum,
@@ -611,14 +621,9 @@ extern "C" int cruse_conv_gather_bnin(const float* x_pre, const double* in_sums,
                                       float* in_running_var, const float* in_add, void* in_copy_bf16,
                                       const float* w, const float* bias, float* y, int B, int T, int Cin, int Fin, int Cout, int Fout,
                                       int KT, int S, int pad, int prec, double* out_sums, int zeroed, void* stream) {
-    CRUSE_REQUIRE(x_pre && in_sums && in_gamma && in_beta && in_replicas >= 1 && in_count > 0, CRUSE_E_SHAPE, "conv_gather_bnin: input BatchNorm tensors missing");
-    CRUSE_REQUIRE((in_mean == nullptr) == (in_rstd == nullptr) && (in_running_mean == nullptr) == (in_running_var == nullptr), CRUSE_E_SHAPE,
-                  "conv_gather_bnin: mean / rstd and the running statistics come in pairs");
-    if (out_sums) { int rc = prep_sums(out_sums, Cout, zeroed, stream, "conv_gather_bnin"); if (rc) return rc; }
-    const CruseBnIn bni = {in_sums, in_replicas, in_count, eps, momentum, in_gamma, in_beta, in_mean, in_rstd, in_running_mean, in_running_var,
-                           in_add, in_copy_bf16};
-    return conv_gather_impl(x_pre, w, bias, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, 0, 0, 0, prec, out_sums, stream, nullptr, CRUSE_DT_F32,
-                            CRUSE_DT_F32, &bni);
+    return conv_bnin("conv_gather_bnin", {0, x_pre, w, bias, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, 0, 0, 0, prec, CRUSE_DT_F32, CRUSE_DT_F32, out_sums, (hipStream_t)stream},
+                     {in_sums, in_replicas, in_count, eps, momentum, in_gamma, in_beta, in_mean, in_rstd, in_running_mean, in_running_var, in_add,
+                      in_copy_bf16}, zeroed);
 }
 
 extern "C" int cruse_conv_scatter2_bnin(const float* g_pre, const double* in_sums, int in_replicas, long long in_count, float eps, float momentum,
@@ -626,23 +631,9 @@ extern "C" int cruse_conv_scatter2_bnin(const float* g_pre, const double* in_sum
                                         float* in_running_var, const float* in_add, void* in_copy_bf16,
                                         const float* w, const float* bias, float* y, int B, int T, int Cs, int Fg, int Cout, int Fout,
                                         int KT, int pad, int prec, double* out_sums, int zeroed, void* stream) {
-    CRUSE_REQUIRE(g_pre && in_sums && in_gamma && in_beta && in_replicas >= 1 && in_count > 0, CRUSE_E_SHAPE, "conv_scatter2_bnin: input BatchNorm tensors missing");
-    CRUSE_REQUIRE((in_mean == nullptr) == (in_rstd == nullptr) && (in_running_mean == nullptr) == (in_running_var == nullptr), CRUSE_E_SHAPE,
-                  "conv_scatter2_bnin: mean / rstd and the running statistics come in pairs");
-    if (out_sums) { int rc = prep_sums(out_sums, Cout, zeroed, stream, "conv_scatter2_bnin"); if (rc) return rc; }
-    const CruseBnIn bni = {in_sums, in_replicas, in_count, eps, momentum, in_gamma, in_beta, in_mean, in_rstd, in_running_mean, in_running_var,
-                           in_add, in_copy_bf16};
-    return conv_scatter2_impl(g_pre, w, bias, y, B, T, Cs, Fg, Cout, Fout, KT, pad, 0, 0, prec, out_sums, stream, nullptr, CRUSE_DT_F32,
-                              CRUSE_DT_F32, &bni);
-}
-
-// Data-gradient convolutions with the BatchNorm(+ReLU) BACKWARD of their input applied while staging (see CruseBnBwdIn): one entry point =
-// cruse_bn_act_bwd_apply(dout -> dy_bf16, parameter gradients) + cruse_conv_*[_bnbwd](dy_bf16 -> y).  Shapes / modes the MFMA kernel does not
-// take run exactly those two calls.
-static int bnbwd_in_fallback(const CruseBnBwdIn& bb, const void* dout, int dout_dtype, long long rows, int C, int F, void* stream) {
-    CRUSE_REQUIRE(bb.copy_bf16 != nullptr, CRUSE_E_SHAPE, "conv_*_bnbwd_in: dy_bf16 is required");
-    return cruse_bn_act_bwd_apply(reinterpret_cast<const float*>(dout), bb.y, bb.mean, bb.rstd, bb.gamma, bb.beta, bb.sums, bb.nrep, rows, C, F,
-                                  bb.relu, bb.training, dout_dtype, bb.copy_bf16, CRUSE_DT_BF16, bb.dgamma, bb.dbeta, bb.dbias, stream);
+    return conv_bnin("conv_scatter2_bnin", {1, g_pre, w, bias, y, B, T, Cs, Fg, Cout, Fout, KT, 2, pad, 0, 0, 0, prec, CRUSE_DT_F32, CRUSE_DT_F32, out_sums, (hipStream_t)stream},
+                     {in_sums, in_replicas, in_count, eps, momentum, in_gamma, in_beta, in_mean, in_rstd, in_running_mean, in_running_var, in_add,
+                      in_copy_bf16}, zeroed);
 }
 
 extern "C" int cruse_conv_gather_bnbwd_in(const void* dout, int dout_dtype, const float* in_y, const float* in_mean, const float* in_rstd,
@@ -652,22 +643,9 @@ extern "C" int cruse_conv_gather_bnbwd_in(const void* dout, int dout_dtype, cons
                                           int w_layout, int accum, int prec,
                                           const float* bn_y, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
                                           double* sums, int zeroed, int y_dtype, void* stream) {
-    CRUSE_REQUIRE(dout && in_y && in_mean && in_rstd && in_gamma && in_beta && in_sums && in_replicas >= 1, CRUSE_E_SHAPE,
-                  "conv_gather_bnbwd_in: input BatchNorm tensors missing");
-    CRUSE_REQUIRE((bn_y == nullptr) == (sums == nullptr), CRUSE_E_SHAPE, "conv_gather_bnbwd_in: bn_y and sums come together");
-    if (sums) { int rc = prep_sums(sums, Cout, zeroed, stream, "conv_gather_bnbwd_in"); if (rc) return rc; }
-    const CruseBnBwdIn bb = {in_y, in_sums, in_replicas, (long long)B * T * Fin, in_mean, in_rstd, in_gamma, in_beta, in_relu, in_training, dy_bf16,
-                             in_dgamma, in_dbeta, in_dbias};
-    const CruseBnBwd bnb = {bn_y, mean, rstd, gamma, beta, relu};
-    if (dout_dtype == CRUSE_DT_BF16) {
-        const int rc = conv_gather_impl(reinterpret_cast<const float*>(dout), w, nullptr, reinterpret_cast<float*>(y), B, T, Cin, Fin, Cout, Fout, KT, S,
-                                        pad, w_layout, 0, accum, prec, sums, stream, bn_y ? &bnb : nullptr, CRUSE_DT_BF16, y_dtype, nullptr, &bb);
-        if (rc <= 0) return rc;
-    }
-    int rc = bnbwd_in_fallback(bb, dout, dout_dtype, (long long)B * T, Cin, Fin, stream);
-    if (rc) return rc;
-    return conv_gather_impl(reinterpret_cast<const float*>(dy_bf16), w, nullptr, reinterpret_cast<float*>(y), B, T, Cin, Fin, Cout, Fout, KT, S, pad,
-                            w_layout, 0, accum, prec, sums, stream, bn_y ? &bnb : nullptr, CRUSE_DT_BF16, y_dtype);
+    return conv_bnbwd_in("conv_gather_bnbwd_in", {0, dout, w, nullptr, y, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, 0, accum, prec, dout_dtype, y_dtype, sums, (hipStream_t)stream},
+                         {in_y, in_sums, in_replicas, 0, in_mean, in_rstd, in_gamma, in_beta, in_relu, in_training, dy_bf16, in_dgamma, in_dbeta, in_dbias},
+                         {bn_y, mean, rstd, gamma, beta, relu}, zeroed);
 }
 
 extern "C" int cruse_conv_scatter2_bnbwd_in(const void* dout, int dout_dtype, const float* in_y, const float* in_mean, const float* in_rstd,
@@ -677,22 +655,30 @@ extern "C" int cruse_conv_scatter2_bnbwd_in(const void* dout, int dout_dtype, co
                                             int prec,
                                             const float* bn_y, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
                                             double* sums, int zeroed, int y_dtype, void* stream) {
-    CRUSE_REQUIRE(dout && in_y && in_mean && in_rstd && in_gamma && in_beta && in_sums && in_replicas >= 1, CRUSE_E_SHAPE,
-                  "conv_scatter2_bnbwd_in: input BatchNorm tensors missing");
-    CRUSE_REQUIRE((bn_y == nullptr) == (sums == nullptr), CRUSE_E_SHAPE, "conv_scatter2_bnbwd_in: bn_y and sums come together");
-    if (sums) { int rc = prep_sums(sums, Cout, zeroed, stream, "conv_scatter2_bnbwd_in"); if (rc) return rc; }
-    const CruseBnBwdIn bb = {in_y, in_sums, in_replicas, (long long)B * T * Fg, in_mean, in_rstd, in_gamma, in_beta, in_relu, in_training, dy_bf16,
-                             in_dgamma, in_dbeta, in_dbias};
-    const CruseBnBwd bnb = {bn_y, mean, rstd, gamma, beta, relu};
-    if (dout_dtype == CRUSE_DT_BF16) {
-        const int rc = conv_scatter2_impl(reinterpret_cast<const float*>(dout), w, nullptr, reinterpret_cast<float*>(y), B, T, Cs, Fg, Cout, Fout, KT, pad,
-                                          0, accum, prec, sums, stream, bn_y ? &bnb : nullptr, CRUSE_DT_BF16, y_dtype, nullptr, &bb);
-        if (rc <= 0) return rc;
-    }
-    int rc = bnbwd_in_fallback(bb, dout, dout_dtype, (long long)B * T, Cs, Fg, stream);
-    if (rc) return rc;
-    return conv_scatter2_impl(reinterpret_cast<const float*>(dy_bf16), w, nullptr, reinterpret_cast<float*>(y), B, T, Cs, Fg, Cout, Fout, KT, pad, 0,
-                              accum, prec, sums, stream, bn_y ? &bnb : nullptr, CRUSE_DT_BF16, y_dtype);
+    return conv_bnbwd_in("conv_scatter2_bnbwd_in", {1, dout, w, nullptr, y, B, T, Cs, Fg, Cout, Fout, KT, 2, pad, 0, 0, accum, prec, dout_dtype, y_dtype, sums, (hipStream_t)stream},
+                         {in_y, in_sums, in_replicas, 0, in_mean, in_rstd, in_gamma, in_beta, in_relu, in_training, dy_bf16, in_dgamma, in_dbeta, in_dbias},
+                         {bn_y, mean, rstd, gamma, beta, relu}, zeroed);
+}
+
+// Host-only (no device is touched): what a call of this shape, mode and forms would launch -- conv_run's own decision with the launches left
+// out.  forms: CRUSE_CONV_FORM_* bits; BNB implies output-side sums; with BBI, x_dtype is the dtype of dout and the two-call fallback reports
+// the plan of its data-gradient call.  Pointers are taken as 16-byte aligned.
+extern "C" int cruse_conv_plan(int scatter, int Cin, int Fin, int Cout, int Fout, int KT, int S, int pad, int w_layout,
+                               int B, int T, int prec, int x_dtype, int y_dtype, int act, int accum, int forms, int* out) {
+    CRUSE_REQUIRE(out != nullptr && forms >= 0 && forms < 16, CRUSE_E_SHAPE, "conv_plan: out is NULL or forms = %d", forms);
+    CRUSE_REQUIRE(!scatter || (S == 2 && w_layout == 0), CRUSE_E_SHAPE, "conv_plan: the scatter2 form has S = 2 and w_layout = 0");
+    alignas(16) static float buf[4];                 // stands for every tensor: never dereferenced
+    static double dsums[1];
+    const CruseBnBwd bnb = {buf, buf, buf, buf, buf, 1};
+    const CruseBnIn bni = {dsums, 1, (long long)B * T * Fin, 1e-5f, 0.1f, buf, buf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const CruseBnBwdIn bbi = {buf, dsums, 1, 0, buf, buf, buf, buf, 1, 1, buf, nullptr, nullptr, nullptr};
+    const bool has_bnb = (forms & CRUSE_CONV_FORM_BNB) != 0;
+    CruseConvCall c = {scatter ? 1 : 0, buf, buf, nullptr, buf, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, act, accum, prec, x_dtype, y_dtype,
+                       (forms & CRUSE_CONV_FORM_SUMS) || has_bnb ? dsums : nullptr, nullptr, has_bnb ? &bnb : nullptr,
+                       (forms & CRUSE_CONV_FORM_BNI) ? &bni : nullptr};
+    for (int i = 0; i < CRUSE_CP_N; ++i) out[i] = 0;
+    if (forms & CRUSE_CONV_FORM_BBI) return conv_bnbwd_in(scatter ? "conv_scatter2_bnbwd_in" : "conv_gather_bnbwd_in", c, bbi, has_bnb ? bnb : CruseBnBwd{}, 1, out);
+    return conv_run(c, out);
 }
 
 extern "C" size_t cruse_conv_wgrad_ws_bytes(int Ca, int Cb, int KT) {

@@ -13,7 +13,7 @@
 // so every class is a dense GEMM.  The kernel moves 2 x 640 floats per frame through HBM
 // against <= 0.25 MFLOP per frame: it is HBM-bound, the MFMA time is negligible.
 //
-// BUILD: this source is compiled FOUR times (build.sh, -DCM_TU=k): k = 0 the dispatcher (cruse_conv_mfma_try, no kernels), k = 1 / 2 / 3
+// BUILD: this source is compiled FOUR times (build.sh, -DCM_TU=k): k = 0 the dispatcher (cm_plan / cm_launch behind cruse_conv_mfma_try, no kernels), k = 1 / 2 / 3
 // the kernels of one precision mode each (exact f32 / split-bf16 x3 / plain bf16) -- ~100 kernels per object in parallel compile jobs
 // instead of ~300 in one (100 s).
 #include "common.h"
@@ -1069,20 +1069,24 @@ CM_DEFINE_TU(bf16, CRUSE_PREC_BF16)
 #else
 static int g_cm_last_prec = CRUSE_PREC_F32;
 
-// Returns 1 if the MFMA path handled the call, 0 if the shape is not eligible (caller falls back
-// to the VALU kernel), < 0 on error.
-int cruse_conv_mfma_try(int scatter, const float* x, const float* w, const float* bias, float* y,
-                        int B, int T, int Cin, int Fin, int Cout, int Fout, int KT, int S, int pad,
-                        int w_layout, int act, int accum, int prec, double* bn_sums, const CruseBnBwd* bnb, int x_bf16, int y_bf16,
-                        const CruseBnIn* bni, hipStream_t stream, const CruseBnBwdIn* bbi) {
-    if (bni != nullptr && (prec != CRUSE_PREC_BF16X3 || Cin > 64 || accum || bnb != nullptr || x_bf16)) return 0;
-    if (bbi != nullptr && (prec != CRUSE_PREC_BF16 || Cin > 64 || !x_bf16 || bni != nullptr || act)) return 0;
-    if (y_bf16 && !x_bf16) return 0;                                    // (a bf16 output comes with a bf16 input: the backward chain)
-    if (Cin % 8 != 0 || (Cin & (Cin - 1)) != 0 || Cout < 8 || Cout > 64 || (TFM * (Fout / (scatter ? 2 : 1))) % 16 != 0) return 0;
-    CMArgs a = {};
-    a.x = x; a.w = w; a.bias = bias; a.y = y;
-    a.B = B; a.T = T; a.Cin = Cin; a.Fin = Fin; a.Cout = Cout; a.Fout = Fout;
-    a.act = act; a.accum = accum; a.sums = bn_sums;
+// what one eligible call launches: the kernel's arguments and its launch shape
+struct CMPlan { CMArgs a; int mt, nw, grid; size_t lds; };
+
+// Host-only: does the MFMA kernel take this call (false: the caller falls back to the VALU kernel), and with which arguments, tile
+// and grid.  Touches no device; the one pointer it looks at is x (16-byte alignment of the staged rows).
+static bool cm_plan(const CruseConvCall& c, CMPlan& p) {
+    const int scatter = c.scatter, Cin = c.Cin, Fin = c.Fin, Cout = c.Cout, Fout = c.Fout, KT = c.KT, pad = c.pad, prec = c.prec;
+    const bool x_bf16 = c.x_dtype == CRUSE_DT_BF16, y_bf16 = c.y_dtype == CRUSE_DT_BF16;
+    const CruseBnBwd* bnb = c.bnb; const CruseBnIn* bni = c.bni; const CruseBnBwdIn* bbi = c.bbi;
+    if (bni != nullptr && (prec != CRUSE_PREC_BF16X3 || Cin > 64 || c.accum || bnb != nullptr || x_bf16)) return false;
+    if (bbi != nullptr && (prec != CRUSE_PREC_BF16 || Cin > 64 || !x_bf16 || bni != nullptr || c.act)) return false;
+    if (y_bf16 && !x_bf16) return false;                                // (a bf16 output comes with a bf16 input: the backward chain)
+    if (Cin % 8 != 0 || (Cin & (Cin - 1)) != 0 || Cout < 8 || Cout > 64 || (TFM * (Fout / (scatter ? 2 : 1))) % 16 != 0) return false;
+    CMArgs& a = p.a;
+    a = {};
+    a.x = static_cast<const float*>(c.x); a.w = c.w; a.bias = c.bias; a.y = static_cast<float*>(c.y);
+    a.B = c.B; a.T = c.T; a.Cin = Cin; a.Fin = Fin; a.Cout = Cout; a.Fout = Fout;
+    a.act = c.act; a.accum = c.accum; a.sums = c.sums;
     a.x_bf16 = x_bf16 ? 1 : 0; a.y_bf16 = y_bf16 ? 1 : 0;
     if (bbi != nullptr) {
         a.bb_y = bbi->y; a.bb_sums = bbi->sums; a.bb_nrep = bbi->nrep; a.bb_inv_count = 1.0 / (double)bbi->count;
@@ -1105,69 +1109,81 @@ int cruse_conv_mfma_try(int scatter, const float* x, const float* w, const float
     }
     if (!scatter) {
         // y[co,fo] = sum W(co,ci,kt,kf) x[t-(KT-1)+kt, ci, fo*S - pad + kf]
-        a.S = S; a.OS = 1; a.nclass = 1; a.halo_lo = KT - 1;
+        a.S = c.S; a.OS = 1; a.nclass = 1; a.halo_lo = KT - 1;
         a.cls[0].ntaps = KT * 3; a.cls[0].par = 0;
         for (int kt = 0; kt < KT; ++kt)
             for (int kf = 0; kf < 3; ++kf) {
                 const int i = kt * 3 + kf;
                 a.cls[0].dt[i] = kt - (KT - 1);
                 a.cls[0].df[i] = kf - pad;
-                a.cls[0].wk[i] = w_layout == 0 ? kt * 3 + kf : (2 - kf);
+                a.cls[0].wk[i] = c.w_layout == 0 ? kt * 3 + kf : (2 - kf);
             }
-        if (w_layout == 0) { a.sco = (long long)Cin * KT * 3; a.sci = KT * 3; }
+        if (c.w_layout == 0) { a.sco = (long long)Cin * KT * 3; a.sci = KT * 3; }
         else { a.sco = 3; a.sci = (long long)Cout * 3; }
     } else {
         // y[co,fo] = sum_{(fo+pad-kf) even} w[cs][co][kt][kf] g[t+(KT-1)-kt, cs, (fo+pad-kf)/2]; fo = 2m + par
         a.S = 1; a.OS = 2; a.nclass = 2; a.halo_lo = 0;
         a.sco = (long long)KT * 3; a.sci = (long long)Cout * KT * 3;
         for (int par = 0; par < 2; ++par) {
-            TapClass& c = a.cls[par];
-            c.par = par; c.ntaps = 0;
+            TapClass& tc = a.cls[par];
+            tc.par = par; tc.ntaps = 0;
             for (int kt = 0; kt < KT; ++kt)
                 for (int kf = 0; kf < 3; ++kf) {
                     const int q = par + pad - kf;            // fo + pad - kf = 2m + q
                     if (q & 1) continue;
-                    const int i = c.ntaps++;
-                    c.dt[i] = (KT - 1) - kt;
-                    c.df[i] = q / 2;                         // q in {-2,0,2} -> -1,0,+1 (exact for even q)
-                    c.wk[i] = kt * 3 + kf;
+                    const int i = tc.ntaps++;
+                    tc.dt[i] = (KT - 1) - kt;
+                    tc.df[i] = q / 2;                        // q in {-2,0,2} -> -1,0,+1 (exact for even q)
+                    tc.wk[i] = kt * 3 + kf;
                 }
         }
     }
     a.nrows = TFM + KT - 1;
     const int ks0 = (a.cls[0].ntaps * Cin + 31) / 32, ks1 = a.nclass > 1 ? (a.cls[1].ntaps * Cin + 31) / 32 : 0;
-    const int mt = Cout <= 16 ? 1 : (Cout <= 32 ? 2 : 4);
-    if ((Cin * Fin) % 4 != 0 || ((uintptr_t)x % 16) != 0) return 0;
-    if (x_bf16 && ((Cin * Fin) % 8 != 0 || prec != CRUSE_PREC_BF16 || (bn_sums != nullptr && bnb == nullptr))) return 0;   // (bf16 slots cover 8 elements; bf16 mode, data-gradient forms)
-    if ((TFM + KT - 1) * Cin * Fin > MAXV * 256 * 4) return 0;
-    const size_t wbytes = (size_t)mt * (ks0 + ks1) * 512 *
+    p.mt = Cout <= 16 ? 1 : (Cout <= 32 ? 2 : 4);
+    if ((Cin * Fin) % 4 != 0 || ((uintptr_t)c.x % 16) != 0) return false;
+    if (x_bf16 && ((Cin * Fin) % 8 != 0 || prec != CRUSE_PREC_BF16 || (c.sums != nullptr && bnb == nullptr))) return false;   // (bf16 slots cover 8 elements; bf16 mode, data-gradient forms)
+    if ((TFM + KT - 1) * Cin * Fin > MAXV * 256 * 4) return false;
+    const size_t wbytes = (size_t)p.mt * (ks0 + ks1) * 512 *
                           (prec == CRUSE_PREC_F32 ? 4 : (prec == CRUSE_PREC_BF16X3 ? 4 : 2));
     const bool cf = prec != CRUSE_PREC_F32;      // channel-fastest pre-converted bf16 image (see the kernel)
-    if (cf && ((Fin & 1) != 0 || a.nrows * (Fin / ((Fin & 3) ? 2 : 4)) * (Cin / 8) > ((Fin & 3) ? 2 : 1) * 256)) return 0;
-    const size_t lds = wbytes + (cf ? (size_t)(prec == CRUSE_PREC_BF16X3 ? 2 : 1) * (size_t)((a.nrows * (Fin + 2) * (Cin / 8) + 15) & ~15) * 16
-                                    : (size_t)a.nrows * Cin * Fin * sizeof(float));
-    if (lds > 150 * 1024) return 0;
-    const int ntiles = B * ((T + TFM - 1) / TFM);
+    if (cf && ((Fin & 1) != 0 || a.nrows * (Fin / ((Fin & 3) ? 2 : 4)) * (Cin / 8) > ((Fin & 3) ? 2 : 1) * 256)) return false;
+    p.lds = wbytes + (cf ? (size_t)(prec == CRUSE_PREC_BF16X3 ? 2 : 1) * (size_t)((a.nrows * (Fin + 2) * (Cin / 8) + 15) & ~15) * 16
+                         : (size_t)a.nrows * Cin * Fin * sizeof(float));
+    if (p.lds > 150 * 1024) return false;
+    const int ntiles = c.B * ((c.T + TFM - 1) / TFM);
     // small weight images: more, lighter workgroups hide latency better (44 vs 60 us on the 8->16 layer);
     // large ones (up to 48 KB of fragments per workgroup) amortise their prologue over more tiles
     int gmax = wbytes <= 16 * 1024 ? 1024 : 512;
     gmax = cruse_opt("cm_grid", gmax);
-    const int grid = ntiles < gmax ? ntiles : gmax;
-    int rc;
+    p.grid = ntiles < gmax ? ntiles : gmax;
     const int ntile_wg = a.nclass * (TFM * (Fout / a.OS) / 16);       // N-tiles of one workgroup tile
-    int nw = (ntile_wg == 5 || (ntile_wg == 10 && (Cin >= 64 || Cout >= 64))) ? 5 : 4;
-    { const int e = cruse_opt("cm_nw", 0); if (e == 4 || e == 5) nw = e; }       // profiling option
-    if (prec == CRUSE_PREC_F32) nw = 4;
+    p.nw = (ntile_wg == 5 || (ntile_wg == 10 && (Cin >= 64 || Cout >= 64))) ? 5 : 4;
+    { const int e = cruse_opt("cm_nw", 0); if (e == 4 || e == 5) p.nw = e; }       // profiling option
+    if (prec == CRUSE_PREC_F32) p.nw = 4;
     // the fused input BatchNorm backward holds 48 more prefetch registers per thread: the 5-wave (128-register) and 64-row variants spill
     // (decoder level 4: 223 us against 38 + 49 for the two separate kernels) -- those shapes keep the separate pass
-    if (bbi != nullptr && (nw == 5 || mt > 2)) return 0;
+    if (bbi != nullptr && (p.nw == 5 || p.mt > 2)) return false;
+    return true;
+}
+
+static int cm_launch(const CMPlan& p, int prec, hipStream_t stream) {
+    int rc;
     g_cm_last_prec = prec;
-    if (prec == CRUSE_PREC_F32) rc = cruse_cm_launch_f32(a, grid, lds, nw, stream);
-    else if (prec == CRUSE_PREC_BF16) rc = cruse_cm_launch_bf16(a, grid, lds, nw, stream);
-    else rc = cruse_cm_launch_x3(a, grid, lds, nw, stream);
+    if (prec == CRUSE_PREC_F32) rc = cruse_cm_launch_f32(p.a, p.grid, p.lds, p.nw, stream);
+    else if (prec == CRUSE_PREC_BF16) rc = cruse_cm_launch_bf16(p.a, p.grid, p.lds, p.nw, stream);
+    else rc = cruse_cm_launch_x3(p.a, p.grid, p.lds, p.nw, stream);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { cruse_set_error("conv_mfma: HIP launch failed: %s", hipGetErrorString(e)); return CRUSE_E_HIP; }
+    return 1;
+}
+
+int cruse_conv_mfma_try(const CruseConvCall& c, int* plan) {
+    CMPlan p;
+    if (!cm_plan(c, p)) return 0;
+    if (plan == nullptr) return cm_launch(p, c.prec, c.stream);
+    plan[CRUSE_CP_MT] = p.mt; plan[CRUSE_CP_NW] = p.nw; plan[CRUSE_CP_GRID] = p.grid; plan[CRUSE_CP_LDS] = (int)p.lds;
     return 1;
 }
 

@@ -123,6 +123,7 @@ def istft_bwd(dwave: torch.Tensor, T: int, n_fft: int, hop: int):
 
 
 # ---------------------------------------------------------------- convolutions
+CONV_FORM_SUMS, CONV_FORM_BNB, CONV_FORM_BNI, CONV_FORM_BBI = 1, 2, 4, 8      # cruse_conv_plan
 CONV_PREC = {"f32": PREC_F32, "bf16x3": PREC_BF16X3, "bf16": PREC_BF16X3, "valu": -1}
 
 
@@ -134,40 +135,59 @@ def conv_prec(prec) -> int:
     return CONV_PREC[prec] if isinstance(prec, str) else int(prec)
 
 
+# The eight wrappers below are four forms times (gather, scatter2): one private function per form, the scatter2 wrapper being its gather
+# twin called with scatter=True, S=2, Fout=2*Fg.  The C entry points of a pair differ in their argument lists only -- the scatter2 ones
+# have no S and no w_layout -- which _geom / the `wl` tuples spell out.  _CONV_FN[scatter]: the pair members and their names in messages.
+_CONV_FN = tuple((getattr(lib, f"cruse_conv_{n}"), getattr(lib, f"cruse_conv_{n}_bnbwd"), getattr(lib, f"cruse_conv_{n}_bnbwd_in"),
+                  getattr(lib, f"cruse_conv_{n}_bnin"), getattr(lib, f"cruse_conv_{n}_bnstats"), f"conv_{n}", f"conv_{n} out",
+                  f"conv_{n}_bwd_in out") for n in ("gather", "scatter2"))
+_NO_SUMS = (None, 0)
+_NO_BN_BWD = (None, None, None, None, None, False)
+
+
+def _conv_out(like, B, T, Cout, Fout, bf16=False):
+    return torch.empty(B, T, Cout, Fout, device=like.device, dtype=torch.bfloat16 if bf16 else torch.float32)
+
+
+def _bn_sums(Cout, device):
+    """(sums, zeroed) for the batch sums of a conv's Cout output channels"""
+    return ARENA.take(2 * Cout * BN_STAT_REPLICAS, device)
+
+
+def _bn_bwd_args(bn_bwd):
+    by, mean, rstd, gamma, beta, relu = bn_bwd if bn_bwd is not None else _NO_BN_BWD
+    return _p(by), _p(mean), _p(rstd), _p(gamma), _p(beta), 1 if relu else 0
+
+
+def _geom(scatter, B, T, Cin, Fin, Cout, Fout, KT, S, pad):
+    return (B, T, Cin, Fin, Cout, Fout, KT, pad) if scatter else (B, T, Cin, Fin, Cout, Fout, KT, S, pad)
+
+
+def _conv(scatter, x, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, act, out, accum, prec, bn_bwd, out_bf16):
+    fns = _CONV_FN[scatter]
+    if out is None:
+        out = _conv_out(x, B, T, Cout, Fout, out_bf16)
+    geom, wl = _geom(scatter, B, T, Cin, Fin, Cout, Fout, KT, S, pad), () if scatter else (w_layout,)
+    if bn_bwd is not None:
+        sums, z = _bn_sums(Cout, x.device)
+        check(fns[1](_p(x), _p(w), _p(out), *geom, *wl, 1 if accum else 0, conv_prec(prec), *_bn_bwd_args(bn_bwd), _p(sums), z,
+                     _xdt(x, fns[5]), _xdt(out, fns[6]), _stream()))
+        return out, sums
+    check(fns[0](_p(x), _p(w), _p(bias), _p(out), *geom, *wl, act, 1 if accum else 0, conv_prec(prec), _xdt(x, fns[5]), _xdt(out, fns[6]),
+                 _stream()))
+    return out
+
+
 def conv_gather(x, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout=0, act=0, out=None, accum=False,
                 prec=None, bn_bwd=None, out_bf16=False):
     """bn_bwd = (bn_y, mean, rstd, gamma, beta, relu): the output is the gradient wrt the output of that BatchNorm(+ReLU); returns
     (out, sums) with the backward sums of bn_act_bwd accumulated by the conv's epilogue (cruse_conv_gather_bnbwd)."""
-    if out is None:
-        out = torch.empty(B, T, Cout, Fout, device=x.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
-    if bn_bwd is not None:
-        by, mean, rstd, gamma, beta, relu = bn_bwd
-        sums, z = ARENA.take(2 * Cout * BN_STAT_REPLICAS, x.device)
-        check(lib.cruse_conv_gather_bnbwd(_p(x), _p(w), _p(out), B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout,
-                                          1 if accum else 0, conv_prec(prec), _p(by), _p(mean), _p(rstd), _p(gamma), _p(beta),
-                                          1 if relu else 0, _p(sums), z, _xdt(x, "conv_gather"), _xdt(out, "conv_gather out"), _stream()))
-        return out, sums
-    check(lib.cruse_conv_gather(_p(x), _p(w), _p(bias), _p(out), B, T, Cin, Fin, Cout, Fout, KT, S, pad,
-                                w_layout, act, 1 if accum else 0, conv_prec(prec), _xdt(x, "conv_gather"), _xdt(out, "conv_gather out"),
-                                _stream()))
-    return out
+    return _conv(False, x, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, act, out, accum, prec, bn_bwd, out_bf16)
 
 
 def conv_scatter2(g, w, bias, B, T, Cs, Fg, Cout, KT, pad, act=0, out=None, accum=False, prec=None, bn_bwd=None, out_bf16=False):
     """bn_bwd: as for conv_gather (cruse_conv_scatter2_bnbwd)."""
-    Fout = 2 * Fg
-    if out is None:
-        out = torch.empty(B, T, Cout, Fout, device=g.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
-    if bn_bwd is not None:
-        by, mean, rstd, gamma, beta, relu = bn_bwd
-        sums, z = ARENA.take(2 * Cout * BN_STAT_REPLICAS, g.device)
-        check(lib.cruse_conv_scatter2_bnbwd(_p(g), _p(w), _p(out), B, T, Cs, Fg, Cout, Fout, KT, pad, 1 if accum else 0,
-                                            conv_prec(prec), _p(by), _p(mean), _p(rstd), _p(gamma), _p(beta), 1 if relu else 0,
-                                            _p(sums), z, _xdt(g, "conv_scatter2"), _xdt(out, "conv_scatter2 out"), _stream()))
-        return out, sums
-    check(lib.cruse_conv_scatter2(_p(g), _p(w), _p(bias), _p(out), B, T, Cs, Fg, Cout, Fout, KT, pad, act,
-                                  1 if accum else 0, conv_prec(prec), _xdt(g, "conv_scatter2"), _xdt(out, "conv_scatter2 out"), _stream()))
-    return out
+    return _conv(True, g, w, bias, B, T, Cs, Fg, Cout, 2 * Fg, KT, 2, pad, 0, act, out, accum, prec, bn_bwd, out_bf16)
 
 
 def _bwd_in_args(dout, bn_in):
@@ -177,34 +197,28 @@ def _bwd_in_args(dout, bn_in):
                 1 if relu else 0, 1 if training else 0, _p(dv), _p(dgamma), _p(dbeta), _p(dbias))
 
 
+def _conv_bwd_in(scatter, dout, bn_in, w, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, out, accum, prec, bn_bwd, out_bf16):
+    fns = _CONV_FN[scatter]
+    if out is None:
+        out = _conv_out(dout, B, T, Cout, Fout, out_bf16)
+    dv, head = _bwd_in_args(dout, bn_in)
+    sums, z = _bn_sums(Cout, dout.device) if bn_bwd is not None else _NO_SUMS
+    check(fns[2](*head, _p(w), _p(out), *_geom(scatter, B, T, Cin, Fin, Cout, Fout, KT, S, pad), *(() if scatter else (w_layout,)),
+                 1 if accum else 0, conv_prec(prec), *_bn_bwd_args(bn_bwd), _p(sums), z, _xdt(out, fns[7]), _stream()))
+    return out, sums, dv
+
+
 def conv_gather_bwd_in(dout, bn_in, w, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout=0, out=None, accum=False, prec=None, bn_bwd=None,
                        out_bf16=False):
     """Data gradient with the BatchNorm(+ReLU) backward of its INPUT fused into the staging (cruse_conv_gather_bnbwd_in).
     bn_in = (y_pre, mean, rstd, gamma, beta, sums [BN_STAT_REPLICAS][2*Cin], relu, training, dgamma, dbeta, dbias or None): `dout` is the gradient
     wrt that BatchNorm's output.  Returns (out, output-side sums or None, dy [B,T,Cin,Fin] bf16 -- the weight gradient's operand)."""
-    if out is None:
-        out = torch.empty(B, T, Cout, Fout, device=dout.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
-    dv, head = _bwd_in_args(dout, bn_in)
-    sums, z = (ARENA.take(2 * Cout * BN_STAT_REPLICAS, dout.device) if bn_bwd is not None else (None, 0))
-    by, mean, rstd, gamma, beta, relu = bn_bwd if bn_bwd is not None else (None, None, None, None, None, False)
-    check(lib.cruse_conv_gather_bnbwd_in(*head, _p(w), _p(out), B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, 1 if accum else 0, conv_prec(prec),
-                                         _p(by), _p(mean), _p(rstd), _p(gamma), _p(beta), 1 if relu else 0, _p(sums), z,
-                                         _xdt(out, "conv_gather_bwd_in out"), _stream()))
-    return out, sums, dv
+    return _conv_bwd_in(False, dout, bn_in, w, B, T, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, out, accum, prec, bn_bwd, out_bf16)
 
 
 def conv_scatter2_bwd_in(dout, bn_in, w, B, T, Cs, Fg, Cout, KT, pad, out=None, accum=False, prec=None, bn_bwd=None, out_bf16=False):
     """As conv_gather_bwd_in for the stride-2 transposed form (cruse_conv_scatter2_bnbwd_in)."""
-    Fout = 2 * Fg
-    if out is None:
-        out = torch.empty(B, T, Cout, Fout, device=dout.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
-    dv, head = _bwd_in_args(dout, bn_in)
-    sums, z = (ARENA.take(2 * Cout * BN_STAT_REPLICAS, dout.device) if bn_bwd is not None else (None, 0))
-    by, mean, rstd, gamma, beta, relu = bn_bwd if bn_bwd is not None else (None, None, None, None, None, False)
-    check(lib.cruse_conv_scatter2_bnbwd_in(*head, _p(w), _p(out), B, T, Cs, Fg, Cout, Fout, KT, pad, 1 if accum else 0, conv_prec(prec),
-                                           _p(by), _p(mean), _p(rstd), _p(gamma), _p(beta), 1 if relu else 0, _p(sums), z,
-                                           _xdt(out, "conv_scatter2_bwd_in out"), _stream()))
-    return out, sums, dv
+    return _conv_bwd_in(True, dout, bn_in, w, B, T, Cs, Fg, Cout, 2 * Fg, KT, 2, pad, 0, out, accum, prec, bn_bwd, out_bf16)
 
 
 class BnIn:
@@ -229,41 +243,50 @@ def bnin_eligible(prec, Cin, Cout) -> bool:
             and (Cin & (Cin - 1)) == 0 and 8 <= Cout <= 64)
 
 
+def _conv_bnin(scatter, bn, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, prec, publish, copy_bf16, want_sums, out):
+    if out is None:
+        out = _conv_out(w, B, T, Cout, Fout)
+    sums, z = _bn_sums(Cout, w.device) if want_sums else _NO_SUMS
+    check(_CONV_FN[scatter][3](*bn.args(publish, copy_bf16), _p(w), _p(bias), _p(out), *_geom(scatter, B, T, Cin, Fin, Cout, Fout, KT, S, pad),
+                               conv_prec(prec), _p(sums), z, _stream()))
+    return (out, sums) if want_sums else out
+
+
 def conv_gather_bnin(bn: BnIn, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, prec, publish=False, copy_bf16=None, want_sums=False,
                      out=None):
     """conv_gather on relu(bn(y_pre)) [+ add] without materialising it -> y, or (y, sums) with want_sums."""
-    if out is None:
-        out = torch.empty(B, T, Cout, Fout, device=w.device, dtype=torch.float32)
-    sums, z = ARENA.take(2 * Cout * BN_STAT_REPLICAS, w.device) if want_sums else (None, 0)
-    check(lib.cruse_conv_gather_bnin(*bn.args(publish, copy_bf16), _p(w), _p(bias), _p(out), B, T, Cin, Fin, Cout, Fout, KT, S, pad,
-                                     conv_prec(prec), _p(sums), z, _stream()))
-    return (out, sums) if want_sums else out
+    return _conv_bnin(False, bn, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, prec, publish, copy_bf16, want_sums, out)
 
 
 def conv_scatter2_bnin(bn: BnIn, w, bias, B, T, Cs, Fg, Cout, KT, pad, prec, publish=False, copy_bf16=None, want_sums=False):
-    out = torch.empty(B, T, Cout, 2 * Fg, device=w.device, dtype=torch.float32)
-    sums, z = ARENA.take(2 * Cout * BN_STAT_REPLICAS, w.device) if want_sums else (None, 0)
-    check(lib.cruse_conv_scatter2_bnin(*bn.args(publish, copy_bf16), _p(w), _p(bias), _p(out), B, T, Cs, Fg, Cout, 2 * Fg, KT, pad,
-                                       conv_prec(prec), _p(sums), z, _stream()))
-    return (out, sums) if want_sums else out
+    return _conv_bnin(True, bn, w, bias, B, T, Cs, Fg, Cout, 2 * Fg, KT, 2, pad, prec, publish, copy_bf16, want_sums, None)
+
+
+def _conv_bnstats(scatter, x, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, prec):
+    out = _conv_out(x, B, T, Cout, Fout)
+    sums, z = _bn_sums(Cout, x.device)
+    check(_CONV_FN[scatter][4](_p(x), _p(w), _p(bias), _p(out), *_geom(scatter, B, T, Cin, Fin, Cout, Fout, KT, S, pad), conv_prec(prec),
+                               _p(sums), z, _stream()))
+    return out, sums
 
 
 def conv_gather_bnstats(x, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, prec=None):
     """conv_gather + the BatchNorm batch sums of its output, accumulated by the conv's epilogue -> (y, sums)."""
-    out = torch.empty(B, T, Cout, Fout, device=x.device, dtype=torch.float32)
-    sums, z = ARENA.take(2 * Cout * BN_STAT_REPLICAS, x.device)
-    check(lib.cruse_conv_gather_bnstats(_p(x), _p(w), _p(bias), _p(out), B, T, Cin, Fin, Cout, Fout, KT, S, pad,
-                                        conv_prec(prec), _p(sums), z, _stream()))
-    return out, sums
+    return _conv_bnstats(False, x, w, bias, B, T, Cin, Fin, Cout, Fout, KT, S, pad, prec)
 
 
 def conv_scatter2_bnstats(g, w, bias, B, T, Cs, Fg, Cout, KT, pad, prec=None):
-    Fout = 2 * Fg
-    out = torch.empty(B, T, Cout, Fout, device=g.device, dtype=torch.float32)
-    sums, z = ARENA.take(2 * Cout * BN_STAT_REPLICAS, g.device)
-    check(lib.cruse_conv_scatter2_bnstats(_p(g), _p(w), _p(bias), _p(out), B, T, Cs, Fg, Cout, Fout, KT, pad,
-                                          conv_prec(prec), _p(sums), z, _stream()))
-    return out, sums
+    return _conv_bnstats(True, g, w, bias, B, T, Cs, Fg, Cout, 2 * Fg, KT, 2, pad, prec)
+
+
+def conv_plan(scatter, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, B, T, prec, x_dtype=0, y_dtype=0, act=0, accum=0, forms=0) -> dict:
+    """what a frame-major convolution call launches (cruse_conv_plan; host-only): the route and its tile, grid and LDS bytes.  forms: bit set of
+    CONV_FORM_SUMS / _BNB / _BNI / _BBI; with _BBI `fused` tells the fused kernel from the two-call fallback and x_dtype is that of dout."""
+    out = (ctypes.c_int * 7)()
+    check(lib.cruse_conv_plan(1 if scatter else 0, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, B, T, conv_prec(prec), x_dtype, y_dtype, act,
+                              1 if accum else 0, forms, ctypes.cast(out, ctypes.c_void_p)))
+    return {"route": "mfma" if out[0] else "valu", "fused": bool(out[1]), "mt": out[2], "nw": out[3], "grid": out[4], "lds_bytes": out[5],
+            "co_t": out[6]}
 
 
 _wgrad_ws = {}

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CRUSE_ABI_VERSION 13
+#define CRUSE_ABI_VERSION 14
 
 enum {
     CRUSE_OK = 0,
@@ -197,6 +197,19 @@ int cruse_conv_scatter2_bnbwd_in(const void* dout, int dout_dtype, const float* 
  * boundaries; this copies the sums of the LAST such launch to out8 (host memory, 8 values: prologue, tile staging incl. the wait
  * for the prefetch, k-loops, epilogues, tiles, N-tiles of wave 0, total; cycles) -- tools/conv_probe.py */
 int cruse_conv_mfma_stamps(unsigned long long* out8);
+
+/* (ABI 14) Host-only, touches no device: what a frame-major convolution call of this shape, mode and forms launches -- the decision the ten
+ * entry points above make, without the launch.  scatter: 0 cruse_conv_gather*, 1 cruse_conv_scatter2* (then Cin = Cs, Fin = Fg, S = 2,
+ * w_layout = 0); forms: which of the fused forms the call carries -- SUMS (_bnstats, out_sums of _bnin), BNB (_bnbwd; implies SUMS), BNI (_bnin),
+ * BBI (_bnbwd_in; x_dtype is then dout_dtype).  Tensors are taken as 16-byte aligned.  out[7]:
+ *   [0] route: 0 VALU kernel, 1 MFMA kernel          [1] BBI: 1 the fused kernel takes the call, 0 the two-call fallback (out = its conv)
+ *   [2] mt (16-row tiles of Cout: 1, 2, 4)  [3] nw (waves per workgroup)      -- MFMA route, else 0
+ *   [4] grid (workgroups)                   [5] dynamic LDS bytes             -- of the route taken
+ *   [6] CO_T, the outputs per thread the VALU kernel is instantiated for (4 / 1 gather, 2 / 1 scatter2)   -- VALU route, else 0
+ * Returns what the entry point would: an error code and cruse_last_error() where the call is refused. */
+enum { CRUSE_CONV_FORM_SUMS = 1, CRUSE_CONV_FORM_BNB = 2, CRUSE_CONV_FORM_BNI = 4, CRUSE_CONV_FORM_BBI = 8 };
+int cruse_conv_plan(int scatter, int Cin, int Fin, int Cout, int Fout, int KT, int S, int pad, int w_layout,
+                    int B, int T, int prec, int x_dtype, int y_dtype, int act, int accum, int forms, int* out);
 
 /* weight gradient of either form:
  *   dw[ca][cb][kt][kf] += sum_{b,t,fa} a[b,t,ca,fa] * bt[b, t-(KT-1)+kt, cb, fa*S - pad + kf]
