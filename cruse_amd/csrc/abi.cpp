@@ -19,14 +19,16 @@ extern "C" const char* cruse_last_error(void) { return g_err; }
 extern "C" int cruse_abi_version(void) { return CRUSE_ABI_VERSION; }
 
 // ---- library options: explicit, set by the HOST through the C ABI (the library reads no environment variables) ---------
-// name -> value; unset options take the default the call site passes to cruse_opt().
+// name -> value; unset options take the default the call site passes to cruse_opt().  The names are those of CRUSE_OPTIONS (common.h).
 #include <atomic>
 #include <limits.h>
 #include <string.h>
+#include "common.h"
 namespace {
-const char* const OPT_NAMES[] = {"gru_bwd_rs", "gru_fwd_lean", "gru_tf", "gru_poll_fwd", "gru_poll_bwd", "gru_wlo", "gru_dbg", "cm_dbg", "cm_nw", "cm_grid", "cm_kint", "cm_swap",
-                                 "pw_valu", "wg_dbg", "wg_rd", "wg_grid"};
-constexpr int N_OPT = sizeof(OPT_NAMES) / sizeof(OPT_NAMES[0]);
+#define CRUSE_OPT_NAME(name) #name,
+const char* const OPT_NAMES[] = {CRUSE_OPTIONS(CRUSE_OPT_NAME)};
+#undef CRUSE_OPT_NAME
+constexpr int N_OPT = CRUSE_OPT_N;
 std::atomic<int> g_opt[N_OPT];
 struct OptInit { OptInit() { for (auto& o : g_opt) o.store(INT_MIN); } } g_opt_init;
 int opt_index(const char* name) {
@@ -35,10 +37,8 @@ int opt_index(const char* name) {
     return -1;
 }
 }  // namespace
-int cruse_opt(const char* name, int dflt) {
-    const int i = opt_index(name);
-    if (i < 0) return dflt;
-    const int v = g_opt[i].load(std::memory_order_relaxed);
+int cruse_opt(CruseOpt opt, int dflt) {
+    const int v = g_opt[opt].load(std::memory_order_relaxed);
     return v == INT_MIN ? dflt : v;
 }
 extern "C" int cruse_set_option(const char* name, int value, int unset) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 #include "../../include/cruse_hip.h"
 
 // the BatchNorm(+ReLU) whose input gradient a data-gradient convolution produces (cruse_conv_*_bnbwd): its pre-BN tensor and
@@ -37,6 +38,16 @@ enum { CRUSE_CP_ROUTE, CRUSE_CP_FUSED, CRUSE_CP_MT, CRUSE_CP_NW, CRUSE_CP_GRID, 
 // 1: the MFMA kernel took the call, 0: the shape / mode is not eligible (the caller goes on to the VALU kernel), < 0: error.
 // plan != null: nothing is launched, plan[CRUSE_CP_MT .. CRUSE_CP_LDS] receive what would have been (conv_mfma.hip)
 int cruse_conv_mfma_try(const CruseConvCall& c, int* plan);
+
+// what a general NCHW convolution / weight-gradient call would launch, as cruse_conv2d_nchw_plan reports it (generic.hip):
+// form id, two template integers, grid, block, dynamic LDS bytes, an auxiliary integer (conv: the epilogue instance of the LDS-transposed
+// pointwise kernel; wgrad: `run` of the pointwise MFMA kernel, `band` of the depthwise one), the requests the kernel serves in its
+// epilogue (CRUSE_NCHW_REQ_*) and the pass that is owed beside it
+enum { CRUSE_NP_FORM, CRUSE_NP_T0, CRUSE_NP_T1, CRUSE_NP_GX, CRUSE_NP_GY, CRUSE_NP_GZ, CRUSE_NP_BLOCK, CRUSE_NP_LDS, CRUSE_NP_AUX, CRUSE_NP_SERVED,
+       CRUSE_NP_PASS, CRUSE_NP_N };
+enum { CRUSE_NCF_PW_TR_F16, CRUSE_NCF_PW_MFMA_F16, CRUSE_NCF_PW, CRUSE_NCF_DW_LDS_F16, CRUSE_NCF_DW, CRUSE_NCF_GENERAL, CRUSE_NCF_N };     // conv forms
+enum { CRUSE_NWF_PW_MFMA_F16, CRUSE_NWF_DW_LDS_F16, CRUSE_NWF_DW, CRUSE_NWF_ROWS, CRUSE_NWF_WEIGHT, CRUSE_NWF_N };                         // wgrad forms
+enum { CRUSE_NPASS_NONE, CRUSE_NPASS_ADD, CRUSE_NPASS_STATS, CRUSE_NPASS_CHANNEL_SUM };      // cruse_add_nchw / cruse_bn_nchw_stats_ex after, cruse_nchw_channel_sum before
 
 extern "C" void cruse_set_error(const char* fmt, ...);
 
@@ -74,11 +85,25 @@ int cruse_ensure_dyn_lds(const void* fn, size_t bytes, const char* name);
 // inside a captured hipGraph, memset nodes were observed to race with the neighbouring kernel nodes).
 int cruse_zero_async(void* p, size_t bytes, hipStream_t stream, const char* name);
 
-// library option `name` (cruse_set_option), or dflt when the host has not set it; the library reads no environment variables
-int cruse_opt(const char* name, int dflt);
+// library options: this list is both enum CruseOpt (what the kernels' host code reads) and the names cruse_set_option / cruse_get_option accept
+#define CRUSE_OPTIONS(X) X(gru_bwd_rs) X(gru_fwd_lean) X(gru_tf) X(gru_poll_fwd) X(gru_poll_bwd) X(gru_wlo) X(gru_dbg) X(cm_dbg) X(cm_nw) X(cm_grid) \
+    X(cm_kint) X(cm_swap) X(pw_valu) X(dw_nolds) X(wg_dbg) X(wg_rd) X(wg_grid)
+#define CRUSE_OPT_ENUM(name) CRUSE_OPT_##name,
+enum CruseOpt { CRUSE_OPTIONS(CRUSE_OPT_ENUM) CRUSE_OPT_N };
+#undef CRUSE_OPT_ENUM
+// the value the host gave the option (cruse_set_option), or dflt when it has not set it; the library reads no environment variables
+int cruse_opt(CruseOpt opt, int dflt);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }
+
+// Run-time integer -> template parameter: f(std::integral_constant<int, V>{}) for the first V of the list equal to v, for the LAST one
+// if none is (the kernels' largest instance serves as the default).
+template <int V0, int... Vs, typename F>
+inline int dispatch_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<Vs...>(v, f);
+}
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;

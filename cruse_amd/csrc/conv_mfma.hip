@@ -1100,9 +1100,9 @@ static bool cm_plan(const CruseConvCall& c, CMPlan& p) {
         a.in_mean_o = bni->mean_o; a.in_rstd_o = bni->rstd_o; a.in_rmean = bni->rmean; a.in_rvar = bni->rvar;
         a.in_add = bni->add; a.in_copy = bni->copy_bf16;
     }
-    a.tdbg = cruse_opt("cm_dbg", 0);
-    a.kint = cruse_opt("cm_kint", 1);
-    a.swp_ok = cruse_opt("cm_swap", 1);                  // (A/B switch: 0 = channels in rows for every form)
+    a.tdbg = cruse_opt(CRUSE_OPT_cm_dbg, 0);
+    a.kint = cruse_opt(CRUSE_OPT_cm_kint, 1);
+    a.swp_ok = cruse_opt(CRUSE_OPT_cm_swap, 1);                  // (A/B switch: 0 = channels in rows for every form)
     if (bnb != nullptr) {
         a.bn_y = bnb->y; a.bn_mean = bnb->mean; a.bn_rstd = bnb->rstd; a.bn_gamma = bnb->gamma; a.bn_beta = bnb->beta;
         a.bn_relu = bnb->relu;
@@ -1155,11 +1155,11 @@ static bool cm_plan(const CruseConvCall& c, CMPlan& p) {
     // small weight images: more, lighter workgroups hide latency better (44 vs 60 us on the 8->16 layer);
     // large ones (up to 48 KB of fragments per workgroup) amortise their prologue over more tiles
     int gmax = wbytes <= 16 * 1024 ? 1024 : 512;
-    gmax = cruse_opt("cm_grid", gmax);
+    gmax = cruse_opt(CRUSE_OPT_cm_grid, gmax);
     p.grid = ntiles < gmax ? ntiles : gmax;
     const int ntile_wg = a.nclass * (TFM * (Fout / a.OS) / 16);       // N-tiles of one workgroup tile
     p.nw = (ntile_wg == 5 || (ntile_wg == 10 && (Cin >= 64 || Cout >= 64))) ? 5 : 4;
-    { const int e = cruse_opt("cm_nw", 0); if (e == 4 || e == 5) p.nw = e; }       // profiling option
+    { const int e = cruse_opt(CRUSE_OPT_cm_nw, 0); if (e == 4 || e == 5) p.nw = e; }       // profiling option
     if (prec == CRUSE_PREC_F32) p.nw = 4;
     // the fused input BatchNorm backward holds 48 more prefetch registers per thread: the 5-wave (128-register) and 64-row variants spill
     // (decoder level 4: 223 us against 38 + 49 for the two separate kernels) -- those shapes keep the separate pass

@@ -1396,201 +1396,270 @@ inline int gblocks(long long n, int per = 1024, int cap = 8192) {
 #define CRUSE_DT_CHECK(name) CRUSE_REQUIRE(dtype == CRUSE_DT_F32 || dtype == CRUSE_DT_F16, CRUSE_E_DTYPE, name ": unknown storage dtype %d", dtype)
 
 namespace {
-template <typename T>
-int conv2d_nchw_t(const void* x, const float* w, const float* bias, void* y, int B, int Cin, int Hin, int Win, int Cout, int Hout,
-                  int Wout, int KH, int KW, int sh, int sw, int dh, int dw, int pt, int pl, int groups, int up_w, int transposed,
-                  int act, const float* slope, int accumulate, hipStream_t s, double* bn_sums = nullptr, int bn_nrep = 1,
-                  bool* bn_done = nullptr, const void* res = nullptr, bool* res_done = nullptr, const GConv<T>* bb = nullptr, bool* bb_done = nullptr) {
-    GConv<T> a = {(const T*)x, w, bias, (T*)y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w,
-                  transposed, act, accumulate, slope, nullptr, 1, nullptr};
-    if (bn_done) *bn_done = false;
-    if (res_done) *res_done = false;
-    if (bb_done) *bb_done = false;
-    auto set_bb = [&]() {
-        if (bb == nullptr) return;
-        a.bb_x = bb->bb_x; a.bb_mean = bb->bb_mean; a.bb_rstd = bb->bb_rstd; a.bb_gamma = bb->bb_gamma; a.bb_beta = bb->bb_beta; a.bb_slope = bb->bb_slope;
-        a.bb_act = bb->bb_act; a.bb_r = bb->bb_r; a.bb_nrep = bb->bb_nrep;
-        *bb_done = true;
+
+// pointwise MFMA weight gradient: positions per 16-wave block (a multiple of 1024), blocks below which that halves, run_dbg's debug bits
+constexpr int WGPW_RUN = 4096, WGPW_BLOCKS = 256, WGPW_DBG = 0;
+
+// f(T{}) with T the storage type `dtype` names (the caller has checked dtype)
+template <typename F> inline int dispatch_dtype(int dtype, F&& f) { return dtype == CRUSE_DT_F16 ? f(f16{}) : f(float{}); }
+
+// grid of the per-channel reductions: channel x up to `cap` images x chunks of a plane
+inline dim3 plane_grid(int C, int N, int cap, int HW) { const int gy = N < cap ? N : cap; return dim3(C, gy, zchunks(C, gy, HW)); }
+
+// the BatchNorm (+ act) in front of a data-gradient convolution (cruse_conv2d_nchw_bnbwd): GConv's bb_* fields
+struct NchwBnBwd { const void* x; const float* mean; const float* rstd; const float* gamma; const float* beta; const float* slope; int act; double* r; int nrep; };
+
+// one NCHW convolution call, whichever of cruse_conv2d_nchw / _ex / _bnbwd it came through; `entry` names it in error messages.  What all
+// three have comes first, in the order of their signatures (brace-initialised); what only some have -- the activation, accumulation and the
+// three optional requests bn_sums (+ bn_nrep), residual, bb -- is set by name and neutral otherwise
+struct NchwConvCall {
+    const char* entry;
+    const void* x; const float* w; const float* bias; void* y;
+    int B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w, transposed;
+    int dtype; hipStream_t stream;
+    int act = 0; const float* slope = nullptr; int accumulate = 0;
+    double* bn_sums = nullptr; int bn_nrep = 1; const void* residual = nullptr; const NchwBnBwd* bb = nullptr;
+};
+// one weight-gradient call (cruse_conv2d_nchw_wgrad / _wgrad_ex); db is set by name
+struct NchwWgradCall {
+    const char* entry;
+    const void* S; const void* Bg; float* dw;
+    int N, CA, HS, WS, CB, HB, WB, KH, KW, sh, sw, dh, dw_, pt, pl, groups, up_w;
+    int dtype; hipStream_t stream;
+    float* db = nullptr;
+};
+// what a call launches: the figures cruse_conv2d_nchw_plan reports (CRUSE_NP_*) and the kernel arguments of the depthwise forms
+struct NchwPlan { int v[CRUSE_NP_N]; TapTab tt; DwGeom g; };
+
+inline void plan_set(NchwPlan& p, int form, int t0, int t1, dim3 grid, int block, size_t lds, int aux, int served, int pass) {
+    const int v[CRUSE_NP_N] = {form, t0, t1, (int)grid.x, (int)grid.y, (int)grid.z, block, (int)lds, aux, served, pass};
+    for (int i = 0; i < CRUSE_NP_N; ++i) p.v[i] = v[i];
+}
+
+inline TapTab tap_table(int KH, int KW, int dh, int dw, int pt, int pl, int transposed) {
+    TapTab tt = {};
+    tt.n = KH * KW;
+    for (int kh = 0; kh < KH; ++kh)
+        for (int kw = 0; kw < KW; ++kw) {
+            tt.dh[kh * KW + kw] = transposed ? pt - kh * dh : kh * dh - pt;
+            tt.dw[kh * KW + kw] = transposed ? pl - kw * dw : kw * dw - pl;
+        }
+    return tt;
+}
+
+template <typename K, typename... A>
+int plan_launch(K kernel, const NchwPlan& p, hipStream_t s, const char* big_lds, const char* what, const A&... args) {      // big_lds: the kernel may ask for > 48 KB
+    const size_t lds = (size_t)p.v[CRUSE_NP_LDS];
+    const int rc = big_lds ? cruse_ensure_dyn_lds((const void*)kernel, lds, big_lds) : CRUSE_OK;
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3(p.v[CRUSE_NP_GX], p.v[CRUSE_NP_GY], p.v[CRUSE_NP_GZ]), dim3(p.v[CRUSE_NP_BLOCK]), lds, s, args...);
+    CRUSE_LAUNCH_CHECK(what);
+    return CRUSE_OK;
+}
+
+int nchw_conv_check(const NchwConvCall& c) {
+    CRUSE_REQUIRE(c.B > 0 && c.Cin > 0 && c.Cout > 0 && c.Hin > 0 && c.Win > 0 && c.Hout > 0 && c.Wout > 0, CRUSE_E_SHAPE,
+                  "%s: bad shape B=%d Cin=%d Cout=%d in %dx%d out %dx%d", c.entry, c.B, c.Cin, c.Cout, c.Hin, c.Win, c.Hout, c.Wout);
+    CRUSE_REQUIRE(c.KH > 0 && c.KW > 0 && c.sh > 0 && c.sw > 0 && c.dh > 0 && c.dw > 0 && c.groups > 0 && c.up_w > 0, CRUSE_E_SHAPE, "%s: bad kernel geometry", c.entry);
+    CRUSE_REQUIRE(c.Cin % c.groups == 0 && c.Cout % c.groups == 0, CRUSE_E_SHAPE, "%s: channels %d/%d not divisible by groups %d", c.entry, c.Cin, c.Cout, c.groups);
+    CRUSE_REQUIRE(!(c.transposed && c.up_w != 1), CRUSE_E_SHAPE, "%s: upsampling only with the conv form", c.entry);
+    CRUSE_REQUIRE(c.act >= 0 && c.act <= 2 && (c.act != 2 || c.slope) && !(c.accumulate && c.act), CRUSE_E_SHAPE, "%s: bad activation", c.entry);
+    CRUSE_REQUIRE((c.bn_sums == nullptr || c.bn_nrep >= 1) && !(c.bn_sums && c.residual), CRUSE_E_SHAPE, "%s: arguments (statistics of a sum are not offered)", c.entry);
+    CRUSE_REQUIRE(c.bb == nullptr || (c.bb->x && c.bb->mean && c.bb->rstd && c.bb->gamma && c.bb->beta && c.bb->act >= 0 && c.bb->act <= 3 &&
+                                      (c.bb->act != 2 || c.bb->slope) && c.bb->r && c.bb->nrep >= 1),
+                  CRUSE_E_SHAPE, "%s: BatchNorm arguments", c.entry);
+    CRUSE_REQUIRE(c.dtype == CRUSE_DT_F32 || c.dtype == CRUSE_DT_F16, CRUSE_E_DTYPE, "%s: unknown storage dtype %d", c.entry, c.dtype);
+    return CRUSE_OK;
+}
+
+// which kernel takes a (checked) call, its launch figures, the requests it serves in its epilogue and the pass owed for the others
+void nchw_conv_plan(const NchwConvCall& c, NchwPlan& p) {
+    const bool f16s = c.dtype == CRUSE_DT_F16;
+    const int pw_valu = cruse_opt(CRUSE_OPT_pw_valu, 0);                           // (1: VALU kernels only, 2: the gather pointwise kernel)
+    const int want = (c.bn_sums ? CRUSE_NCHW_REQ_BN_SUMS : 0) | (c.residual ? CRUSE_NCHW_REQ_RESIDUAL : 0) | (c.bb ? CRUSE_NCHW_REQ_BNBWD : 0);
+    auto set = [&](int form, int t0, int t1, dim3 grid, size_t lds, int aux, int served) {
+        const int owed = want & ~served;
+        plan_set(p, form, t0, t1, grid, 256, lds, aux, served,
+                 (owed & CRUSE_NCHW_REQ_RESIDUAL) ? CRUSE_NPASS_ADD : (owed & CRUSE_NCHW_REQ_BN_SUMS) ? CRUSE_NPASS_STATS : CRUSE_NPASS_NONE);
     };
-    const bool pointwise = KH == 1 && KW == 1 && sh == 1 && sw == 1 && pt == 0 && pl == 0 && groups == 1 && up_w == 1 &&
-                           Hout == Hin && Wout == Win;
-    if constexpr (sizeof(T) == 2) {
-        // f16 storage: the pointwise convolutions run on the matrix cores (weights resident as A fragments)
-        const int MT = cdiv(Cout, 16), KS = cdiv(Cin, 32);
-        if (pointwise && MT <= 2 && KS <= 2 && !accumulate && !cruse_opt("pw_valu", 0)) {        // (pw_valu = 2: the gather kernel below)
-            // operand transposed through LDS (gconv_pointwise_tr_f16_kernel): 16-byte accesses on both sides
-            const long long nchunk = (long long)B * cdivl((long long)Hin * Win, 64);
-            const int cap = 768;                                                             // (blocks; measured 256 .. 2048 at the config-5 shape: 26.9 / 19.0 / 17.9 / 19.2 / 21.3 / 23.3 us)
-            const int nb = (int)(cdivl(nchunk, 4) > cap ? cap : cdivl(nchunk, 4));
-            const int mtc = MT <= 1 ? 1 : 2, ksc = KS <= 1 ? 1 : 2;
-            const size_t lds = (size_t)4 * (ksc * 32 + mtc * 16) * 144;
-            if (bn_sums) { a.bn_sums = bn_sums; a.bn_nrep = bn_nrep; *bn_done = true; }
-            if (res) { a.res = (const T*)res; *res_done = true; }
-            set_bb();
-            const int epi = a.bb_r ? 2 : (a.bn_sums ? 1 : 0);                                // (never both: the sums of the output / of the BatchNorm in front of a data gradient)
-#define PWT_LAUNCH(mt, ks, ep) do { int rc = cruse_ensure_dyn_lds((const void*)gconv_pointwise_tr_f16_kernel<mt, ks, ep>, lds, "conv2d_nchw pointwise"); \
-                if (rc) return rc; \
-                hipLaunchKernelGGL((gconv_pointwise_tr_f16_kernel<mt, ks, ep>), dim3(nb), dim3(256), lds, s, a); } while (0)
-#define PWT_CASE(mt, ks) do { if (epi == 0) PWT_LAUNCH(mt, ks, 0); else if (epi == 1) PWT_LAUNCH(mt, ks, 1); else PWT_LAUNCH(mt, ks, 2); } while (0)
-            if (mtc == 1 && ksc == 1) PWT_CASE(1, 1); else if (mtc == 1) PWT_CASE(1, 2); else if (ksc == 1) PWT_CASE(2, 1); else PWT_CASE(2, 2);
-#undef PWT_CASE
-#undef PWT_LAUNCH
-            CRUSE_LAUNCH_CHECK("conv2d_nchw pointwise mfma f16 (LDS-transposed)");
-            return CRUSE_OK;
-        }
-        if (pointwise && MT <= 4 && KS <= 4 && cruse_opt("pw_valu", 0) != 1) {
-            const long long ntile = (long long)B * cdivl((long long)Hin * Win, 16);
-            const int nb = (int)(cdivl(ntile, 16) > 8192 ? 8192 : cdivl(ntile, 16));
-#define PW_CASE(mt, ks) hipLaunchKernelGGL((gconv_pointwise_mfma_f16_kernel<mt, ks>), dim3(nb), dim3(256), 0, s, a)
-            const int mtc = MT <= 1 ? 1 : MT <= 2 ? 2 : 4, ksc = KS <= 1 ? 1 : KS <= 2 ? 2 : 4;
-            if (mtc == 1 && ksc == 1) PW_CASE(1, 1); else if (mtc == 1 && ksc == 2) PW_CASE(1, 2); else if (mtc == 1) PW_CASE(1, 4);
-            else if (mtc == 2 && ksc == 1) PW_CASE(2, 1); else if (mtc == 2 && ksc == 2) PW_CASE(2, 2); else if (mtc == 2) PW_CASE(2, 4);
-            else if (ksc == 1) PW_CASE(4, 1); else if (ksc == 2) PW_CASE(4, 2); else PW_CASE(4, 4);
-#undef PW_CASE
-            CRUSE_LAUNCH_CHECK("conv2d_nchw pointwise mfma f16");
-            return CRUSE_OK;
-        }
+    const bool pointwise = c.KH == 1 && c.KW == 1 && c.sh == 1 && c.sw == 1 && c.pt == 0 && c.pl == 0 && c.groups == 1 && c.up_w == 1 &&
+                           c.Hout == c.Hin && c.Wout == c.Win;
+    // f16 storage: the pointwise convolutions run on the matrix cores (weights resident as A fragments)
+    const int MT = cdiv(c.Cout, 16), KS = cdiv(c.Cin, 32);
+    if (f16s && pointwise && MT <= 2 && KS <= 2 && !c.accumulate && !pw_valu) {
+        // operand transposed through LDS (gconv_pointwise_tr_f16_kernel): 16-byte accesses on both sides
+        const long long nchunk = (long long)c.B * cdivl((long long)c.Hin * c.Win, 64);
+        const int cap = 768;                                                             // (blocks; measured 256 .. 2048 at the config-5 shape: 26.9 / 19.0 / 17.9 / 19.2 / 21.3 / 23.3 us)
+        const int nb = (int)(cdivl(nchunk, 4) > cap ? cap : cdivl(nchunk, 4));
+        const int mtc = MT <= 1 ? 1 : 2, ksc = KS <= 1 ? 1 : 2;
+        const int epi = c.bb ? 2 : (c.bn_sums ? 1 : 0);                                  // (never both: the sums of the output / of the BatchNorm in front of a data gradient)
+        return set(CRUSE_NCF_PW_TR_F16, mtc, ksc, dim3(nb), (size_t)4 * (ksc * 32 + mtc * 16) * 144, epi, want);
     }
-    if (pointwise && Cout <= 64 && Cin <= 256) {
-        const size_t lds = (size_t)Cout * Cin * sizeof(float);
-        const int nb = gblocks((long long)B * Hin * Win, 256, 8192);
-        if (Cout <= 16) hipLaunchKernelGGL((gconv_pointwise_kernel<T, 16>), dim3(nb), dim3(256), lds, s, a);
-        else if (Cout <= 32) hipLaunchKernelGGL((gconv_pointwise_kernel<T, 32>), dim3(nb), dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((gconv_pointwise_kernel<T, 64>), dim3(nb), dim3(256), lds, s, a);
-        CRUSE_LAUNCH_CHECK("conv2d_nchw pointwise");
-        return CRUSE_OK;
+    if (f16s && pointwise && MT <= 4 && KS <= 4 && pw_valu != 1) {
+        const long long ntile = (long long)c.B * cdivl((long long)c.Hin * c.Win, 16);
+        const int nb = (int)(cdivl(ntile, 16) > 8192 ? 8192 : cdivl(ntile, 16));
+        return set(CRUSE_NCF_PW_MFMA_F16, MT <= 1 ? 1 : MT <= 2 ? 2 : 4, KS <= 1 ? 1 : KS <= 2 ? 2 : 4, dim3(nb), 0, 0, 0);
     }
-    if (groups == Cin && Cin == Cout && up_w == 1 && sh == 1 && sw == 1 && KH * KW <= 9 && (long long)B * Cout < 65536 &&
-        (long long)Hin * Win < (1ll << 30) && (long long)Hout * Wout < (1ll << 30) && cruse_opt("pw_valu", 0) != 1) {
-        TapTab tt = {};
-        tt.n = KH * KW;
-        for (int kh = 0; kh < KH; ++kh)
-            for (int kw = 0; kw < KW; ++kw) {
-                tt.dh[kh * KW + kw] = transposed ? pt - kh * dh : kh * dh - pt;
-                tt.dw[kh * KW + kw] = transposed ? pl - kw * dw : kw * dw - pl;
-            }
-        if constexpr (sizeof(T) == 2) {
-            DwGeom g;
-            size_t lds;
-            if (!cruse_opt("dw_nolds", 0) && dw_geometry(tt, Hout, Win, Wout, B * Cout, &g, &lds)) {
-                int rc = cruse_ensure_dyn_lds((const void*)gconv_depthwise_f16_kernel, lds, "conv2d_nchw depthwise");
-                if (rc) return rc;
-                if (bn_sums) { a.bn_sums = bn_sums; a.bn_nrep = bn_nrep; *bn_done = true; }
-                set_bb();
-                hipLaunchKernelGGL(gconv_depthwise_f16_kernel, dim3(cdiv(Hout, g.RB), B * Cout), dim3(256), lds, s, a, tt, g);
-                CRUSE_LAUNCH_CHECK("conv2d_nchw depthwise (f16, LDS image)");
-                return CRUSE_OK;
-            }
-        }
-        hipLaunchKernelGGL(gconv_depthwise_kernel<T>, dim3(cdiv(Hout * Wout, 8 * 256), B * Cout), dim3(256), 0, s, a, tt);
-        CRUSE_LAUNCH_CHECK("conv2d_nchw depthwise");
-        return CRUSE_OK;
+    if (pointwise && c.Cout <= 64 && c.Cin <= 256)
+        return set(CRUSE_NCF_PW, c.Cout <= 16 ? 16 : c.Cout <= 32 ? 32 : 64, 0, dim3(gblocks((long long)c.B * c.Hin * c.Win, 256, 8192)),
+                   (size_t)c.Cout * c.Cin * sizeof(float), 0, 0);
+    if (c.groups == c.Cin && c.Cin == c.Cout && c.up_w == 1 && c.sh == 1 && c.sw == 1 && c.KH * c.KW <= 9 && (long long)c.B * c.Cout < 65536 &&
+        (long long)c.Hin * c.Win < (1ll << 30) && (long long)c.Hout * c.Wout < (1ll << 30) && pw_valu != 1) {
+        p.tt = tap_table(c.KH, c.KW, c.dh, c.dw, c.pt, c.pl, c.transposed);
+        size_t lds;
+        if (f16s && !cruse_opt(CRUSE_OPT_dw_nolds, 0) && dw_geometry(p.tt, c.Hout, c.Win, c.Wout, c.B * c.Cout, &p.g, &lds))
+            return set(CRUSE_NCF_DW_LDS_F16, 0, 0, dim3(cdiv(c.Hout, p.g.RB), c.B * c.Cout), lds, 0, want & (CRUSE_NCHW_REQ_BN_SUMS | CRUSE_NCHW_REQ_BNBWD));
+        return set(CRUSE_NCF_DW, 0, 0, dim3(cdiv(c.Hout * c.Wout, 8 * 256), c.B * c.Cout), 0, 0, 0);
     }
-    hipLaunchKernelGGL(gconv_kernel<T>, dim3(gblocks((long long)B * Cout * Hout * Wout, 256, 16384)), dim3(256), 0, s, a);
-    CRUSE_LAUNCH_CHECK("conv2d_nchw");
-    return CRUSE_OK;
+    set(CRUSE_NCF_GENERAL, 0, 0, dim3(gblocks((long long)c.B * c.Cout * c.Hout * c.Wout, 256, 16384)), 0, 0, 0);
 }
 
 template <typename T>
-int wgrad_nchw_t(const void* S, const void* Bg, float* dw, int N, int CA, int HS, int WS, int CB, int HB, int WB, int KH, int KW,
-                 int sh, int sw, int dh, int dw_, int pt, int pl, int groups, int up_w, hipStream_t s, float* db = nullptr) {
-    GWgrad<T> a = {(const T*)S, (const T*)Bg, dw, N, CA, HS, WS, CB, HB, WB, KH, KW, sh, sw, dh, dw_, pt, pl, groups, up_w, nullptr};
-    const bool fast = cruse_opt("pw_valu", 0) != 1;
-    // db: only the pointwise MFMA kernel delivers it (a spare column of its last column tile carries the constant 1); every other form
-    // runs the channel-sum pass first
-    const bool pw_db = db != nullptr && sizeof(T) == 2 && fast && KH == 1 && KW == 1 && groups == 1 && sh == 1 && sw == 1 && pt == 0 && pl == 0 &&
-                       up_w == 1 && HS == HB && WS == WB && CA <= 32 && CB < 32 && CB % 16 != 0;
-    if (db != nullptr && !pw_db) {
-        const int rc = cruse_nchw_channel_sum(S, N, CA, HS * WS, db, sizeof(T) == 2 ? CRUSE_DT_F16 : CRUSE_DT_F32, s);
-        if (rc) return rc;
+int nchw_conv_launch(const NchwConvCall& c, const NchwPlan& p) {
+    GConv<T> a = {(const T*)c.x, c.w, c.bias, (T*)c.y, c.B, c.Cin, c.Hin, c.Win, c.Cout, c.Hout, c.Wout, c.KH, c.KW, c.sh, c.sw, c.dh, c.dw, c.pt, c.pl,
+                  c.groups, c.up_w, c.transposed, c.act, c.accumulate, c.slope, nullptr, 1, nullptr};
+    const int served = p.v[CRUSE_NP_SERVED], form = p.v[CRUSE_NP_FORM], t0 = p.v[CRUSE_NP_T0], t1 = p.v[CRUSE_NP_T1];
+    if (served & CRUSE_NCHW_REQ_BN_SUMS) { a.bn_sums = c.bn_sums; a.bn_nrep = c.bn_nrep; }
+    if (served & CRUSE_NCHW_REQ_RESIDUAL) a.res = (const T*)c.residual;
+    if (served & CRUSE_NCHW_REQ_BNBWD) {
+        const NchwBnBwd& b = *c.bb;
+        a.bb_x = (const T*)b.x; a.bb_mean = b.mean; a.bb_rstd = b.rstd; a.bb_gamma = b.gamma; a.bb_beta = b.beta; a.bb_slope = b.slope;
+        a.bb_act = b.act; a.bb_r = b.r; a.bb_nrep = b.nrep;
     }
-    a.db = pw_db ? db : nullptr;
+    const hipStream_t s = c.stream;
     if constexpr (sizeof(T) == 2) {
-        if (fast && KH == 1 && KW == 1 && groups == 1 && sh == 1 && sw == 1 && pt == 0 && pl == 0 && up_w == 1 && HS == HB && WS == WB &&
-            CA <= 32 && CB <= 32) {
-            const long long hw = (long long)HS * WS;
-            int run = cruse_opt("wgpw_run", 4096);              // positions per 16-wave block (a multiple of 1024)
-            { const long long want = cruse_opt("wgpw_blocks", 256); while ((long long)N * cdivl(hw, run) < want && run > 1024) run >>= 1; }
-            const dim3 grid((unsigned)((long long)N * cdivl(hw, run)));
-            run |= cruse_opt("wgpw_dbg", 0) << 24;
-            const int mt = cdiv(CA, 16), ntl = cdiv(CB, 16);
-#define WGPW_CASE(m_, n_) do { const size_t lds = (size_t)16 * m_ * n_ * 256 * sizeof(float); \
-                int rc = cruse_ensure_dyn_lds((const void*)gconv_wgrad_pw_mfma_f16_kernel<m_, n_>, lds, "conv2d_nchw_wgrad pointwise"); \
-                if (rc) return rc; \
-                hipLaunchKernelGGL((gconv_wgrad_pw_mfma_f16_kernel<m_, n_>), grid, dim3(1024), lds, s, a, run); } while (0)
-            if (mt == 1 && ntl == 1) WGPW_CASE(1, 1);
-            else if (mt == 1) WGPW_CASE(1, 2);
-            else if (ntl == 1) WGPW_CASE(2, 1);
-            else WGPW_CASE(2, 2);
-#undef WGPW_CASE
-            CRUSE_LAUNCH_CHECK("conv2d_nchw_wgrad pointwise mfma f16");
-            return CRUSE_OK;
-        }
+        if (form == CRUSE_NCF_PW_TR_F16)
+            return dispatch_int<1, 2>(t0, [&](auto mt) { return dispatch_int<1, 2>(t1, [&](auto ks) { return dispatch_int<0, 1, 2>(p.v[CRUSE_NP_AUX], [&](auto ep) {
+                return plan_launch(gconv_pointwise_tr_f16_kernel<decltype(mt)::value, decltype(ks)::value, decltype(ep)::value>, p, s,
+                                   "conv2d_nchw pointwise", "conv2d_nchw pointwise mfma f16 (LDS-transposed)", a); }); }); });
+        if (form == CRUSE_NCF_PW_MFMA_F16)
+            return dispatch_int<1, 2, 4>(t0, [&](auto mt) { return dispatch_int<1, 2, 4>(t1, [&](auto ks) {
+                return plan_launch(gconv_pointwise_mfma_f16_kernel<decltype(mt)::value, decltype(ks)::value>, p, s, nullptr, "conv2d_nchw pointwise mfma f16", a); }); });
+        if (form == CRUSE_NCF_DW_LDS_F16) return plan_launch(gconv_depthwise_f16_kernel, p, s, "conv2d_nchw depthwise", "conv2d_nchw depthwise (f16, LDS image)", a, p.tt, p.g);
     }
-    if (fast && groups == CA && CA == CB && up_w == 1 && KH * KW <= 9 && (long long)N * CA < 65536 && (long long)HB * WB < (1ll << 30) &&
-        (long long)HS * WS < (1ll << 30)) {
-        int band = 16;                                   // S positions per thread
-        while ((long long)N * CA * cdiv(HS * WS, band * 256) < 2048 && band > 4) band >>= 1;
-        TapTab tt = {};
-        tt.n = KH * KW;
-        for (int kh = 0; kh < KH; ++kh)
-            for (int kw = 0; kw < KW; ++kw) { tt.dh[kh * KW + kw] = kh * dh - pt; tt.dw[kh * KW + kw] = kw * dw_ - pl; }
-        if constexpr (sizeof(T) == 2) {
-            DwGeom g;
-            size_t lds;
-            if (sh == 1 && sw == 1 && !cruse_opt("dw_nolds", 0) && dw_geometry(tt, HS, WB, WS, N * CA, &g, &lds)) {
-                int rc = cruse_ensure_dyn_lds((const void*)gconv_wgrad_depthwise_f16_kernel, lds, "conv2d_nchw_wgrad depthwise");
-                if (rc) return rc;
-                hipLaunchKernelGGL(gconv_wgrad_depthwise_f16_kernel, dim3(cdiv(HS, g.RB), N * CA), dim3(256), lds, s, a, tt, g);
-                CRUSE_LAUNCH_CHECK("conv2d_nchw_wgrad depthwise (f16, LDS image)");
-                return CRUSE_OK;
-            }
-        }
-        hipLaunchKernelGGL(gconv_wgrad_depthwise_kernel<T>, dim3(cdiv(HS * WS, band * 256), N * CA), dim3(256), 0, s, a, band, tt);
-        CRUSE_LAUNCH_CHECK("conv2d_nchw_wgrad depthwise");
-        return CRUSE_OK;
-    }
-    const size_t row_lds = ((size_t)CA * WS + (size_t)CB * WB) * sizeof(float);
-    if (row_lds <= 150 * 1024 && (long long)N * HS >= 8) {        // a row pair fits LDS (the per-weight kernel below is the fallback)
-        int rc = cruse_ensure_dyn_lds((const void*)gconv_wgrad_rows_kernel<T>, row_lds, "conv2d_nchw_wgrad");
-        if (rc) return rc;
-        hipLaunchKernelGGL(gconv_wgrad_rows_kernel<T>, dim3(N * HS), dim3(256), row_lds, s, a);
-        CRUSE_LAUNCH_CHECK("conv2d_nchw_wgrad rows");
-        return CRUSE_OK;
-    }
-    const int nw = CA * (CB / groups) * KH * KW;
-    int ny = 1;
-    while (ny < N && (long long)nw * ny < 2048) ny *= 2;
-    if (ny > N) ny = N;
-    hipLaunchKernelGGL(gconv_wgrad_kernel<T>, dim3(nw, ny), dim3(256), 0, s, a);
-    CRUSE_LAUNCH_CHECK("conv2d_nchw_wgrad");
+    if (form == CRUSE_NCF_PW)
+        return dispatch_int<16, 32, 64>(t0, [&](auto co) { return plan_launch(gconv_pointwise_kernel<T, decltype(co)::value>, p, s, nullptr, "conv2d_nchw pointwise", a); });
+    if (form == CRUSE_NCF_DW) return plan_launch(gconv_depthwise_kernel<T>, p, s, nullptr, "conv2d_nchw depthwise", a, p.tt);
+    return plan_launch(gconv_kernel<T>, p, s, nullptr, "conv2d_nchw", a);
+}
+
+// check, plan, and -- unless the caller wants the plan alone -- launch the kernel and the pass owed after it
+int nchw_conv_run(const NchwConvCall& c, NchwPlan& p, bool launch = true) {
+    int rc = nchw_conv_check(c);
+    if (rc) return rc;
+    nchw_conv_plan(c, p);
+    if (!launch) return CRUSE_OK;
+    rc = dispatch_dtype(c.dtype, [&](auto t) { return nchw_conv_launch<decltype(t)>(c, p); });
+    if (rc) return rc;
+    if (p.v[CRUSE_NP_PASS] == CRUSE_NPASS_ADD) return cruse_add_nchw(c.y, c.residual, c.y, (long long)c.B * c.Cout * c.Hout * c.Wout, c.dtype, c.stream);
+    if (p.v[CRUSE_NP_PASS] == CRUSE_NPASS_STATS) return cruse_bn_nchw_stats_ex(c.y, c.B, c.Cout, c.Hout * c.Wout, c.bn_sums, 1, c.dtype, c.stream);
     return CRUSE_OK;
 }
 
-}  // namespace
-extern "C" int cruse_nchw_channel_sum(const void* x, int N, int C, int HW, float* out, int dtype, void* stream);
-namespace {
+int nchw_wgrad_check(const NchwWgradCall& c) {
+    CRUSE_REQUIRE(c.N > 0 && c.CA > 0 && c.CB > 0 && c.HS > 0 && c.WS > 0 && c.HB > 0 && c.WB > 0 && c.KH > 0 && c.KW > 0, CRUSE_E_SHAPE, "%s: bad shape", c.entry);
+    CRUSE_REQUIRE(c.groups > 0 && c.sh > 0 && c.sw > 0 && c.dh > 0 && c.dw_ > 0, CRUSE_E_SHAPE, "%s: bad kernel geometry", c.entry);
+    CRUSE_REQUIRE(c.CA % c.groups == 0 && c.CB % c.groups == 0 && c.up_w > 0, CRUSE_E_SHAPE, "%s: groups", c.entry);
+    CRUSE_REQUIRE(c.dtype == CRUSE_DT_F32 || c.dtype == CRUSE_DT_F16, CRUSE_E_DTYPE, "%s: unknown storage dtype %d", c.entry, c.dtype);
+    return CRUSE_OK;
+}
+
+void nchw_wgrad_plan(const NchwWgradCall& c, NchwPlan& p) {
+    const bool f16s = c.dtype == CRUSE_DT_F16, fast = cruse_opt(CRUSE_OPT_pw_valu, 0) != 1;
+    const int want = c.db ? CRUSE_NCHW_REQ_DB : 0;
+    // db: only the pointwise MFMA kernel delivers it (a spare column of its last column tile carries the constant 1); else the channel-sum pass
+    auto set = [&](int form, int t0, int t1, dim3 grid, int block, size_t lds, int aux, int served) {
+        plan_set(p, form, t0, t1, grid, block, lds, aux, served, (want & ~served) ? CRUSE_NPASS_CHANNEL_SUM : CRUSE_NPASS_NONE);
+    };
+    if (f16s && fast && c.KH == 1 && c.KW == 1 && c.groups == 1 && c.sh == 1 && c.sw == 1 && c.pt == 0 && c.pl == 0 && c.up_w == 1 && c.HS == c.HB &&
+        c.WS == c.WB && c.CA <= 32 && c.CB <= 32) {
+        const long long hw = (long long)c.HS * c.WS;
+        int run = WGPW_RUN;
+        while ((long long)c.N * cdivl(hw, run) < WGPW_BLOCKS && run > 1024) run >>= 1;
+        const int mt = c.CA <= 16 ? 1 : 2, nt = c.CB <= 16 ? 1 : 2;
+        return set(CRUSE_NWF_PW_MFMA_F16, mt, nt, dim3((unsigned)((long long)c.N * cdivl(hw, run))), 1024, (size_t)16 * mt * nt * 256 * sizeof(float), run,
+                   c.CB < 32 && c.CB % 16 != 0 ? want : 0);
+    }
+    if (fast && c.groups == c.CA && c.CA == c.CB && c.up_w == 1 && c.KH * c.KW <= 9 && (long long)c.N * c.CA < 65536 &&
+        (long long)c.HB * c.WB < (1ll << 30) && (long long)c.HS * c.WS < (1ll << 30)) {
+        int band = 16;                                   // S positions per thread
+        while ((long long)c.N * c.CA * cdiv(c.HS * c.WS, band * 256) < 2048 && band > 4) band >>= 1;
+        p.tt = tap_table(c.KH, c.KW, c.dh, c.dw_, c.pt, c.pl, 0);
+        size_t lds;
+        if (f16s && c.sh == 1 && c.sw == 1 && !cruse_opt(CRUSE_OPT_dw_nolds, 0) && dw_geometry(p.tt, c.HS, c.WB, c.WS, c.N * c.CA, &p.g, &lds))
+            return set(CRUSE_NWF_DW_LDS_F16, 0, 0, dim3(cdiv(c.HS, p.g.RB), c.N * c.CA), 256, lds, 0, 0);
+        return set(CRUSE_NWF_DW, 0, 0, dim3(cdiv(c.HS * c.WS, band * 256), c.N * c.CA), 256, 0, band, 0);
+    }
+    const size_t row_lds = ((size_t)c.CA * c.WS + (size_t)c.CB * c.WB) * sizeof(float);
+    if (row_lds <= 150 * 1024 && (long long)c.N * c.HS >= 8)        // a row pair fits LDS (the per-weight kernel below is the fallback)
+        return set(CRUSE_NWF_ROWS, 0, 0, dim3(c.N * c.HS), 256, row_lds, 0, 0);
+    const int nw = c.CA * (c.CB / c.groups) * c.KH * c.KW;
+    int ny = 1;
+    while (ny < c.N && (long long)nw * ny < 2048) ny *= 2;
+    if (ny > c.N) ny = c.N;
+    set(CRUSE_NWF_WEIGHT, 0, 0, dim3(nw, ny), 256, 0, 0, 0);
+}
+
+template <typename T>
+int nchw_wgrad_launch(const NchwWgradCall& c, const NchwPlan& p) {
+    const GWgrad<T> a = {(const T*)c.S, (const T*)c.Bg, c.dw, c.N, c.CA, c.HS, c.WS, c.CB, c.HB, c.WB, c.KH, c.KW, c.sh, c.sw, c.dh, c.dw_, c.pt, c.pl,
+                         c.groups, c.up_w, (p.v[CRUSE_NP_SERVED] & CRUSE_NCHW_REQ_DB) ? c.db : nullptr};
+    const int form = p.v[CRUSE_NP_FORM], aux = p.v[CRUSE_NP_AUX];
+    const hipStream_t s = c.stream;
+    if constexpr (sizeof(T) == 2) {
+        if (form == CRUSE_NWF_PW_MFMA_F16)
+            return dispatch_int<1, 2>(p.v[CRUSE_NP_T0], [&](auto mt) { return dispatch_int<1, 2>(p.v[CRUSE_NP_T1], [&](auto nt) {
+                return plan_launch(gconv_wgrad_pw_mfma_f16_kernel<decltype(mt)::value, decltype(nt)::value>, p, s, "conv2d_nchw_wgrad pointwise", "conv2d_nchw_wgrad pointwise mfma f16", a,
+                                   aux | (WGPW_DBG << 24)); }); });
+        if (form == CRUSE_NWF_DW_LDS_F16) return plan_launch(gconv_wgrad_depthwise_f16_kernel, p, s, "conv2d_nchw_wgrad depthwise", "conv2d_nchw_wgrad depthwise (f16, LDS image)", a, p.tt, p.g);
+    }
+    if (form == CRUSE_NWF_DW) return plan_launch(gconv_wgrad_depthwise_kernel<T>, p, s, nullptr, "conv2d_nchw_wgrad depthwise", a, aux, p.tt);
+    if (form == CRUSE_NWF_ROWS) return plan_launch(gconv_wgrad_rows_kernel<T>, p, s, "conv2d_nchw_wgrad", "conv2d_nchw_wgrad rows", a);
+    return plan_launch(gconv_wgrad_kernel<T>, p, s, nullptr, "conv2d_nchw_wgrad", a);
+}
+
+int nchw_wgrad_run(const NchwWgradCall& c, NchwPlan& p, bool launch = true) {
+    int rc = nchw_wgrad_check(c);
+    if (rc) return rc;
+    nchw_wgrad_plan(c, p);
+    if (!launch) return CRUSE_OK;
+    if (p.v[CRUSE_NP_PASS] == CRUSE_NPASS_CHANNEL_SUM && (rc = cruse_nchw_channel_sum(c.S, c.N, c.CA, c.HS * c.WS, c.db, c.dtype, c.stream))) return rc;
+    return dispatch_dtype(c.dtype, [&](auto t) { return nchw_wgrad_launch<decltype(t)>(c, p); });
+}
+
+int bn_nchw_stats_run(const char* entry, const void* x, int N, int C, int HW, double* sums, int zeroed, int dtype, hipStream_t s) {
+    CRUSE_REQUIRE(N > 0 && C > 0 && HW > 0, CRUSE_E_SHAPE, "%s: bad shape", entry);
+    CRUSE_REQUIRE(dtype == CRUSE_DT_F32 || dtype == CRUSE_DT_F16, CRUSE_E_DTYPE, "%s: unknown storage dtype %d", entry, dtype);
+    if (!zeroed) { int rc = cruse_zero_async(sums, 2 * (size_t)C * sizeof(double), s, entry); if (rc) return rc; }
+    if (dtype == CRUSE_DT_F16)
+        hipLaunchKernelGGL(bn_nchw_stats_f16v_kernel, plane_grid(C, N, 32, HW), dim3(256), 0, s, (const f16*)x, N, C, HW, sums);
+    else
+        hipLaunchKernelGGL(bn_nchw_stats_kernel<float>, plane_grid(C, N, 32, HW), dim3(256), 0, s, (const float*)x, N, C, HW, sums);
+    CRUSE_LAUNCH_CHECK(entry);
+    return CRUSE_OK;
+}
+
+// the kernels of a (checked) BatchNorm backward; r_nrep > 0: scratch holds that many replicas of the sums already (no reduce pass)
 template <typename T>
 int bn_nchw_bwd_t(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                   const float* slope, int act, int training, int N, int C, int HW, double* scratch, void* dx, float* dgamma,
-                  float* dbeta, float* dslope, hipStream_t s, float* dx_sum = nullptr, int reduce_done = 0, int r_nrep = 1) {
+                  float* dbeta, float* dslope, hipStream_t s, float* dx_sum, int r_nrep) {
     const long long total = (long long)N * C * HW;
     if constexpr (sizeof(T) == 2) {
         if ((long long)N * C < 65536) {                      // (grid.y = planes)
-            if (!reduce_done) {
-                hipLaunchKernelGGL(bn_nchw_bwd_reduce_f16v_kernel, dim3(C, N < 32 ? N : 32, zchunks(C, N < 32 ? N : 32, HW)), dim3(256), 0, s, (const f16*)dy,
+            if (!r_nrep) {
+                hipLaunchKernelGGL(bn_nchw_bwd_reduce_f16v_kernel, plane_grid(C, N, 32, HW), dim3(256), 0, s, (const f16*)dy,
                                    (const f16*)x, mean, rstd, gamma, beta, slope, act, N, C, HW, scratch, dx_sum != nullptr ? 1 : 0);
                 CRUSE_LAUNCH_CHECK("bn_nchw_bwd_reduce");
             }
             hipLaunchKernelGGL(bn_nchw_bwd_apply_f16v_kernel, dim3(cdiv(cdiv(HW, 8), 256), N * C), dim3(256), 0, s, (const f16*)dy, (const f16*)x, mean, rstd,
-                               gamma, beta, slope, act, scratch, reduce_done ? r_nrep : 1, 1.0 / ((double)N * HW), training, C, HW, (f16*)dx, dx_sum, 1,
+                               gamma, beta, slope, act, scratch, r_nrep ? r_nrep : 1, 1.0 / ((double)N * HW), training, C, HW, (f16*)dx, dx_sum, 1,
                                mean ? dgamma : nullptr, mean ? dbeta : nullptr, act == 2 ? dslope : nullptr);
             CRUSE_LAUNCH_CHECK("bn_nchw_bwd_apply");
             return CRUSE_OK;
         }
     }
-    if (reduce_done) { cruse_set_error("bn_nchw_bwd_ex: sums delivered by a convolution come with the f16 kernels only"); return CRUSE_E_SHAPE; }
-    hipLaunchKernelGGL(bn_nchw_bwd_reduce_kernel<T>, dim3(C, N < 32 ? N : 32, zchunks(C, N < 32 ? N : 32, HW)), dim3(256), 0, s, (const T*)dy, (const T*)x, mean, rstd,
+    hipLaunchKernelGGL(bn_nchw_bwd_reduce_kernel<T>, plane_grid(C, N, 32, HW), dim3(256), 0, s, (const T*)dy, (const T*)x, mean, rstd,
                        gamma, beta, slope, act, N, C, HW, scratch);
     CRUSE_LAUNCH_CHECK("bn_nchw_bwd_reduce");
     hipLaunchKernelGGL(bn_nchw_bwd_apply_kernel<T>, dim3(gblocks(total)), dim3(256), 0, s, (const T*)dy, (const T*)x, mean, rstd, gamma,
@@ -1602,6 +1671,20 @@ int bn_nchw_bwd_t(const void* dy, const void* x, const float* mean, const float*
     if (dx_sum != nullptr) return cruse_nchw_channel_sum(dx, N, C, HW, dx_sum, sizeof(T) == 2 ? CRUSE_DT_F16 : CRUSE_DT_F32, s);
     return CRUSE_OK;
 }
+
+// cruse_bn_nchw_bwd (scratch_width = 3 sums per channel, no dx_sum, no delivered sums) and cruse_bn_nchw_bwd_ex (4)
+int bn_nchw_bwd_run(const char* entry, const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                    const float* slope, int act, int training, int N, int C, int HW, double* scratch, int scratch_width, int scratch_zeroed,
+                    int sums_replicas, void* dx, float* dgamma, float* dbeta, float* dslope, float* dx_sum, int dtype, hipStream_t s) {
+    CRUSE_REQUIRE(N > 0 && C > 0 && HW > 0 && act >= 0 && act <= 3 && (act != 2 || slope) && sums_replicas >= 0, CRUSE_E_SHAPE, "%s: bad arguments", entry);
+    CRUSE_REQUIRE(dtype == CRUSE_DT_F32 || dtype == CRUSE_DT_F16, CRUSE_E_DTYPE, "%s: unknown storage dtype %d", entry, dtype);
+    if (sums_replicas > 0)         // scratch = [sums_replicas][4][C], ALREADY FILLED by cruse_conv2d_nchw_bnbwd: the reduce pass is skipped
+        CRUSE_REQUIRE(dtype == CRUSE_DT_F16 && (long long)N * C < 65536, CRUSE_E_SHAPE, "%s: delivered sums come with the f16 kernels", entry);
+    else if (!scratch_zeroed) { int rc = cruse_zero_async(scratch, scratch_width * (size_t)C * sizeof(double), s, entry); if (rc) return rc; }
+    return dispatch_dtype(dtype, [&](auto t) { return bn_nchw_bwd_t<decltype(t)>(dy, x, mean, rstd, gamma, beta, slope, act, training, N, C, HW, scratch, dx, dgamma,
+                                                                                 dbeta, dslope, s, dx_sum, sums_replicas); });
+}
+
 }  // namespace
 
 extern "C" int cruse_conv2d_nchw(const void* x, const float* w, const float* bias, void* y,
@@ -1609,24 +1692,11 @@ extern "C" int cruse_conv2d_nchw(const void* x, const float* w, const float* bia
                                  int KH, int KW, int sh, int sw, int dh, int dw, int pt, int pl,
                                  int groups, int up_w, int transposed, int act, const float* slope, int accumulate,
                                  int dtype, void* stream) {
-    CRUSE_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0, CRUSE_E_SHAPE,
-                  "conv2d_nchw: bad shape B=%d Cin=%d Cout=%d in %dx%d out %dx%d", B, Cin, Cout, Hin, Win, Hout, Wout);
-    CRUSE_REQUIRE(KH > 0 && KW > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0 && groups > 0 && up_w > 0, CRUSE_E_SHAPE,
-                  "conv2d_nchw: bad kernel geometry");
-    CRUSE_REQUIRE(Cin % groups == 0 && Cout % groups == 0, CRUSE_E_SHAPE, "conv2d_nchw: channels %d/%d not divisible by groups %d", Cin, Cout, groups);
-    CRUSE_REQUIRE(!(transposed && up_w != 1), CRUSE_E_SHAPE, "conv2d_nchw: upsampling only with the conv form");
-    CRUSE_REQUIRE(act >= 0 && act <= 2 && (act != 2 || slope) && !(accumulate && act), CRUSE_E_SHAPE, "conv2d_nchw: bad activation");
-    CRUSE_DT_CHECK("conv2d_nchw");
-    if (dtype == CRUSE_DT_F16)
-        return conv2d_nchw_t<f16>(x, w, bias, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w,
-                                  transposed, act, slope, accumulate, ST(stream));
-    return conv2d_nchw_t<float>(x, w, bias, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w,
-                                transposed, act, slope, accumulate, ST(stream));
+    NchwConvCall c = {"conv2d_nchw", x, w, bias, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w, transposed, dtype, ST(stream)};
+    c.act = act; c.slope = slope; c.accumulate = accumulate;
+    NchwPlan p;
+    return nchw_conv_run(c, p);
 }
-
-extern "C" int cruse_bn_nchw_stats_ex(const void* x, int N, int C, int HW, double* sums, int zeroed, int dtype, void* stream);
-
-extern "C" int cruse_add_nchw(const void* a, const void* b, void* out, long long n, int dtype, void* stream);
 
 // cruse_conv2d_nchw (no bias, no activation, no accumulation) whose output y is the GRADIENT wrt the output of a BatchNorm2d (+ act) with input
 // bn_x (the data gradient of the convolution that consumed that BatchNorm's output): the f16 pointwise / depthwise kernels also accumulate that
@@ -1637,25 +1707,15 @@ extern "C" int cruse_conv2d_nchw_bnbwd(const void* x, const float* w, void* y,
                                        int KH, int KW, int sh, int sw, int dh, int dw, int pt, int pl, int groups, int transposed,
                                        const void* bn_x, const float* bn_mean, const float* bn_rstd, const float* bn_gamma, const float* bn_beta,
                                        const float* bn_slope, int bn_act, double* r, int r_nrep, int* delivered, int dtype, void* stream) {
-    CRUSE_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0, CRUSE_E_SHAPE, "conv2d_nchw_bnbwd: bad shape");
-    CRUSE_REQUIRE(KH > 0 && KW > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0 && groups > 0 && Cin % groups == 0 && Cout % groups == 0, CRUSE_E_SHAPE,
-                  "conv2d_nchw_bnbwd: bad kernel geometry");
-    CRUSE_REQUIRE(bn_x && bn_mean && bn_rstd && bn_gamma && bn_beta && bn_act >= 0 && bn_act <= 3 && (bn_act != 2 || bn_slope) && r && r_nrep >= 1 && delivered,
-                  CRUSE_E_SHAPE, "conv2d_nchw_bnbwd: BatchNorm arguments");
-    CRUSE_DT_CHECK("conv2d_nchw_bnbwd");
-    bool done = false;
-    int rc;
-    if (dtype == CRUSE_DT_F16) {
-        GConv<f16> bb = {};
-        bb.bb_x = (const f16*)bn_x; bb.bb_mean = bn_mean; bb.bb_rstd = bn_rstd; bb.bb_gamma = bn_gamma; bb.bb_beta = bn_beta; bb.bb_slope = bn_slope;
-        bb.bb_act = bn_act; bb.bb_r = r; bb.bb_nrep = r_nrep;
-        rc = conv2d_nchw_t<f16>(x, w, nullptr, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, 1, transposed, 0, nullptr,
-                                0, ST(stream), nullptr, 1, nullptr, nullptr, nullptr, &bb, &done);
-    } else {
-        rc = conv2d_nchw_t<float>(x, w, nullptr, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, 1, transposed, 0, nullptr,
-                                  0, ST(stream));
-    }
-    *delivered = done ? 1 : 0;
+    CRUSE_REQUIRE(delivered, CRUSE_E_SHAPE, "conv2d_nchw_bnbwd: BatchNorm arguments");
+    const NchwBnBwd bb = {bn_x, bn_mean, bn_rstd, bn_gamma, bn_beta, bn_slope, bn_act, r, r_nrep};
+    NchwConvCall c = {"conv2d_nchw_bnbwd", x, w, /* bias */ nullptr, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, /* up_w */ 1,
+                      transposed, dtype, ST(stream)};
+    c.bb = &bb;
+    NchwPlan p;
+    p.v[CRUSE_NP_FORM] = -1;
+    const int rc = nchw_conv_run(c, p);
+    if (p.v[CRUSE_NP_FORM] >= 0) *delivered = (p.v[CRUSE_NP_SERVED] & CRUSE_NCHW_REQ_BNBWD) ? 1 : 0;       // (past validation, whatever the launch answered)
     return rc;
 }
 
@@ -1670,38 +1730,19 @@ extern "C" int cruse_conv2d_nchw_ex(const void* x, const float* w, const float* 
                                     int KH, int KW, int sh, int sw, int dh, int dw, int pt, int pl,
                                     int groups, int up_w, int transposed, int act, const float* slope,
                                     double* bn_sums, int bn_nrep, int dtype, void* stream) {
-    CRUSE_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0, CRUSE_E_SHAPE, "conv2d_nchw_ex: bad shape");
-    CRUSE_REQUIRE(KH > 0 && KW > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0 && groups > 0 && up_w > 0, CRUSE_E_SHAPE,
-                  "conv2d_nchw_ex: bad kernel geometry");
-    CRUSE_REQUIRE(Cin % groups == 0 && Cout % groups == 0 && !(transposed && up_w != 1), CRUSE_E_SHAPE, "conv2d_nchw_ex: groups / form");
-    CRUSE_REQUIRE(act >= 0 && act <= 2 && (act != 2 || slope) && (bn_sums == nullptr || bn_nrep >= 1) && !(bn_sums && residual), CRUSE_E_SHAPE,
-                  "conv2d_nchw_ex: arguments (statistics of a sum are not offered)");
-    CRUSE_DT_CHECK("conv2d_nchw_ex");
-    bool done = false, rdone = false;
-    int rc;
-    if (dtype == CRUSE_DT_F16)
-        rc = conv2d_nchw_t<f16>(x, w, bias, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w, transposed, act, slope,
-                                0, ST(stream), bn_sums, bn_nrep, &done, residual, &rdone);
-    else
-        rc = conv2d_nchw_t<float>(x, w, bias, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w, transposed, act, slope,
-                                  0, ST(stream), bn_sums, bn_nrep, &done, residual, &rdone);
-    if (rc) return rc;
-    if (residual && !rdone) return cruse_add_nchw(y, residual, y, (long long)B * Cout * Hout * Wout, dtype, stream);
-    if (bn_sums && !done) return cruse_bn_nchw_stats_ex(y, B, Cout, Hout * Wout, bn_sums, 1, dtype, stream);
-    return CRUSE_OK;
+    NchwConvCall c = {"conv2d_nchw_ex", x, w, bias, y, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w, transposed, dtype, ST(stream)};
+    c.act = act; c.slope = slope; c.bn_sums = bn_sums; c.bn_nrep = bn_nrep; c.residual = residual;
+    NchwPlan p;
+    return nchw_conv_run(c, p);
 }
 
 extern "C" int cruse_conv2d_nchw_wgrad(const void* S, const void* Bg, float* dw,
                                        int N, int CA, int HS, int WS, int CB, int HB, int WB,
                                        int KH, int KW, int sh, int sw, int dh, int dw_, int pt, int pl,
                                        int groups, int up_w, int dtype, void* stream) {
-    CRUSE_REQUIRE(N > 0 && CA > 0 && CB > 0 && HS > 0 && WS > 0 && HB > 0 && WB > 0 && KH > 0 && KW > 0, CRUSE_E_SHAPE,
-                  "conv2d_nchw_wgrad: bad shape");
-    CRUSE_REQUIRE(CA % groups == 0 && CB % groups == 0 && up_w > 0, CRUSE_E_SHAPE, "conv2d_nchw_wgrad: groups");
-    CRUSE_DT_CHECK("conv2d_nchw_wgrad");
-    if (dtype == CRUSE_DT_F16)
-        return wgrad_nchw_t<f16>(S, Bg, dw, N, CA, HS, WS, CB, HB, WB, KH, KW, sh, sw, dh, dw_, pt, pl, groups, up_w, ST(stream));
-    return wgrad_nchw_t<float>(S, Bg, dw, N, CA, HS, WS, CB, HB, WB, KH, KW, sh, sw, dh, dw_, pt, pl, groups, up_w, ST(stream));
+    const NchwWgradCall c = {"conv2d_nchw_wgrad", S, Bg, dw, N, CA, HS, WS, CB, HB, WB, KH, KW, sh, sw, dh, dw_, pt, pl, groups, up_w, dtype, ST(stream)};
+    NchwPlan p;
+    return nchw_wgrad_run(c, p);
 }
 
 // cruse_conv2d_nchw_wgrad of a Conv2d (S = dy) that also accumulates the bias gradient db[ca] += sum_{n,h,w} dy[n,ca,h,w] -- inside the
@@ -1710,22 +1751,52 @@ extern "C" int cruse_conv2d_nchw_wgrad_ex(const void* S, const void* Bg, float* 
                                           int N, int CA, int HS, int WS, int CB, int HB, int WB,
                                           int KH, int KW, int sh, int sw, int dh, int dw_, int pt, int pl,
                                           int groups, int up_w, int dtype, void* stream) {
-    CRUSE_REQUIRE(N > 0 && CA > 0 && CB > 0 && HS > 0 && WS > 0 && HB > 0 && WB > 0 && KH > 0 && KW > 0, CRUSE_E_SHAPE,
-                  "conv2d_nchw_wgrad_ex: bad shape");
-    CRUSE_REQUIRE(CA % groups == 0 && CB % groups == 0 && up_w > 0, CRUSE_E_SHAPE, "conv2d_nchw_wgrad_ex: groups");
-    CRUSE_DT_CHECK("conv2d_nchw_wgrad_ex");
-    if (dtype == CRUSE_DT_F16)
-        return wgrad_nchw_t<f16>(S, Bg, dw, N, CA, HS, WS, CB, HB, WB, KH, KW, sh, sw, dh, dw_, pt, pl, groups, up_w, ST(stream), db);
-    return wgrad_nchw_t<float>(S, Bg, dw, N, CA, HS, WS, CB, HB, WB, KH, KW, sh, sw, dh, dw_, pt, pl, groups, up_w, ST(stream), db);
+    NchwWgradCall c = {"conv2d_nchw_wgrad_ex", S, Bg, dw, N, CA, HS, WS, CB, HB, WB, KH, KW, sh, sw, dh, dw_, pt, pl, groups, up_w, dtype, ST(stream)};
+    c.db = db;
+    NchwPlan p;
+    return nchw_wgrad_run(c, p);
+}
+
+// what the conv (wgrad = 0) or weight-gradient (wgrad = 1) entry points launch for a call: see include/cruse_hip.h
+extern "C" int cruse_conv2d_nchw_plan(int wgrad, int B, int Cin, int Hin, int Win, int Cout, int Hout, int Wout,
+                                      int KH, int KW, int sh, int sw, int dh, int dw, int pt, int pl,
+                                      int groups, int up_w, int transposed, int act, int accumulate, int dtype, int requests, int* out) {
+    static double stand_in[2];              // a tensor is only ever asked "null or not" on the host
+    void* const P = stand_in;
+    const bool ex = requests & (CRUSE_NCHW_REQ_BN_SUMS | CRUSE_NCHW_REQ_RESIDUAL), bnbwd = requests & CRUSE_NCHW_REQ_BNBWD;
+    CRUSE_REQUIRE(out != nullptr && requests >= 0 && requests < (wgrad ? 2 : 8) && !(ex && bnbwd), CRUSE_E_SHAPE,
+                  "conv2d_nchw_plan: out is NULL or requests = %d name no entry point", requests);
+    CRUSE_REQUIRE(wgrad ? !transposed && !act && !accumulate : !(ex && accumulate) && !(bnbwd && (up_w != 1 || act || accumulate)), CRUSE_E_SHAPE,
+                  "conv2d_nchw_plan: the entry point these requests name has no such argument");
+    NchwPlan p;
+    int rc;
+    if (wgrad) {
+        NchwWgradCall c = {requests ? "conv2d_nchw_wgrad_ex" : "conv2d_nchw_wgrad", P, P, (float*)P, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw,
+                           pt, pl, groups, up_w, dtype, /* stream */ nullptr};
+        if (requests) c.db = (float*)P;
+        rc = nchw_wgrad_run(c, p, false);
+    } else {
+        const NchwBnBwd bb = {P, (float*)P, (float*)P, (float*)P, (float*)P, nullptr, 0, (double*)P, 1};
+        NchwConvCall c = {bnbwd ? "conv2d_nchw_bnbwd" : ex ? "conv2d_nchw_ex" : "conv2d_nchw", P, (float*)P, /* bias */ nullptr, P, B, Cin, Hin, Win, Cout, Hout, Wout,
+                          KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w, transposed, dtype, /* stream */ nullptr};
+        c.act = act; c.slope = act == 2 ? (float*)P : nullptr; c.accumulate = accumulate;
+        if (requests & CRUSE_NCHW_REQ_BN_SUMS) c.bn_sums = (double*)P;
+        if (requests & CRUSE_NCHW_REQ_RESIDUAL) c.residual = P;
+        if (bnbwd) c.bb = &bb;
+        rc = nchw_conv_run(c, p, false);
+    }
+    if (rc) return rc;
+    for (int i = 0; i < CRUSE_NP_N; ++i) out[i] = p.v[i];
+    return CRUSE_OK;
 }
 
 extern "C" int cruse_nchw_channel_sum(const void* x, int N, int C, int HW, float* out, int dtype, void* stream) {
     CRUSE_REQUIRE(N > 0 && C > 0 && HW > 0, CRUSE_E_SHAPE, "nchw_channel_sum: bad shape");
     CRUSE_DT_CHECK("nchw_channel_sum");
     if (dtype == CRUSE_DT_F16)
-        hipLaunchKernelGGL(nchw_channel_sum_f16v_kernel, dim3(C, N < 16 ? N : 16, zchunks(C, N < 16 ? N : 16, HW)), dim3(256), 0, ST(stream), (const f16*)x, N, C, HW, out);
+        hipLaunchKernelGGL(nchw_channel_sum_f16v_kernel, plane_grid(C, N, 16, HW), dim3(256), 0, ST(stream), (const f16*)x, N, C, HW, out);
     else
-        hipLaunchKernelGGL(nchw_channel_sum_kernel<float>, dim3(C, N < 16 ? N : 16, zchunks(C, N < 16 ? N : 16, HW)), dim3(256), 0, ST(stream), (const float*)x, N, C, HW, out);
+        hipLaunchKernelGGL(nchw_channel_sum_kernel<float>, plane_grid(C, N, 16, HW), dim3(256), 0, ST(stream), (const float*)x, N, C, HW, out);
     CRUSE_LAUNCH_CHECK("nchw_channel_sum");
     return CRUSE_OK;
 }
@@ -1738,10 +1809,8 @@ extern "C" int cruse_downsum_w(const void* dxu, long long rows, int W, int up, v
         CRUSE_LAUNCH_CHECK("downsum_w");
         return CRUSE_OK;
     }
-    if (dtype == CRUSE_DT_F16)
-        hipLaunchKernelGGL(downsum_w_kernel<f16>, dim3(gblocks(rows * W)), dim3(256), 0, ST(stream), (const f16*)dxu, rows, W, up, (f16*)dx);
-    else
-        hipLaunchKernelGGL(downsum_w_kernel<float>, dim3(gblocks(rows * W)), dim3(256), 0, ST(stream), (const float*)dxu, rows, W, up, (float*)dx);
+    dispatch_dtype(dtype, [&](auto t) { typedef decltype(t) T;
+        hipLaunchKernelGGL(downsum_w_kernel<T>, dim3(gblocks(rows * W)), dim3(256), 0, ST(stream), (const T*)dxu, rows, W, up, (T*)dx); return 0; });
     CRUSE_LAUNCH_CHECK("downsum_w");
     return CRUSE_OK;
 }
@@ -1751,37 +1820,19 @@ extern "C" int cruse_upsample_w(const void* x, long long rows, int W, int up, vo
     CRUSE_DT_CHECK("upsample_w");
     if (dtype == CRUSE_DT_F32 && up == 2 && ((rows * W) & 1) == 0 && (((uintptr_t)x | (uintptr_t)xu) & 15) == 0)
         hipLaunchKernelGGL(upsample_w2_f32_kernel, dim3(gblocks(rows * W / 2)), dim3(256), 0, ST(stream), (const float2*)x, rows * W / 2, (float4*)xu);
-    else if (dtype == CRUSE_DT_F16)
-        hipLaunchKernelGGL(upsample_w_kernel<f16>, dim3(gblocks(rows * W)), dim3(256), 0, ST(stream), (const f16*)x, rows, W, up, (f16*)xu);
-    else
-        hipLaunchKernelGGL(upsample_w_kernel<float>, dim3(gblocks(rows * W)), dim3(256), 0, ST(stream), (const float*)x, rows, W, up, (float*)xu);
+    else dispatch_dtype(dtype, [&](auto t) { typedef decltype(t) T;
+        hipLaunchKernelGGL(upsample_w_kernel<T>, dim3(gblocks(rows * W)), dim3(256), 0, ST(stream), (const T*)x, rows, W, up, (T*)xu); return 0; });
     CRUSE_LAUNCH_CHECK("upsample_w");
     return CRUSE_OK;
 }
 
 extern "C" int cruse_bn_nchw_stats(const void* x, int N, int C, int HW, double* sums, int dtype, void* stream) {
-    CRUSE_REQUIRE(N > 0 && C > 0 && HW > 0, CRUSE_E_SHAPE, "bn_nchw_stats: bad shape");
-    CRUSE_DT_CHECK("bn_nchw_stats");
-    { int rc = cruse_zero_async(sums, 2 * (size_t)C * sizeof(double), ST(stream), "bn_nchw_stats"); if (rc) return rc; }
-    if (dtype == CRUSE_DT_F16)
-        hipLaunchKernelGGL(bn_nchw_stats_f16v_kernel, dim3(C, N < 32 ? N : 32, zchunks(C, N < 32 ? N : 32, HW)), dim3(256), 0, ST(stream), (const f16*)x, N, C, HW, sums);
-    else
-        hipLaunchKernelGGL(bn_nchw_stats_kernel<float>, dim3(C, N < 32 ? N : 32, zchunks(C, N < 32 ? N : 32, HW)), dim3(256), 0, ST(stream), (const float*)x, N, C, HW, sums);
-    CRUSE_LAUNCH_CHECK("bn_nchw_stats");
-    return CRUSE_OK;
+    return bn_nchw_stats_run("bn_nchw_stats", x, N, C, HW, sums, 0, dtype, ST(stream));
 }
 
 // cruse_bn_nchw_stats into sums the caller has already cleared (zeroed != 0: no fill launch in front of the pass)
 extern "C" int cruse_bn_nchw_stats_ex(const void* x, int N, int C, int HW, double* sums, int zeroed, int dtype, void* stream) {
-    CRUSE_REQUIRE(N > 0 && C > 0 && HW > 0, CRUSE_E_SHAPE, "bn_nchw_stats_ex: bad shape");
-    CRUSE_DT_CHECK("bn_nchw_stats_ex");
-    if (!zeroed) { int rc = cruse_zero_async(sums, 2 * (size_t)C * sizeof(double), ST(stream), "bn_nchw_stats_ex"); if (rc) return rc; }
-    if (dtype == CRUSE_DT_F16)
-        hipLaunchKernelGGL(bn_nchw_stats_f16v_kernel, dim3(C, N < 32 ? N : 32, zchunks(C, N < 32 ? N : 32, HW)), dim3(256), 0, ST(stream), (const f16*)x, N, C, HW, sums);
-    else
-        hipLaunchKernelGGL(bn_nchw_stats_kernel<float>, dim3(C, N < 32 ? N : 32, zchunks(C, N < 32 ? N : 32, HW)), dim3(256), 0, ST(stream), (const float*)x, N, C, HW, sums);
-    CRUSE_LAUNCH_CHECK("bn_nchw_stats_ex");
-    return CRUSE_OK;
+    return bn_nchw_stats_run("bn_nchw_stats_ex", x, N, C, HW, sums, zeroed, dtype, ST(stream));
 }
 
 extern "C" int cruse_bn_nchw_fwd(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
@@ -1793,12 +1844,9 @@ extern "C" int cruse_bn_nchw_fwd(const void* x, const float* mean, const float* 
     if (dtype == CRUSE_DT_F16 && (long long)N * C < 65536)
         hipLaunchKernelGGL(bn_nchw_fwd_f16v_kernel, dim3(cdiv(cdiv(HW, 8), 256), N * C), dim3(256), 0, ST(stream), (const f16*)x, mean, rstd, gamma, beta,
                            slope, act, C, HW, (f16*)y);
-    else if (dtype == CRUSE_DT_F16)
-        hipLaunchKernelGGL(bn_nchw_fwd_kernel<f16>, dim3(gblocks(total)), dim3(256), 0, ST(stream), (const f16*)x, mean, rstd, gamma, beta,
-                           slope, act, total, C, HW, (f16*)y);
-    else
-        hipLaunchKernelGGL(bn_nchw_fwd_kernel<float>, dim3(gblocks(total)), dim3(256), 0, ST(stream), (const float*)x, mean, rstd, gamma,
-                           beta, slope, act, total, C, HW, (float*)y);
+    else dispatch_dtype(dtype, [&](auto t) { typedef decltype(t) T;
+        hipLaunchKernelGGL(bn_nchw_fwd_kernel<T>, dim3(gblocks(total)), dim3(256), 0, ST(stream), (const T*)x, mean, rstd, gamma, beta, slope, act, total, C,
+                           HW, (T*)y); return 0; });
     CRUSE_LAUNCH_CHECK("bn_nchw_fwd");
     return CRUSE_OK;
 }
@@ -1806,12 +1854,8 @@ extern "C" int cruse_bn_nchw_fwd(const void* x, const float* mean, const float* 
 extern "C" int cruse_bn_nchw_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                                  const float* beta, const float* slope, int act, int training, int N, int C, int HW,
                                  double* scratch, void* dx, float* dgamma, float* dbeta, float* dslope, int dtype, void* stream) {
-    CRUSE_REQUIRE(N > 0 && C > 0 && HW > 0 && act >= 0 && act <= 3 && (act != 2 || slope), CRUSE_E_SHAPE, "bn_nchw_bwd: bad arguments");
-    CRUSE_DT_CHECK("bn_nchw_bwd");
-    { int rc = cruse_zero_async(scratch, 3 * (size_t)C * sizeof(double), ST(stream), "bn_nchw_bwd"); if (rc) return rc; }
-    if (dtype == CRUSE_DT_F16)
-        return bn_nchw_bwd_t<f16>(dy, x, mean, rstd, gamma, beta, slope, act, training, N, C, HW, scratch, dx, dgamma, dbeta, dslope, ST(stream));
-    return bn_nchw_bwd_t<float>(dy, x, mean, rstd, gamma, beta, slope, act, training, N, C, HW, scratch, dx, dgamma, dbeta, dslope, ST(stream));
+    return bn_nchw_bwd_run("bn_nchw_bwd", dy, x, mean, rstd, gamma, beta, slope, act, training, N, C, HW, scratch, 3, 0, 0, dx, dgamma, dbeta, dslope,
+                           nullptr, dtype, ST(stream));
 }
 
 // cruse_bn_nchw_bwd that ALSO accumulates dx_sum[c] += sum of the stored dx of channel c (nullable): the bias gradient of the convolution in
@@ -1820,22 +1864,9 @@ extern "C" int cruse_bn_nchw_bwd_ex(const void* dy, const void* x, const float* 
                                     const float* beta, const float* slope, int act, int training, int N, int C, int HW,
                                     double* scratch, int scratch_zeroed, int sums_replicas, void* dx, float* dgamma, float* dbeta, float* dslope,
                                     float* dx_sum, int dtype, void* stream) {
-    CRUSE_REQUIRE(N > 0 && C > 0 && HW > 0 && act >= 0 && act <= 3 && (act != 2 || slope) && sums_replicas >= 0, CRUSE_E_SHAPE, "bn_nchw_bwd_ex: bad arguments");
-    CRUSE_DT_CHECK("bn_nchw_bwd_ex");
-    if (sums_replicas > 0) {       // scratch = [sums_replicas][4][C], ALREADY FILLED by cruse_conv2d_nchw_bnbwd: the reduce pass is skipped
-        CRUSE_REQUIRE(dtype == CRUSE_DT_F16 && (long long)N * C < 65536, CRUSE_E_SHAPE, "bn_nchw_bwd_ex: delivered sums come with the f16 kernels");
-        return bn_nchw_bwd_t<f16>(dy, x, mean, rstd, gamma, beta, slope, act, training, N, C, HW, scratch, dx, dgamma, dbeta, dslope, ST(stream), dx_sum, 1,
-                                  sums_replicas);
-    }
-    if (!scratch_zeroed) { int rc = cruse_zero_async(scratch, 4 * (size_t)C * sizeof(double), ST(stream), "bn_nchw_bwd_ex"); if (rc) return rc; }
-    if (dtype == CRUSE_DT_F16)
-        return bn_nchw_bwd_t<f16>(dy, x, mean, rstd, gamma, beta, slope, act, training, N, C, HW, scratch, dx, dgamma, dbeta, dslope, ST(stream), dx_sum);
-    return bn_nchw_bwd_t<float>(dy, x, mean, rstd, gamma, beta, slope, act, training, N, C, HW, scratch, dx, dgamma, dbeta, dslope, ST(stream), dx_sum);
+    return bn_nchw_bwd_run("bn_nchw_bwd_ex", dy, x, mean, rstd, gamma, beta, slope, act, training, N, C, HW, scratch, 4, scratch_zeroed, sums_replicas, dx,
+                           dgamma, dbeta, dslope, dx_sum, dtype, ST(stream));
 }
-
-extern "C" int cruse_bn_finalize(const double* sums, long long count, int C, float eps, float momentum,
-                                 float* mean, float* rstd, float* running_mean, float* running_var, void* stream);
-extern "C" int cruse_counters_add(long long* const* counters, int n, long long v, void* stream);
 
 // Training-mode BatchNorm2d (+ activation) forward from the batch SUMS of cruse_bn_nchw_stats: mean / rstd are formed in the kernel and written to
 // mean_out / rstd_out for the backward pass, the running statistics (nullable pair) and the batch counter (nullable) are updated as
@@ -1865,10 +1896,8 @@ extern "C" int cruse_bn_nchw_fwd_train(const void* x, const double* sums, int su
 extern "C" int cruse_add_nchw(const void* a, const void* b, void* out, long long n, int dtype, void* stream) {
     CRUSE_REQUIRE(n > 0 && a && b && out, CRUSE_E_SHAPE, "add_nchw: bad arguments");
     CRUSE_DT_CHECK("add_nchw");
-    if (dtype == CRUSE_DT_F16)
-        hipLaunchKernelGGL(add_t_kernel<f16>, dim3(gblocks(n)), dim3(256), 0, ST(stream), (const f16*)a, (const f16*)b, (f16*)out, n);
-    else
-        hipLaunchKernelGGL(add_t_kernel<float>, dim3(gblocks(n)), dim3(256), 0, ST(stream), (const float*)a, (const float*)b, (float*)out, n);
+    dispatch_dtype(dtype, [&](auto t) { typedef decltype(t) T;
+        hipLaunchKernelGGL(add_t_kernel<T>, dim3(gblocks(n)), dim3(256), 0, ST(stream), (const T*)a, (const T*)b, (T*)out, n); return 0; });
     CRUSE_LAUNCH_CHECK("add_nchw");
     return CRUSE_OK;
 }

@@ -1316,22 +1316,22 @@ struct Route {
 };
 
 bool bwd_rs_eligible(int Bg, int Hg, int prec) {
-    if (cruse_opt("gru_bwd_rs", 1) == 0) return false;    // A/B switch (tests, probes)
+    if (cruse_opt(CRUSE_OPT_gru_bwd_rs, 1) == 0) return false;    // A/B switch (tests, probes)
     return prec == CRUSE_PREC_BF16 && Bg == 8 && Hg % 32 == 0 && Hg <= 640;
 }
 bool fwd_lean_eligible(int Bg, int Hg, int prec) {
-    if (cruse_opt("gru_fwd_lean", 1) == 0) return false;   // A/B switch (tests, probes)
+    if (cruse_opt(CRUSE_OPT_gru_fwd_lean, 1) == 0) return false;   // A/B switch (tests, probes)
     return prec == CRUSE_PREC_BF16 && Bg == 8 && Hg % 32 == 0 && Hg <= 640;
 }
 // Hg = 640: the lean kernel's K-split step on the tag-free hand-off with the register-direct sweep (library option gru_tf = 0: the tagged
 // hand-off); needs |h| < 1 (h0 = NULL) and is built for one weight plane
 bool fwd_lean_tf_eligible(int Hg, bool wlo, bool has_h0) {
-    return Hg == 640 && !wlo && !has_h0 && cruse_opt("gru_tf", 1) != 0;
+    return Hg == 640 && !wlo && !has_h0 && cruse_opt(CRUSE_OPT_gru_tf, 1) != 0;
 }
 // W_hh low plane in the lean forward recurrence: CRUSE_GRU_WLO = 1 always, 0 never; default: when the second plane is
 // nearly free (Hg <= 320: at most 48 extra registers and 12 extra MFMAs per wave and step)
 bool fwd_wlo(int Hg) {
-    const int e = cruse_opt("gru_wlo", -1);
+    const int e = cruse_opt(CRUSE_OPT_gru_wlo, -1);
     if (e >= 0) return e != 0;
     return Hg <= 320;
 }
@@ -1408,12 +1408,12 @@ int select_route(const char* name, int B, int G, int Hg, int prec, bool fwd, int
     } else if (!fast) {
         r.fam = FAM_GENERIC;
     } else if (fwd) {
-        if (fwd_tf_eligible(r.Bg, Hg, prec, has_h0, gi_f16)) { r.fam = FAM_TF; r.poll_delay = cruse_opt("gru_poll_fwd", 8); }
-        else { r.fam = fwd_lean_tf_eligible(Hg, r.wlo, has_h0) ? FAM_LEAN_TF : FAM_LEAN; r.poll_delay = cruse_opt("gru_poll_fwd", 0); }
+        if (fwd_tf_eligible(r.Bg, Hg, prec, has_h0, gi_f16)) { r.fam = FAM_TF; r.poll_delay = cruse_opt(CRUSE_OPT_gru_poll_fwd, 8); }
+        else { r.fam = fwd_lean_tf_eligible(Hg, r.wlo, has_h0) ? FAM_LEAN_TF : FAM_LEAN; r.poll_delay = cruse_opt(CRUSE_OPT_gru_poll_fwd, 0); }
         // f16 gi rows: built for the bench step's kernel only
         if (gi_f16 && r.fam != FAM_LEAN_TF) { cruse_set_error("gru_seq_fwd: f16 gi rows are served at Hg = 640 with h0 = NULL on chains of 8 only (cruse_gru_plan)"); return CRUSE_E_SHAPE; }
     } else {
-        if (bwd_tf_eligible(r.Bg, Hg, prec)) { r.fam = FAM_AG; r.poll_delay = cruse_opt("gru_poll_bwd", Hg == 640 ? 5 : 7); }
+        if (bwd_tf_eligible(r.Bg, Hg, prec)) { r.fam = FAM_AG; r.poll_delay = cruse_opt(CRUSE_OPT_gru_poll_bwd, Hg == 640 ? 5 : 7); }
         else r.fam = FAM_RS;
     }
     r.gpp = family_gpp(r.fam, fwd, r.Bg, Hg);
@@ -1504,7 +1504,7 @@ int run_launches(GruArgs& a, const Route& r, int G, int Hg, int prec, void* pane
     unsigned* tickets_base = (unsigned*)(xg_base + xg_bytes_total(a.B, G, Hg));        // [launch][8]
     a.Bg = r.Bg; a.P = r.P;
     a.poll_delay = r.poll_delay;
-    a.dbg = cruse_opt("gru_dbg", 0);
+    a.dbg = cruse_opt(CRUSE_OPT_gru_dbg, 0);
     CRUSE_REQUIRE(r.nlaunch <= MAX_LAUNCH_TICKETS, CRUSE_E_SHAPE, "gru_seq: batch %d needs %d launches (max %d)", a.B, r.nlaunch,
                   MAX_LAUNCH_TICKETS);
     for (int L = 0; L < r.nlaunch; ++L) {

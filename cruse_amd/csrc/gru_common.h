@@ -355,14 +355,6 @@ __device__ __forceinline__ unsigned tag_bit(unsigned epoch) { return ((epoch + 1
 // (x & ~TAGM) | tag  in one VOP3 (v_and_or_b32)
 __device__ __forceinline__ unsigned with_tag(unsigned x, unsigned tagm) { return (x & ~TAGM) | tagm; }
 
-// Run-time integer -> template parameter: f(std::integral_constant<int, V>{}) for the first V of the list equal to v, for the LAST one
-// if none is (the kernels' largest instance serves as the default).
-template <int V0, int... Vs, typename F>
-inline int dispatch_int(int v, F&& f) {
-    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
-    else return v == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<Vs...>(v, f);
-}
-
 template <typename Kern>
 inline int launch_one(Kern k, const GruArgs& a, int grid, size_t lds, hipStream_t s, const char* name, int threads = 256) {
     int rc0 = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(k), lds, name);

@@ -643,7 +643,7 @@ __global__ __launch_bounds__(TF_THREADS) void gru_bwd_ag_kernel(GruArgs a) {
 namespace cruse_gru {
 
 bool fwd_tf_eligible(int Bg, int Hg, int prec, bool has_h0, bool gi_f16) {
-    if (cruse_opt("gru_tf", 1) == 0) return false;             // A/B switch (tests, probes): 0 = the tagged kernels of gru.hip
+    if (cruse_opt(CRUSE_OPT_gru_tf, 1) == 0) return false;             // A/B switch (tests, probes): 0 = the tagged kernels of gru.hip
     // Hg = 640: the K-split-free step measured slower than the lean kernel's (1.36 against 1.27 us per step; 40 instead of 30 MFMAs
     // per wave on the serial chain) -- there the lean kernel runs on the tag-free hand-off instead (gru.hip, TF)
     return prec == CRUSE_PREC_BF16 && Bg == 8 && !has_h0 && !gi_f16 && (Hg == 160 || Hg == 320);
@@ -658,7 +658,7 @@ int dispatch_fwd_tf(const GruArgs& a, int grid, bool wlo, hipStream_t s) {
 }
 
 bool bwd_tf_eligible(int Bg, int Hg, int prec) {
-    if (cruse_opt("gru_tf", 1) == 0) return false;
+    if (cruse_opt(CRUSE_OPT_gru_tf, 1) == 0) return false;
     return prec == CRUSE_PREC_BF16 && Bg == 8 && (Hg == 160 || Hg == 320 || Hg == 640);
 }
 

@@ -949,7 +949,7 @@ extern "C" int cruse_ln_fwd_c(const float* x, const float* gamma, const float* b
     return CRUSE_OK;
 }
 
-static int lnb_grid() { return cruse_opt("lnb_grid", 512); }
+constexpr int LNB_GRID = 512;          // grid cap of the vector LayerNorm backward kernels
 
 static int ln_bwd_impl(const float* dy, const float* x, const float* mean, const float* rstd,
                        const float* gamma, long long rows, int H, int interleave_g,
@@ -962,10 +962,10 @@ static int ln_bwd_impl(const float* dy, const float* x, const float* mean, const
     const bool vec = interleave_g == 1 && H % 4 == 0 && H <= 256 * LNV_MAXQ &&
                      ((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)gamma) & 15) == 0);
     if (vec && H <= 768)
-        hipLaunchKernelGGL((ln_bwd_vec_kernel<3, 2>), dim3(grid_for(rows, 16, lnb_grid())), dim3(256), 0, ST(stream), dy, x, mean,
+        hipLaunchKernelGGL((ln_bwd_vec_kernel<3, 2>), dim3(grid_for(rows, 16, LNB_GRID)), dim3(256), 0, ST(stream), dy, x, mean,
                            rstd, gamma, rows, H, dx, dgamma, dbeta, sg);
     else if (vec)
-        hipLaunchKernelGGL((ln_bwd_vec_kernel<4, 1>), dim3(grid_for(rows, 16, lnb_grid())), dim3(256), 0, ST(stream), dy, x, mean,
+        hipLaunchKernelGGL((ln_bwd_vec_kernel<4, 1>), dim3(grid_for(rows, 16, LNB_GRID)), dim3(256), 0, ST(stream), dy, x, mean,
                            rstd, gamma, rows, H, dx, dgamma, dbeta, sg);
     else {
         CRUSE_REQUIRE(seg_len == 0, CRUSE_E_SHAPE, "ln_bwd: row segments need the vector form (one group, H %% 4 == 0, aligned)");

@@ -410,7 +410,7 @@ int cruse_wgrad_mfma_try(const float* a, const float* bt, float* partial, int ma
     p.B = B; p.T = T; p.Ca = Ca; p.Fa = Fa; p.Cb = Cb; p.Fb = Fb; p.KT = KT; p.S = S; p.pad = pad;
     p.FaP = FaP; p.NCH = NCH; p.ntaps = ntaps; p.nrows = tfw + KT - 1;
     p.ntiles_total = B * ((T + tfw - 1) / tfw);
-    p.dbg = cruse_opt("wg_dbg", 0);
+    p.dbg = cruse_opt(CRUSE_OPT_wg_dbg, 0);
     p.a_bf16 = a_bf16 ? 1 : 0; p.bt_bf16 = bt_bf16 ? 1 : 0;
     int grid = p.ntiles_total < max_slabs ? p.ntiles_total : max_slabs;
     if (grid > gcap) grid = gcap;               // resident blocks only; fewer partial slabs to reduce

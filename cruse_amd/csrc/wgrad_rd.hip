@@ -343,7 +343,7 @@ int launch_form(const WRArgs& p, int S, int pad, int grid, hipStream_t s) {
 int cruse_wgrad_rd_try(const float* a, const float* bt, float* partial, size_t ws_bytes, float* dw,
                        int B, int T, int Ca, int Fa, int Cb, int Fb, int KT, int S, int pad, int prec, int a_bf16, int bt_bf16,
                        int* nblk_out, hipStream_t stream) {
-    if (prec != CRUSE_PREC_BF16 || cruse_opt("wg_rd", 1) == 0) return 0;
+    if (prec != CRUSE_PREC_BF16 || cruse_opt(CRUSE_OPT_wg_rd, 1) == 0) return 0;
     const int ntaps = KT * 3;
     const int MT = (Ca + 15) / 16, npairs = KT * ((Cb + 15) / 16);        // row tiles; source windows (frame offset, 16 channels of bt)
     if (Ca > 64 || npairs > 4 || Fa < 8 || (Fa & 1) || Fb != S * Fa || !((S == 1 && pad == 1) || S == 2) || (KT != 1 && KT != 2)) return 0;
@@ -362,7 +362,7 @@ int cruse_wgrad_rd_try(const float* a, const float* bt, float* partial, size_t w
     // ONE 8-wave workgroup per CU (256 in all; a slab is written by TG of them, one per group of source windows): measured at the bench shapes,
     // 128 / 256 / 512 / 1024 workgroups: 363 / 266 / 322 / 447 us for the twelve launches of a step (tools/wgrad_probe.py) -- the per-workgroup
     // costs (index set-up, the LDS tree, the slab and its reduction) outweigh what more waves hide; deeper unrolling (U x 2) measured equal
-    int ns = cruse_opt("wg_grid", 0) > 0 ? cruse_opt("wg_grid", 0) : 256 / TG;
+    int ns = cruse_opt(CRUSE_OPT_wg_grid, 0) > 0 ? cruse_opt(CRUSE_OPT_wg_grid, 0) : 256 / TG;
     const size_t slab_bytes = (size_t)TG * mtw * nwp * 3 * 256 * sizeof(float);
     if (slab_bytes > ws_bytes) return 0;
     if ((size_t)ns * slab_bytes > ws_bytes) ns = (int)(ws_bytes / slab_bytes);

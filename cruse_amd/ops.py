@@ -289,6 +289,24 @@ def conv_plan(scatter, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, B, T, prec, x
             "co_t": out[6]}
 
 
+NCHW_REQ_BN_SUMS, NCHW_REQ_RESIDUAL, NCHW_REQ_BNBWD, NCHW_REQ_DB = 1, 2, 4, 1      # cruse_conv2d_nchw_plan
+NCHW_CONV_FORMS = ("pw_tr_f16", "pw_mfma_f16", "pw", "dw_lds_f16", "dw", "general")
+NCHW_WGRAD_FORMS = ("pw_mfma_f16", "dw_lds_f16", "dw", "rows", "weight")
+NCHW_PASSES = (None, "add", "stats", "channel_sum")
+
+
+def nchw_conv_plan(wgrad, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh=1, sw=1, dh=1, dw=1, pt=0, pl=0, groups=1, up_w=1, transposed=0,
+                   act=0, accumulate=0, dtype=0, requests=0) -> dict:
+    """what an NCHW convolution (wgrad = 0) or weight-gradient (wgrad = 1: N, CA, HS, WS, CB, HB, WB) call launches (cruse_conv2d_nchw_plan;
+    host-only): the kernel form, its template integers, grid, block and LDS bytes, which of the requests (bit set of NCHW_REQ_*) the kernel
+    serves in its epilogue and the pass owed for the others.  "raw" is the array as the library wrote it."""
+    out = (ctypes.c_int * 11)()
+    check(lib.cruse_conv2d_nchw_plan(1 if wgrad else 0, B, Cin, Hin, Win, Cout, Hout, Wout, KH, KW, sh, sw, dh, dw, pt, pl, groups, up_w,
+                                     1 if transposed else 0, act, 1 if accumulate else 0, dtype, requests, ctypes.cast(out, ctypes.c_void_p)))
+    return {"form": (NCHW_WGRAD_FORMS if wgrad else NCHW_CONV_FORMS)[out[0]], "form_id": out[0], "t0": out[1], "t1": out[2], "grid": (out[3], out[4], out[5]),
+            "block": out[6], "lds_bytes": out[7], "aux": out[8], "served": out[9], "pass": NCHW_PASSES[out[10]], "raw": list(out)}
+
+
 _wgrad_ws = {}
 _ws_retired = []          # outgrown workspaces: captured HIP graphs may still point at them, so they are never freed
 

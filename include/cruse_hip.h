@@ -60,10 +60,13 @@ enum {
 int cruse_abi_version(void);
 const char* cruse_last_error(void);
 /* Library options -- kernel-selection A/B switches and profiling aids, set EXPLICITLY by the host (the library reads no
- * environment variables): "gru_bwd_rs" / "gru_fwd_lean" 0 = the generic recurrence kernels in bf16 mode; "gru_wlo" 0 / 1 =
- * W_hh low plane of the lean forward recurrence off / on for every Hg (unset: on for Hg <= 320); "gru_bg" 16; "gru_dbg",
- * "wg_dbg" phase-skip profiling; "cm_grid", "cm_nw", "gb_deep_min", "gb_deep", "lnb_grid", "wg_tfw", "wg_grid" launch
- * geometry overrides; "pw_valu" 1 = VALU pointwise convolutions in f16 storage.  unset != 0 restores the default. */
+ * environment variables).  The 17 names (any other is refused): "gru_bwd_rs" / "gru_fwd_lean" 0 = the generic recurrence kernels
+ * in bf16 mode; "gru_tf" 0 = the tagged hand-off kernels; "gru_poll_fwd" / "gru_poll_bwd" poll delay of the hand-off; "gru_wlo"
+ * 0 / 1 = W_hh low plane of the lean forward recurrence off / on for every Hg (unset: on for Hg <= 320); "gru_dbg", "cm_dbg",
+ * "wg_dbg" phase-skip / phase-stamp profiling; "cm_nw", "cm_grid", "wg_grid" launch geometry overrides; "cm_kint", "cm_swap",
+ * "wg_rd" 0 = without the k-interleaved weights / swapped operand roles / direct-read weight gradient; "pw_valu" 1 = VALU kernels
+ * for the NCHW convolutions in f16 storage, 2 = their gather pointwise MFMA kernel; "dw_nolds" 1 = the f16 depthwise kernels
+ * without the LDS image.  unset != 0 restores the default. */
 int cruse_set_option(const char* name, int value, int unset);
 int cruse_get_option(const char* name, int* value, int* is_set);
 
@@ -631,6 +634,25 @@ int cruse_conv2d_nchw_bnbwd(const void* x, const float* w, void* y,
                             int KH, int KW, int sh, int sw, int dh, int dw, int pt, int pl, int groups, int transposed,
                             const void* bn_x, const float* bn_mean, const float* bn_rstd, const float* bn_gamma, const float* bn_beta,
                             const float* bn_slope, int bn_act, double* r, int r_nrep, int* delivered, int dtype, void* stream);
+/* Host-only, touches no device: what cruse_conv2d_nchw / _ex / _bnbwd (wgrad = 0) or cruse_conv2d_nchw_wgrad / _wgrad_ex (wgrad = 1) launch for
+ * a call -- the same validation and the same decision as the call, without the launches.  The geometry is that of the entry point (wgrad:
+ * B, Cin, Hin, Win, Cout, Hout, Wout = N, CA, HS, WS, CB, HB, WB, dw = dw_; transposed, act, accumulate = 0).  requests: the optional outputs
+ * the call asks for -- BN_SUMS / RESIDUAL (cruse_conv2d_nchw_ex: bn_sums, residual), BNBWD (cruse_conv2d_nchw_bnbwd), DB (wgrad_ex: db) -- and
+ * with them the entry point; an argument that entry point does not have must be neutral.  out[11]:
+ *   [0] kernel form: conv 0 f16 pointwise MFMA, operand transposed through LDS; 1 f16 pointwise MFMA, gather; 2 pointwise VALU;
+ *       3 f16 depthwise on an LDS image; 4 depthwise; 5 general -- wgrad 0 f16 pointwise MFMA; 1 f16 depthwise on an LDS image; 2 depthwise;
+ *       3 a row pair in LDS; 4 one block row per weight
+ *   [1] [2] the kernel's template integers (16-row tiles x 32-deep k-steps; MAXCO of form 2; else 0)   [3] [4] [5] grid x, y, z   [6] block
+ *   [7] dynamic LDS bytes    [8] conv form 0: epilogue instance (0 plain, 1 batch sums, 2 BatchNorm-backward sums); wgrad form 0: positions
+ *       per block, form 2: positions per thread
+ *   [9] the requests served in the kernel's epilogue (cruse_conv2d_nchw_bnbwd's *delivered is its BNBWD bit)
+ *   [10] the pass owed for the others: 0 none, 1 cruse_add_nchw after, 2 cruse_bn_nchw_stats_ex after, 3 cruse_nchw_channel_sum before
+ * Returns what the entry point would: an error code and cruse_last_error() where the call is refused. */
+enum { CRUSE_NCHW_REQ_BN_SUMS = 1, CRUSE_NCHW_REQ_RESIDUAL = 2, CRUSE_NCHW_REQ_BNBWD = 4, CRUSE_NCHW_REQ_DB = 1 };
+int cruse_conv2d_nchw_plan(int wgrad, int B, int Cin, int Hin, int Win, int Cout, int Hout, int Wout,
+                           int KH, int KW, int sh, int sw, int dh, int dw, int pt, int pl,
+                           int groups, int up_w, int transposed, int act, int accumulate, int dtype, int requests, int* out);
+
 /* cruse_bn_nchw_stats into sums the caller cleared itself (zeroed != 0; like scratch_zeroed above: one fill launch per pool chunk of
  * accumulators instead of one per call) */
 int cruse_bn_nchw_stats_ex(const void* x, int N, int C, int HW, double* sums, int zeroed, int dtype, void* stream);
