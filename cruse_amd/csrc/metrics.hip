@@ -12,6 +12,12 @@
 //                                                  bins the 15 bands cover against an LDS cos / sin table, band sums -> tob
 //   5 stoi_segments   grid (ceil(nSeg/256), 15, B) one thread per (segment, band): clip, centre, normalise, correlate; block tree in f64
 //   6 stoi_final      grid (B)                     sums the block partials in order -> out[b]
+//
+// Ragged batches (cruse_si_sdr_ragged, cruse_stoi_ragged): clip b is ref[b][0 : len[b]], len a DEVICE array that only the kernels read.
+// si_sdr, stoi_resample, stoi_energy and stoi_mask exist a second time (RAG = true) with the clip's own length, L10 and nF in place of
+// the batch's; every later stage reads n_kept already.  Same taps, same trees: a clip scores the same in a ragged batch and alone.
+// extended != 0 (ESTOI, Jensen & Taal 2016) replaces launch 5:
+//   5e stoi_eseg      grid (ceil(nSeg/256), B)     half a wave per segment, lane = frame: rows then columns normalised, f64 block tree
 #include <math.h>
 #include <algorithm>
 #include <string.h>
@@ -109,13 +115,20 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
     return red[0];
 }
 
+// the ragged kernels' view of clip b: its length clamped to [0, L], and the stage sizes that follow from it
+__device__ __forceinline__ int clip_len(const int* __restrict__ len, int b, int L) { return min(max(len[b], 0), L); }
+__device__ __forceinline__ int clip_l10(int n) { return (UP * n + DOWN - 1) / DOWN; }                  // n <= 2^28
+__device__ __forceinline__ int clip_frames(int l10) { return l10 >= FRAME ? (l10 - FRAME) / HOPF + 1 : 0; }
+
 // ---- SI-SDR: one workgroup per clip, f64 sums --------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(THREADS) si_sdr_kernel(const float* __restrict__ ref, const float* __restrict__ est, int L,
-                                                         float* __restrict__ out) {
+template <bool RAG>
+__global__ void __launch_bounds__(THREADS) si_sdr_kernel(const float* __restrict__ ref, const float* __restrict__ est, int Lrow,
+                                                         const int* __restrict__ len, float* __restrict__ out) {
     __shared__ double red[THREADS];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float* r = ref + (size_t)b * L;
-    const float* e = est + (size_t)b * L;
+    const float* r = ref + (size_t)b * Lrow;
+    const float* e = est + (size_t)b * Lrow;
+    const int L = RAG ? clip_len(len, b, Lrow) : Lrow;                 // 0: 0 / 0 = NaN, as numpy
     double sre = 0.0, srr = 0.0;
     for (int i = tid; i < L; i += THREADS) {
         const double x = r[i], y = e[i];
@@ -136,15 +149,20 @@ __global__ void __launch_bounds__(THREADS) si_sdr_kernel(const float* __restrict
 
 // ---- STOI ------------------------------------------------------------------------------------------------------------------------
 // x10[n] = 5 sum_k h[k] v[8 n + 128 - k], v[5 i] = u[i]: the taps k = k0 + 5 j with 8 n + 128 - k = 5 i, ascending
-__global__ void __launch_bounds__(THREADS) stoi_resample_kernel(const float* __restrict__ ref, const float* __restrict__ est, int L,
-                                                                StoiLayout Y, const float* __restrict__ tab, float* __restrict__ ws) {
+template <bool RAG>
+__global__ void __launch_bounds__(THREADS) stoi_resample_kernel(const float* __restrict__ ref, const float* __restrict__ est, int Lrow,
+                                                                const int* __restrict__ len, StoiLayout Y, const float* __restrict__ tab,
+                                                                float* __restrict__ ws) {
     __shared__ float h[TAPS];
     const int tid = threadIdx.x, b = blockIdx.z, r = blockIdx.y;
+    const int L = RAG ? clip_len(len, b, Lrow) : Lrow;                 // samples >= L are outside the clip: never loaded
+    const int L10 = RAG ? clip_l10(L) : Y.L10;                         // outputs beyond the clip's own L10 stay unwritten
+    if (RAG && blockIdx.x * THREADS >= L10) return;
     for (int k = tid; k < TAPS; k += THREADS) h[k] = tab[TB_H + k];
     __syncthreads();
     const int n = blockIdx.x * THREADS + tid;
-    if (n >= Y.L10) return;
-    const float* u = (r == 0 ? ref : est) + (size_t)b * L;
+    if (n >= L10) return;
+    const float* u = (r == 0 ? ref : est) + (size_t)b * Lrow;
     const int m = DOWN * n + (TAPS - 1) / 2;                           // <= 5 L + 134
     const int k0 = m % UP;
     int i = (m - k0) / UP;                                             // the input sample under tap k0; one less per step
@@ -157,10 +175,12 @@ __global__ void __launch_bounds__(THREADS) stoi_resample_kernel(const float* __r
 }
 
 // e[i] = 20 log10(|| w * ref10[128 i : 128 i + 256] || + eps): one wave per frame
-__global__ void __launch_bounds__(THREADS) stoi_energy_kernel(StoiLayout Y, const float* __restrict__ tab, float* __restrict__ ws) {
+template <bool RAG>
+__global__ void __launch_bounds__(THREADS) stoi_energy_kernel(StoiLayout Y, int Lrow, const int* __restrict__ len,
+                                                              const float* __restrict__ tab, float* __restrict__ ws) {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int i = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
-    if (i >= Y.nF) return;
+    if (i >= (RAG ? clip_frames(clip_l10(clip_len(len, b, Lrow))) : Y.nF)) return;
     const float* x = ws + Y.x10 + (size_t)b * 2 * Y.L10 + (size_t)i * HOPF;            // the last frame ends at 128 (nF - 1) + 256 <= L10
     float s = 0.f;
     for (int q = 0; q < FRAME / 64; ++q) {
@@ -172,11 +192,12 @@ __global__ void __launch_bounds__(THREADS) stoi_energy_kernel(StoiLayout Y, cons
 }
 
 // kept = the frames with e[i] > max(e) - 40, ascending; nk = their count
-__global__ void __launch_bounds__(THREADS) stoi_mask_kernel(StoiLayout Y, float* __restrict__ ws) {
+template <bool RAG>
+__global__ void __launch_bounds__(THREADS) stoi_mask_kernel(StoiLayout Y, int Lrow, const int* __restrict__ len, float* __restrict__ ws) {
     __shared__ float wmax[THREADS / 64];
     __shared__ int wcnt[THREADS / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int nF = Y.nF, nFa = max(nF, 1);
+    const int nFa = max(Y.nF, 1), nF = RAG ? clip_frames(clip_l10(clip_len(len, b, Lrow))) : Y.nF;
     const float* e = ws + Y.e + (size_t)b * nFa;
     int* kept = (int*)ws + Y.kept + (size_t)b * nFa;
     float mx = -INFINITY;
@@ -296,6 +317,75 @@ __global__ void __launch_bounds__(THREADS) stoi_segments_kernel(StoiLayout Y, fl
     if (tid == 0) ((double*)(ws + Y.part))[((size_t)b * NBANDS + k) * Y.nSB + blockIdx.x] = t;
 }
 
+// sum of `v` over the 32 lanes of a half wave in a fixed xor tree (no lane leaves its half); every lane of the half holds the result
+__device__ __forceinline__ float half_sum(float v) {
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// ESTOI's normalisation of a 15 x 30 segment, lane = frame, v[k] = band k: every row (a band over its 30 frames) less its mean over
+// (its norm + eps), by half-wave trees; then every column (a frame over its 15 bands) the same, in registers.  A lane that holds no
+// frame carries zeros in and out.
+__device__ __forceinline__ void estoi_normalise(float (&v)[NBANDS], bool live) {
+#pragma unroll
+    for (int k = 0; k < NBANDS; ++k) {
+        const float mean = half_sum(v[k]) / (float)SEG;
+        const float c = live ? v[k] - mean : 0.f;
+        v[k] = c / (sqrtf(half_sum(c * c)) + EPS);
+    }
+    float m = 0.f, n = 0.f;
+#pragma unroll
+    for (int k = 0; k < NBANDS; ++k) m += v[k];
+    m /= (float)NBANDS;
+#pragma unroll
+    for (int k = 0; k < NBANDS; ++k) {
+        v[k] -= m;
+        n = fmaf(v[k], v[k], n);
+    }
+    const float inv = sqrtf(n) + EPS;
+#pragma unroll
+    for (int k = 0; k < NBANDS; ++k) v[k] /= inv;
+}
+
+// ESTOI (extended != 0) in place of stoi_segments: segment s = frames [s, s + 30) of all 15 bands, half a wave each.  No clipping and no
+// alpha: X and Y normalised as above, the segment scores sum(X^ Y^) / 30.  A workgroup owns 256 consecutive segments, half wave h of its
+// eight the segments h, h + 8, ...: their f64 sum in that order, then the eight sums in a fixed tree -> part[b][0][block].  The order of
+// every sum follows from the segment index alone, so a score does not depend on B; no atomics.
+__global__ void __launch_bounds__(THREADS) stoi_eseg_kernel(StoiLayout Y, float* __restrict__ ws) {
+    __shared__ double red[THREADS / 32];
+    const int b = blockIdx.y, tid = threadIdx.x, f = tid & 31, hw = tid >> 5;
+    const int nSeg = ((const int*)ws)[Y.nk + b] - 1 - (SEG - 1);       // nG - 29
+    const int s0 = blockIdx.x * THREADS;
+    if (s0 >= nSeg) return;
+    const float* X = ws + Y.tob + (size_t)b * 2 * NBANDS * Y.nGs;
+    const float* Yr = X + (size_t)NBANDS * Y.nGs;
+    double acc = 0.0;
+    for (int j = 0; j < 32 && s0 + 8 * j < nSeg; ++j) {                // the bound is the workgroup's: every lane takes every shuffle
+        const int s = s0 + 8 * j + hw;
+        const bool live = s < nSeg && f < SEG;                         // s + f <= nSeg - 1 + 29 = nG - 1
+        float x[NBANDS], y[NBANDS];
+#pragma unroll
+        for (int k = 0; k < NBANDS; ++k) {
+            x[k] = live ? X[(size_t)k * Y.nGs + s + f] : 0.f;
+            y[k] = live ? Yr[(size_t)k * Y.nGs + s + f] : 0.f;
+        }
+        estoi_normalise(x, live);
+        estoi_normalise(y, live);
+        float d = 0.f;
+#pragma unroll
+        for (int k = 0; k < NBANDS; ++k) d = fmaf(x[k], y[k], d);
+        acc += (double)(half_sum(d) / (float)SEG);                     // a half wave past the last segment adds 0
+    }
+    if (f == 0) red[hw] = acc;
+    __syncthreads();
+    if (tid == 0)
+        ((double*)(ws + Y.part))[(size_t)b * NBANDS * Y.nSB + blockIdx.x] =
+            ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
+}
+
+// EXT: the partials of stoi_eseg (one row of blocks, part[b][0][.]) over nSeg; else those of stoi_segments over 15 nSeg
+template <bool EXT>
 __global__ void __launch_bounds__(THREADS) stoi_final_kernel(StoiLayout Y, const float* __restrict__ ws, float* __restrict__ out) {
     __shared__ double red[THREADS];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -307,20 +397,69 @@ __global__ void __launch_bounds__(THREADS) stoi_final_kernel(StoiLayout Y, const
     const int nb = (nSeg + THREADS - 1) / THREADS;
     const double* part = (const double*)(ws + Y.part) + (size_t)b * NBANDS * Y.nSB;
     double acc = 0.0;
-    for (int i = tid; i < NBANDS * nb; i += THREADS) acc += part[(size_t)(i / nb) * Y.nSB + i % nb];
+    constexpr int ROWS = EXT ? 1 : NBANDS;
+    for (int i = tid; i < ROWS * nb; i += THREADS) acc += part[(size_t)(i / nb) * Y.nSB + i % nb];
     acc = block_sum_d(acc, red);
-    if (tid == 0) out[b] = (float)(acc / ((double)NBANDS * (double)nSeg));
+    if (tid == 0) out[b] = (float)(acc / ((double)ROWS * (double)nSeg));
+}
+
+// the launches of cruse_stoi (RAG = false: len and extended unused) and cruse_stoi_ragged, after the same refusals
+template <bool RAG>
+int stoi_run(const char* who, const float* ref, const float* est, int B, int L, const int* len, int extended, const float* tab, void* ws,
+             size_t ws_bytes, float* out, void* stream) {
+    CRUSE_REQUIRE(ref && est && tab && ws && out, CRUSE_E_SHAPE, "%s: null buffer", who);
+    CRUSE_REQUIRE(!RAG || len, CRUSE_E_SHAPE, "%s: null len (the clips' lengths, int[B] on the device)", who);
+    StoiLayout Y;
+    const int rc = make_layout(who, B, L, Y);
+    if (rc) return rc;
+    CRUSE_REQUIRE(ws_bytes >= (size_t)Y.total * 4, CRUSE_E_SHAPE, "%s: workspace of %zu bytes, cruse_stoi_ws_bytes(%d, %d) = %zu", who, ws_bytes, B,
+                  L, (size_t)Y.total * 4);
+    CRUSE_REQUIRE(((uintptr_t)ws & 7) == 0, CRUSE_E_ALIGN, "%s: workspace not 8-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    float* w = (float*)ws;
+    const Bands& bd = bands();
+    hipLaunchKernelGGL(stoi_resample_kernel<RAG>, dim3(cdiv(Y.L10, THREADS), 2, B), dim3(THREADS), 0, s, ref, est, L, len, Y, tab, w);
+    CRUSE_LAUNCH_CHECK("cruse_stoi (resample)");
+    if (Y.nF >= 1) {
+        hipLaunchKernelGGL(stoi_energy_kernel<RAG>, dim3(cdiv(Y.nF, THREADS / 64), B), dim3(THREADS), 0, s, Y, L, len, tab, w);
+        CRUSE_LAUNCH_CHECK("cruse_stoi (energy)");
+    }
+    hipLaunchKernelGGL(stoi_mask_kernel<RAG>, dim3(B), dim3(THREADS), 0, s, Y, L, len, w);         // nF = 0: writes nk = 0
+    CRUSE_LAUNCH_CHECK("cruse_stoi (mask)");
+    if (Y.nF >= 2) {
+        hipLaunchKernelGGL(stoi_spectra_kernel, dim3(Y.nF - 1, B), dim3(THREADS), 0, s, Y, bd, tab, w);
+        CRUSE_LAUNCH_CHECK("cruse_stoi (spectra)");
+    }
+    if (Y.nF - 1 >= SEG) {                                              // else no clip can hold a segment
+        if (RAG && extended) hipLaunchKernelGGL(stoi_eseg_kernel, dim3(Y.nSB, B), dim3(THREADS), 0, s, Y, w);
+        else hipLaunchKernelGGL(stoi_segments_kernel, dim3(Y.nSB, NBANDS, B), dim3(THREADS), 0, s, Y, w);
+        CRUSE_LAUNCH_CHECK("cruse_stoi (segments)");
+    }
+    if (RAG && extended) hipLaunchKernelGGL(stoi_final_kernel<true>, dim3(B), dim3(THREADS), 0, s, Y, (const float*)w, out);
+    else hipLaunchKernelGGL(stoi_final_kernel<false>, dim3(B), dim3(THREADS), 0, s, Y, (const float*)w, out);
+    CRUSE_LAUNCH_CHECK("cruse_stoi (final)");
+    return CRUSE_OK;
+}
+
+template <bool RAG>
+int si_sdr_run(const char* who, const float* ref, const float* est, int B, int L, const int* len, float* out, void* stream) {
+    CRUSE_REQUIRE(ref && est && out, CRUSE_E_SHAPE, "%s: null buffer", who);
+    CRUSE_REQUIRE(!RAG || len, CRUSE_E_SHAPE, "%s: null len (the clips' lengths, int[B] on the device)", who);
+    CRUSE_REQUIRE(B >= 1 && L >= 1, CRUSE_E_SHAPE, "%s: B = %d, L = %d", who, B, L);
+    CRUSE_REQUIRE(L <= MAX_L, CRUSE_E_SHAPE, "%s: L = %d > %d", who, L, MAX_L);
+    hipLaunchKernelGGL(si_sdr_kernel<RAG>, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, ref, est, L, len, out);
+    CRUSE_LAUNCH_CHECK("cruse_si_sdr");
+    return CRUSE_OK;
 }
 
 }  // namespace
 
 extern "C" int cruse_si_sdr(const float* ref, const float* est, int B, int L, float* out, void* stream) {
-    CRUSE_REQUIRE(ref && est && out, CRUSE_E_SHAPE, "si_sdr: null buffer");
-    CRUSE_REQUIRE(B >= 1 && L >= 1, CRUSE_E_SHAPE, "si_sdr: B = %d, L = %d", B, L);
-    CRUSE_REQUIRE(L <= MAX_L, CRUSE_E_SHAPE, "si_sdr: L = %d > %d", L, MAX_L);
-    hipLaunchKernelGGL(si_sdr_kernel, dim3(B), dim3(THREADS), 0, (hipStream_t)stream, ref, est, L, out);
-    CRUSE_LAUNCH_CHECK("cruse_si_sdr");
-    return CRUSE_OK;
+    return si_sdr_run<false>("si_sdr", ref, est, B, L, nullptr, out, stream);
+}
+
+extern "C" int cruse_si_sdr_ragged(const float* ref, const float* est, int B, int L, const int* len, float* out, void* stream) {
+    return si_sdr_run<true>("si_sdr_ragged", ref, est, B, L, len, out, stream);
 }
 
 extern "C" int cruse_stoi_layout(int B, int L, int* out) {
@@ -366,33 +505,10 @@ extern "C" int cruse_stoi_tables(float* tab, void* stream) {
 
 extern "C" int cruse_stoi(const float* ref, const float* est, int B, int L, const float* tab, void* ws, size_t ws_bytes, float* out,
                           void* stream) {
-    CRUSE_REQUIRE(ref && est && tab && ws && out, CRUSE_E_SHAPE, "stoi: null buffer");
-    StoiLayout Y;
-    const int rc = make_layout("stoi", B, L, Y);
-    if (rc) return rc;
-    CRUSE_REQUIRE(ws_bytes >= (size_t)Y.total * 4, CRUSE_E_SHAPE, "stoi: workspace of %zu bytes, cruse_stoi_ws_bytes(%d, %d) = %zu", ws_bytes, B,
-                  L, (size_t)Y.total * 4);
-    CRUSE_REQUIRE(((uintptr_t)ws & 7) == 0, CRUSE_E_ALIGN, "stoi: workspace not 8-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    float* w = (float*)ws;
-    const Bands& bd = bands();
-    hipLaunchKernelGGL(stoi_resample_kernel, dim3(cdiv(Y.L10, THREADS), 2, B), dim3(THREADS), 0, s, ref, est, L, Y, tab, w);
-    CRUSE_LAUNCH_CHECK("cruse_stoi (resample)");
-    if (Y.nF >= 1) {
-        hipLaunchKernelGGL(stoi_energy_kernel, dim3(cdiv(Y.nF, THREADS / 64), B), dim3(THREADS), 0, s, Y, tab, w);
-        CRUSE_LAUNCH_CHECK("cruse_stoi (energy)");
-    }
-    hipLaunchKernelGGL(stoi_mask_kernel, dim3(B), dim3(THREADS), 0, s, Y, w);                      // nF = 0: writes nk = 0
-    CRUSE_LAUNCH_CHECK("cruse_stoi (mask)");
-    if (Y.nF >= 2) {
-        hipLaunchKernelGGL(stoi_spectra_kernel, dim3(Y.nF - 1, B), dim3(THREADS), 0, s, Y, bd, tab, w);
-        CRUSE_LAUNCH_CHECK("cruse_stoi (spectra)");
-    }
-    if (Y.nF - 1 >= SEG) {                                              // else no clip can hold a segment
-        hipLaunchKernelGGL(stoi_segments_kernel, dim3(Y.nSB, NBANDS, B), dim3(THREADS), 0, s, Y, w);
-        CRUSE_LAUNCH_CHECK("cruse_stoi (segments)");
-    }
-    hipLaunchKernelGGL(stoi_final_kernel, dim3(B), dim3(THREADS), 0, s, Y, (const float*)w, out);
-    CRUSE_LAUNCH_CHECK("cruse_stoi (final)");
-    return CRUSE_OK;
+    return stoi_run<false>("stoi", ref, est, B, L, nullptr, 0, tab, ws, ws_bytes, out, stream);
+}
+
+extern "C" int cruse_stoi_ragged(const float* ref, const float* est, int B, int L, const int* len, int extended, const float* tab, void* ws,
+                                 size_t ws_bytes, float* out, void* stream) {
+    return stoi_run<true>("stoi_ragged", ref, est, B, L, len, extended, tab, ws, ws_bytes, out, stream);
 }

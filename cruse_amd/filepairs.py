@@ -56,6 +56,53 @@ def parse_snr_range(snr_range) -> List[int]:
     return list(range(low, high + 1))
 
 
+def load_pool(paths: Sequence[str], device, sr: int = 16000, chunk_values: int = 1 << 26, files=None):
+    """Read the 16-bit PCM files `paths` (wavio.read_pcm16; `files`: what it returned for them, where the caller has read them already),
+    group them by (rate, channels), upload each group as concatenated PCM in chunks of at most chunk_values samples and convert every
+    chunk with one cruse_resample_poly launch (channel 0, x / 32768) into one flat f32 pool at `sr`, laid out group by group.
+    -> (pool, start int64 [n], len int64 [n]: where file i lies in the pool, one stats row per group)"""
+    from . import ops
+    t_read = [0.0] * len(paths)
+    if files is None:
+        files = []
+        for k, p in enumerate(paths):
+            t0 = time.perf_counter()
+            files.append(wavio.read_pcm16(p))
+            t_read[k] = time.perf_counter() - t0
+    groups = {}
+    for i, (_, ch, rate) in enumerate(files):
+        groups.setdefault((rate, ch), []).append(i)
+    start, lens = np.zeros(len(files), dtype=np.int64), np.zeros(len(files), dtype=np.int64)
+    pos = 0
+    for (rate, ch), members in sorted(groups.items()):
+        up, down = D.ratio(sr, rate)
+        for i in members:
+            start[i], lens[i] = pos, D.out_len(files[i][0].shape[0] // ch, up, down)
+            pos += lens[i]
+    pool = torch.empty(pos, device=device, dtype=torch.float32)
+    stats = []
+    for (rate, ch), members in sorted(groups.items()):
+        up, down = D.ratio(sr, rate)
+        t0 = time.perf_counter()
+        k = 0
+        while k < len(members):                                # chunks of bounded size; a file is never split
+            e, values = k, 0
+            while e < len(members) and (e == k or values + files[members[e]][0].shape[0] <= chunk_values):
+                values += files[members[e]][0].shape[0]
+                e += 1
+            part = members[k:e]
+            frames = np.array([files[i][0].shape[0] // ch for i in part], dtype=np.int64)
+            off_in = np.concatenate([[0], np.cumsum(frames)])
+            off_out = np.concatenate([[start[part[0]]], start[part[0]] + np.cumsum(lens[part])])
+            src = torch.from_numpy(np.concatenate([files[i][0] for i in part])).to(device)
+            ops.resample_poly(src, off_in, off_out, up, down, pool, channels=ch, channel=0)          # repair (2): channel 0
+            k = e
+        torch.cuda.synchronize(device)                         # once per group, at preload only: the time below is the device's
+        stats.append(dict(rate=rate, channels=ch, files=len(members), frames=int(sum(files[i][0].shape[0] // ch for i in members)),
+                          read_s=sum(t_read[i] for i in members), device_s=time.perf_counter() - t0))
+    return pool, start, lens, stats
+
+
 class DeviceFilePairs(DevicePairs):
     """[train_dataset] / [validation_dataset] plug-in: the reference's SynDataset on file lists, DEVICE-RESIDENT.
     path = "cruse_amd.filepairs.DeviceFilePairs" (also dataset.dataset.DeviceFilePairs), args = the reference constructor's names:
@@ -146,42 +193,8 @@ class DeviceFilePairs(DevicePairs):
     # ---- preload -----------------------------------------------------------------------------------------------------
     def _load_pool(self, name: str, paths: List[str], device) -> torch.Tensor:
         """read, upload and convert the files of one list -> the flat 16 kHz pool; fills self.<name>_utt_start / _utt_len"""
-        from . import ops
-        files, t_read = [], []
-        for p in paths:
-            t0 = time.perf_counter()
-            files.append(wavio.read_pcm16(p))
-            t_read.append(time.perf_counter() - t0)
-        groups = {}
-        for i, (_, ch, rate) in enumerate(files):
-            groups.setdefault((rate, ch), []).append(i)
-        start, lens = np.zeros(len(files), dtype=np.int64), np.zeros(len(files), dtype=np.int64)
-        pos = 0
-        for (rate, ch), members in sorted(groups.items()):
-            up, down = D.ratio(self.SR, rate)
-            for i in members:
-                start[i], lens[i] = pos, D.out_len(files[i][0].shape[0] // ch, up, down)
-                pos += lens[i]
-        pool = torch.empty(pos, device=device, dtype=torch.float32)
-        for (rate, ch), members in sorted(groups.items()):
-            up, down = D.ratio(self.SR, rate)
-            t0 = time.perf_counter()
-            k = 0
-            while k < len(members):                            # chunks of bounded size; a file is never split
-                e, values = k, 0
-                while e < len(members) and (e == k or values + files[members[e]][0].shape[0] <= self.CHUNK_VALUES):
-                    values += files[members[e]][0].shape[0]
-                    e += 1
-                part = members[k:e]
-                frames = np.array([files[i][0].shape[0] // ch for i in part], dtype=np.int64)
-                off_in = np.concatenate([[0], np.cumsum(frames)])
-                off_out = np.concatenate([[start[part[0]]], start[part[0]] + np.cumsum(lens[part])])
-                src = torch.from_numpy(np.concatenate([files[i][0] for i in part])).to(device)
-                ops.resample_poly(src, off_in, off_out, up, down, pool, channels=ch, channel=0)          # repair (2): channel 0
-                k = e
-            torch.cuda.synchronize(device)                     # once per group, at preload only: the time below is the device's
-            self.preload_stats.append(dict(pool=name, rate=rate, channels=ch, files=len(members), frames=int(sum(files[i][0].shape[0] // ch for i in members)),
-                                           read_s=sum(t_read[i] for i in members), device_s=time.perf_counter() - t0))
+        pool, start, lens, stats = load_pool(paths, device, self.SR, self.CHUNK_VALUES)
+        self.preload_stats += [dict(pool=name, **row) for row in stats]
         setattr(self, name + "_utt_start", start)
         setattr(self, name + "_utt_len", lens)
         return pool

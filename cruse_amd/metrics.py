@@ -2,6 +2,13 @@
 
     si_sdr(ref, est)            SI_SDR (:60-82), dB
     stoi(ref, est, sr=16000)    STOI (:85-86): the classic, non-extended measure as DESIGN.md section 13 defines it
+    estoi(ref, est, sr=16000)   extended STOI (Jensen & Taal 2016; pystoi's extended=True), DESIGN.md section 13f: an EXTENSION metric,
+                                not in the reference's registry
+
+Every one takes lengths=: clip b of a zero-padded (or anyhow padded) batch is its first lengths[b] samples and scores bit for bit what
+it scores alone; nothing beyond is read.  lengths is a device int tensor [B] (used as it is, never read back: a captured graph
+replays with the lengths the tensor then holds), or a host sequence / numpy array / CPU tensor (checked for 0 <= len <= L, copied
+once).  Without the keyword the calls launch what they always did.
 
 Inputs are device tensors [B, L] or [L] (f32, 16 kHz for stoi); the result is a device tensor [B] (a 0-d tensor for [L]) and
 nothing is read back, so a call can be captured into a HIP graph once its tables and workspace exist (they are made on the first call
@@ -16,7 +23,7 @@ Deviations from the reference, recorded here and in DESIGN.md section 13:
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -25,6 +32,7 @@ from . import ops
 STOI_RATE = 16000
 _TABLES: Dict[torch.device, torch.Tensor] = {}
 _WORKSPACES: Dict[Tuple[torch.device, int, int], torch.Tensor] = {}
+_FULL_LENGTHS: Dict[Tuple[torch.device, int, int], torch.Tensor] = {}
 
 
 def _pair(ref: torch.Tensor, est: torch.Tensor, name: str):
@@ -42,38 +50,80 @@ def _pair(ref: torch.Tensor, est: torch.Tensor, name: str):
     return ref2.float().contiguous(), est2.float().contiguous(), single
 
 
-def si_sdr(ref: torch.Tensor, est: torch.Tensor) -> torch.Tensor:
+def _lengths(lengths, B: int, L: int, single: bool, device, name: str) -> Optional[torch.Tensor]:
+    """lengths= of the metrics -> int32 [B] on `device` (None stays None).  A device tensor is taken on trust (the kernels clamp to
+    [0, L]); anything on the host is judged here, before the device is touched."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, torch.Tensor) and lengths.device.type != "cpu":
+        if lengths.dtype in (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool):
+            raise TypeError(f"{name}: lengths must be an integer tensor, got {lengths.dtype}")
+        t = lengths.reshape(1) if single and lengths.numel() == 1 else lengths
+        if t.shape != (B,):
+            raise ValueError(f"{name}: lengths {tuple(lengths.shape)} for {B} clip(s): expected [{B}]")
+        return t.to(device=device, dtype=torch.int32).contiguous()
+    import numpy as np
+    a = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"{name}: lengths must be integers, got {a.dtype}")
+    if single and a.size == 1:
+        a = a.reshape(1)
+    if a.shape != (B,):
+        raise ValueError(f"{name}: lengths of shape {a.shape} for {B} clip(s): expected [{B}]" + (" or one value" if single else ""))
+    if a.min() < 0 or a.max() > L:
+        raise ValueError(f"{name}: lengths must lie in 0 .. L = {L}, got {int(a.min())} .. {int(a.max())}")
+    return torch.from_numpy(a.astype(np.int32)).to(device)
+
+
+def si_sdr(ref: torch.Tensor, est: torch.Tensor, lengths=None) -> torch.Tensor:
     r, e, single = _pair(ref, est, "si_sdr")
-    out = ops.si_sdr(r, e)
+    out = ops.si_sdr(r, e, _lengths(lengths, r.shape[0], r.shape[1], single, r.device, "si_sdr"))
     return out[0] if single else out
 
 
-def stoi(ref: torch.Tensor, est: torch.Tensor, sr: int = STOI_RATE) -> torch.Tensor:
+def stoi(ref: torch.Tensor, est: torch.Tensor, sr: int = STOI_RATE, extended: bool = False, lengths=None) -> torch.Tensor:
+    name = "estoi" if extended else "stoi"
     if sr != STOI_RATE:
-        raise ValueError(f"stoi: sr must be {STOI_RATE} (the only rate built), got {sr!r}")
-    r, e, single = _pair(ref, est, "stoi")
+        raise ValueError(f"{name}: sr must be {STOI_RATE} (the only rate built), got {sr!r}")
+    r, e, single = _pair(ref, est, name)
     dev = r.device
+    B, L = r.shape
+    lens = _lengths(lengths, B, L, single, dev, name)
     tab = _TABLES.get(dev)
     if tab is None:
         tab = _TABLES[dev] = ops.stoi_tables(dev)
-    key = (dev, r.shape[0], r.shape[1])
+    key = (dev, B, L)
     ws = _WORKSPACES.get(key)
     if ws is None:
-        ws = _WORKSPACES[key] = ops.stoi_workspace(r.shape[0], r.shape[1], dev)
-    out = ops.stoi(r, e, tab, ws)
+        ws = _WORKSPACES[key] = ops.stoi_workspace(B, L, dev)
+    if extended and lens is None:                                        # the C entry point of ESTOI takes lengths: the whole rows
+        lens = _FULL_LENGTHS.get(key)
+        if lens is None:
+            lens = _FULL_LENGTHS[key] = torch.full((B,), L, device=dev, dtype=torch.int32)
+    out = ops.stoi(r, e, tab, ws, lengths=lens, extended=bool(extended))
     return out[0] if single else out
 
 
+def estoi(ref: torch.Tensor, est: torch.Tensor, sr: int = STOI_RATE, lengths=None) -> torch.Tensor:
+    return stoi(ref, est, sr=sr, extended=True, lengths=lengths)
+
+
 class _Registry(dict):
-    """REGISTERED_METRICS of train_base/metrics.py:129-135, less the PESQ entries, which say why they are missing"""
+    """REGISTERED_METRICS of train_base/metrics.py:129-135, less the PESQ entries, which say why they are missing.  A name of
+    EXTENSION_METRICS is found by lookup without being listed: the registry's keys stay the reference's."""
 
     def __missing__(self, name):
+        if name in EXTENSION_METRICS:
+            return EXTENSION_METRICS[name]
         if name in ("WB_PESQ", "NB_PESQ"):
             raise KeyError(f"{name}: PESQ is not built on this path (it is an ITU reference program, not closed-form signal processing); "
                            f"registered metrics: {sorted(self)}")
-        raise KeyError(f"{name!r} is not a registered metric; registered metrics: {sorted(self)}")
+        raise KeyError(f"{name!r} is not a registered metric; registered metrics: {sorted(self)}; extension metrics: "
+                       f"{sorted(EXTENSION_METRICS)}")
 
 
 REGISTERED_METRICS = _Registry({"SI_SDR": si_sdr, "STOI": stoi})
+# metrics beyond the reference's registry, looked up through REGISTERED_METRICS by name ([trainer.validation] metrics = ["ESTOI", ...])
+EXTENSION_METRICS = {"ESTOI": estoi}
 # the reference's spellings (train_base/metrics.py:60,85)
-SI_SDR, STOI = si_sdr, stoi
+SI_SDR, STOI, ESTOI = si_sdr, stoi, estoi

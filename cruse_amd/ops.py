@@ -1295,11 +1295,22 @@ def _clip_pair(ref: torch.Tensor, est: torch.Tensor, name: str):
     return _p(_f32(ref, name)), _p(_f32(est, name)), ref.shape[0], ref.shape[1]
 
 
-def si_sdr(ref: torch.Tensor, est: torch.Tensor) -> torch.Tensor:
-    """SI-SDR in dB of every clip of est [B, L] against ref [B, L] -> [B] f32"""
+def _clip_lengths(lengths: torch.Tensor, B: int, device, name: str) -> torch.Tensor:
+    """lengths of a ragged batch: int32 [B] on the clips' device, read by the kernels only"""
+    if not isinstance(lengths, torch.Tensor):
+        raise RuntimeError(f"{name}: lengths must be an int32 device tensor [{B}] (cruse_amd.metrics takes host sequences)")
+    return _i32(lengths, B, device, f"{name}: lengths")
+
+
+def si_sdr(ref: torch.Tensor, est: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SI-SDR in dB of every clip of est [B, L] against ref [B, L] -> [B] f32; with lengths (int32 [B] on the device) clip b is its
+    first lengths[b] samples (cruse_si_sdr_ragged: clamped to [0, L], nothing beyond is loaded, 0 scores NaN)"""
     r, e, B, L = _clip_pair(ref, est, "si_sdr")
     out = torch.empty(B, device=ref.device, dtype=torch.float32)
-    check(lib.cruse_si_sdr(r, e, B, L, _p(out), _stream()))
+    if lengths is None:
+        check(lib.cruse_si_sdr(r, e, B, L, _p(out), _stream()))
+    else:
+        check(lib.cruse_si_sdr_ragged(r, e, B, L, _p(_clip_lengths(lengths, B, ref.device, "si_sdr")), _p(out), _stream()))
     return out
 
 
@@ -1323,12 +1334,22 @@ def stoi_workspace(B: int, L: int, device) -> torch.Tensor:
     return torch.empty(n, device=device, dtype=torch.float32)
 
 
-def stoi(ref: torch.Tensor, est: torch.Tensor, tab: torch.Tensor, ws: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """classic STOI of every clip of est [B, L] against ref [B, L], both at 16 kHz -> [B] f32; the stages stay in ws (stoi_layout)"""
+def stoi(ref: torch.Tensor, est: torch.Tensor, tab: torch.Tensor, ws: torch.Tensor, out: Optional[torch.Tensor] = None,
+         lengths: Optional[torch.Tensor] = None, extended: bool = False) -> torch.Tensor:
+    """classic STOI of every clip of est [B, L] against ref [B, L], both at 16 kHz -> [B] f32; the stages stay in ws (stoi_layout).
+    With lengths (int32 [B] on the device: clip b is its first lengths[b] samples) or extended (ESTOI) the call is cruse_stoi_ragged,
+    with the same tables and workspace; extended without lengths scores the whole rows."""
     r, e, B, L = _clip_pair(ref, est, "stoi")
     if out is None:
         out = torch.empty(B, device=ref.device, dtype=torch.float32)
-    check(lib.cruse_stoi(r, e, B, L, _p(_f32(tab, "stoi")), _p(ws), ws.numel() * ws.element_size(), _p(_f32(out, "stoi")), _stream()))
+    nbytes = ws.numel() * ws.element_size()
+    if lengths is None and not extended:
+        check(lib.cruse_stoi(r, e, B, L, _p(_f32(tab, "stoi")), _p(ws), nbytes, _p(_f32(out, "stoi")), _stream()))
+        return out
+    if lengths is None:
+        lengths = torch.full((B,), L, device=ref.device, dtype=torch.int32)
+    check(lib.cruse_stoi_ragged(r, e, B, L, _p(_clip_lengths(lengths, B, ref.device, "stoi")), 1 if extended else 0, _p(_f32(tab, "stoi")),
+                                _p(ws), nbytes, _p(_f32(out, "stoi")), _stream()))
     return out
 
 

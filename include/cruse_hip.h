@@ -943,6 +943,17 @@ size_t cruse_stoi_ws_bytes(int B, int L);
 int cruse_stoi_tables(float* tab, void* stream);
 /* ws: 8-byte aligned (CRUSE_E_ALIGN), ws_bytes >= cruse_stoi_ws_bytes(B, L) (CRUSE_E_SHAPE); its contents need no initialisation */
 int cruse_stoi(const float* ref, const float* est, int B, int L, const float* tab, void* ws, size_t ws_bytes, float* out, void* stream);
+/* Ragged batches and extended STOI (additive).  ref, est [B][L] as above; len: int[B] on the DEVICE, read by the
+ * kernels only and never by the host, so a captured graph replays with whatever lengths the array then holds.  Clip b is scored as the
+ * clip ref[b][0 : n], n = len[b] clamped to [0, L]: no sample at an index >= n is loaded (the padding may hold anything), the STOI
+ * stages use the clip's own L10 = (5 n + 7) / 8 and nF, and a clip scores bit for bit what cruse_si_sdr / cruse_stoi give it alone at
+ * L = n.  n = 0: SI-SDR NaN (0 / 0), STOI 1e-5.  extended != 0 scores ESTOI (Jensen & Taal 2016): stages 1 - 3 unchanged, then per
+ * 30-frame segment the 15 x 30 band matrices of ref and est, rows then columns less their mean and over (norm + 2^-52), no clipping;
+ * the segment scores sum(X^ Y^) / 30, the clip the mean over its segments (1e-5 without one).  Workspace, tables, bounds, refusals
+ * and the six launches are cruse_stoi's; a null len is refused too (CRUSE_E_SHAPE), all before any HIP call. */
+int cruse_si_sdr_ragged(const float* ref, const float* est, int B, int L, const int* len, float* out, void* stream);
+int cruse_stoi_ragged(const float* ref, const float* est, int B, int L, const int* len, int extended, const float* tab, void* ws,
+                      size_t ws_bytes, float* out, void* stream);
 
 /* ---- biquad cascade over whole clips (ABI 13, additive; csrc/biquad.hip) -----------------------------------
  * The lfilter under the reference's EQ augmentation (train_base/acoustics/audioAug.py:149-178; torchaudio.functional.lfilter there).
