@@ -171,6 +171,12 @@ SIGNATURES = {
     "cruse_peak_scale": ("ppiifpp", "i"),
     "cruse_resample_poly": ("piiippppiiipiipp", "i"),
     "cruse_assemble_clips": ("pppiiipp", "i"),
+    "cruse_grouped_linear_fwd": ("ppqqqpiiiiiipp", "i"),
+    "cruse_grouped_linear_bwd_dx": ("pppqqqiiiiiipp", "i"),
+    "cruse_grouped_linear_dw_ws_bytes": ("iiii", "z"),
+    "cruse_grouped_linear_bwd_dw": ("pppiiiiiipqqqppzp", "i"),
+    "cruse_band_pool": ("ppiiiipp", "i"),
+    "cruse_band_expand": ("ppiiiipp", "i"),
 }
 
 

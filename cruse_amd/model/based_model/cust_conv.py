@@ -319,3 +319,279 @@ class GroupGRU(nn.Module):
             else:
                 output = input
         return output, torch.cat(outstates, dim=0)
+
+
+# ======================================================================================================================
+# grouped linears, squeezed GRUs, ERB bands (cust_conv.py:187-247, :419-579)
+# ======================================================================================================================
+class GroupedLinearEinsum(nn.Module):
+    """cust_conv.py:503-542: weight [G, I/G, H/G], einsum("btgi,gih->btgh") flattened to [B, T, H] -- one cruse_grouped_linear_fwd
+    launch for all groups (exact-f32 MFMA), gradients through cruse_grouped_linear_bwd_dx / _bwd_dw."""
+
+    def __init__(self, input_size: int, hidden_size: int, groups: int = 1):
+        super().__init__()
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        self.groups = groups
+        assert input_size % groups == 0, f"Input size {input_size} not divisible by {groups}"
+        assert hidden_size % groups == 0, f"Hidden size {hidden_size} not divisible by {groups}"
+        self.ws = input_size // groups
+        self.register_parameter("weight", nn.Parameter(torch.zeros(groups, input_size // groups, hidden_size // groups),
+                                                       requires_grad=True))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+
+    def _run(self, x: Tensor, relu: bool) -> Tensor:
+        b, t, i = x.shape                                                               # (:530: three dimensions, as there)
+        if i != self.input_size:
+            raise RuntimeError(f"GroupedLinearEinsum: input has {i} features, expected {self.input_size}")
+        y = ops.GroupedLinearFn.apply(x.reshape(b * t, i), self.weight, None, "gih", relu, False)
+        return y.view(b, t, self.hidden_size)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self._run(x, False)
+
+    def __repr__(self):
+        cls = self.__class__.__name__
+        return f"{cls}(input_size: {self.input_size}, hidden_size: {self.hidden_size}, groups: {self.groups})"
+
+
+class GroupedLinear(nn.Module):
+    """cust_conv.py:545-579: `groups` nn.Linear layers over feature slices, outputs concatenated and, with shuffle, interleaved by
+    view(-1, H/G, G).transpose(-1, -2).  The layers are the parameter containers: per call their weights are gathered into one
+    [G, H/G, I/G] operand (and the biases into [H]) for one launch, the shuffle is the kernel's store index, and autograd scatters the
+    gradients of the gathered operands back to the layers.  Any leading dimensions, as the reference's slicing allows."""
+
+    def __init__(self, input_size: int, hidden_size: int, groups: int = 1, shuffle: bool = True):
+        super().__init__()
+        assert input_size % groups == 0
+        assert hidden_size % groups == 0
+        self.groups = groups
+        self.input_size = input_size // groups
+        self.hidden_size = hidden_size // groups
+        if groups == 1:
+            shuffle = False
+        self.shuffle = shuffle
+        self.layers = nn.ModuleList(nn.Linear(self.input_size, self.hidden_size) for _ in range(groups))
+
+    def forward(self, x: Tensor) -> Tensor:
+        if x.shape[-1] != self.groups * self.input_size:
+            raise RuntimeError(f"GroupedLinear: input has {x.shape[-1]} features, expected {self.groups * self.input_size}")
+        w = torch.stack([layer.weight for layer in self.layers])                       # [G, H/G, I/G]
+        bias = torch.cat([layer.bias for layer in self.layers])                         # [H], group-major
+        y = ops.GroupedLinearFn.apply(x.reshape(-1, x.shape[-1]), w, bias, "ghi", False, self.shuffle)
+        return y.view(*x.shape[:-1], self.groups * self.hidden_size)
+
+
+def _linear_act(seq: nn.Module, x: Tensor) -> Tensor:
+    """Sequential(GroupedLinearEinsum, act) of SqueezedGRU(_S): nn.Identity / nn.ReLU run in the kernel's epilogue, any other
+    activation module is applied to the kernel's output as it is."""
+    if isinstance(seq, nn.Identity):
+        return x
+    lin, act = seq[0], seq[1]
+    if type(act) is nn.Identity:
+        return lin._run(x, False)
+    if type(act) is nn.ReLU:
+        return lin._run(x, True)
+    return act(lin._run(x, False))
+
+
+class _StackedGruFn(_GroupedGruFn):
+    """_GroupedGruFn at g = 1 -- its forward, its recurrence backward and its gate gradients -- with the parameter gradients summed
+    in one order: _GroupedGruFn's bias gradients (ops.col_sum) and, from 1024 rows, its split-K weight gradients add with atomics,
+    so two runs differ in the last bits.  Here dW_ih / db_ih and dW_hh / db_hh each come from one cruse_grouped_linear_bwd_dw
+    launch (G = 1, the nn.GRU layout [3H, I] is its stacked-Linear layout; fixed-order row split), the latter against
+    h_{t-1} = (h0 or 0, h_0 .. h_{T-2}) laid out by one device copy, and dX from cruse_grouped_linear_bwd_dx."""
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, h, coef, an, z, w_ih, w_hh, _, _ = ctx.saved_tensors
+        B, T, I, _, H = ctx.dims
+        rows = B * T
+        dh = ops.gru_seq_bwd(dout.contiguous(), [w_hh.contiguous()], coef, z, B, T, 1, H, "f32")
+        dgi, dgh = ops.gru_gate_grads(dh, coef, an, rows, 1, H, "f32")
+        dgi, dgh = dgi.view(rows, 3 * H), dgh.view(rows, 3 * H)
+        first = ctx.h0.view(B, 1, H) if ctx.h0 is not None else h.new_zeros(B, 1, H)
+        h_prev = torch.cat((first, h[:, :-1]), dim=1).view(rows, H)
+        dw_ih, db_ih = ops.grouped_linear_bwd_dw(dgi, x.view(rows, I), (1, 3 * H, I), "ghi", want_db=True)
+        dw_hh, db_hh = ops.grouped_linear_bwd_dw(dgh, h_prev, (1, 3 * H, H), "ghi", want_db=True)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.grouped_linear_bwd_dx(dgi, w_ih.contiguous().view(1, 3 * H, I), "ghi").view(B, T, I)
+        return dx, None, None, dw_ih[0], dw_hh[0], db_ih, db_hh
+
+
+class _SqueezedBase(nn.Module):
+    def __init__(self, input_size: int, hidden_size: int, output_size: Optional[int] = None, num_layers: int = 1, linear_groups: int = 8,
+                 batch_first: bool = True, gru_skip_op=None, linear_act_layer=nn.Identity):
+        super().__init__()
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        if hidden_size % 32:
+            raise RuntimeError(f"cruse_amd {type(self).__name__}: hidden size {hidden_size} must be a multiple of 32")
+        self.linear_in = nn.Sequential(GroupedLinearEinsum(input_size, hidden_size, linear_groups), linear_act_layer())
+        self.gru = nn.GRU(hidden_size, hidden_size, num_layers=num_layers, batch_first=batch_first)   # the parameter container
+        self.gru_skip = gru_skip_op() if gru_skip_op is not None else None
+        if output_size is not None:
+            self.linear_out = nn.Sequential(GroupedLinearEinsum(hidden_size, output_size, linear_groups), linear_act_layer())
+        else:
+            self.linear_out = nn.Identity()
+
+    def _gru(self, x: Tensor, h: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+        """The stacked nn.GRU on batch-major x [B, T, hidden]: every layer is _GroupedGruFn with one group (_StackedGruFn: the same
+        forward and recurrence, parameter gradients in a fixed order)."""
+        L, B, H = self.gru.num_layers, x.shape[0], self.hidden_size
+        if h is not None:
+            if tuple(h.shape) != (L, B, H):
+                raise RuntimeError(f"{type(self).__name__}: state {tuple(h.shape)} != {(L, B, H)}")
+            h = h.detach().to(x.device, torch.float32)
+        states = []
+        for k in range(L):
+            params = [getattr(self.gru, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+            x = _StackedGruFn.apply(x, 1, None if h is None else h[k].contiguous(), *params)
+            states.append(x[:, -1, :])
+        return x, torch.stack(states, dim=0)
+
+    def _skip(self, x: Tensor, inp: Tensor) -> Tensor:
+        from ...nn_generic import add
+        if self.gru_skip is None:
+            return x
+        if type(self.gru_skip) is not nn.Identity:
+            inp = self.gru_skip(inp)
+        return add(x, inp.contiguous())
+
+    def forward(self, input: Tensor, h: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        if not self.gru.batch_first:
+            # [T, B, I]: the kernels are batch-major -- one device transposition in, one out; h is [num_layers, B, hidden] either way
+            y, hn = self._forward_bf(input.transpose(0, 1).contiguous(), h)
+            return y.transpose(0, 1).contiguous(), hn
+        return self._forward_bf(input.contiguous(), h)
+
+
+class SqueezedGRU(_SqueezedBase):
+    """cust_conv.py:419-458: grouped linear in (+ activation), nn.GRU(hidden, hidden, num_layers), the skip added after the GRU and
+    before linear_out, grouped linear out (+ activation) or Identity.  Same arguments, children (linear_in, gru, gru_skip, linear_out)
+    and state-dict keys.  h is [num_layers, B, hidden] in and out.  A passed h is DETACHED, as GroupedGRULayer's is: torch's nn.GRU
+    would propagate a gradient into it, this block does not.  hidden_size must be a multiple of 32 (RuntimeError)."""
+
+    def _forward_bf(self, input: Tensor, h: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+        input = _linear_act(self.linear_in, input)
+        x, h = self._gru(input, h)
+        x = self._skip(x, input)
+        return _linear_act(self.linear_out, x), h
+
+
+class SqueezedGRU_S(_SqueezedBase):
+    """cust_conv.py:461-500: as SqueezedGRU, but the skip is added after linear_out, onto the block's own input (so output_size must
+    equal input_size when a skip is used).  A passed h is DETACHED (see SqueezedGRU)."""
+
+    def _forward_bf(self, input: Tensor, h: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+        x = _linear_act(self.linear_in, input)
+        x, h = self._gru(x, h)
+        x = _linear_act(self.linear_out, x)
+        return self._skip(x, input), h
+
+
+def freq2erb(freq_hz):
+    """cust_conv.py:210-211"""
+    return 9.265 * torch.log1p(freq_hz / (24.7 * 9.265))
+
+
+def erb2freq(n_erb):
+    """cust_conv.py:214-215"""
+    return 24.7 * 9.265 * (torch.exp(n_erb / 9.265) - 1.)
+
+
+def erb_fb(sr, fft_size, nb_bands, min_nb_freqs):
+    """cust_conv.py:218-247: widths (int16 [nb_bands]) of non-overlapping ERB-spaced bands over the fft_size / 2 + 1 bins, every band at
+    least min_nb_freqs wide; f32 arithmetic as there, so the widths are the reference's integer for integer."""
+    freq_width = sr / fft_size
+    erb_low = freq2erb(torch.Tensor([0.]))
+    erb_high = freq2erb(torch.Tensor([sr / 2]))
+    step = (erb_high - erb_low) / nb_bands
+    erb = torch.zeros([nb_bands], dtype=torch.int16)
+    prev_freq, freq_over = 0, 0
+    for i in range(nb_bands):
+        fb = int(torch.round(erb2freq(erb_low + (i + 1) * step) / freq_width))
+        nb_freqs = fb - prev_freq - freq_over
+        if nb_freqs < min_nb_freqs:
+            freq_over = min_nb_freqs - nb_freqs                                         # borrowed from the next band
+            nb_freqs = min_nb_freqs
+        else:
+            freq_over = 0
+        erb[i] = nb_freqs
+        prev_freq = fb
+    erb[nb_bands - 1] += 1                                                              # the Nyquist bin
+    too_large = torch.sum(erb) - (fft_size / 2 + 1)
+    if too_large > 0:
+        erb[nb_bands - 1] -= too_large
+    assert torch.sum(erb) == (fft_size / 2 + 1)
+    return erb
+
+
+def _widths(width) -> List[int]:
+    w = width.tolist() if hasattr(width, "tolist") else list(width)
+    return [int(v) for v in w]
+
+
+def erb_fb_use(width, sr: int, normalized: bool = True, inverse: bool = False) -> Tensor:
+    """cust_conv.py:187-207: the dense filterbank matrix, [F, n_bands] with 1 (normalized: 1 / width) over every band's bins, or its
+    transpose [n_bands, F] with 1 (NOT normalized: 1 / width -- the reference's asymmetry).  For users who want the matrix; the device
+    products are erb_apply / erb_apply_inverse.  sr does not enter the values (the reference builds a frequency axis only for its length)."""
+    w = _widths(width)
+    fb = torch.zeros((sum(w), len(w)))
+    b = 0
+    for i, n in enumerate(w):
+        fb[b:b + n, i] = 1
+        b += n
+    if inverse:
+        fb = fb.t()
+        if not normalized:
+            fb /= fb.sum(dim=1, keepdim=True)
+    elif normalized:
+        fb /= fb.sum(dim=0)
+    return fb
+
+
+_BAND_TABLES = {}
+
+
+def _band_table(width, device) -> Tuple[Tensor, int]:
+    """int32 [n_bands + 1] start offsets of the bands on `device` (built once per width list and device, so that a captured graph
+    replays without a host copy) and F = the sum of the widths; the table is judged here, on the host."""
+    w = tuple(_widths(width))
+    key = (w, str(device))
+    hit = _BAND_TABLES.get(key)
+    if hit is None:
+        if not w or min(w) < 1:
+            raise RuntimeError(f"erb bands: every width must be >= 1, got {list(w)}")
+        if sum(w) > ops.BAND_MAX_F:
+            raise RuntimeError(f"erb bands: {sum(w)} bins, at most {ops.BAND_MAX_F}")
+        starts = [0]
+        for n in w:
+            starts.append(starts[-1] + n)
+        hit = (torch.tensor(starts, dtype=torch.int32).to(device), starts[-1])
+        _BAND_TABLES[key] = hit
+    return hit
+
+
+def erb_apply(x: Tensor, width, normalized: bool = True) -> Tensor:
+    """x [..., F] @ erb_fb_use(width, sr, normalized) -> [..., n_bands] as band sums (cruse_band_pool): no matrix of zeros."""
+    starts, F = _band_table(width, x.device)
+    if x.shape[-1] != F:
+        raise RuntimeError(f"erb_apply: {x.shape[-1]} bins, the widths sum to {F}")
+    y = ops.BandPoolFn.apply(x.reshape(-1, F), starts, bool(normalized))
+    return y.view(*x.shape[:-1], starts.numel() - 1)
+
+
+def erb_apply_inverse(m: Tensor, width, normalized: bool = True) -> Tensor:
+    """m [..., n_bands] @ erb_fb_use(width, sr, normalized, inverse=True) -> [..., F] (cruse_band_expand); divides by the width when
+    NOT normalized, as the reference's matrix does."""
+    starts, F = _band_table(width, m.device)
+    nb = starts.numel() - 1
+    if m.shape[-1] != nb:
+        raise RuntimeError(f"erb_apply_inverse: {m.shape[-1]} bands, the table has {nb}")
+    y = ops.BandExpandFn.apply(m.reshape(-1, nb), starts, F, not normalized)
+    return y.view(*m.shape[:-1], F)

@@ -1597,3 +1597,162 @@ def assemble_clips(pool: torch.Tensor, seg, seg_first, L: int, out: Optional[tor
     check(lib.cruse_assemble_clips(_p(_f32(pool, "assemble_clips")), _p(seg_dev) if nseg else None, _p(first_dev), nseg, B, L,
                                    _p(_f32(out, "assemble_clips")), _stream()))
     return out
+
+
+# ======================================================================================================================
+# grouped linears and band pooling (cruse_grouped_linear_*, cruse_band_*; model/based_model/cust_conv.py builds GroupedLinearEinsum,
+# GroupedLinear, SqueezedGRU(_S) and the ERB products on them)
+# ======================================================================================================================
+GL_CAT, GL_SHUFFLED = 0, 1
+BAND_MAX_F = 2048           # CRUSE_BAND_MAX_F (include/cruse_hip.h)
+
+
+def _gl_dims(w_shape, layout: str):
+    """(G, Ig, Hg) and the element strides (group, in, out) of a contiguous weight: "gih" = [G, Ig, Hg] (GroupedLinearEinsum),
+    "ghi" = [G, Hg, Ig] (the stacked nn.Linear weights of GroupedLinear)."""
+    if len(w_shape) != 3:
+        raise RuntimeError(f"grouped_linear: the weight must be [G, ., .], got {tuple(w_shape)}")
+    if layout == "gih":
+        G, Ig, Hg = (int(v) for v in w_shape)
+        return G, Ig, Hg, (Ig * Hg, Hg, 1)
+    if layout == "ghi":
+        G, Hg, Ig = (int(v) for v in w_shape)
+        return G, Ig, Hg, (Hg * Ig, 1, Ig)
+    raise RuntimeError(f"grouped_linear: unknown weight layout {layout!r} (\"gih\" or \"ghi\")")
+
+
+def _gl_rows(t: torch.Tensor, width: int, name: str) -> int:
+    if t.dim() != 2 or t.shape[1] != width or t.shape[0] < 1:
+        raise RuntimeError(f"grouped_linear: {name} must be [rows >= 1, {width}], got {tuple(t.shape)}")
+    return int(t.shape[0])
+
+
+def grouped_linear(x: torch.Tensor, w: torch.Tensor, layout: str = "gih", bias: Optional[torch.Tensor] = None, relu: bool = False,
+                   shuffle: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [rows, G * Ig] -> y [rows, G * Hg]: group g maps its slice of x through its own [Ig -> Hg] weight (+ bias [G * Hg], group-major;
+    then ReLU), one launch for all groups.  shuffle: the outputs go where GroupedLinear(shuffle=True)'s view(-1, Hg, G).transpose(-1, -2)
+    puts them, in the store index."""
+    G, Ig, Hg, (sg, si, so) = _gl_dims(w.shape, layout)
+    rows = _gl_rows(x, G * Ig, "x")
+    if bias is not None and bias.numel() != G * Hg:
+        raise RuntimeError(f"grouped_linear: bias of {bias.numel()} elements, expected {G * Hg}")
+    if out is None:
+        out = torch.empty(rows, G * Hg, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (rows, G * Hg):
+        raise RuntimeError(f"grouped_linear: out {tuple(out.shape)} != {(rows, G * Hg)}")
+    check(lib.cruse_grouped_linear_fwd(_p(_f32(x, "grouped_linear")), _p(_f32(w, "grouped_linear")), sg, si, so,
+                                       _p(None if bias is None else _f32(bias, "grouped_linear")), rows, G, Ig, Hg, 1 if relu else 0,
+                                       GL_SHUFFLED if shuffle else GL_CAT, _p(_f32(out, "grouped_linear")), _stream()))
+    return out
+
+
+def grouped_linear_bwd_dx(dy: torch.Tensor, w: torch.Tensor, layout: str = "gih", y: Optional[torch.Tensor] = None,
+                          shuffle: bool = False) -> torch.Tensor:
+    """dx [rows, G * Ig] of grouped_linear; y: the saved output when the forward applied ReLU (its sign is the mask), else None."""
+    G, Ig, Hg, (sg, si, so) = _gl_dims(w.shape, layout)
+    rows = _gl_rows(dy, G * Hg, "dy")
+    if y is not None and y.shape != dy.shape:
+        raise RuntimeError(f"grouped_linear_bwd_dx: y {tuple(y.shape)} != dy {tuple(dy.shape)}")
+    dx = torch.empty(rows, G * Ig, device=dy.device, dtype=torch.float32)
+    check(lib.cruse_grouped_linear_bwd_dx(_p(_f32(dy, "grouped_linear_bwd_dx")), _p(None if y is None else _f32(y, "grouped_linear_bwd_dx")),
+                                          _p(_f32(w, "grouped_linear_bwd_dx")), sg, si, so, rows, G, Ig, Hg, 0 if y is None else 1,
+                                          GL_SHUFFLED if shuffle else GL_CAT, _p(dx), _stream()))
+    return dx
+
+
+def grouped_linear_bwd_dw(dy: torch.Tensor, x: torch.Tensor, w_shape, layout: str = "gih", y: Optional[torch.Tensor] = None,
+                          shuffle: bool = False, want_db: bool = False, ws: Optional[torch.Tensor] = None):
+    """(dw in the shape and layout of the weight, db [G * Hg] or None) of grouped_linear, all groups in one call; the row split and the
+    order of its sums depend on the shape alone.  ws: cruse_grouped_linear_dw_ws_bytes bytes, taken here when None."""
+    G, Ig, Hg, (sg, si, so) = _gl_dims(tuple(w_shape), layout)
+    rows = _gl_rows(dy, G * Hg, "dy")
+    if _gl_rows(x, G * Ig, "x") != rows:
+        raise RuntimeError(f"grouped_linear_bwd_dw: x has {x.shape[0]} rows, dy {rows}")
+    if y is not None and y.shape != dy.shape:
+        raise RuntimeError(f"grouped_linear_bwd_dw: y {tuple(y.shape)} != dy {tuple(dy.shape)}")
+    dw = torch.empty(tuple(w_shape), device=dy.device, dtype=torch.float32)
+    db = torch.empty(G * Hg, device=dy.device, dtype=torch.float32) if want_db else None
+    need = lib.cruse_grouped_linear_dw_ws_bytes(rows, G, Ig, Hg)
+    if ws is None and need:
+        ws = torch.empty(need // 4, device=dy.device, dtype=torch.float32)
+    nbytes = 0 if ws is None else ws.numel() * ws.element_size()
+    check(lib.cruse_grouped_linear_bwd_dw(_p(_f32(dy, "grouped_linear_bwd_dw")), _p(None if y is None else _f32(y, "grouped_linear_bwd_dw")),
+                                          _p(_f32(x, "grouped_linear_bwd_dw")), rows, G, Ig, Hg, 0 if y is None else 1,
+                                          GL_SHUFFLED if shuffle else GL_CAT, _p(dw), sg, si, so, _p(db), _p(ws), nbytes, _stream()))
+    return dw, db
+
+
+class GroupedLinearFn(torch.autograd.Function):
+    """grouped_linear with its three gradients; x [rows, G * Ig], w in `layout`, bias [G * Hg] or None."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, layout, relu, shuffle):
+        x, w = x.contiguous(), w.contiguous()
+        y = grouped_linear(x, w, layout, None if bias is None else bias.contiguous(), relu, shuffle)
+        ctx.cfg = (layout, bool(relu), bool(shuffle), tuple(w.shape), None if bias is None else tuple(bias.shape))
+        if any(ctx.needs_input_grad[:3]):
+            ng = ctx.needs_input_grad
+            # x only for the weight gradient, w only for the input gradient, y only as the ReLU mask
+            ctx.save_for_backward(x if (ng[1] or ng[2]) else None, w if ng[0] else None, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        layout, relu, shuffle, w_shape, b_shape = ctx.cfg
+        dy = dy.contiguous()
+        ng = ctx.needs_input_grad
+        dx = grouped_linear_bwd_dx(dy, w, layout, y, shuffle) if ng[0] else None
+        dw = db = None
+        if ng[1] or ng[2]:
+            dw, db = grouped_linear_bwd_dw(dy, x, w_shape, layout, y, shuffle, want_db=bool(ng[2]))
+            if db is not None:
+                db = db.view(b_shape)
+        return dx, dw if ng[1] else None, db, None, None, None
+
+
+def _band_args(t: torch.Tensor, starts: torch.Tensor, width: int, name: str):
+    if t.dim() != 2 or t.shape[1] != width or t.shape[0] < 1:
+        raise RuntimeError(f"{name}: expected [rows >= 1, {width}], got {tuple(t.shape)}")
+    if starts.dtype != torch.int32 or starts.dim() != 1 or starts.numel() < 2 or starts.device != t.device:
+        raise RuntimeError(f"{name}: the band table must be int32 [n_bands + 1] on {t.device}")
+    return int(t.shape[0]), int(starts.numel()) - 1
+
+
+def band_pool(x: torch.Tensor, starts: torch.Tensor, mean: bool) -> torch.Tensor:
+    """y[r, b] = w_b * sum of x[r, starts[b]:starts[b + 1]], w_b = 1 / width_b with `mean`, else 1.  x [rows, F] -> [rows, n_bands]."""
+    F = int(x.shape[-1])
+    rows, nb = _band_args(x, starts, F, "band_pool")
+    y = torch.empty(rows, nb, device=x.device, dtype=torch.float32)
+    check(lib.cruse_band_pool(_p(_f32(x, "band_pool")), _p(starts), rows, F, nb, 1 if mean else 0, _p(y), _stream()))
+    return y
+
+
+def band_expand(m: torch.Tensor, starts: torch.Tensor, F: int, mean: bool) -> torch.Tensor:
+    """y[r, f] = w_b * m[r, b] for the band b that holds bin f (0 where none does).  m [rows, n_bands] -> [rows, F]: band_pool's adjoint."""
+    rows, nb = _band_args(m, starts, int(starts.numel()) - 1, "band_expand")
+    y = torch.empty(rows, int(F), device=m.device, dtype=torch.float32)
+    check(lib.cruse_band_expand(_p(_f32(m, "band_expand")), _p(starts), rows, int(F), nb, 1 if mean else 0, _p(y), _stream()))
+    return y
+
+
+class BandPoolFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, starts, mean):
+        ctx.starts, ctx.mean, ctx.F = starts, bool(mean), int(x.shape[-1])
+        return band_pool(x.contiguous(), starts, mean)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return band_expand(dy.contiguous(), ctx.starts, ctx.F, ctx.mean), None, None
+
+
+class BandExpandFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, m, starts, F, mean):
+        ctx.starts, ctx.mean = starts, bool(mean)
+        return band_expand(m.contiguous(), starts, F, mean)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return band_pool(dy.contiguous(), ctx.starts, ctx.mean), None, None, None

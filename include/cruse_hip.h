@@ -1033,6 +1033,47 @@ int cruse_resample_poly(const void* src, int fmt, int channels, int chan, const 
  * before any HIP call: a null pool / seg_first / out, a null seg with nseg > 0, B < 1, L < 1, L > 2^31 - 1025, nseg < 0. */
 int cruse_assemble_clips(const float* pool, const long long* seg, const int* seg_first, int nseg, int B, int L, float* out, void* stream);
 
+/* ---- grouped linears and band pooling (ABI 14, additive; csrc/grouped_linear.hip) ----------------------------
+ * G independent linears over the feature slices of x [rows][G Ig]: group g maps columns [g Ig, (g + 1) Ig) to Hg outputs with
+ * w[g w_sg + i w_si + j w_so] (element strides, all >= 1), so one kernel serves GroupedLinearEinsum's weight [G][Ig][Hg]
+ * (model/based_model/cust_conv.py:517-522, :536; strides (Ig Hg, Hg, 1)) and the stacked nn.Linear weights [G][Hg][Ig] of
+ * GroupedLinear (:565-573; strides (Hg Ig, 1, Ig)).  bias [G Hg] (group-major, nullable), then ReLU if relu != 0.  Output j of group g
+ * goes to column g Hg + j (CRUSE_GL_CAT: the flatten of :537, the cat of :574) or, CRUSE_GL_SHUFFLED, to where GroupedLinear's
+ * view(-1, Hg, G).transpose(-1, -2) (:575-578) moves it: with c = g Hg + j, column (c % G) Hg + c / G -- applied in the store index.
+ * Exact f32 (v_mfma_f32_16x16x4_f32), no atomics, one summation order: bit-identical from run to run.  No allocation, no host
+ * synchronisation (the calls capture into a HIP graph).  Any rows, Ig, Hg >= 1: fragments are padded with zeros in registers and
+ * nothing is read or written outside x, w, bias, y.  Refused with CRUSE_E_SHAPE before any HIP call: a null x / w / y / dy / dx / dw,
+ * rows, G, Ig or Hg < 1, rows > 2^30, G Ig or G Hg >= 2^31, a stride < 1, an unknown out_map, G * ceil(max(Ig, Hg) / 64) > 65535,
+ * relu != 0 with a null y (backward), a workspace that is missing or too small. */
+#define CRUSE_GL_CAT 0
+#define CRUSE_GL_SHUFFLED 1
+int cruse_grouped_linear_fwd(const float* x, const float* w, long long w_sg, long long w_si, long long w_so, const float* bias, int rows,
+                             int G, int Ig, int Hg, int relu, int out_map, float* y, void* stream);
+/* dx [rows][G Ig] = (dy under the ReLU mask y > 0 when relu != 0; dy and y in the forward's column map) times the groups' weights
+ * transposed.  One launch. */
+int cruse_grouped_linear_bwd_dx(const float* dy, const float* y, const float* w, long long w_sg, long long w_si, long long w_so, int rows,
+                                int G, int Ig, int Hg, int relu, int out_map, float* dx, void* stream);
+/* dw[g w_sg + i w_si + j w_so] = sum over rows of x[row][g Ig + i] dy'[row][g, j], db[g Hg + j] = sum over rows of dy'[row][g, j]
+ * (db nullable), dy' = dy under the ReLU mask; both are WRITTEN, not added to.  One launch covers all groups; when the rows are
+ * split over parts (a function of the shape alone) every part writes its own slab of ws and a second launch adds the slabs in
+ * ascending order of the part.  ws: cruse_grouped_linear_dw_ws_bytes() bytes (0: ws may be null), needs no initialisation. */
+size_t cruse_grouped_linear_dw_ws_bytes(int rows, int G, int Ig, int Hg);
+int cruse_grouped_linear_bwd_dw(const float* dy, const float* y, const float* x, int rows, int G, int Ig, int Hg, int relu, int out_map,
+                                float* dw, long long w_sg, long long w_si, long long w_so, float* db, void* ws, size_t ws_bytes,
+                                void* stream);
+/* The products with erb_fb_use's matrices (model/based_model/cust_conv.py:187-207) as sums over contiguous bands.  starts: int32
+ * [n_bands + 1] on the device, band b = bins [starts[b], starts[b + 1]); the kernels clamp every entry into [0, F] and never touch
+ * memory outside a row whatever the table holds (a bin no band covers expands to 0).  w_b = 1 / width_b if mean != 0, else 1.
+ *   cruse_band_pool:   y[r][b] = w_b sum_{f in band b} x[r][f]      x [rows][F]       -> y [rows][n_bands]   (x @ fb, :197-206)
+ *   cruse_band_expand: y[r][f] = w_b(f) m[r][b(f)]                  m [rows][n_bands] -> y [rows][F]         (m @ fb.t(), :200-203)
+ * Each is the other's adjoint at the same `mean`, so each is the other's backward.  One pass, f32 adds in ascending f and one
+ * multiply, 16-byte accesses on the [rows][F] side when its base is 16-byte aligned (a block holds 4 rows, which start on a 16-byte
+ * boundary for any F).  One launch, capturable.  Refused with CRUSE_E_SHAPE before any HIP call: a null pointer, rows outside
+ * 1..2^30, F outside 1..CRUSE_BAND_MAX_F, n_bands outside 1..F. */
+#define CRUSE_BAND_MAX_F 2048
+int cruse_band_pool(const float* x, const int* starts, int rows, int F, int n_bands, int mean, float* y, void* stream);
+int cruse_band_expand(const float* m, const int* starts, int rows, int F, int n_bands, int mean, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
