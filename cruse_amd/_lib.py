@@ -162,6 +162,8 @@ SIGNATURES = {
     "cruse_stoi": ("ppiippzpp", "i"),
     "cruse_si_sdr_ragged": ("ppiippp", "i"),
     "cruse_stoi_ragged": ("ppiipippzpp", "i"),
+    "cruse_sdr_ws_bytes": ("iii", "z"),
+    "cruse_sdr": ("pppiiipppp", "i"),
     "cruse_biquad_ws_bytes": ("iii", "z"),
     "cruse_biquad_cascade": ("ppiiiiippp", "i"),
     "cruse_fftconv_spec_bytes": ("iii", "z"),

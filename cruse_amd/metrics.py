@@ -1,9 +1,12 @@
-"""Validation metrics on the device: the two closed-form entries of the reference's train_base/metrics.py.
+"""Validation metrics on the device: the closed-form entries of the reference's train_base/metrics.py.
 
     si_sdr(ref, est)            SI_SDR (:60-82), dB
     stoi(ref, est, sr=16000)    STOI (:85-86): the classic, non-extended measure as DESIGN.md section 13 defines it
     estoi(ref, est, sr=16000)   extended STOI (Jensen & Taal 2016; pystoi's extended=True), DESIGN.md section 13f: an EXTENSION metric,
                                 not in the reference's registry
+    sdr(ref, est, sr=16000, filter_len=512)
+                                SDR (:55-57): bss_eval_sources for one source as DESIGN.md section 13g defines it, dB; the reference
+                                defines it without registering it (UNREGISTERED_REFERENCE_METRICS)
 
 Every one takes lengths=: clip b of a zero-padded (or anyhow padded) batch is its first lengths[b] samples and scores bit for bit what
 it scores alone; nothing beyond is read.  lengths is a device int tensor [B] (used as it is, never read back: a captured graph
@@ -20,6 +23,8 @@ Deviations from the reference, recorded here and in DESIGN.md section 13:
   * The reference's best-epoch score is (STOI + (WB_PESQ + 0.5) / 5) / 2 (base_trainer.py:370-376), which needs PESQ; the trainer
     here scores an epoch by the enhanced mean of ONE metric, [trainer.validation] score_metric.
   * pystoi is not installed where this was written: agreement with it is not claimed, only with the stated definition.
+  * mir_eval is not installed either: the same holds for sdr.  Where mir_eval raises or falls back to lstsq (an empty clip, an all-zero
+    reference, a Toeplitz system that is not positive definite in floating point) sdr returns NaN.
 """
 from __future__ import annotations
 
@@ -33,6 +38,8 @@ STOI_RATE = 16000
 _TABLES: Dict[torch.device, torch.Tensor] = {}
 _WORKSPACES: Dict[Tuple[torch.device, int, int], torch.Tensor] = {}
 _FULL_LENGTHS: Dict[Tuple[torch.device, int, int], torch.Tensor] = {}
+SDR_FILTER_LEN = 512                                                      # bss_eval_sources' flen
+_SDR_WORKSPACES: Dict[Tuple[torch.device, int, int, int], torch.Tensor] = {}
 
 
 def _pair(ref: torch.Tensor, est: torch.Tensor, name: str):
@@ -108,22 +115,45 @@ def estoi(ref: torch.Tensor, est: torch.Tensor, sr: int = STOI_RATE, lengths=Non
     return stoi(ref, est, sr=sr, extended=True, lengths=lengths)
 
 
+def sdr(ref: torch.Tensor, est: torch.Tensor, sr: int = STOI_RATE, filter_len: int = SDR_FILTER_LEN, lengths=None) -> torch.Tensor:
+    """bss_eval SDR of one source: est may be any filter_len-tap filtering of ref before anything counts as error"""
+    if sr != STOI_RATE:
+        raise ValueError(f"sdr: sr must be {STOI_RATE} (the only rate built), got {sr!r}")
+    if isinstance(filter_len, bool) or not isinstance(filter_len, int) or not 1 <= filter_len <= ops.SDR_MAX_TAPS:
+        raise ValueError(f"sdr: filter_len must be an integer in 1 .. {ops.SDR_MAX_TAPS}, got {filter_len!r}")
+    r, e, single = _pair(ref, est, "sdr")
+    dev = r.device
+    B, L = r.shape
+    lens = _lengths(lengths, B, L, single, dev, "sdr")
+    key = (dev, B, L, filter_len)
+    ws = _SDR_WORKSPACES.get(key)
+    if ws is None:
+        ws = _SDR_WORKSPACES[key] = ops.sdr_workspace(B, L, filter_len, dev)
+    out = ops.sdr(r, e, ws, filter_len, lengths=lens)
+    return out[0] if single else out
+
+
 class _Registry(dict):
     """REGISTERED_METRICS of train_base/metrics.py:129-135, less the PESQ entries, which say why they are missing.  A name of
-    EXTENSION_METRICS is found by lookup without being listed: the registry's keys stay the reference's."""
+    EXTENSION_METRICS, then of UNREGISTERED_REFERENCE_METRICS, is found by lookup without being listed: the registry's keys stay the
+    reference's."""
 
     def __missing__(self, name):
         if name in EXTENSION_METRICS:
             return EXTENSION_METRICS[name]
+        if name in UNREGISTERED_REFERENCE_METRICS:
+            return UNREGISTERED_REFERENCE_METRICS[name]
         if name in ("WB_PESQ", "NB_PESQ"):
             raise KeyError(f"{name}: PESQ is not built on this path (it is an ITU reference program, not closed-form signal processing); "
                            f"registered metrics: {sorted(self)}")
         raise KeyError(f"{name!r} is not a registered metric; registered metrics: {sorted(self)}; extension metrics: "
-                       f"{sorted(EXTENSION_METRICS)}")
+                       f"{sorted(EXTENSION_METRICS)}; reference metrics outside its registry: {sorted(UNREGISTERED_REFERENCE_METRICS)}")
 
 
 REGISTERED_METRICS = _Registry({"SI_SDR": si_sdr, "STOI": stoi})
 # metrics beyond the reference's registry, looked up through REGISTERED_METRICS by name ([trainer.validation] metrics = ["ESTOI", ...])
 EXTENSION_METRICS = {"ESTOI": estoi}
-# the reference's spellings (train_base/metrics.py:60,85)
-SI_SDR, STOI, ESTOI = si_sdr, stoi, estoi
+# metrics that the reference's file defines but does not register (train_base/metrics.py:55-57), looked up the same way
+UNREGISTERED_REFERENCE_METRICS = {"SDR": sdr}
+# the reference's spellings (train_base/metrics.py:55,60,85)
+SI_SDR, STOI, ESTOI, SDR = si_sdr, stoi, estoi, sdr

@@ -1353,6 +1353,41 @@ def stoi(ref: torch.Tensor, est: torch.Tensor, tab: torch.Tensor, ws: torch.Tens
     return out
 
 
+SDR_CHUNK = 2048            # CRUSE_SDR_CHUNK (include/cruse_hip.h): samples of a correlation chunk and outputs of a projection tile
+SDR_MAX_TAPS = 1024         # CRUSE_SDR_MAX_TAPS
+
+
+def sdr_workspace(B: int, L: int, K: int, device) -> torch.Tensor:
+    """a float64 tensor of cruse_sdr_ws_bytes(B, L, K) bytes (raises where the shape is refused)"""
+    n = lib.cruse_sdr_ws_bytes(int(B), int(L), int(K))
+    if n == 0:
+        raise RuntimeError(f"sdr_workspace: cruse_hip error -1: {(lib.cruse_last_error() or b'').decode()}")
+    return torch.empty(n // 8, device=device, dtype=torch.float64)
+
+
+def sdr(ref: torch.Tensor, est: torch.Tensor, ws: torch.Tensor, filter_len: int = 512, out: Optional[torch.Tensor] = None,
+        lengths: Optional[torch.Tensor] = None, dbg: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bss_eval SDR in dB (one source, filter_len taps) of every clip of est [B, L] against ref [B, L] -> [B]
+    f32.  ws: sdr_workspace(B, L, filter_len, device).  lengths: int32 [B] on the device, clip b is its first lengths[b] samples.
+    dbg: float64 [B, 3 K + 2] on the device, receives raa, rab, C and the energies of s_target and of the error per clip."""
+    r, e, B, L = _clip_pair(ref, est, "sdr")
+    K = int(filter_len)
+    need = lib.cruse_sdr_ws_bytes(B, L, K)
+    if need == 0:
+        check(-1)
+    if ws.numel() * ws.element_size() < need:
+        raise RuntimeError(f"sdr: workspace of {ws.numel() * ws.element_size()} bytes, cruse_sdr_ws_bytes({B}, {L}, {K}) = {need}")
+    if out is None:
+        out = torch.empty(B, device=ref.device, dtype=torch.float32)
+    elif out.numel() != B:
+        raise RuntimeError(f"sdr: out of {out.numel()} elements for {B} clip(s)")
+    if dbg is not None and (dbg.dtype != torch.float64 or dbg.numel() != B * (3 * K + 2)):
+        raise RuntimeError(f"sdr: dbg must be float64 [{B}, {3 * K + 2}], got {dbg.dtype} {tuple(dbg.shape)}")
+    ln = None if lengths is None else _p(_clip_lengths(lengths, B, ref.device, "sdr"))
+    check(lib.cruse_sdr(r, e, ln, B, L, K, _p(ws), _p(_f32(out, "sdr")), _p(dbg), _stream()))
+    return out
+
+
 # ======================================================================================================================
 # biquad cascade (cruse_biquad_cascade; cruse_amd/acoustics/audio_aug.py designs the sections, data.DevicePairs applies them)
 # ======================================================================================================================

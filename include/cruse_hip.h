@@ -954,6 +954,24 @@ int cruse_stoi(const float* ref, const float* est, int B, int L, const float* ta
 int cruse_si_sdr_ragged(const float* ref, const float* est, int B, int L, const int* len, float* out, void* stream);
 int cruse_stoi_ragged(const float* ref, const float* est, int B, int L, const int* len, int extended, const float* tab, void* ws,
                       size_t ws_bytes, float* out, void* stream);
+/* bss_eval SDR of one source (additive; csrc/sdr.hip): SDR of train_base/metrics.py:55-57, which is
+ * mir_eval.separation.bss_eval_sources(reference[None, :], estimation[None, :]) -- the estimate may be any K-tap time-invariant
+ * filtering of the reference before anything counts as error.  Per clip of n samples (n = len[b] clamped to [0, L]; len null: n = L;
+ * len is an int[B] DEVICE array that only the kernels read) and K taps, 1 <= K <= CRUSE_SDR_MAX_TAPS (bss_eval_sources uses 512):
+ *   raa[k] = sum_i ref[i] ref[i+k], rab[k] = sum_i ref[i] est[i+k], 0 <= k < K, samples outside [0, n) zero;  toeplitz(raa) C = rab;
+ *   s[m] = sum_k C[k] ref[m-k], e[m] = est[m] - s[m] (est zero from n on), 0 <= m < n + K - 1;  out[b] = 10 log10(sum s^2 / sum e^2).
+ * f32 in, every product, sum, the solve (Levinson) and the projection in f64, out f32.  out[b] = NaN, and nothing faults, for n = 0, an
+ * all-zero ref, or a solve that meets a non-positive r[0] / prediction error (mir_eval raises or falls back to lstsq there).  No sample
+ * at an index >= n is loaded; the order of every sum follows from n and K alone, no atomics: a clip scores bit for bit the same alone,
+ * in a batch and from run to run.  Four launches, none waited for by the host: the call captures into a HIP graph.
+ * ws: cruse_sdr_ws_bytes(B, L, K) bytes (0 where the shape is refused), 8-byte aligned (CRUSE_E_ALIGN), no initialisation needed.
+ * dbg (nullable, 8-byte aligned): per clip 3 K + 2 doubles: raa[K], rab[K], C[K] (NaN without a solution), sum s^2, sum e^2.
+ * The correlations are summed per chunk of CRUSE_SDR_CHUNK samples and the chunks in ascending order.  Refused with CRUSE_E_SHAPE before
+ * any HIP call: null ref / est / ws / out, B < 1 or > 65535, L < 1 or > 2^28, K < 1 or > CRUSE_SDR_MAX_TAPS. */
+#define CRUSE_SDR_CHUNK 2048
+#define CRUSE_SDR_MAX_TAPS 1024
+size_t cruse_sdr_ws_bytes(int B, int L, int K);
+int cruse_sdr(const float* ref, const float* est, const int* len, int B, int L, int K, void* ws, float* out, double* dbg, void* stream);
 
 /* ---- biquad cascade over whole clips (ABI 13, additive; csrc/biquad.hip) -----------------------------------
  * The lfilter under the reference's EQ augmentation (train_base/acoustics/audioAug.py:149-178; torchaudio.functional.lfilter there).

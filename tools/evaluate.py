@@ -1,7 +1,7 @@
 """Score a checkpoint on a list of paired WAV files (cruse_amd.evaluate.evaluate_files):
 
     python tools/evaluate.py --config cfg.toml --checkpoint runs/cfg/checkpoints/best_model.tar \\
-        --clean-list clean.txt --noisy-list noisy.txt [--batch-size 16] [--metrics SI_SDR STOI ESTOI] [--csv scores.csv]
+        --clean-list clean.txt --noisy-list noisy.txt [--batch-size 16] [--metrics SI_SDR STOI ESTOI SDR] [--csv scores.csv]
 
 The model is built from the config's [model] section as tools/train_stand.py builds it; the checkpoint is a *.tar of the trainer
 (its "model" entry) or a bare state dict (model_NNNN.pth).  Prints one line per metric with the Noisy and Enhanced means."""
