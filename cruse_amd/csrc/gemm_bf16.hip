@@ -60,6 +60,17 @@ __device__ __forceinline__ long long seg_row(const GbArgs& g, int m) {
     return (long long)q * g.seg_stride + g.seg_off + (m - q * g.seg_len);
 }
 
+// ATR: one A fragment from the k-major LDS image (see the kernel's header) -- two transposing reads, k-rows 4 apart
+__device__ __forceinline__ bf16x8 read_a_tr(const unsigned char* p) {
+    typedef __attribute__((ext_vector_type(4))) short s16x4_;
+    typedef __attribute__((address_space(3))) s16x4_ lds_s16x4;
+    typedef __attribute__((ext_vector_type(8))) short s16x8_;
+    const s16x4_ lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
+    const s16x4_ hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * 128));
+    const s16x8_ both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, both);
+}
+
 // MODE: C update -- 0 store, 1 read-add-store, 2 atomic add (split-K), 3 store as bf16 (C is then a bf16 tensor, ldc in its elements),
 // 4 split-K with every k-slice STORING its partial sums to its own slab C + tz * slab (summed by gemm_slab_reduce_kernel): the
 // f32 atomics of MODE 2 from the 8 XCDs meet at the memory side -- 9.8 M of them per weight-gradient product, 0.14 ms per step.
@@ -67,11 +78,7 @@ __device__ __forceinline__ long long seg_row(const GbArgs& g, int m) {
 // overlap the other block's k-loop); 3 = two k-tiles in flight behind counted vmcnt waits and one raw barrier per
 // k-tile, one block per CU (the split-K weight gradients: hundreds of k-tiles streamed once, where the k-loop is
 // bound by the latency of the next tile's loads).
-// BMT: 1 = 128 x 128 tiles on 4 wavefronts; 2 = 256 x 128 tiles on 8 wavefronts (4 x 2, the same 64 x 64 block per wave) with THREE
-// stages -- 96 KB of operands in flight per CU instead of 64, 48 KB instead of 64 KB per 256 x 128 x 64 of work.  MEASURED SLOWER and off
-// (library option gb_bm256): gi 96 -> 118 us, dX 85 -> 105 us alone (r4): one 8-wave block per CU loses more at its barriers than two
-// independent 4-wave blocks that fill each other's stalls.  Alone these two products run at 0.66 / 0.74 PFLOP/s; their 150-165 us in the
-// step are cold operands and the side stream's traffic, not this loop.
+// (A 256 x 128 tile on 8 wavefronts and a pinned MFMA / LDS-read schedule were measured and not kept: DESIGN.md section 8.)
 // F16: the operands are IEEE f16 (same bytes per element, same staging and fragment layout; v_mfma_f32_16x16x32_f16): the forward gate
 // projection as ONE pass -- 11 significant bits on both operands against 8 + the W_ih low-plane pass of the split-bf16 form (cruse_gemm_f16_nt).
 // ATR: the A tile is staged from a k-major source ([64 k][64 m] per 64-row block: 8 KB contiguous per block and k-tile, lane-linear LDS-DMA as
@@ -80,13 +87,13 @@ __device__ __forceinline__ long long seg_row(const GbArgs& g, int m) {
 // bytes (32 banks) apart, and a 32-lane service group reads rows {0..3} + 8 kg of one parity class each: the 16-byte chunks of row k are XOR-swizzled
 // (on the global SOURCE address, as for the row-major image) by ((k >> 1 & 1) | (k >> 3 & 1) << 1) << 1, which puts the four same-parity rows of a
 // group on four different 32-byte bank windows -- conflict-free.
-template <int MODE, int NST, int BMT = 1, bool F16 = false, bool ATR = false, bool PIPE = false>
-__global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gemm_bf16_nt_kernel(const GbArgs g) {
-    static_assert(!ATR || (BMT == 1 && !F16), "transposed-A staging: 128-row tiles, bf16");
-    constexpr int BM_ = BM * BMT, A_BYTES = TILE_BYTES * BMT, STAGE_BYTES = A_BYTES + TILE_BYTES;
+template <int MODE, int NST, bool F16 = false, bool ATR = false>
+__global__ __launch_bounds__(256, NST == 2 ? 2 : 1) void gemm_bf16_nt_kernel(const GbArgs g) {
+    static_assert(!ATR || !F16, "transposed-A staging: bf16");
+    constexpr int STAGE_BYTES = 2 * TILE_BYTES;
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem_dyn[];
     auto As_ = [&](int buf) -> unsigned char* { return smem_dyn + (size_t)buf * STAGE_BYTES; };            // [stage][A | B]
-    auto Bs_ = [&](int buf) -> unsigned char* { return smem_dyn + (size_t)buf * STAGE_BYTES + A_BYTES; };
+    auto Bs_ = [&](int buf) -> unsigned char* { return smem_dyn + (size_t)buf * STAGE_BYTES + TILE_BYTES; };
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wm = wv >> 1, wn = wv & 1;
     // XCD-aware tile order, as in gemm.hip: a unit -- the n-tiles of one m-tile, or with split-K the m-tiles of one
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
     }
     const int gq = g.tn_per_g > 0 ? tn / g.tn_per_g : 0;                  // product (GRU group) of this column tile
     if (g.tn_per_g > 0) tn -= gq * g.tn_per_g;
-    const int m0 = tm * BM_, n0 = tn * BN;
+    const int m0 = tm * BM, n0 = tn * BN;
     const __bf16* Abase = g.A + gq * g.a_gstep;
     const __bf16* Bbase = g.B + gq * g.b_gstep;
     int m_lim = g.m_end0, c_sh = 0;
@@ -124,11 +131,9 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
     const int nreal = kt1 - kt0;
     const int nvirt = (g.b_lo ? (g.a_lo ? 3 : 2) : 1) * nreal;      // (hi,hi) [, (hi,lo) [, (lo,hi)]]
 
-    // staging: wave wv fills rows [wv*32, wv*32+32) of the A tile and its share of the B tile (32 rows of 128 on 4 waves, 16 on 8),
-    // 8 rows (1 KiB) per instruction
-    constexpr int NB_I = 4 / BMT;
+    // staging: wave wv fills rows [wv*32, wv*32+32) of the A tile and of the B tile, 8 rows (1 KiB) per instruction
     const __bf16* ap[4];
-    const __bf16* bp[NB_I];
+    const __bf16* bp[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if constexpr (ATR) {
@@ -144,8 +149,8 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
         }
     }
 #pragma unroll
-    for (int i = 0; i < NB_I; ++i) {
-        const int r = (wv * NB_I + i) * 8 + (lane >> 3);
+    for (int i = 0; i < 4; ++i) {
+        const int r = (wv * 4 + i) * 8 + (lane >> 3);
         const int ch = (lane & 7) ^ (lane >> 3);
         bp[i] = Bbase + (long long)min(n0 + r, g.N - 1) * g.ldb + ch * 8;
     }
@@ -158,8 +163,8 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
         for (int i = 0; i < 4; ++i)
             __builtin_amdgcn_global_load_lds((glb_ptr_t*)(ap[i] + oa), (lds_ptr_t*)(As_(buf) + (wv * 4 + i) * 1024), 16, 0, 0);
 #pragma unroll
-        for (int i = 0; i < NB_I; ++i)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t*)(bp[i] + ob), (lds_ptr_t*)(Bs_(buf) + (wv * NB_I + i) * 1024), 16, 0, 0);
+        for (int i = 0; i < 4; ++i)
+            __builtin_amdgcn_global_load_lds((glb_ptr_t*)(bp[i] + ob), (lds_ptr_t*)(Bs_(buf) + (wv * 4 + i) * 1024), 16, 0, 0);
     };
 
     f32x4 acc[4][4];
@@ -187,54 +192,8 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
             offt[i] = wm * 8192 + (kg * 8 + q) * 128 + (((i ^ gsw) * 2 + ((c15 & 3) >> 1)) * 16) + (c15 & 1) * 8;
     }
 
-    // One k-tile = two 32-deep halves of 16 MFMAs per wave.  CRUSE_GB_PIPE: the fragment reads of both halves first, the order then pinned with
-    // sched_group_barrier (reads of half 0, one read of half 1 behind each of the first MFMAs of half 0, the remaining MFMAs) -- left to itself the
-    // scheduler re-uses the A fragment registers and waits with lgkmcnt(0) in front of every group of 4 to 8 MFMAs, which measured no slower.
-    auto compute_pipe = [&](int buf) {
-        const unsigned char* As = As_(buf);
-        const unsigned char* Bs = Bs_(buf);
-        bf16x8 fa[2][4], fb[2][4];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if constexpr (ATR) {
-                    typedef __attribute__((ext_vector_type(4))) short s16x4_;
-                    typedef __attribute__((address_space(3))) s16x4_ lds_s16x4;
-                    typedef __attribute__((ext_vector_type(8))) short s16x8_;
-                    const s16x4_ lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(As + offt[i] + kk * 32 * 128));
-                    const s16x4_ hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(As + offt[i] + kk * 32 * 128 + 4 * 128));
-                    const s16x8_ both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    fa[kk][i] = __builtin_bit_cast(bf16x8, both);
-                } else {
-                    fa[kk][i] = *reinterpret_cast<const bf16x8*>(As + offa[kk] + i * 16 * 128);
-                }
-                fb[kk][i] = *reinterpret_cast<const bf16x8*>(Bs + offb[kk] + i * 16 * 128);
-            }
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if constexpr (F16) {
-                        typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_;
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_, fa[kk][i]), __builtin_bit_cast(f16x8_, fb[kk][j]),
-                                                                           acc[i][j], 0, 0, 0);
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][i], fb[kk][j], acc[i][j], 0, 0, 0);
-                    }
-        constexpr int NLH = ATR ? 12 : 8;                    // LDS reads per half
-        __builtin_amdgcn_sched_group_barrier(0x100, NLH, 0);
-#pragma unroll
-        for (int r = 0; r < NLH; ++r) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 32 - NLH, 0);
-    };
-    auto compute_plain = [&](int buf) {
+    // one k-tile = two 32-deep halves of 16 MFMAs per wave
+    auto compute = [&](int buf) {
         const unsigned char* As = As_(buf);
         const unsigned char* Bs = Bs_(buf);
 #pragma unroll
@@ -242,17 +201,8 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
             bf16x8 fa[4], fb[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                if constexpr (ATR) {
-                    typedef __attribute__((ext_vector_type(4))) short s16x4_;
-                    typedef __attribute__((address_space(3))) s16x4_ lds_s16x4;
-                    typedef __attribute__((ext_vector_type(8))) short s16x8_;
-                    const s16x4_ lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(As + offt[i] + kk * 32 * 128));
-                    const s16x4_ hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(As + offt[i] + kk * 32 * 128 + 4 * 128));
-                    const s16x8_ both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    fa[i] = __builtin_bit_cast(bf16x8, both);
-                } else {
-                    fa[i] = *reinterpret_cast<const bf16x8*>(As + offa[kk] + i * 16 * 128);
-                }
+                if constexpr (ATR) fa[i] = read_a_tr(As + offt[i] + kk * 32 * 128);
+                else fa[i] = *reinterpret_cast<const bf16x8*>(As + offa[kk] + i * 16 * 128);
                 fb[i] = *reinterpret_cast<const bf16x8*>(Bs + offb[kk] + i * 16 * 128);
             }
 #pragma unroll
@@ -268,7 +218,6 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
                     }
         }
     };
-    auto compute = [&](int buf) { if constexpr (PIPE) compute_pipe(buf); else compute_plain(buf); };
     if constexpr (NST == 2) {
         if (nvirt > 0) stage(0, 0);
         for (int v = 0; v < nvirt; ++v) {
@@ -278,12 +227,12 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
             compute(buf);
         }
     } else {
-        // each stage() is 8 (BMT 2: 6) LDS-DMA loads per wave, retired in order: vmcnt(8 / 6) == "all but the newest tile landed"
+        // each stage() is 8 LDS-DMA loads per wave, retired in order: vmcnt(8) == "all but the newest tile landed"
         if (nvirt > 0) stage(0, 0);
         if (nvirt > 1) stage(1, 1);
         int buf = 0;
         for (int v = 0; v < nvirt; ++v) {
-            if (v + 1 < nvirt) { if constexpr (BMT == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
+            if (v + 1 < nvirt) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();      // tile v is in LDS for every wave; stage (v+2)%3 == (v-1)%3 is drained
             if (v + 2 < nvirt) stage(v + 2, buf == 0 ? 2 : buf - 1);
@@ -324,6 +273,7 @@ __global__ __launch_bounds__(256 * BMT, (NST == 2 && BMT == 1) ? 2 : 1) void gem
             v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
             if (m < m_lim) {
                 if constexpr (MODE == 3) {                 // bf16 rows: 8-byte stores, 128-byte row segments
+                    // (the two bodies below differ in the element type alone; written as one generic lambda they compile to other instructions)
                     __bf16* cb = reinterpret_cast<__bf16*>(g.C) + seg_row(g, m) * g.ldc + nq;
                     if (g.c_f16) {                          // (same rows, IEEE f16 elements: the gi rows cruse_gru_seq_fwd_gi16 reads)
                         _Float16* ch = reinterpret_cast<_Float16*>(cb);
@@ -499,249 +449,202 @@ __global__ __launch_bounds__(256) void gemm_slab_reduce_kernel(const float* slab
 
 }  // namespace
 
-struct GbGroups { int G; long long a_gstep, b_gstep, c_gstep, bias_gstep; };
-struct GbCat { int tm_b1, tm_b2; long long a_shift1, a_shift2; const __bf16* B1; const __bf16* B2; int m_end[3], c_rows[3], M_out; };
+namespace {
 
-static int gemm_bf16_impl(int M, int N, int K, const void* A, const void* A_lo, long long lda, long long a_kstride,
-                          const void* B, const void* B_lo, long long ldb, long long b_kstride,
-                          float* C, long long ldc, const float* bias, int accumulate, int splitk, void* stream,
-                          int seg_len = 0, long long seg_stride = 0, long long seg_off = 0, bool c_bf16 = false,
-                          float* slabs = nullptr, size_t slab_bytes = 0, bool f16 = false, const GbCat* cat = nullptr,
-                          long long atr_mbs = 0, int atr_mb_last = 0, const GbGroups* grp = nullptr, bool c_f16 = false) {
-    CRUSE_REQUIRE(!grp || (!c_bf16 && !slabs && splitk == 1 && !cat && atr_mbs == 0 && seg_len == 0 && a_kstride == BK), CRUSE_E_SHAPE,
+// One GEMM call, whichever of the ten entry points it came through.  The optional forms are nested members whose zero value means "absent";
+// an entry point names the fields it uses and leaves the others out.
+struct GbSeg { int len; long long stride, off; };                                   // row segments (GbArgs::seg_*); len == 0: none
+struct GbSlabs { float* scratch; size_t bytes; };                                   // split-K partial sums stored, then summed in slice order
+struct GbCat { int tm_b1, tm_b2; long long a_shift1, a_shift2; const __bf16* B1; const __bf16* B2; int m_end[3], c_rows[3], M_out; };   // M_out == 0: none
+struct GbAtr { long long mb_stride; int mb_last; };                                 // time-major A (GbArgs::a_mbs); mb_stride == 0: none
+struct GbGroups { int G; long long a_gstep, b_gstep, c_gstep, bias_gstep; };        // G == 0: none
+struct GbCall {
+    int M, N, K;
+    const void* A; const void* A_lo; long long lda, a_kstride;
+    const void* B; const void* B_lo; long long ldb, b_kstride;
+    void* C; long long ldc; int c_dtype;                                            // CRUSE_DT_F32, or _F16 / _BF16 rows (stored, never accumulated)
+    const float* bias; int accumulate, splitk; bool operands_f16; void* stream;
+    GbSeg seg; GbSlabs slabs; GbCat cat; GbAtr atr; GbGroups grp;
+};
+
+// what a call launches, as cruse_gemm_bf16_plan reports it
+enum { GB_P_MODE, GB_P_NST, GB_P_F16, GB_P_ATR, GB_P_GRID, GB_P_LDS, GB_P_SPLITK, GB_P_KT_CHUNK, GB_P_XCDK, GB_P_TILES_M, GB_P_TILES_N, GB_P_NUNITS,
+       GB_P_INNER, GB_P_M_OUT, GB_P_SLAB, GB_P_REDUCE_GRID, GB_P_N };
+
+struct GbVariant { int mode, nst; bool f16, atr; const char* name; };
+constexpr int variant_key(int mode, int nst, bool f16 = false, bool atr = false) { return mode * 8 + (nst - 2) * 4 + (f16 ? 2 : 0) + (atr ? 1 : 0); }
+
+// which of the 14 instantiated kernels a call takes.  deep (long k-loops): three stages, one block per CU -- the f16 and ATR forms stay on two
+GbVariant gemm_variant(const GbCall& c, int splitk, int kt_chunk, bool use_slabs) {
+    const bool out16 = c.c_dtype != CRUSE_DT_F32;
+    const int nst = kt_chunk >= 64 ? 3 : 2;
+    if (use_slabs) return {4, nst, false, false, "gemm_bf16_nt"};
+    if (c.atr.mb_stride != 0) return {c.accumulate ? 1 : 0, 2, false, true, "gemm_bf16_nt_atr"};
+    if (c.operands_f16) return {out16 ? 3 : 0, 2, true, false, out16 ? "gemm_nt_out16" : "gemm_f16_nt"};
+    return {out16 ? 3 : splitk > 1 ? 2 : c.accumulate ? 1 : 0, nst, false, false, "gemm_bf16_nt"};
+}
+
+template <int MODE, int NST, bool F16 = false, bool ATR = false>
+int gemm_launch(const GbArgs& g, unsigned nblk, size_t lds, hipStream_t st, const char* name) {
+    const int rc = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_bf16_nt_kernel<MODE, NST, F16, ATR>), lds, name);
+    if (rc) return rc;
+    hipLaunchKernelGGL((gemm_bf16_nt_kernel<MODE, NST, F16, ATR>), dim3(nblk), dim3(256), lds, st, g);
+    CRUSE_LAUNCH_CHECK(name);
+    return CRUSE_OK;
+}
+
+// The one host path of the ten entry points: admission, geometry, kernel selection and launch.
+// plan != null (cruse_gemm_bf16_plan): decide the same way, write what would be launched and launch nothing.
+int gemm_run(const GbCall& c, int* plan = nullptr) {
+    const bool out16 = c.c_dtype != CRUSE_DT_F32, atr = c.atr.mb_stride != 0, cat = c.cat.M_out != 0;
+    const int M = c.M, N = c.N, K = c.K;
+    // ---- admission: the forms that exclude each other, then shape, strides and alignment
+    CRUSE_REQUIRE(c.grp.G == 0 || (!out16 && !c.slabs.scratch && c.splitk == 1 && !cat && !atr && c.seg.len == 0 && c.a_kstride == BK), CRUSE_E_SHAPE,
                   "gemm_bf16_nt_groups: row-major A, f32 result, no split-K");
-    const bool atr = atr_mbs != 0;
-    CRUSE_REQUIRE(!atr || (!A_lo && !B_lo && !c_bf16 && !slabs && splitk == 1 && !f16 && !cat && seg_len == 0), CRUSE_E_SHAPE,
+    CRUSE_REQUIRE(!atr || (!c.A_lo && !c.B_lo && !out16 && !c.slabs.scratch && c.splitk == 1 && !c.operands_f16 && !cat && c.seg.len == 0), CRUSE_E_SHAPE,
                   "gemm_bf16_nt_atr: plain bf16, one pass, no split-K");
-    CRUSE_REQUIRE(!f16 || (!A_lo && !slabs && splitk == 1 && !accumulate), CRUSE_E_SHAPE,
+    CRUSE_REQUIRE(!c.operands_f16 || (!c.A_lo && !c.slabs.scratch && c.splitk == 1 && !c.accumulate), CRUSE_E_SHAPE,
                   "gemm_f16_nt: f32 result stored (no A low plane, no split-K, no accumulation)");
-    CRUSE_REQUIRE(!c_bf16 || (!accumulate && splitk == 1), CRUSE_E_SHAPE, "gemm_bf16_nt: a bf16 result is stored, not accumulated");
-    CRUSE_REQUIRE(seg_len >= 0 && (seg_len == 0 || (seg_stride >= seg_len && seg_off >= 0 && M % seg_len == 0 && a_kstride == BK)),
-                  CRUSE_E_SHAPE, "gemm_bf16_nt: bad row segments (len %d stride %lld off %lld, M %d; row-major A only)", seg_len,
-                  seg_stride, seg_off, M);
+    CRUSE_REQUIRE(!out16 || (!c.accumulate && c.splitk == 1), CRUSE_E_SHAPE, "gemm_bf16_nt: a bf16 result is stored, not accumulated");
+    CRUSE_REQUIRE(c.seg.len >= 0 && (c.seg.len == 0 || (c.seg.stride >= c.seg.len && c.seg.off >= 0 && M % c.seg.len == 0 && c.a_kstride == BK)),
+                  CRUSE_E_SHAPE, "gemm_bf16_nt: bad row segments (len %d stride %lld off %lld, M %d; row-major A only)", c.seg.len,
+                  c.seg.stride, c.seg.off, M);
     CRUSE_REQUIRE(M > 0 && N > 0 && K > 0, CRUSE_E_SHAPE, "gemm_bf16_nt: empty shape M=%d N=%d K=%d", M, N, K);
     CRUSE_REQUIRE(K % BK == 0, CRUSE_E_SHAPE, "gemm_bf16_nt: K=%d must be a multiple of %d (pad with zeros)", K, BK);
-    CRUSE_REQUIRE(a_kstride >= BK && b_kstride >= BK && ldc >= N, CRUSE_E_SHAPE, "gemm_bf16_nt: strides too small");
-    CRUSE_REQUIRE((a_kstride == BK ? lda >= K : lda >= BK) && (b_kstride == BK ? ldb >= K : ldb >= BK), CRUSE_E_SHAPE,
-                  "gemm_bf16_nt: lda=%lld / ldb=%lld too small for the operand layout", lda, ldb);
-    CRUSE_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && a_kstride % 8 == 0 && b_kstride % 8 == 0 &&
-                  ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, CRUSE_E_ALIGN,
+    CRUSE_REQUIRE(c.a_kstride >= BK && c.b_kstride >= BK && c.ldc >= N, CRUSE_E_SHAPE, "gemm_bf16_nt: strides too small");
+    CRUSE_REQUIRE((c.a_kstride == BK ? c.lda >= K : c.lda >= BK) && (c.b_kstride == BK ? c.ldb >= K : c.ldb >= BK), CRUSE_E_SHAPE,
+                  "gemm_bf16_nt: lda=%lld / ldb=%lld too small for the operand layout", c.lda, c.ldb);
+    CRUSE_REQUIRE(c.lda % 8 == 0 && c.ldb % 8 == 0 && c.a_kstride % 8 == 0 && c.b_kstride % 8 == 0 &&
+                  ((uintptr_t)c.A % 16) == 0 && ((uintptr_t)c.B % 16) == 0, CRUSE_E_ALIGN,
                   "gemm_bf16_nt: operands need 16-byte aligned rows and k-tiles (strides multiples of 8)");
+    // (the k-slices and the grid they make, on which the last checks rest: plain arithmetic, filled into GbArgs below)
     const int nkt = K / BK;
-    const bool xcdk = splitk < -1;             // negative: |splitk| k-slices pinned to XCDs
-    if (xcdk) splitk = -splitk;
+    const bool pinned = c.splitk < -1;         // negative: |splitk| k-slices pinned to XCDs
+    int splitk = pinned ? -c.splitk : c.splitk;
     if (splitk < 1) splitk = 1;
     if (splitk > nkt) splitk = nkt;
     const int kt_chunk = cdiv(nkt, splitk);
     splitk = cdiv(nkt, kt_chunk);
-    GbArgs g;
-    g.A = (const __bf16*)A; g.B = (const __bf16*)B; g.C = C; g.bias = bias;
-    g.a_lo = A_lo ? (const __bf16*)A_lo - (const __bf16*)A : 0;
-    g.b_lo = B_lo ? (const __bf16*)B_lo - (const __bf16*)B : 0;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.a_ks = a_kstride; g.b_ks = b_kstride;
-    g.accumulate = accumulate; g.splitk = splitk; g.kt_chunk = kt_chunk;
-    g.seg_len = seg_len; g.seg_stride = seg_stride; g.seg_off = seg_off;
-    g.a_mbs = atr_mbs; g.a_mb_last = atr_mb_last;
-    g.c_f16 = c_f16 ? 1 : 0;
-    g.tn_per_g = 0; g.a_gstep = g.b_gstep = g.c_gstep = g.bias_gstep = 0;
-    g.tm_b1 = g.tm_b2 = 0x7fffffff; g.a_shift1 = g.a_shift2 = 0; g.B1 = g.B2 = nullptr;
-    g.m_end0 = g.m_end1 = g.m_end2 = M; g.c_rows1 = g.c_rows2 = 0;
-    int M_out = M;                                   // rows of the output (cat: the products' rows without the tile padding between them)
-    if (cat) {
-        g.tm_b1 = cat->tm_b1; g.tm_b2 = cat->tm_b2; g.a_shift1 = cat->a_shift1; g.a_shift2 = cat->a_shift2; g.B1 = cat->B1; g.B2 = cat->B2;
-        g.m_end0 = cat->m_end[0]; g.m_end1 = cat->m_end[1]; g.m_end2 = cat->m_end[2]; g.c_rows1 = cat->c_rows[1]; g.c_rows2 = cat->c_rows[2];
-        M_out = cat->M_out;
-    }
-    g.tiles_m = cdiv(M, BM); g.tiles_n = cdiv(N, BN);
-    if (grp) {
-        g.tn_per_g = g.tiles_n; g.tiles_n *= grp->G;
-        g.a_gstep = grp->a_gstep; g.b_gstep = grp->b_gstep; g.c_gstep = grp->c_gstep; g.bias_gstep = grp->bias_gstep;
-    }
-    g.xcdk = (xcdk && splitk > 1) ? 1 : 0;
-    g.slab = 0;
-    const bool use_slabs = slabs != nullptr && splitk > 1;
-    float* const c_final = C;
-    const long long ldc_final = ldc;
+    const int xcdk = (pinned && splitk > 1) ? 1 : 0;
+    const int M_out = cat ? c.cat.M_out : M;   // rows of the output (cat: the products' rows without the tile padding between them)
+    const int tiles_m = cdiv(M, BM), tiles_n = cdiv(N, BN) * (c.grp.G ? c.grp.G : 1);
+    const int nunits = splitk > 1 ? splitk * tiles_n : tiles_m, inner = splitk > 1 ? tiles_m : tiles_n;
+    const long long nblk = xcdk ? (long long)cdiv(splitk, 8) * 8 * tiles_m * tiles_n : (long long)cdiv(nunits, 8) * 8 * inner;
+    const bool use_slabs = c.slabs.scratch != nullptr && splitk > 1;
     if (use_slabs) {                           // partial sums [slice][M][N] in the caller's scratch, then one ordered sum into C
-        CRUSE_REQUIRE(N % 4 == 0 && ((uintptr_t)slabs % 16) == 0 && seg_len == 0, CRUSE_E_ALIGN, "gemm_bf16_nt: slab form needs N %% 4 == 0");
-        CRUSE_REQUIRE((size_t)splitk * M_out * N * sizeof(float) <= slab_bytes, CRUSE_E_SHAPE,
-                      "gemm_bf16_nt: %d slabs of %d x %d floats do not fit the %zu-byte scratch", splitk, M_out, N, slab_bytes);
-        g.C = slabs; g.ldc = N; g.slab = (long long)M_out * N; g.bias = nullptr;
-        CRUSE_REQUIRE(bias == nullptr, CRUSE_E_SHAPE, "gemm_bf16_nt: slab form has no bias");
+        CRUSE_REQUIRE(N % 4 == 0 && ((uintptr_t)c.slabs.scratch % 16) == 0 && c.seg.len == 0, CRUSE_E_ALIGN, "gemm_bf16_nt: slab form needs N %% 4 == 0");
+        CRUSE_REQUIRE((size_t)splitk * M_out * N * sizeof(float) <= c.slabs.bytes, CRUSE_E_SHAPE,
+                      "gemm_bf16_nt: %d slabs of %d x %d floats do not fit the %zu-byte scratch", splitk, M_out, N, c.slabs.bytes);
+        CRUSE_REQUIRE(c.bias == nullptr, CRUSE_E_SHAPE, "gemm_bf16_nt: slab form has no bias");
     }
-    if (splitk > 1) { g.nunits = splitk * g.tiles_n; g.inner = g.tiles_m; }
-    else { g.nunits = g.tiles_m; g.inner = g.tiles_n; }
-    const long long nblk = g.xcdk ? (long long)cdiv(splitk, 8) * 8 * g.tiles_m * g.tiles_n
-                                  : (long long)cdiv(g.nunits, 8) * 8 * g.inner;
     CRUSE_REQUIRE(nblk < (1ll << 31), CRUSE_E_SHAPE, "gemm_bf16_nt: grid too large");
-    CRUSE_REQUIRE(splitk == 1 || accumulate, CRUSE_E_SHAPE, "gemm_bf16_nt: split-K adds into C (accumulate = 1)");
-    const dim3 grid((unsigned)nblk);
-    hipStream_t st = (hipStream_t)stream;
-    const bool deep = kt_chunk >= 64;          // long k-loops: three stages, one block per CU
-    const size_t lds = (size_t)(deep ? 3 : 2) * 2 * TILE_BYTES;
-#define CRUSE_GB_LAUNCH(MODE, NST)                                                                               \
-    do {                                                                                                         \
-        int rc0 = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_bf16_nt_kernel<MODE, NST>), lds,       \
-                                       "gemm_bf16_nt");                                                          \
-        if (rc0) return rc0;                                                                                     \
-        hipLaunchKernelGGL((gemm_bf16_nt_kernel<MODE, NST>), grid, dim3(256), lds, st, g);                       \
-    } while (0)
-    if (use_slabs) {
-        if (deep) CRUSE_GB_LAUNCH(4, 3); else CRUSE_GB_LAUNCH(4, 2);
-        CRUSE_LAUNCH_CHECK("gemm_bf16_nt");
-        const long long n4 = (long long)M_out * (N / 4);
-        hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, slabs, splitk, g.slab, M_out, N,
-                           c_final, ldc_final);
-        CRUSE_LAUNCH_CHECK("gemm_slab_reduce");
+    CRUSE_REQUIRE(splitk == 1 || c.accumulate, CRUSE_E_SHAPE, "gemm_bf16_nt: split-K adds into C (accumulate = 1)");
+
+    // ---- geometry
+    GbArgs g;
+    g.A = (const __bf16*)c.A; g.B = (const __bf16*)c.B; g.C = (float*)c.C; g.bias = c.bias;
+    g.a_lo = c.A_lo ? (const __bf16*)c.A_lo - g.A : 0;
+    g.b_lo = c.B_lo ? (const __bf16*)c.B_lo - g.B : 0;
+    g.M = M; g.N = N; g.K = K; g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc; g.a_ks = c.a_kstride; g.b_ks = c.b_kstride;
+    g.accumulate = c.accumulate; g.splitk = splitk; g.kt_chunk = kt_chunk;
+    g.tiles_m = tiles_m; g.tiles_n = tiles_n; g.nunits = nunits; g.inner = inner; g.xcdk = xcdk;
+    g.seg_len = c.seg.len; g.seg_stride = c.seg.stride; g.seg_off = c.seg.off;
+    g.a_mbs = c.atr.mb_stride; g.a_mb_last = c.atr.mb_last;
+    g.c_f16 = c.c_dtype == CRUSE_DT_F16 ? 1 : 0;
+    g.tn_per_g = c.grp.G ? tiles_n / c.grp.G : 0;
+    g.a_gstep = c.grp.a_gstep; g.b_gstep = c.grp.b_gstep; g.c_gstep = c.grp.c_gstep; g.bias_gstep = c.grp.bias_gstep;
+    g.tm_b1 = cat ? c.cat.tm_b1 : 0x7fffffff; g.tm_b2 = cat ? c.cat.tm_b2 : 0x7fffffff;
+    g.a_shift1 = c.cat.a_shift1; g.a_shift2 = c.cat.a_shift2; g.B1 = c.cat.B1; g.B2 = c.cat.B2;
+    g.m_end0 = cat ? c.cat.m_end[0] : M; g.m_end1 = cat ? c.cat.m_end[1] : M; g.m_end2 = cat ? c.cat.m_end[2] : M;
+    g.c_rows1 = c.cat.c_rows[1]; g.c_rows2 = c.cat.c_rows[2];
+    g.slab = 0;
+    if (use_slabs) { g.C = c.slabs.scratch; g.ldc = N; g.slab = (long long)M_out * N; g.bias = nullptr; }
+    const long long reduce_blk = use_slabs ? ((long long)M_out * (N / 4) + 255) / 256 : 0;
+
+    // ---- selection and launch
+    const GbVariant v = gemm_variant(c, splitk, kt_chunk, use_slabs);
+    const size_t lds = (size_t)v.nst * 2 * TILE_BYTES;
+    if (plan) {
+        const int p[GB_P_N] = {v.mode, v.nst, v.f16, v.atr, (int)nblk, (int)lds, splitk, kt_chunk, xcdk, tiles_m, tiles_n, nunits, inner, M_out,
+                               (int)g.slab, (int)reduce_blk};
+        for (int i = 0; i < GB_P_N; ++i) plan[i] = p[i];
         return CRUSE_OK;
     }
-    if (atr) {
-        const size_t ldsa = (size_t)2 * 2 * TILE_BYTES;
-        if (accumulate) {
-            int rc0 = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_bf16_nt_kernel<1, 2, 1, false, true>), ldsa, "gemm_bf16_nt_atr");
-            if (rc0) return rc0;
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<1, 2, 1, false, true>), grid, dim3(256), ldsa, st, g);
-        } else {
-            int rc0 = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_bf16_nt_kernel<0, 2, 1, false, true>), ldsa, "gemm_bf16_nt_atr");
-            if (rc0) return rc0;
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<0, 2, 1, false, true>), grid, dim3(256), ldsa, st, g);
-        }
-        CRUSE_LAUNCH_CHECK("gemm_bf16_nt_atr");
-        return CRUSE_OK;
+    hipStream_t st = (hipStream_t)c.stream;
+    const unsigned grid = (unsigned)nblk;
+    int rc = CRUSE_OK;
+    switch (variant_key(v.mode, v.nst, v.f16, v.atr)) {
+        case variant_key(0, 2): rc = gemm_launch<0, 2>(g, grid, lds, st, v.name); break;
+        case variant_key(0, 3): rc = gemm_launch<0, 3>(g, grid, lds, st, v.name); break;
+        case variant_key(1, 2): rc = gemm_launch<1, 2>(g, grid, lds, st, v.name); break;
+        case variant_key(1, 3): rc = gemm_launch<1, 3>(g, grid, lds, st, v.name); break;
+        case variant_key(2, 2): rc = gemm_launch<2, 2>(g, grid, lds, st, v.name); break;
+        case variant_key(2, 3): rc = gemm_launch<2, 3>(g, grid, lds, st, v.name); break;
+        case variant_key(3, 2): rc = gemm_launch<3, 2>(g, grid, lds, st, v.name); break;
+        case variant_key(3, 3): rc = gemm_launch<3, 3>(g, grid, lds, st, v.name); break;
+        case variant_key(4, 2): rc = gemm_launch<4, 2>(g, grid, lds, st, v.name); break;
+        case variant_key(4, 3): rc = gemm_launch<4, 3>(g, grid, lds, st, v.name); break;
+        case variant_key(0, 2, false, true): rc = gemm_launch<0, 2, false, true>(g, grid, lds, st, v.name); break;
+        case variant_key(1, 2, false, true): rc = gemm_launch<1, 2, false, true>(g, grid, lds, st, v.name); break;
+        case variant_key(0, 2, true): rc = gemm_launch<0, 2, true>(g, grid, lds, st, v.name); break;
+        case variant_key(3, 2, true): rc = gemm_launch<3, 2, true>(g, grid, lds, st, v.name); break;
+        default: CRUSE_REQUIRE(false, CRUSE_E_SHAPE, "gemm_bf16_nt: no kernel for mode %d with %d stages", v.mode, v.nst);
     }
-    if (f16 && c_bf16) {
-        const size_t lds16 = (size_t)2 * 2 * TILE_BYTES;
-        int rc0 = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_bf16_nt_kernel<3, 2, 1, true>), lds16, "gemm_nt_out16");
-        if (rc0) return rc0;
-        hipLaunchKernelGGL((gemm_bf16_nt_kernel<3, 2, 1, true>), grid, dim3(256), lds16, st, g);
-        CRUSE_LAUNCH_CHECK("gemm_nt_out16");
-        return CRUSE_OK;
-    }
-    if (f16) {
-        const size_t lds16 = (size_t)2 * 2 * TILE_BYTES;
-        int rc0 = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(gemm_bf16_nt_kernel<0, 2, 1, true>), lds16, "gemm_f16_nt");
-        if (rc0) return rc0;
-        hipLaunchKernelGGL((gemm_bf16_nt_kernel<0, 2, 1, true>), grid, dim3(256), lds16, st, g);
-        CRUSE_LAUNCH_CHECK("gemm_f16_nt");
-        return CRUSE_OK;
-    }
-    if (deep) {
-        if (c_bf16) CRUSE_GB_LAUNCH(3, 3);
-        else if (splitk > 1) CRUSE_GB_LAUNCH(2, 3); else if (accumulate) CRUSE_GB_LAUNCH(1, 3); else CRUSE_GB_LAUNCH(0, 3);
-    } else {
-        if (c_bf16) CRUSE_GB_LAUNCH(3, 2);
-        else if (splitk > 1) CRUSE_GB_LAUNCH(2, 2); else if (accumulate) CRUSE_GB_LAUNCH(1, 2); else CRUSE_GB_LAUNCH(0, 2);
-    }
-#undef CRUSE_GB_LAUNCH
-    CRUSE_LAUNCH_CHECK("gemm_bf16_nt");
+    if (rc || !use_slabs) return rc;
+    hipLaunchKernelGGL(gemm_slab_reduce_kernel, dim3((unsigned)reduce_blk), dim3(256), 0, st, c.slabs.scratch, splitk, g.slab, M_out, N,
+                       (float*)c.C, c.ldc);
+    CRUSE_LAUNCH_CHECK("gemm_slab_reduce");
     return CRUSE_OK;
 }
 
-extern "C" int cruse_gemm_bf16_nt(int M, int N, int K, const void* A, long long lda, long long a_kstride,
-                                  const void* B, long long ldb, long long b_kstride,
-                                  float* C, long long ldc, const float* bias, int accumulate, int splitk,
-                                  void* stream) {
-    return gemm_bf16_impl(M, N, K, A, nullptr, lda, a_kstride, B, nullptr, ldb, b_kstride, C, ldc, bias, accumulate, splitk,
-                          stream);
+// what an entry point (form: CRUSE_GEMM_FORM_*) checks of its own arguments, then the path they share; cruse_gemm_bf16_plan comes the same way
+int gemm_enter(int form, const GbCall& c, int* plan = nullptr) {
+    const bool lo_aligned = ((uintptr_t)c.A_lo % 16) == 0 && ((uintptr_t)c.B_lo % 16) == 0;
+    const int n_mb = c.atr.mb_last + 1;
+    switch (form) {
+    case CRUSE_GEMM_FORM_X3:
+        CRUSE_REQUIRE(c.B_lo != nullptr && c.A_lo != c.A && c.B_lo != c.B, CRUSE_E_SHAPE, "gemm_bf16x3_nt: B_lo missing");
+        CRUSE_REQUIRE(lo_aligned, CRUSE_E_ALIGN, "gemm_bf16x3_nt: unaligned low planes");
+        break;
+    case CRUSE_GEMM_FORM_F16X2:
+        CRUSE_REQUIRE(c.B_lo != nullptr, CRUSE_E_SHAPE, "gemm_f16x2_nt: B_lo is required (one plane: cruse_gemm_f16_nt)");
+        break;
+    case CRUSE_GEMM_FORM_OUT16:
+        CRUSE_REQUIRE(c.c_dtype == CRUSE_DT_F16 || c.c_dtype == CRUSE_DT_BF16, CRUSE_E_DTYPE, "gemm_nt_out16: out_dtype %d (CRUSE_DT_F16, CRUSE_DT_BF16)", c.c_dtype);
+        CRUSE_REQUIRE((c.A_lo == nullptr || (c.B_lo != nullptr && !c.operands_f16)) && lo_aligned, CRUSE_E_ALIGN,
+                      "gemm_nt_out16: low planes (A_lo needs B_lo and bf16 operands; 16-byte aligned)");
+        break;
+    case CRUSE_GEMM_FORM_ATR:
+        CRUSE_REQUIRE(c.atr.mb_stride >= (long long)c.K * 64 && c.atr.mb_stride % 8 == 0 && n_mb >= 1 && (long long)n_mb * 64 >= c.M, CRUSE_E_SHAPE,
+                      "gemm_bf16_nt_atr: a_mb_stride=%lld n_mb=%d for M=%d K=%d", c.atr.mb_stride, n_mb, c.M, c.K);
+        break;
+    case CRUSE_GEMM_FORM_GROUPS:
+        CRUSE_REQUIRE(c.grp.G >= 1 && c.grp.a_gstep % 8 == 0 && c.grp.b_gstep % 8 == 0 && c.grp.c_gstep >= c.N &&
+                      (long long)(c.grp.G - 1) * c.grp.c_gstep + c.N <= c.ldc, CRUSE_E_SHAPE,
+                      "gemm_bf16_nt_groups: G=%d a_gstep=%lld b_gstep=%lld c_gstep=%lld", c.grp.G, c.grp.a_gstep, c.grp.b_gstep, c.grp.c_gstep);
+        CRUSE_REQUIRE((c.A_lo == nullptr || c.B_lo != nullptr) && lo_aligned, CRUSE_E_ALIGN, "gemm_bf16_nt_groups: low planes (A_lo needs B_lo; 16-byte aligned)");
+        break;
+    case CRUSE_GEMM_FORM_SLABS:
+        CRUSE_REQUIRE(c.slabs.scratch != nullptr, CRUSE_E_SHAPE, "gemm_bf16_nt_slabs: scratch is NULL");
+        break;
+    case CRUSE_GEMM_FORM_SEG:
+        CRUSE_REQUIRE(c.seg.len > 0, CRUSE_E_SHAPE, "gemm_bf16_nt_seg: seg_len=%d", c.seg.len);
+        CRUSE_REQUIRE((c.A_lo == nullptr || c.B_lo != nullptr) && lo_aligned, CRUSE_E_ALIGN, "gemm_bf16_nt_seg: low planes (A_lo needs B_lo; 16-byte aligned)");
+        break;
+    }
+    return gemm_run(c, plan);
 }
 
-// ... with B = B_hi + B_lo (two f16 planes, same layout): C = A . B_hi^T + A . B_lo^T in one launch (the second k-range on the same accumulators) --
-// 11 significant bits on the activations and ~20 on the weights: the forward gate projection of GGRU layer 1 (the rounding of W_ih is the same in
-// every frame and does not average out of the gradients the way the per-frame rounding of x does)
-extern "C" int cruse_gemm_f16x2_nt(int M, int N, int K, const void* A, long long lda, long long a_kstride,
-                                   const void* B_hi, const void* B_lo, long long ldb, long long b_kstride,
-                                   float* C, long long ldc, const float* bias, void* stream) {
-    CRUSE_REQUIRE(B_lo != nullptr, CRUSE_E_SHAPE, "gemm_f16x2_nt: B_lo is required (one plane: cruse_gemm_f16_nt)");
-    return gemm_bf16_impl(M, N, K, A, nullptr, lda, a_kstride, B_hi, B_lo, ldb, b_kstride, C, ldc, bias, 0, 1, stream, 0, 0, 0, false,
-                          nullptr, 0, true);
-}
-
-// The forward gate projections with a 2-BYTE RESULT: C[M,N] = (A_hi + A_lo) . (B_hi + B_lo)^T + bias stored as IEEE f16 (out_dtype = CRUSE_DT_F16) or
-// bf16 (CRUSE_DT_BF16) rows -- gi is the largest tensor of the forward pass (197 MB at the bench shape), written once here and read once by the
-// recurrence (cruse_gru_seq_fwd_gi16).  operands_f16 = 0: bf16 operand planes (the forms of cruse_gemm_bf16_nt / cruse_gemm_bf16x3_nt: A_lo, B_lo
-// nullable, A_lo needs B_lo); 1: IEEE-f16 planes (cruse_gemm_f16_nt / cruse_gemm_f16x2_nt: no A_lo).  The accumulation is the f32 one of
-// those entry points; the result is rounded once at the store.  Replaces the output side of nn.GRU's input projection (model/cruse_net.py:23-31).
-extern "C" int cruse_gemm_nt_out16(int M, int N, int K, const void* A_hi, const void* A_lo, long long lda, long long a_kstride,
-                                   const void* B_hi, const void* B_lo, long long ldb, long long b_kstride,
-                                   void* C, long long ldc, const float* bias, int operands_f16, int out_dtype, void* stream) {
-    CRUSE_REQUIRE(out_dtype == CRUSE_DT_F16 || out_dtype == CRUSE_DT_BF16, CRUSE_E_DTYPE, "gemm_nt_out16: out_dtype %d (CRUSE_DT_F16, CRUSE_DT_BF16)", out_dtype);
-    CRUSE_REQUIRE((A_lo == nullptr || (B_lo != nullptr && !operands_f16)) && ((uintptr_t)A_lo % 16) == 0 && ((uintptr_t)B_lo % 16) == 0, CRUSE_E_ALIGN,
-                  "gemm_nt_out16: low planes (A_lo needs B_lo and bf16 operands; 16-byte aligned)");
-    return gemm_bf16_impl(M, N, K, A_hi, A_lo, lda, a_kstride, B_hi, B_lo, ldb, b_kstride, reinterpret_cast<float*>(C), ldc, bias, 0, 1, stream, 0, 0, 0,
-                          true, nullptr, 0, operands_f16 != 0, nullptr, 0, 0, nullptr, out_dtype == CRUSE_DT_F16);
-}
-
-// C[M,N] = A[M,K] . B[N,K]^T + bias with IEEE-f16 operands (layouts as cruse_gemm_bf16_nt): the forward gate projection in one pass
-extern "C" int cruse_gemm_f16_nt(int M, int N, int K, const void* A, long long lda, long long a_kstride,
-                                 const void* B, long long ldb, long long b_kstride,
-                                 float* C, long long ldc, const float* bias, void* stream) {
-    return gemm_bf16_impl(M, N, K, A, nullptr, lda, a_kstride, B, nullptr, ldb, b_kstride, C, ldc, bias, 0, 1, stream, 0, 0, 0, false,
-                          nullptr, 0, true);
-}
-
-
-// C[M,N] (+)= A[M,K] . B[N,K]^T with A given as its TIME-MAJOR K-tiled image: element (m, k) at A_T[(m / 64) * a_mb_stride + k * 64 + m % 64],
-// n_mb 64-row blocks present (rows M <= m < 64 * n_mb hold finite values).  This is the layout of the gate-gradient tensor dgT
-// [ceil(rows / 64)][G][4][Hg][64] the weight-gradient GEMMs consume (A_T = dgT + group * 4 * Hg * 64, a_mb_stride = G * 4 * Hg * 64): the input
-// gradient dX = dgi . W_ih is formed from it directly and the row-major copy dgi is never written (round 4; back in round 6 for its bytes).  K % 64 == 0.
-extern "C" int cruse_gemm_bf16_nt_atr(int M, int N, int K, const void* A_T, long long a_mb_stride, int n_mb,
-                                      const void* B, long long ldb, long long b_kstride,
-                                      float* C, long long ldc, int accumulate, void* stream) {
-    CRUSE_REQUIRE(a_mb_stride >= (long long)K * 64 && a_mb_stride % 8 == 0 && n_mb >= 1 && (long long)n_mb * 64 >= M, CRUSE_E_SHAPE,
-                  "gemm_bf16_nt_atr: a_mb_stride=%lld n_mb=%d for M=%d K=%d", a_mb_stride, n_mb, M, K);
-    return gemm_bf16_impl(M, N, K, A_T, nullptr, 64, 64 * 64, B, nullptr, ldb, b_kstride, C, ldc, nullptr, accumulate, 1, stream, 0, 0, 0, false,
-                          nullptr, 0, false, nullptr, a_mb_stride, n_mb - 1);
-}
-
-// G products of the same shape in ONE launch, side by side along N -- the GRU groups of a layer:
-//   C[:, q * c_gstep + (0 .. N)] (+)= A[:, q * a_gstep + (0 .. K)] . B_q^T + bias_q      B_q = B + q * b_gstep, bias_q = bias + q * bias_gstep
-// A row-major [M, lda] (planes A_hi / A_lo nullable as cruse_gemm_bf16x3_nt), B in the layouts of cruse_gemm_bf16_nt (B_lo nullable, the same
-// group stride).  The forward gate projections gi_q = x_q W_ih,q^T + b_ih,q and the input gradients dx_q = dgi_q W_ih,q of a grouped GGRU layer
-// (cruse_net.py:14-55 with rnn_groups > 1) were G launches of [rows x 3 Hg or Hg] each -- 2 to 4 column tiles, 400 to 800 blocks.
-extern "C" int cruse_gemm_bf16_nt_groups(int M, int N, int K, int G, const void* A_hi, const void* A_lo, long long lda, long long a_gstep,
-                                         const void* B_hi, const void* B_lo, long long ldb, long long b_kstride, long long b_gstep,
-                                         float* C, long long ldc, long long c_gstep, const float* bias, long long bias_gstep, int accumulate,
-                                         void* stream) {
-    CRUSE_REQUIRE(G >= 1 && a_gstep % 8 == 0 && b_gstep % 8 == 0 && c_gstep >= N && (long long)(G - 1) * c_gstep + N <= ldc, CRUSE_E_SHAPE,
-                  "gemm_bf16_nt_groups: G=%d a_gstep=%lld b_gstep=%lld c_gstep=%lld", G, a_gstep, b_gstep, c_gstep);
-    CRUSE_REQUIRE((A_lo == nullptr || B_lo != nullptr) && ((uintptr_t)A_lo % 16) == 0 && ((uintptr_t)B_lo % 16) == 0, CRUSE_E_ALIGN,
-                  "gemm_bf16_nt_groups: low planes (A_lo needs B_lo; 16-byte aligned)");
-    const GbGroups grp = {G, a_gstep, b_gstep, c_gstep, bias_gstep};
-    return gemm_bf16_impl(M, N, K, A_hi, A_lo, lda, BK, B_hi, B_lo, ldb, b_kstride, C, ldc, bias, accumulate, 1, stream, 0, 0, 0, false, nullptr, 0,
-                          false, nullptr, 0, 0, &grp);
-}
-
-extern "C" size_t cruse_gemm_bf16_slab_bytes(int M, int N, int splitk) {
-    const int z = splitk < 0 ? -splitk : splitk;
-    return (size_t)(z < 1 ? 1 : z) * M * N * sizeof(float);
-}
-
-extern "C" int cruse_gemm_bf16_nt_slabs(int M, int N, int K, const void* A, long long lda, long long a_kstride,
-                                        const void* B, long long ldb, long long b_kstride,
-                                        float* C, long long ldc, int splitk, void* scratch, size_t scratch_bytes, void* stream) {
-    CRUSE_REQUIRE(scratch != nullptr, CRUSE_E_SHAPE, "gemm_bf16_nt_slabs: scratch is NULL");
-    return gemm_bf16_impl(M, N, K, A, nullptr, lda, a_kstride, B, nullptr, ldb, b_kstride, C, ldc, nullptr, 1, splitk, stream, 0, 0, 0,
-                          false, reinterpret_cast<float*>(scratch), scratch_bytes);
-}
-
-// Up to three products that share N, K, the operand strides and the A tensor, concatenated along M into ONE launch and one output:
-//   C[sum M_i, N] += cat_i( A[a_rows[i] .. a_rows[i] + M_i) . B_i^T )          (slab form: split-K without atomics, as above)
-// The three weight-gradient products of a GRU layer -- (r, z, n_i)^T x, (r, z)^T h_{t-1}, n_h^T h_{t-1} -- are such a set: their A rows are
-// slabs of the one time-major gate-gradient tensor, and dW_ih / dW_hh lie back to back in the flat gradient buffer.  One launch walks all 150
-// output tiles of a k-slice on its XCD: the gate-gradient k-tiles are fetched once for the three products, and two launches + two reduce
-// passes with their ramps and tails go.  A product whose M_i is not a multiple of 128 still starts on a row tile of its own (the padding rows are
-// computed and dropped); the output rows stay contiguous.
-extern "C" int cruse_gemm_bf16_nt_slabs_cat(int nprob, const int* Ms, int N, int K, const void* A, const long long* a_rows, long long lda,
-                                            long long a_kstride, const void* const* Bs, long long ldb, long long b_kstride,
-                                            float* C, long long ldc, int splitk, void* scratch, size_t scratch_bytes, void* stream) {
-    CRUSE_REQUIRE(nprob >= 1 && nprob <= 3 && Ms && a_rows && Bs && scratch, CRUSE_E_SHAPE, "gemm_bf16_nt_slabs_cat: 1..3 products");
-    GbCat cat = {};
+// cruse_gemm_bf16_nt_slabs_cat: c holds A (the whole tensor), the strides and the scratch; this checks the products and sets c.cat, M (the virtual
+// rows: a product starts on a row tile, the rows that pad its last tile are computed and dropped) and A, B of product 0
+int gemm_enter_cat(GbCall c, int nprob, const int* Ms, const long long* a_rows, const void* const* Bs, int* plan = nullptr) {
+    CRUSE_REQUIRE(nprob >= 1 && nprob <= 3 && Ms && a_rows && Bs && c.slabs.scratch, CRUSE_E_SHAPE, "gemm_bf16_nt_slabs_cat: 1..3 products");
+    GbCat& cat = c.cat;
     int tiles = 0, rows = 0, first[3] = {0, 0, 0};
-    for (int i = 0; i < 3; ++i) { cat.m_end[i] = 0; cat.c_rows[i] = 0; }
     for (int i = 0; i < nprob; ++i) {
         CRUSE_REQUIRE(Ms[i] > 0 && a_rows[i] >= 0 && Bs[i] != nullptr && ((uintptr_t)Bs[i] % 16) == 0, CRUSE_E_SHAPE,
                       "gemm_bf16_nt_slabs_cat: product %d (M = %d)", i, Ms[i]);
-        first[i] = tiles * BM;                       // a product starts on a row tile; the rows that pad its last tile are computed and dropped
+        first[i] = tiles * BM;
         cat.m_end[i] = first[i] + Ms[i];
         cat.c_rows[i] = rows - first[i];
         tiles += cdiv(Ms[i], BM); rows += Ms[i];
@@ -749,35 +652,127 @@ extern "C" int cruse_gemm_bf16_nt_slabs_cat(int nprob, const int* Ms, int N, int
     cat.M_out = rows;
     cat.tm_b1 = nprob > 1 ? first[1] / BM : 0x7fffffff; cat.tm_b2 = nprob > 2 ? first[2] / BM : 0x7fffffff;
     // virtual row m of product i is A row a_rows[i] + (m - first[i]); the kernel adds m * lda itself
-    cat.a_shift1 = nprob > 1 ? (a_rows[1] - a_rows[0] - first[1]) * lda : 0;
-    cat.a_shift2 = nprob > 2 ? (a_rows[2] - a_rows[0] - first[2]) * lda : 0;
+    cat.a_shift1 = nprob > 1 ? (a_rows[1] - a_rows[0] - first[1]) * c.lda : 0;
+    cat.a_shift2 = nprob > 2 ? (a_rows[2] - a_rows[0] - first[2]) * c.lda : 0;
     cat.B1 = nprob > 1 ? (const __bf16*)Bs[1] : nullptr; cat.B2 = nprob > 2 ? (const __bf16*)Bs[2] : nullptr;
-    const __bf16* A0 = (const __bf16*)A + a_rows[0] * lda;
-    CRUSE_REQUIRE(a_kstride > BK, CRUSE_E_SHAPE, "gemm_bf16_nt_slabs_cat: K-tiled A operand (rows lda apart inside a k-tile)");
-    const int M_virtual = first[nprob - 1] + Ms[nprob - 1];
-    return gemm_bf16_impl(M_virtual, N, K, A0, nullptr, lda, a_kstride, Bs[0], nullptr, ldb, b_kstride, C, ldc, nullptr, 1, splitk, stream, 0, 0, 0,
-                          false, reinterpret_cast<float*>(scratch), scratch_bytes, false, &cat);
+    CRUSE_REQUIRE(c.a_kstride > BK, CRUSE_E_SHAPE, "gemm_bf16_nt_slabs_cat: K-tiled A operand (rows lda apart inside a k-tile)");
+    c.A = (const __bf16*)c.A + a_rows[0] * c.lda; c.B = Bs[0]; c.M = first[nprob - 1] + Ms[nprob - 1];
+    return gemm_run(c, plan);
 }
 
+}  // namespace
+
+// The ten entry points (include/cruse_hip.h says what each computes): each names the descriptor fields its argument list carries.
+extern "C" int cruse_gemm_bf16_nt(int M, int N, int K, const void* A, long long lda, long long a_kstride, const void* B, long long ldb, long long b_kstride,
+                                  float* C, long long ldc, const float* bias, int accumulate, int splitk, void* stream) {
+    return gemm_enter(CRUSE_GEMM_FORM_PLAIN, {.M = M, .N = N, .K = K, .A = A, .lda = lda, .a_kstride = a_kstride, .B = B, .ldb = ldb, .b_kstride = b_kstride,
+                                              .C = C, .ldc = ldc, .bias = bias, .accumulate = accumulate, .splitk = splitk, .stream = stream});
+}
+
+// B = B_hi + B_lo (two f16 planes, same layout), the second k-range on the same accumulators: the rounding of W_ih is the same in every frame and
+// does not average out of the gradients the way the per-frame rounding of x does
+extern "C" int cruse_gemm_f16x2_nt(int M, int N, int K, const void* A, long long lda, long long a_kstride,
+                                   const void* B_hi, const void* B_lo, long long ldb, long long b_kstride,
+                                   float* C, long long ldc, const float* bias, void* stream) {
+    return gemm_enter(CRUSE_GEMM_FORM_F16X2, {.M = M, .N = N, .K = K, .A = A, .lda = lda, .a_kstride = a_kstride, .B = B_hi, .B_lo = B_lo, .ldb = ldb,
+                                              .b_kstride = b_kstride, .C = C, .ldc = ldc, .bias = bias, .splitk = 1, .operands_f16 = true, .stream = stream});
+}
+
+// a 2-byte result (f16 or bf16 rows): the f32 accumulation of the entry points above, rounded once at the store
+extern "C" int cruse_gemm_nt_out16(int M, int N, int K, const void* A_hi, const void* A_lo, long long lda, long long a_kstride,
+                                   const void* B_hi, const void* B_lo, long long ldb, long long b_kstride,
+                                   void* C, long long ldc, const float* bias, int operands_f16, int out_dtype, void* stream) {
+    return gemm_enter(CRUSE_GEMM_FORM_OUT16, {.M = M, .N = N, .K = K, .A = A_hi, .A_lo = A_lo, .lda = lda, .a_kstride = a_kstride, .B = B_hi, .B_lo = B_lo,
+                                              .ldb = ldb, .b_kstride = b_kstride, .C = C, .ldc = ldc, .c_dtype = out_dtype, .bias = bias, .splitk = 1,
+                                              .operands_f16 = operands_f16 != 0, .stream = stream});
+}
+
+extern "C" int cruse_gemm_f16_nt(int M, int N, int K, const void* A, long long lda, long long a_kstride, const void* B, long long ldb, long long b_kstride,
+                                 float* C, long long ldc, const float* bias, void* stream) {
+    return gemm_enter(CRUSE_GEMM_FORM_F16, {.M = M, .N = N, .K = K, .A = A, .lda = lda, .a_kstride = a_kstride, .B = B, .ldb = ldb, .b_kstride = b_kstride,
+                                            .C = C, .ldc = ldc, .bias = bias, .splitk = 1, .operands_f16 = true, .stream = stream});
+}
+
+// A given as its TIME-MAJOR K-tiled image (GbArgs::a_mbs), n_mb 64-row blocks present (rows M <= m < 64 * n_mb hold finite values): the layout of
+// the gate-gradient tensor dgT [ceil(rows / 64)][G][4][Hg][64] (A_T = dgT + group * 4 * Hg * 64, a_mb_stride = G * 4 * Hg * 64)
+extern "C" int cruse_gemm_bf16_nt_atr(int M, int N, int K, const void* A_T, long long a_mb_stride, int n_mb, const void* B, long long ldb, long long b_kstride,
+                                      float* C, long long ldc, int accumulate, void* stream) {
+    return gemm_enter(CRUSE_GEMM_FORM_ATR, {.M = M, .N = N, .K = K, .A = A_T, .lda = 64, .a_kstride = 64 * 64, .B = B, .ldb = ldb, .b_kstride = b_kstride,
+                                            .C = C, .ldc = ldc, .accumulate = accumulate, .splitk = 1, .stream = stream, .atr = {a_mb_stride, n_mb - 1}});
+}
+
+// G products of the same shape in ONE launch, side by side along N (GbArgs::tn_per_g) -- the GRU groups of a layer, which were G launches of
+// [rows x 3 Hg or Hg] each: 2 to 4 column tiles, 400 to 800 blocks
+extern "C" int cruse_gemm_bf16_nt_groups(int M, int N, int K, int G, const void* A_hi, const void* A_lo, long long lda, long long a_gstep,
+                                         const void* B_hi, const void* B_lo, long long ldb, long long b_kstride, long long b_gstep,
+                                         float* C, long long ldc, long long c_gstep, const float* bias, long long bias_gstep, int accumulate, void* stream) {
+    return gemm_enter(CRUSE_GEMM_FORM_GROUPS, {.M = M, .N = N, .K = K, .A = A_hi, .A_lo = A_lo, .lda = lda, .a_kstride = BK, .B = B_hi, .B_lo = B_lo, .ldb = ldb,
+                                               .b_kstride = b_kstride, .C = C, .ldc = ldc, .bias = bias, .accumulate = accumulate, .splitk = 1,
+                                               .stream = stream, .grp = {G, a_gstep, b_gstep, c_gstep, bias_gstep}});
+}
+
+extern "C" size_t cruse_gemm_bf16_slab_bytes(int M, int N, int splitk) {
+    const int z = splitk < 0 ? -splitk : splitk;
+    return (size_t)(z < 1 ? 1 : z) * M * N * sizeof(float);
+}
+
+extern "C" int cruse_gemm_bf16_nt_slabs(int M, int N, int K, const void* A, long long lda, long long a_kstride, const void* B, long long ldb, long long b_kstride,
+                                        float* C, long long ldc, int splitk, void* scratch, size_t scratch_bytes, void* stream) {
+    return gemm_enter(CRUSE_GEMM_FORM_SLABS, {.M = M, .N = N, .K = K, .A = A, .lda = lda, .a_kstride = a_kstride, .B = B, .ldb = ldb, .b_kstride = b_kstride,
+                                              .C = C, .ldc = ldc, .accumulate = 1, .splitk = splitk, .stream = stream,
+                                              .slabs = {reinterpret_cast<float*>(scratch), scratch_bytes}});
+}
+
+// Up to three slab products that share N, K, the operand strides and the A tensor, concatenated along M into ONE launch and one output -- the three
+// weight-gradient products of a GRU layer: one launch walks all 150 output tiles of a k-slice on its XCD, the gate-gradient k-tiles are fetched once
+// for the three products, and two launches + two reduce passes with their ramps and tails go
+extern "C" int cruse_gemm_bf16_nt_slabs_cat(int nprob, const int* Ms, int N, int K, const void* A, const long long* a_rows, long long lda,
+                                            long long a_kstride, const void* const* Bs, long long ldb, long long b_kstride,
+                                            float* C, long long ldc, int splitk, void* scratch, size_t scratch_bytes, void* stream) {
+    return gemm_enter_cat({.N = N, .K = K, .A = A, .lda = lda, .a_kstride = a_kstride, .ldb = ldb, .b_kstride = b_kstride, .C = C, .ldc = ldc, .accumulate = 1,
+                           .splitk = splitk, .stream = stream, .slabs = {reinterpret_cast<float*>(scratch), scratch_bytes}}, nprob, Ms, a_rows, Bs);
+}
 
 extern "C" int cruse_gemm_bf16_nt_seg(int M, int N, int K, const void* A_hi, const void* A_lo, long long lda,
                                       const void* B_hi, const void* B_lo, long long ldb, long long b_kstride,
                                       float* C, long long ldc, const float* bias, int accumulate,
                                       int seg_len, long long seg_stride, long long seg_off, void* stream) {
-    CRUSE_REQUIRE(seg_len > 0, CRUSE_E_SHAPE, "gemm_bf16_nt_seg: seg_len=%d", seg_len);
-    CRUSE_REQUIRE((A_lo == nullptr || B_lo != nullptr) && ((uintptr_t)A_lo % 16) == 0 && ((uintptr_t)B_lo % 16) == 0, CRUSE_E_ALIGN,
-                  "gemm_bf16_nt_seg: low planes (A_lo needs B_lo; 16-byte aligned)");
-    return gemm_bf16_impl(M, N, K, A_hi, A_lo, lda, BK, B_hi, B_lo, ldb, b_kstride, C, ldc, bias, accumulate, 1, stream, seg_len,
-                          seg_stride, seg_off);
+    return gemm_enter(CRUSE_GEMM_FORM_SEG, {.M = M, .N = N, .K = K, .A = A_hi, .A_lo = A_lo, .lda = lda, .a_kstride = BK, .B = B_hi, .B_lo = B_lo, .ldb = ldb,
+                                            .b_kstride = b_kstride, .C = C, .ldc = ldc, .bias = bias, .accumulate = accumulate, .splitk = 1, .stream = stream,
+                                            .seg = {seg_len, seg_stride, seg_off}});
 }
 
-extern "C" int cruse_gemm_bf16x3_nt(int M, int N, int K, const void* A_hi, const void* A_lo, long long lda,
-                                    long long a_kstride, const void* B_hi, const void* B_lo, long long ldb,
-                                    long long b_kstride, float* C, long long ldc, const float* bias, int accumulate,
-                                    void* stream) {
-    CRUSE_REQUIRE(B_lo != nullptr && A_lo != A_hi && B_lo != B_hi, CRUSE_E_SHAPE, "gemm_bf16x3_nt: B_lo missing");
-    CRUSE_REQUIRE(((uintptr_t)A_lo % 16) == 0 && ((uintptr_t)B_lo % 16) == 0, CRUSE_E_ALIGN, "gemm_bf16x3_nt: unaligned low planes");
-    return gemm_bf16_impl(M, N, K, A_hi, A_lo, lda, a_kstride, B_hi, B_lo, ldb, b_kstride, C, ldc, bias, accumulate, 1, stream);
+extern "C" int cruse_gemm_bf16x3_nt(int M, int N, int K, const void* A_hi, const void* A_lo, long long lda, long long a_kstride,
+                                    const void* B_hi, const void* B_lo, long long ldb, long long b_kstride,
+                                    float* C, long long ldc, const float* bias, int accumulate, void* stream) {
+    return gemm_enter(CRUSE_GEMM_FORM_X3, {.M = M, .N = N, .K = K, .A = A_hi, .A_lo = A_lo, .lda = lda, .a_kstride = a_kstride, .B = B_hi, .B_lo = B_lo,
+                                           .ldb = ldb, .b_kstride = b_kstride, .C = C, .ldc = ldc, .bias = bias, .accumulate = accumulate, .splitk = 1,
+                                           .stream = stream});
+}
+
+// Host-only (no device is touched): what a call of this form and these scalars would launch (include/cruse_hip.h) -- the entry point's own checks and
+// gemm_run's decision, with the launches left out.  A static buffer stands for every tensor: never dereferenced.
+extern "C" int cruse_gemm_bf16_plan(int form, int M, int N, int K, long long lda, long long a_kstride, long long ldb, long long b_kstride, long long ldc,
+                                    int planes, int has_bias, int accumulate, int splitk, int operands_f16, int out_dtype, const long long* x, int* out) {
+    CRUSE_REQUIRE(out != nullptr && form >= 0 && form < CRUSE_GEMM_FORM_N && (x != nullptr || form < CRUSE_GEMM_FORM_ATR), CRUSE_E_SHAPE,
+                  "gemm_bf16_plan: out is NULL, form = %d, or the form's extras are missing", form);
+    alignas(16) static unsigned char buf[80];
+    const int off = (planes & 4) ? 2 : 0;
+    const bool slab_form = form == CRUSE_GEMM_FORM_SLABS || form == CRUSE_GEMM_FORM_SLABS_CAT;
+    GbCall c = {.M = M, .N = N, .K = K, .A = buf, .A_lo = (planes & 1) ? buf + 16 + off : nullptr, .lda = lda, .a_kstride = a_kstride,
+                .B = buf + 32, .B_lo = (planes & 2) ? buf + 48 + off : nullptr, .ldb = ldb, .b_kstride = b_kstride, .C = buf, .ldc = ldc,
+                .c_dtype = form == CRUSE_GEMM_FORM_OUT16 ? out_dtype : CRUSE_DT_F32, .bias = has_bias ? reinterpret_cast<const float*>(buf) : nullptr,
+                .accumulate = slab_form ? 1 : accumulate, .splitk = splitk,
+                .operands_f16 = operands_f16 != 0 || form == CRUSE_GEMM_FORM_F16 || form == CRUSE_GEMM_FORM_F16X2};
+    for (int i = 0; i < GB_P_N; ++i) out[i] = 0;
+    if (slab_form) c.slabs = {reinterpret_cast<float*>(buf), (size_t)x[0]};
+    if (form == CRUSE_GEMM_FORM_ATR) { c.lda = 64; c.a_kstride = 64 * 64; c.atr = {x[0], (int)x[1] - 1}; }
+    if (form == CRUSE_GEMM_FORM_GROUPS) { c.a_kstride = BK; c.grp = {(int)x[0], x[1], x[2], x[3], x[4]}; }
+    if (form == CRUSE_GEMM_FORM_SEG) { c.a_kstride = BK; c.seg = {(int)x[0], x[1], x[2]}; }
+    if (form != CRUSE_GEMM_FORM_SLABS_CAT) return gemm_enter(form, c, out);
+    const int Ms[3] = {(int)x[2], (int)x[3], (int)x[4]};
+    const void* const Bs[3] = {buf + 32, buf + 32, buf + 32};
+    return gemm_enter_cat(c, (int)x[1], Ms, x + 5, Bs, out);
 }
 
 extern "C" int cruse_cast_bf16(const float* x, void* y, long long n, void* stream) {

@@ -28,6 +28,11 @@ def _p(t: Optional[torch.Tensor]):
     return t.data_ptr()
 
 
+def _at(t: Optional[torch.Tensor], off: int, esize: int = 2):
+    """address of element `off` of t's storage view (esize bytes per element: the 2-byte GEMM operands by default); None stays None"""
+    return None if t is None else t.data_ptr() + esize * off
+
+
 def _xdt(t: torch.Tensor, name: str) -> int:
     """CRUSE_DT_* of a conv / weight-gradient INPUT: f32, or bf16 for the backward-only tensors of the bf16 mode."""
     if t.dtype == torch.float32:
@@ -553,15 +558,15 @@ def gemm_bf16_nt(M, N, K, A, a_off, lda, Bm, b_off, ldb, C, c_off, ldc, bias=Non
             raise RuntimeError("gemm_bf16_nt needs bf16 operands")
         nbytes = lib.cruse_gemm_bf16_slab_bytes(M, N, splitk)
         ws = _ws(("gemm_slabs", _stream()), nbytes, C.device, zero=False)
-        check(lib.cruse_gemm_bf16_nt_slabs(M, N, K, A.data_ptr() + 2 * a_off, lda, a_kstride, Bm.data_ptr() + 2 * b_off, ldb, b_kstride,
-                                           C.data_ptr() + 4 * c_off, ldc, splitk, _p(ws), ws.numel(), _stream()))
+        check(lib.cruse_gemm_bf16_nt_slabs(M, N, K, _at(A, a_off), lda, a_kstride, _at(Bm, b_off), ldb, b_kstride,
+                                           _at(C, c_off, 4), ldc, splitk, _p(ws), ws.numel(), _stream()))
         return
     if C.dtype in _OUT16 and A.dtype == torch.bfloat16 and Bm.dtype == torch.bfloat16 and not accumulate and abs(splitk) <= 1:
         return _gemm_nt_out16(M, N, K, A, None, a_off, lda, a_kstride, Bm, None, b_off, ldb, b_kstride, C, c_off, ldc, bias, False)
     if A.dtype != torch.bfloat16 or Bm.dtype != torch.bfloat16 or C.dtype != torch.float32:
         raise RuntimeError("gemm_bf16_nt needs bf16 operands and an f32 result")
-    check(lib.cruse_gemm_bf16_nt(M, N, K, A.data_ptr() + 2 * a_off, lda, a_kstride, Bm.data_ptr() + 2 * b_off, ldb, b_kstride,
-                                 C.data_ptr() + 4 * c_off, ldc, _p(bias), 1 if accumulate else 0, splitk, _stream()))
+    check(lib.cruse_gemm_bf16_nt(M, N, K, _at(A, a_off), lda, a_kstride, _at(Bm, b_off), ldb, b_kstride,
+                                 _at(C, c_off, 4), ldc, _p(bias), 1 if accumulate else 0, splitk, _stream()))
 
 
 def gemm_bf16_nt_cat(Ms, N, K, A, a_rows, lda, Bs, b_off, ldb, C, c_off, ldc, splitk, a_kstride=64, b_kstride=64):
@@ -574,9 +579,9 @@ def gemm_bf16_nt_cat(Ms, N, K, A, a_rows, lda, Bs, b_off, ldb, C, c_off, ldc, sp
     ws = _ws(("gemm_slabs", _stream()), nbytes, C.device, zero=False)
     ms = (ctypes.c_int * n)(*[int(m) for m in Ms])
     ar = (ctypes.c_longlong * n)(*[int(r) for r in a_rows])
-    bs = (ctypes.c_void_p * n)(*[b.data_ptr() + 2 * b_off for b in Bs])
+    bs = (ctypes.c_void_p * n)(*[_at(b, b_off) for b in Bs])
     check(lib.cruse_gemm_bf16_nt_slabs_cat(n, ctypes.cast(ms, ctypes.c_void_p), N, K, A.data_ptr(), ctypes.cast(ar, ctypes.c_void_p), lda, a_kstride,
-                                           ctypes.cast(bs, ctypes.c_void_p), ldb, b_kstride, C.data_ptr() + 4 * c_off, ldc, splitk, _p(ws),
+                                           ctypes.cast(bs, ctypes.c_void_p), ldb, b_kstride, _at(C, c_off, 4), ldc, splitk, _p(ws),
                                            ws.numel(), _stream()))
 
 
@@ -585,8 +590,8 @@ def gemm_bf16_nt_atr(M, N, K, A_T, a_off, a_mb_stride, n_mb, Bm, b_off, ldb, C, 
     cruse_gemm_bf16_nt_atr -- dX straight from the gate-gradient tensor dgT, no row-major dgi."""
     if A_T.dtype != torch.bfloat16 or Bm.dtype != torch.bfloat16 or C.dtype != torch.float32:
         raise RuntimeError("gemm_bf16_nt_atr needs bf16 operands and an f32 result")
-    check(lib.cruse_gemm_bf16_nt_atr(M, N, K, A_T.data_ptr() + 2 * a_off, a_mb_stride, n_mb, Bm.data_ptr() + 2 * b_off, ldb, b_kstride,
-                                     C.data_ptr() + 4 * c_off, ldc, 1 if accumulate else 0, _stream()))
+    check(lib.cruse_gemm_bf16_nt_atr(M, N, K, _at(A_T, a_off), a_mb_stride, n_mb, _at(Bm, b_off), ldb, b_kstride,
+                                     _at(C, c_off, 4), ldc, 1 if accumulate else 0, _stream()))
     return C
 
 
@@ -619,9 +624,8 @@ def gemm_bf16_nt_seg(M, N, K, A_hi, A_lo, a_off, lda, B_hi, B_lo, b_off, ldb, C,
                      b_kstride=64):
     """gemm_bf16_nt / gemm_bf16x3_nt (A_lo / B_lo None: plain bf16) on the rows of ONE TIME CHUNK: seg = (seg_len, seg_stride,
     seg_off), M = B * seg_len (cruse_gemm_bf16_nt_seg)."""
-    lo = lambda t_, off: None if t_ is None else t_.data_ptr() + 2 * off
-    check(lib.cruse_gemm_bf16_nt_seg(M, N, K, A_hi.data_ptr() + 2 * a_off, lo(A_lo, a_off), lda, B_hi.data_ptr() + 2 * b_off,
-                                     lo(B_lo, b_off), ldb, b_kstride, C.data_ptr() + 4 * c_off, ldc, _p(bias),
+    check(lib.cruse_gemm_bf16_nt_seg(M, N, K, _at(A_hi, a_off), _at(A_lo, a_off), lda, _at(B_hi, b_off),
+                                     _at(B_lo, b_off), ldb, b_kstride, _at(C, c_off, 4), ldc, _p(bias),
                                      1 if accumulate else 0, seg[0], seg[1], seg[2], _stream()))
 
 
@@ -660,9 +664,8 @@ _OUT16 = {torch.float16: 1, torch.bfloat16: 2}        # CRUSE_DT_F16 / CRUSE_DT_
 
 def _gemm_nt_out16(M, N, K, A_hi, A_lo, a_off, lda, a_kstride, B_hi, B_lo, b_off, ldb, b_kstride, C, c_off, ldc, bias, operands_f16):
     """2-byte result rows (cruse_gemm_nt_out16): C is an f16 / bf16 tensor -- the gi rows gru_seq_fwd reads in that dtype"""
-    check(lib.cruse_gemm_nt_out16(M, N, K, A_hi.data_ptr() + 2 * a_off, None if A_lo is None else A_lo.data_ptr() + 2 * a_off, lda, a_kstride,
-                                  B_hi.data_ptr() + 2 * b_off, None if B_lo is None else B_lo.data_ptr() + 2 * b_off, ldb, b_kstride,
-                                  C.data_ptr() + 2 * c_off, ldc, _p(bias), 1 if operands_f16 else 0, _OUT16[C.dtype], _stream()))
+    check(lib.cruse_gemm_nt_out16(M, N, K, _at(A_hi, a_off), _at(A_lo, a_off), lda, a_kstride, _at(B_hi, b_off), _at(B_lo, b_off), ldb, b_kstride,
+                                  _at(C, c_off), ldc, _p(bias), 1 if operands_f16 else 0, _OUT16[C.dtype], _stream()))
     return C
 
 
@@ -676,11 +679,11 @@ def gemm_f16_nt(M, N, K, A, a_off, lda, B, b_off, ldb, C, c_off, ldc, bias=None,
     if C.dtype != torch.float32:
         raise RuntimeError("gemm_f16_nt: the result is f32, or f16 / bf16 rows (cruse_gemm_nt_out16)")
     if B_lo is not None:
-        check(lib.cruse_gemm_f16x2_nt(M, N, K, A.data_ptr() + 2 * a_off, lda, a_kstride, B.data_ptr() + 2 * b_off, B_lo.data_ptr() + 2 * b_off, ldb,
-                                      b_kstride, C.data_ptr() + 4 * c_off, ldc, _p(bias), _stream()))
+        check(lib.cruse_gemm_f16x2_nt(M, N, K, _at(A, a_off), lda, a_kstride, _at(B, b_off), _at(B_lo, b_off), ldb,
+                                      b_kstride, _at(C, c_off, 4), ldc, _p(bias), _stream()))
         return C
-    check(lib.cruse_gemm_f16_nt(M, N, K, A.data_ptr() + 2 * a_off, lda, a_kstride, B.data_ptr() + 2 * b_off, ldb, b_kstride,
-                                C.data_ptr() + 4 * c_off, ldc, _p(bias), _stream()))
+    check(lib.cruse_gemm_f16_nt(M, N, K, _at(A, a_off), lda, a_kstride, _at(B, b_off), ldb, b_kstride,
+                                _at(C, c_off, 4), ldc, _p(bias), _stream()))
     return C
 
 
@@ -709,10 +712,28 @@ def gemm_bf16x3_nt(M, N, K, A_hi, A_lo, a_off, lda, B_hi, B_lo, b_off, ldb, C, c
         return _gemm_nt_out16(M, N, K, A_hi, A_lo, a_off, lda, a_kstride, B_hi, B_lo, b_off, ldb, b_kstride, C, c_off, ldc, bias, False)
     if C.dtype != torch.float32:
         raise RuntimeError("gemm_bf16x3_nt needs an f32 result (f16 / bf16 rows without accumulation: cruse_gemm_nt_out16)")
-    check(lib.cruse_gemm_bf16x3_nt(M, N, K, A_hi.data_ptr() + 2 * a_off,
-                                   None if A_lo is None else A_lo.data_ptr() + 2 * a_off, lda, a_kstride,
-                                   B_hi.data_ptr() + 2 * b_off, B_lo.data_ptr() + 2 * b_off, ldb, b_kstride,
-                                   C.data_ptr() + 4 * c_off, ldc, _p(bias), 1 if accumulate else 0, _stream()))
+    check(lib.cruse_gemm_bf16x3_nt(M, N, K, _at(A_hi, a_off), _at(A_lo, a_off), lda, a_kstride, _at(B_hi, b_off), _at(B_lo, b_off), ldb, b_kstride,
+                                   _at(C, c_off, 4), ldc, _p(bias), 1 if accumulate else 0, _stream()))
+
+
+GEMM_FORMS = ("plain", "x3", "f16", "f16x2", "out16", "atr", "groups", "slabs", "slabs_cat", "seg")       # CRUSE_GEMM_FORM_*
+GEMM_PLANE_A_LO, GEMM_PLANE_B_LO, GEMM_PLANES_UNALIGNED = 1, 2, 4
+_GEMM_PLAN_KEYS = ("mode", "nst", "f16", "atr", "grid", "lds_bytes", "splitk", "kt_chunk", "xcdk", "tiles_m", "tiles_n", "nunits", "inner", "m_out",
+                   "slab", "reduce_grid")
+
+
+def gemm_bf16_plan(form, M, N, K, lda, a_kstride, ldb, b_kstride, ldc, planes=0, bias=False, accumulate=False, splitk=1, operands_f16=False,
+                   out_dtype=0, extras=()) -> dict:
+    """what a call of the bf16 / f16 GEMM entry points launches (cruse_gemm_bf16_plan; host-only): the kernel (mode, stages, f16, atr), its grid and
+    LDS bytes and the tile geometry.  form: one of GEMM_FORMS, the entry point whose checks run first; planes: bit set of GEMM_PLANE_*; extras: the
+    form's own numbers (cruse_hip.h) -- atr (a_mb_stride, n_mb), groups (G, a_gstep, b_gstep, c_gstep, bias_gstep), slabs (scratch_bytes),
+    slabs_cat (scratch_bytes, nprob, Ms[3], a_rows[3]), seg (seg_len, seg_stride, seg_off).  "raw" is the array as the library wrote it."""
+    out = (ctypes.c_int * len(_GEMM_PLAN_KEYS))()
+    x = (ctypes.c_longlong * max(len(extras), 8))(*[int(v) for v in extras])
+    check(lib.cruse_gemm_bf16_plan(GEMM_FORMS.index(form), M, N, K, lda, a_kstride, ldb, b_kstride, ldc, planes, 1 if bias else 0,
+                                   1 if accumulate else 0, splitk, 1 if operands_f16 else 0, out_dtype, ctypes.cast(x, ctypes.c_void_p),
+                                   ctypes.cast(out, ctypes.c_void_p)))
+    return dict(zip(_GEMM_PLAN_KEYS, out), raw=list(out))
 
 
 def transpose_bf16(x, rows, cols, shift_T=0, out=None):

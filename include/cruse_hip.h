@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CRUSE_ABI_VERSION 14
+#define CRUSE_ABI_VERSION 15
 
 enum {
     CRUSE_OK = 0,
@@ -396,6 +396,26 @@ int cruse_cast_bf16_split(const float* x, void* y, void* y_lo, long long n, void
 int cruse_gemm_bf16x3_nt(int M, int N, int K, const void* A_hi, const void* A_lo, long long lda, long long a_kstride,
                          const void* B_hi, const void* B_lo, long long ldb, long long b_kstride,
                          float* C, long long ldc, const float* bias, int accumulate, void* stream);
+/* (ABI 15) Host-only, touches no device: what a call of the ten bf16 / f16 GEMM entry points above launches -- the decision they make, without
+ * the launch.  form: whose checks run first (PLAIN cruse_gemm_bf16_nt, X3 cruse_gemm_bf16x3_nt, F16 / F16X2 cruse_gemm_f16_nt / _f16x2_nt, OUT16
+ * cruse_gemm_nt_out16, ATR / GROUPS / SLABS / SLABS_CAT / SEG cruse_gemm_bf16_nt_<form>).  planes: bit 0 A_lo present, bit 1 B_lo present, bit 2 the
+ * low planes lie 2 bytes off their 16-byte alignment; has_bias: a bias is given; every other tensor counts as present and 16-byte aligned.
+ * accumulate, splitk, operands_f16, out_dtype as the entry points take them.  A scalar the form's entry point has no argument for reaches the
+ * shared checks as given, except what defines the form (ATR: lda, a_kstride; GROUPS, SEG: a_kstride = 64; the slab forms accumulate; out_dtype
+ * counts for OUT16 alone; F16 / F16X2 are operands_f16).  extras (HOST, NULL for the forms before ATR), the form's own numbers:
+ *   ATR {a_mb_stride, n_mb}   GROUPS {G, a_gstep, b_gstep, c_gstep, bias_gstep}   SLABS {scratch_bytes}   SEG {seg_len, seg_stride, seg_off}
+ *   SLABS_CAT {scratch_bytes, nprob, Ms[3], a_rows[3]} (8 numbers whatever nprob; M is ignored)
+ * out[16]:
+ *   [0] MODE of the kernel (0 store, 1 add, 2 atomic split-K, 3 2-byte rows, 4 slabs)   [1] LDS stages (2, 3)   [2] f16 operands   [3] time-major A
+ *   [4] grid (workgroups)   [5] dynamic LDS bytes   [6] k-slices after clamping   [7] k-tiles per slice   [8] 1: the slices are pinned to XCDs
+ *   [9] row tiles   [10] column tiles (all groups)   [11] units   [12] tiles per unit        -- the kernel's XCD-aware tile order
+ *   [13] output rows   [14] floats between two slabs, [15] workgroups of the slab sum        -- 0 without slabs
+ * Returns what the entry point would: an error code and cruse_last_error() where the call is refused. */
+enum { CRUSE_GEMM_FORM_PLAIN, CRUSE_GEMM_FORM_X3, CRUSE_GEMM_FORM_F16, CRUSE_GEMM_FORM_F16X2, CRUSE_GEMM_FORM_OUT16, CRUSE_GEMM_FORM_ATR,
+       CRUSE_GEMM_FORM_GROUPS, CRUSE_GEMM_FORM_SLABS, CRUSE_GEMM_FORM_SLABS_CAT, CRUSE_GEMM_FORM_SEG, CRUSE_GEMM_FORM_N };
+int cruse_gemm_bf16_plan(int form, int M, int N, int K, long long lda, long long a_kstride, long long ldb, long long b_kstride, long long ldc,
+                         int planes, int has_bias, int accumulate, int splitk, int operands_f16, int out_dtype,
+                         const long long* extras, int* out);
 /* K-tiled time-major transpose: yT[(r/64)*cols*64 + c*64 + r%64] = bf16(x[(r - s)*ld + c]) with s = 0, or s = 1
  * when shift_T > 0 (then 0 where r % shift_T == 0: the h_{t-1} operand of dW_hh); frames rows <= r < ldT are
  * zero-filled (ldT % 64 == 0). */

@@ -123,7 +123,7 @@ def test_interface_without_a_device():
     hdr = parse_header()
     for name in ("cruse_biquad_ws_bytes", "cruse_biquad_cascade"):
         assert name in hdr and SIGNATURES[name] == hdr[name], name
-    assert re.search(r"^#define CRUSE_ABI_VERSION 14$", hdr_src, flags=re.M) and lib.cruse_abi_version() == 14
+    assert re.search(r"^#define CRUSE_ABI_VERSION 15$", hdr_src, flags=re.M) and lib.cruse_abi_version() == 15
     defs = dict(re.findall(r"^#define (CRUSE_BIQUAD_\w+) (\d+)$", hdr_src, flags=re.M))
     assert int(defs["CRUSE_BIQUAD_CHUNK"]) == ops.BIQUAD_CHUNK and int(defs["CRUSE_BIQUAD_TILE"]) == ops.BIQUAD_TILE
     assert ops.BIQUAD_TILE % ops.BIQUAD_CHUNK == 0

@@ -23,7 +23,7 @@ def test_header_signatures_and_library_agree():
     hdr = parse_header()
     for name in NAMES:
         assert name in hdr and SIGNATURES[name] == hdr[name] and hasattr(lib, name), name
-    assert re.search(r"^#define CRUSE_ABI_VERSION 14$", hdr_src, flags=re.M) and lib.cruse_abi_version() == 14
+    assert re.search(r"^#define CRUSE_ABI_VERSION 15$", hdr_src, flags=re.M) and lib.cruse_abi_version() == 15
     part = int(re.search(r"^#define CRUSE_FFTCONV_PART (\d+)$", hdr_src, flags=re.M).group(1))
     assert part == ops.FFTCONV_PART == F.P
 

@@ -972,6 +972,34 @@ def test_gemm_bf16x3_forward_projection(ops):
         assert rel_l2(C1, ref) > 50 * rel_l2(C, ref)                # the plain bf16 product is two orders coarser
 
 
+@pytest.mark.parametrize("variant", ["plain", "planes", "accumulate"])
+@pytest.mark.parametrize("B,T,seg", [(3, 17, (5, 17, 7)), (2, 401, (130, 401, 200))])      # (the second: a 128-row tile straddles two clips)
+def test_gemm_row_segments_of_a_time_chunk(ops, B, T, seg, variant):
+    """gemm_bf16_nt_seg on frames [seg_off, seg_off + seg_len) of every clip: the bits of the same product on a dense copy of those rows (same
+    kernel, tiles and accumulation order), and not one element outside them written."""
+    N, K = 96, 128
+    lda, ldc, M = K + 64, N + 4, B * seg[0]
+    gen = torch.Generator().manual_seed(T + seg[0])
+    x = torch.randn(B * T, lda, generator=gen).cuda()
+    x_hi = x.to(torch.bfloat16); x_lo = (x - x_hi.float()).to(torch.bfloat16)
+    w_hi, w_lo = ops.ktile_bf16(torch.randn(N, K, generator=gen).cuda(), N, K, split=True)
+    bias = torch.randn(N, generator=gen).cuda()
+    acc, lo = variant == "accumulate", variant == "planes"
+    C0 = torch.randn(B * T, ldc, generator=gen).cuda() if acc else torch.full((B * T, ldc), 7.0).cuda()
+    rows = torch.cat([torch.arange(b * T + seg[2], b * T + seg[2] + seg[0]) for b in range(B)]).cuda()
+    d_hi, d_lo, ref = x_hi[rows].contiguous(), x_lo[rows].contiguous(), C0[rows].contiguous()
+    if lo:
+        ops.gemm_bf16x3_nt(M, N, K, d_hi, d_lo, 0, lda, w_hi, w_lo, 0, 64, ref, 0, ldc, bias=bias, b_kstride=N * 64)
+    else:
+        ops.gemm_bf16_nt(M, N, K, d_hi, 0, lda, w_hi, 0, 64, ref, 0, ldc, bias=bias, accumulate=acc, b_kstride=N * 64)
+    C = C0.clone()
+    ops.gemm_bf16_nt_seg(M, N, K, x_hi, x_lo if lo else None, 0, lda, w_hi, w_lo if lo else None, 0, 64, C, 0, ldc, seg, bias=bias, accumulate=acc,
+                         b_kstride=N * 64)
+    assert torch.equal(C[rows, :N], ref[:, :N]) and not torch.equal(ref[:, :N], C0[rows, :N])
+    outside = torch.ones(B * T, dtype=torch.bool, device="cuda"); outside[rows] = False
+    assert torch.equal(C[outside], C0[outside]) and torch.equal(C[:, N:], C0[:, N:])
+
+
 def test_bf16_operand_copies_from_bn_and_ln(ops):
     """bn_finalize_act_fwd / ln_fwd also write the bf16 copy the next gate GEMM reads: identical to a cast of their f32
     output (vectorised LayerNorm in-kernel, the group-interleaved form through the cast kernel)."""

@@ -72,7 +72,7 @@ def test_a_cut_clip_is_the_padded_clip_with_an_explicit_length(length):
 def test_c_symbols_header_and_abi_version():
     from cruse_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "cruse_hip.h")).read()
-    assert "#define CRUSE_ABI_VERSION 14" in hdr and _lib.ABI_VERSION == 14 and _lib.lib.cruse_abi_version() == 14
+    assert "#define CRUSE_ABI_VERSION 15" in hdr and _lib.ABI_VERSION == 15 and _lib.lib.cruse_abi_version() == 15
     for name in ("cruse_si_sdr_ragged", "cruse_stoi_ragged"):
         assert name in _lib.SIGNATURES
         assert re.search(r"\bint %s\(" % name, hdr), name

@@ -117,7 +117,7 @@ def test_registry_and_refusals():
 def test_c_symbols_header_and_abi_version():
     from cruse_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "cruse_hip.h")).read()
-    assert "#define CRUSE_ABI_VERSION 14" in hdr and _lib.ABI_VERSION == 14 and _lib.lib.cruse_abi_version() == 14
+    assert "#define CRUSE_ABI_VERSION 15" in hdr and _lib.ABI_VERSION == 15 and _lib.lib.cruse_abi_version() == 15
     for name in ("cruse_si_sdr", "cruse_stoi_layout", "cruse_stoi_ws_bytes", "cruse_stoi_tables", "cruse_stoi"):
         assert name in _lib.SIGNATURES
         assert re.search(r"\b(int|size_t) %s\(" % name, hdr), name

@@ -128,7 +128,7 @@ def test_refusals_of_metrics_sdr_need_no_device():
 def test_c_symbols_header_and_constants():
     from cruse_amd import _lib, ops
     hdr = open(os.path.join(ROOT, "include", "cruse_hip.h")).read()
-    assert "#define CRUSE_ABI_VERSION 14" in hdr and _lib.lib.cruse_abi_version() == 14
+    assert "#define CRUSE_ABI_VERSION 15" in hdr and _lib.lib.cruse_abi_version() == 15
     assert _lib.SIGNATURES["cruse_sdr"] == ("pppiiipppp", "i") and _lib.SIGNATURES["cruse_sdr_ws_bytes"] == ("iii", "z")
     assert re.search(r"\bint cruse_sdr\(", hdr) and re.search(r"\bsize_t cruse_sdr_ws_bytes\(", hdr)
     assert hasattr(_lib.lib, "cruse_sdr") and hasattr(_lib.lib, "cruse_sdr_ws_bytes")

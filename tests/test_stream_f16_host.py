@@ -73,7 +73,7 @@ def test_new_entry_points_declared_and_bound():
     for sym in NEW_SYMBOLS:
         assert re.search(rf"\bint {sym}\(", header), f"{sym} is not declared in include/cruse_hip.h"
         assert re.search(rf"\"{sym}\":\s*\(\"[a-zA-Z]+\",\s*\"i\"\)", lib_py), f"{sym} is not in cruse_amd/_lib.py:SIGNATURES"
-    assert "#define CRUSE_ABI_VERSION 14" in header                    # (14: cruse_conv_plan)
+    assert "#define CRUSE_ABI_VERSION 15" in header                    # (15: cruse_gemm_bf16_plan)
 
 
 def test_weight_pack_layout():

@@ -42,7 +42,7 @@ def test_entry_points_declared_and_bound():
         sib = sym[:-3]                                                # the sibling's arguments plus the format / limit / counter
         extra = 1 if "encode" in sym else 3
         assert len(SIGNATURES[sym][0]) == len(SIGNATURES[sib][0]) + extra, sym
-    assert "#define CRUSE_ABI_VERSION 14" in header                   # (14: cruse_conv_plan)
+    assert "#define CRUSE_ABI_VERSION 15" in header                   # (15: cruse_gemm_bf16_plan)
 
 
 def test_constructor_keywords():
