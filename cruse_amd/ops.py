@@ -793,7 +793,7 @@ def gru_seq_fwd(gi, w_hh: List[torch.Tensor], b_hh: List[torch.Tensor], B, T, G,
     h0 [B, G*Hg] ("cat" layout: feature = group*Hg + unit): initial state (cust_conv.py:305-325); None = 0.
     chunk = (t0, n): run only frames [t0, t0+n) of the [B,T] tensors into `out` = (h, coef, an, z) from the call that ran
     the frames before them -- the initial state is then h[:, t0-1] (h0 for t0 == 0).  Consecutive chunks reproduce the
-    single launch (cruse_gru_seq_fwd_ex).  wide: chains of 16 clips (half the workgroups; same results).
+    single launch (cruse_gru_seq_fwd_ex; bit for bit in f32 / bf16x3 and against launches given an h0 -- not bf16 at Hg 160 / 320 against h0 = None, see there).  wide: chains of 16 clips (half the workgroups; same results).
     zeroed: the slot's scratch is already clear
     (gru_step_ws_clear)."""
     if gi.dtype not in (torch.float32, torch.float16):

@@ -468,7 +468,12 @@ int cruse_gru_seq_bwd_on(const float* dout, const float* const* w_hh, const void
  * T steps of tensors whose clips are TS >= T frames apart; every pointer is already advanced to the first frame of the run.
  *   _fwd_ex: h0 [B][G*Hg] ("cat" feature layout, clips h0_bstride floats apart, 16-byte aligned) or NULL (= 0).  A long
  *            sequence can be run as consecutive time chunks: chunk [t0, t0+n) is (gi + t0*G*3*Hg, h + t0*G*Hg, ..., h0 =
- *            h + (t0-1)*G*Hg with h0_bstride = TS*G*Hg, T = n) -- the results are those of the single launch.
+ *            h + (t0-1)*G*Hg with h0_bstride = TS*G*Hg, T = n) -- the results are those of the single launch.  Bit for bit: in the f32 and
+ *            split-bf16 modes, and wherever the launch it is compared with was given an h0 as well (the same kernel then serves every chunk).
+ *            Not in CRUSE_PREC_BF16 at Hg = 160 / 320 on chains of 8 against a launch from h0 == NULL: that launch runs gru_fwd_tf_kernel (its
+ *            hand-off needs |h| < 1; every wave walks the whole K), a continuation gru_fwd_lean_kernel (K split over four waves) -- the f32 sums
+ *            are formed in another order; the results agree to the bf16 operands' precision.  (Observed once, unexplained: at Hg = 160 a
+ *            difference of bits remained with "gru_tf" = 0, the lean kernel on both sides -- no promise is made for that case either.)
  *   _bwd_ex: carry != 0: the first iteration takes dh of the run's LAST frame from the dh buffer (written by the run that
  *            follows it in time) instead of forming it from dout: chunk [t0, t0+n) of a longer sequence is run as the
  *            n + 1 frames [t0, t0+n] with carry = 1 (the last chunk: n frames, carry = 0).  dgi on a sub-sequence is

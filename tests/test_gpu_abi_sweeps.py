@@ -29,6 +29,11 @@ def Z(*shape, dtype=np.float32):
     return D(np.zeros(shape, dtype))
 
 
+def ZP(*shape):
+    """a uint16 OUTPUT of a layout kernel filled with 0x7FC0 (bf16 NaN): 'wrote zeros' must differ from 'wrote nothing'"""
+    return D(np.full(shape, 0x7FC0, np.uint16))
+
+
 def st():
     return torch.cuda.current_stream().cuda_stream
 
@@ -189,7 +194,7 @@ def test_bf16_gemm_family_and_layout_kernels(hip):
         x = rnd(rows, cols)
         ldT = (rows + 63) // 64 * 64
         for shift in sorted({0, rows, rows // 2 if rows % 2 == 0 else rows}):          # (shift_T: frames per clip -- rows are whole clips)
-            yT = Z(ldT // 64, cols, 64, dtype=np.uint16); xd = D(x)
+            yT = ZP(ldT // 64, cols, 64); xd = D(x)
             rc = hip.cruse_transpose_bf16(xd.data_ptr(), rows, cols, cols, yT.data_ptr(), ldT, shift, st())
             torch.cuda.synchronize()
             if rc: print("refused transpose", rows, cols, shift, hip.cruse_last_error()); continue
@@ -200,10 +205,10 @@ def test_bf16_gemm_family_and_layout_kernels(hip):
             wantT = f32_of(bf16(want)).reshape(ldT // 64, 64, cols).transpose(0, 2, 1)
             chk(("transpose_bf16", rows, cols, shift), f32_of(yT.cpu().numpy()), wantT, 0.0)
         kp = (cols + 63) // 64 * 64
-        y, ylo = Z(kp // 64, rows, 64, dtype=np.uint16), Z(kp // 64, rows, 64, dtype=np.uint16); xd = D(x)
+        y, ylo = ZP(kp // 64, rows, 64), ZP(kp // 64, rows, 64); xd = D(x)
         rc = hip.cruse_ktile_bf16(xd.data_ptr(), rows, cols, cols, y.data_ptr(), ylo.data_ptr(), st())
         torch.cuda.synchronize()
-        y16, y16lo = Z(kp // 64, rows, 64, dtype=np.uint16), Z(kp // 64, rows, 64, dtype=np.uint16)
+        y16, y16lo = ZP(kp // 64, rows, 64), ZP(kp // 64, rows, 64)
         rc2 = hip.cruse_ktile_f16_split(xd.data_ptr(), rows, cols, cols, y16.data_ptr(), y16lo.data_ptr(), st())
         torch.cuda.synchronize()
         if rc2: bad.append(("refused ktile_f16_split", rows, cols))
@@ -219,7 +224,7 @@ def test_bf16_gemm_family_and_layout_kernels(hip):
             chk(("ktile hi", rows, cols), f32_of(y.cpu().numpy()), f32_of(hi).reshape(rows, kp // 64, 64).transpose(1, 0, 2), 0.0)
             chk(("ktile lo", rows, cols), f32_of(ylo.cpu().numpy()), f32_of(lo).reshape(rows, kp // 64, 64).transpose(1, 0, 2), 0.0)
         if (rows * cols) % 4 == 0:
-            yh, yl = Z(rows, cols, dtype=np.uint16), Z(rows, cols, dtype=np.uint16)
+            yh, yl = ZP(rows, cols), ZP(rows, cols)
             rc = hip.cruse_cast_bf16_split(xd.data_ptr(), yh.data_ptr(), yl.data_ptr(), rows * cols, st())
             torch.cuda.synchronize()
             if rc: print("refused cast split", rows, cols, hip.cruse_last_error())

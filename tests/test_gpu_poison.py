@@ -1,0 +1,978 @@
+"""Poisoned padding, scratch and outputs for the training kernels.
+
+The other GPU modules hand the kernels zero-filled buffers; training hands them torch.empty outputs, workspaces nobody cleared and operands whose
+leading dimension is larger than their extent.  Here every byte a call has no right to depend on holds a fill pattern (f32 / f64 quiet NaN, bf16 0x7FC0,
+f16 0x7E00, 0xA5 bytes for words) and five properties are checked on the memory the test owns:
+  P1 don't-care inputs: the outputs of a run with those bytes zero and of a run with them poisoned are bit-identical
+  P2 outputs are written in full: a poisoned output holds no fill pattern inside its logical extent afterwards and equals the P1 result
+  P3 nothing else is written: lead, trail and row gaps of the output allocation are unchanged
+  P4 scratch the callee is said to clear or to write in full may hold anything
+  P5 a zero pad a producer is documented to write reads back as exact zeros from a poisoned buffer
+Where an output is accumulated with floating-point atomics (split-K without slabs, weight-gradient and LayerNorm parameter sums, loss words) the order
+of summation is free: there "bit-identical" is replaced by "finite, and within the tolerance the existing test of that entry point uses" of a float64
+reference (each use cites the test).  Refusals (non-zero return codes) are counted per test and compared with the number the entry point's checks give."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ref_lib as R  # noqa: E402
+from ref_lib import LL  # noqa: E402
+from util import bits, embed, embed_out, has_poison, poison_, poisoned_empty, same_bits  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+BF, F16, F32, F64 = torch.bfloat16, torch.float16, torch.float32, torch.float64
+
+
+def st():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def P(x):
+    return None if x is None else x.data_ptr()
+
+
+@pytest.fixture(scope="module")
+def ref():
+    return R.load()
+
+
+@pytest.fixture(scope="module")
+def hip():
+    from cruse_amd._lib import lib
+    return lib
+
+
+def rnd_(seed):
+    g = np.random.default_rng(seed)
+    return lambda *s: np.ascontiguousarray(g.standard_normal(s).astype(np.float32))
+
+
+def bf16(a):      # RNE to bf16, as uint16
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32)
+    return ((u + 0x7fff + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def f32_of(b):
+    return (b.astype(np.uint32) << 16).view(np.float32)
+
+
+def T16(u16, dt=BF):
+    """uint16 bit patterns -> a bf16 / f16 torch tensor (host)"""
+    return torch.from_numpy(np.ascontiguousarray(u16).view(np.int16)).view(dt)
+
+
+def U16(x):
+    """bf16 / f16 device tensor -> uint16 numpy"""
+    return bits(x.contiguous()).cpu().numpy().view(np.uint16)
+
+
+def rel(got, want):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    return float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))
+
+
+class Log:
+    """failures of one test, collected; guards are run through it so that a failing guard names its case"""
+
+    def __init__(self):
+        self.bad, self.n, self.refused = [], 0, 0
+
+    def guard(self, tag, *checks):
+        """runs guard functions: embed()'s (P3) and the tests' own for group gaps and rows outside a segment (also "nothing else written")"""
+        for c in checks:
+            try:
+                c(str(tag))
+            except AssertionError as ex:
+                self.bad.append(("P3", tag, str(ex)[:200]))
+
+    def written(self, tag, *outs):
+        """has_poison sees the EXACT fill bits only; a NaN a kernel derives from poison (another payload, e.g. 0xFFC00000 out of an MFMA) is caught by
+        the L.same / L.close / value comparison every output here also gets -- keep one next to each use"""
+        for i, o in enumerate(outs):
+            if has_poison(o):
+                self.bad.append(("P2 fill pattern left in output", tag, i))
+
+    def same(self, tag, a, b, what="P1"):
+        if not same_bits(a, b):
+            self.bad.append((what + " not bit-identical", tag))
+
+    def close(self, tag, got, want, tol):
+        got = got.detach().double().cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
+        want = want.detach().double().cpu().numpy() if isinstance(want, torch.Tensor) else np.asarray(want, np.float64)
+        e = rel(got, want) if np.isfinite(got).all() else float("inf")
+        if not e <= tol:
+            self.bad.append(("not finite / off the f64 reference", tag, e, tol))
+
+
+# ======================================================================================================================
+# layout producers
+# ======================================================================================================================
+def test_layout_producers_write_all_of_their_output_and_their_zero_pads(hip):
+    """cruse_ktile_bf16 / _f16 / _f16_split: "y[(k/64)*rows*64 + n*64 + k%64] = bf16(x[n*ld + k]), zero for cols <= k < ceil64(cols) ... y_lo (nullable):
+    the low plane bf16(x - y)" -- reads x[n*ld + k] for k < cols only, writes all of [ceil64(cols)/64, rows, 64] of every plane given.
+    cruse_transpose_bf16: "yT[(r/64)*cols*64 + c*64 + r%64] = bf16(x[(r - s)*ld + c]) ... 0 where r % shift_T == 0 ...; frames rows <= r < ldT are
+    zero-filled" -- writes all of [ldT/64, cols, 64].   cruse_cast_bf16 / _split: "y[i] = bf16(x[i]), n % 4 == 0", "y_lo = bf16(x - y) (nullable)".
+    ops.cast_bf16_padded: "bf16 copy of x followed by `pad` zero elements".
+    P1 (row gaps of x under ld), P2, P3, P5.  Refusals expected: 0 (ld >= cols, 16-byte aligned outputs, n % 4 == 0 for all three shapes)."""
+    from cruse_amd import ops
+    rnd, L = rnd_(21), Log()
+    for (rows, cols) in ((1, 32), (65, 160), (130, 96)):
+        x = rnd(rows, cols)
+        kp, ldT = (cols + 63) // 64 * 64, (rows + 63) // 64 * 64
+        xp = np.zeros((rows, kp), np.float32); xp[:, :cols] = x
+        tile = lambda a: np.ascontiguousarray(a.reshape(rows, kp // 64, 64).transpose(1, 0, 2))
+        hi = bf16(xp); lo = bf16(xp - f32_of(hi))
+        h16 = xp.astype(np.float16); l16 = (xp - h16.astype(np.float32)).astype(np.float16)
+        padk = np.zeros((rows, kp), bool); padk[:, cols:] = True; padk = tile(padk)
+        for row_pad in (0, 4, 1):          # ld == cols; 16-byte loads with a row gap; 4-byte loads with a row gap
+            ld = cols + row_pad
+            for fill in (False, True):     # the row gaps of x: zero, then poisoned (P1: same expected bits both times)
+                xd, _ = embed(torch.from_numpy(x), row_pad=row_pad, fill=fill)
+                tag = (rows, cols, ld, fill)
+                for name, dt, want, call in (
+                        ("ktile_bf16", BF, (hi,), lambda y, yl: hip.cruse_ktile_bf16(P(xd), rows, cols, ld, P(y), None, st())),
+                        ("ktile_bf16 split", BF, (hi, lo), lambda y, yl: hip.cruse_ktile_bf16(P(xd), rows, cols, ld, P(y), P(yl), st())),
+                        ("ktile_f16", F16, (h16.view(np.uint16),), lambda y, yl: hip.cruse_ktile_f16(P(xd), rows, cols, ld, P(y), st())),
+                        ("ktile_f16_split", F16, (h16.view(np.uint16), l16.view(np.uint16)),
+                         lambda y, yl: hip.cruse_ktile_f16_split(P(xd), rows, cols, ld, P(y), P(yl), st()))):
+                    y, cy = embed_out((kp // 64, rows, 64), dt); yl, cl = embed_out((kp // 64, rows, 64), dt)
+                    rc = call(y, yl); torch.cuda.synchronize()
+                    if rc: L.refused += 1; continue
+                    L.n += 1
+                    L.guard((name,) + tag, cy, cl)
+                    outs = (y, yl)[:len(want)]
+                    L.written((name,) + tag, *outs)
+                    for o, w in zip(outs, want):
+                        got = U16(o)
+                        if not np.array_equal(got, tile(w)): L.bad.append(("P2 values", name) + tag)
+                        if got[padk].any(): L.bad.append(("P5 pad not exact zeros", name) + tag)
+                for shift in (0, rows):
+                    yT, cT = embed_out((ldT // 64, cols, 64), BF)
+                    rc = hip.cruse_transpose_bf16(P(xd), rows, cols, ld, P(yT), ldT, shift, st()); torch.cuda.synchronize()
+                    if rc: L.refused += 1; continue
+                    L.n += 1
+                    want = np.zeros((ldT, cols), np.float32)
+                    if shift: want[1:rows] = x[:rows - 1]; want[0:rows:shift] = 0
+                    else: want[:rows] = x
+                    wantT = bf16(want).reshape(ldT // 64, 64, cols).transpose(0, 2, 1)
+                    got = U16(yT)
+                    L.guard(("transpose_bf16", shift) + tag, cT); L.written(("transpose_bf16", shift) + tag, yT)
+                    if not np.array_equal(got, wantT): L.bad.append(("P2 values", "transpose_bf16", shift) + tag)
+                    padr = np.zeros((ldT, cols), bool); padr[rows:] = True
+                    if got[padr.reshape(ldT // 64, 64, cols).transpose(0, 2, 1)].any(): L.bad.append(("P5 pad frames not exact zeros", "transpose_bf16", shift) + tag)
+        # the flat casts (no leading dimension)
+        xd = torch.from_numpy(x).cuda(); n = rows * cols
+        hi = bf16(x); lo = bf16(x - f32_of(hi))
+        for name, want, call in (("cast_bf16", (hi,), lambda y, yl: hip.cruse_cast_bf16(P(xd), P(y), n, st())),
+                                 ("cast_bf16_split", (hi, lo), lambda y, yl: hip.cruse_cast_bf16_split(P(xd), P(y), P(yl), n, st()))):
+            y, cy = embed_out((rows, cols), BF); yl, cl = embed_out((rows, cols), BF)
+            rc = call(y, yl); torch.cuda.synchronize()
+            if rc: L.refused += 1; continue
+            L.n += 1
+            L.guard((name, rows, cols), cy, cl); L.written((name, rows, cols), *(y, yl)[:len(want)])
+            for o, w in zip((y, yl), want):
+                if not np.array_equal(U16(o), w): L.bad.append(("P2 values", name, rows, cols))
+        with poisoned_empty():
+            for split in (False, True):
+                r = ops.cast_bf16_padded(xd, 64, split=split); torch.cuda.synchronize()
+                for o, w in zip(r if split else (r,), (hi, lo)):
+                    L.n += 1
+                    got = U16(o)
+                    if not np.array_equal(got[:n], w.reshape(-1)): L.bad.append(("P2 values", "cast_bf16_padded", split, rows, cols))
+                    if got.size != n + 64 or got[n:].any(): L.bad.append(("P5 tail not exact zeros", "cast_bf16_padded", split, rows, cols))
+    assert not L.bad, L.bad[:10]
+    assert L.refused == 0 and L.n == 3 * (3 * 2 * 6 + 2 + 3), (L.refused, L.n)
+
+
+# ======================================================================================================================
+# bf16 / f16 GEMM family
+# ======================================================================================================================
+GEMM_TOL = 2e-5       # test_gpu_abi_sweeps.py::test_bf16_gemm_family_and_layout_kernels, every product of the family
+
+
+def test_bf16_gemm_family_on_poisoned_gaps_outputs_and_slabs(hip):
+    """cruse_gemm_bf16_nt: "Operand element (m, k) is A[(k/64)*a_kstride + m*lda + k%64]: a_kstride == 64 is plain row-major (lda >= K) ... Same for B.
+    splitk > 1 adds atomically and needs accumulate != 0" -- reads m < M, n < N, k < K of the operands and bias[n < N]; C[m*ldc + n] is stored
+    (accumulate == 0: its prior content is don't-care) or added to, nothing else of C is touched.
+    _slabs: "every slice STORING its partial sums to its own [M][N] slab of `scratch` ... and one kernel adding the slabs to C in slice order ...
+    reproducible.  N % 4 == 0" -- the scratch needs no clearing (P4).   _x3 / _f16 / _f16x2 / _groups / _seg / _atr: the same reads per plane / group /
+    segment; _seg: "logical row m of A and of C is physical row (m / seg_len) * seg_stride + seg_off + m % seg_len" -- rows outside the segment are
+    neither read nor written.   _atr: "element (m, k) at A_T[(m / 64) * a_mb_stride + k * 64 + m % 64]".
+    K-tiled and time-major operands are made by cruse_ktile_* / cruse_transpose_bf16 on POISONED buffers: producer and consumer as production pairs
+    them; their zero pads (24 columns / the frames up to ldT) meet finite values of the other operand.
+    _slabs_cat: "C[sum M_i, N] += cat_i( A[a_rows[i] .. a_rows[i] + M_i) . B_i^T )      slab form as above".
+    Refusals expected: 4, the slab form and the _cat form at N = 127 and N = 33 ("slab form needs N % 4 == 0"; ops.gemm_bf16_nt falls back to the atomic form there;
+    at K = 64 the three slices clamp to one, no slab is used and N = 5 is served) -- the slab form is therefore also run at N rounded up to 4."""
+    rnd, L = rnd_(22), Log()
+    slab_refused = 0
+
+    def run2(tag, build, deterministic=True, want=None):
+        """build(fill) -> (rc, [outputs], [guards]); fill False / True: the don't-care bytes zero / poisoned"""
+        res = []
+        for fill in (False, True):
+            rc, outs, guards = build(fill); torch.cuda.synchronize()
+            if rc:
+                L.refused += 1
+                return False
+            if fill:
+                L.guard(tag, *guards); L.written(tag, *outs)
+            res.append([o.clone() for o in outs])
+        L.n += 1
+        for a, b in zip(*res):
+            if deterministic: L.same(tag, a, b)
+            if want is not None: L.close(tag, b, want, GEMM_TOL); L.close(tag, a, want, GEMM_TOL)
+        return True
+
+    for (M, N, K) in ((3, 5, 64), (129, 127, 128), (17, 33, 320), (129, 128, 128), (17, 36, 320)):
+        issue_shape = N % 4 != 0
+        A, Bm, bias, C0 = bf16(rnd(M, K)), bf16(rnd(N, K)), rnd(N), rnd(M, N)
+        Af, Bf = f32_of(A).astype(np.float64), f32_of(Bm).astype(np.float64)
+        want = Af @ Bf.T
+        lda = ldb = K + 8
+        ldc = N + 3
+        biasd = torch.from_numpy(bias).cuda()
+
+        def emb_c(fill, acc):
+            """C: accumulate -> the prior content is input (poison outside the extent only); else all of it is don't-care"""
+            c, chk = embed(torch.from_numpy(C0), row_pad=3, fill=True if acc else fill)
+            if not acc and fill: poison_(c)
+            return c, chk
+        if issue_shape:
+            for acc, sk in ((0, 1), (1, 3)):
+                def build(fill):
+                    a, _ = embed(T16(A), row_pad=8, fill=fill); b, _ = embed(T16(Bm), row_pad=8, fill=fill); c, chk = emb_c(fill, acc)
+                    rc = hip.cruse_gemm_bf16_nt(M, N, K, P(a), lda, 64, P(b), ldb, 64, P(c), ldc, P(biasd) if sk == 1 else None, acc, sk, st())
+                    return rc, [c], [chk]
+                # (splitk > 1: f32 atomics, free order -> the f64 reference within GEMM_TOL, not bit-identity; K = 64 clamps to one slice)
+                run2(("gemm_bf16_nt", M, N, K, acc, sk), build, deterministic=(sk == 1 or K == 64), want=want + (bias if sk == 1 else 0) + (C0 if acc else 0))
+        # slab form: scratch poisoned / zero (P4), C += (prior content is input)
+        def build(fill):
+            a, _ = embed(T16(A), row_pad=8, fill=fill); b, _ = embed(T16(Bm), row_pad=8, fill=fill); c, chk = emb_c(fill, 1)
+            nb = hip.cruse_gemm_bf16_slab_bytes(M, N, 3)
+            ws, cws = embed(torch.zeros(nb // 4), fill=fill)
+            if fill: poison_(ws)
+            rc = hip.cruse_gemm_bf16_nt_slabs(M, N, K, P(a), lda, 64, P(b), ldb, 64, P(c), ldc, 3, P(ws), nb, st())
+            return rc, [c], [chk, cws]
+        if not run2(("gemm_bf16_nt_slabs", M, N, K), build, want=want + C0): slab_refused += 1
+        if not issue_shape:
+            continue
+        # x3: hi / lo planes of both operands
+        Af32, Bf32 = rnd(M, K), rnd(N, K)
+        Ah, Bh = bf16(Af32), bf16(Bf32); Al, Bl = bf16(Af32 - f32_of(Ah)), bf16(Bf32 - f32_of(Bh))
+        d = lambda u: f32_of(u).astype(np.float64)
+        want3 = d(Ah) @ (d(Bh) + d(Bl)).T + d(Al) @ d(Bh).T
+        def build(fill):
+            pl = [embed(T16(u), row_pad=8, fill=fill)[0] for u in (Ah, Al, Bh, Bl)]; c, chk = emb_c(fill, 0)
+            rc = hip.cruse_gemm_bf16x3_nt(M, N, K, P(pl[0]), P(pl[1]), lda, 64, P(pl[2]), P(pl[3]), ldb, 64, P(c), ldc, P(biasd), 0, st())
+            return rc, [c], [chk]
+        run2(("gemm_bf16x3_nt", M, N, K), build, want=want3 + bias)
+        # f16 / f16 + B_lo with B K-tiled by cruse_ktile_f16_split from f32 weights of K - 24 columns, on poisoned planes
+        Kw = K - 24
+        A16 = rnd(M, K).astype(np.float16); Bw = rnd(N, Kw) * 0.05
+        Bhi = Bw.astype(np.float16); Blo = (Bw - Bhi.astype(np.float32)).astype(np.float16)
+        A16f = A16.astype(np.float64)[:, :Kw]
+        for two in (False, True):
+            def build(fill):
+                a, _ = embed(T16(A16.view(np.uint16), F16), row_pad=8, fill=fill); c, chk = emb_c(fill, 0)
+                w, _ = embed(torch.from_numpy(Bw), row_pad=4, fill=fill)
+                bh, c1 = embed_out((K // 64, N, 64), F16); bl, c2 = embed_out((K // 64, N, 64), F16)
+                rc = hip.cruse_ktile_f16_split(P(w), N, Kw, Kw + 4, P(bh), P(bl), st())
+                if rc: return rc, [], []
+                if two: rc = hip.cruse_gemm_f16x2_nt(M, N, K, P(a), lda, 64, P(bh), P(bl), 64, N * 64, P(c), ldc, P(biasd), st())
+                else: rc = hip.cruse_gemm_f16_nt(M, N, K, P(a), lda, 64, P(bh), 64, N * 64, P(c), ldc, P(biasd), st())
+                return rc, [c], [chk, c1, c2]
+            run2(("gemm_f16x2_nt" if two else "gemm_f16_nt", M, N, K), build,
+                 want=A16f @ ((Bhi.astype(np.float64) + Blo.astype(np.float64)) if two else Bhi.astype(np.float64)).T + bias)
+        # plain bf16 with B K-tiled by cruse_ktile_bf16 (K - 24 columns) and, _atr, A from its time-major image made by cruse_transpose_bf16
+        Bw = rnd(N, Kw); Bwb = d(bf16(Bw))
+        def build(fill):
+            a, _ = embed(T16(A), row_pad=8, fill=fill); c, chk = emb_c(fill, 0)
+            w, _ = embed(torch.from_numpy(Bw), row_pad=4, fill=fill)
+            bt, c1 = embed_out((K // 64, N, 64), BF)
+            rc = hip.cruse_ktile_bf16(P(w), N, Kw, Kw + 4, P(bt), None, st())
+            if rc: return rc, [], []
+            rc = hip.cruse_gemm_bf16_nt(M, N, K, P(a), lda, 64, P(bt), 64, N * 64, P(c), ldc, P(biasd), 0, 1, st())
+            return rc, [c], [chk, c1]
+        run2(("gemm_bf16_nt, K-tiled B", M, N, K), build, want=Af[:, :Kw] @ Bwb.T + bias)
+        Ax = rnd(M, K); ldT = (M + 63) // 64 * 64
+        def build(fill):
+            x, _ = embed(torch.from_numpy(Ax), row_pad=4, fill=fill); b, _ = embed(T16(Bm), row_pad=8, fill=fill); c, chk = emb_c(fill, 0)
+            aT, c1 = embed_out((ldT // 64, K, 64), BF)
+            rc = hip.cruse_transpose_bf16(P(x), M, K, K + 4, P(aT), ldT, 0, st())
+            if rc: return rc, [], []
+            rc = hip.cruse_gemm_bf16_nt_atr(M, N, K, P(aT), K * 64, ldT // 64, P(b), ldb, 64, P(c), ldc, 0, st())
+            return rc, [c], [chk, c1]
+        run2(("gemm_bf16_nt_atr", M, N, K), build, want=d(bf16(Ax)) @ Bf.T)
+        # groups: G = 2 products side by side along N
+        G = 2
+        Ag, Bg, bg = bf16(rnd(M, G * K)), bf16(rnd(G, N, K)), rnd(G, N)
+        cg = N + 1; ldcg = G * cg + 2
+        wantg = np.zeros((M, ldcg)); Cg0 = rnd(M, ldcg)
+        def build(fill):
+            a, _ = embed(T16(Ag), row_pad=8, fill=fill); b, _ = embed(T16(Bg.reshape(G * N, K)), row_pad=8, fill=fill)
+            c, chk = embed(torch.from_numpy(Cg0), row_pad=1, fill=fill); poison_(c) if fill else c.zero_()
+            bd = torch.from_numpy(bg).cuda()
+            rc = hip.cruse_gemm_bf16_nt_groups(M, N, K, G, P(a), None, G * K + 8, K, P(b), None, ldb, 64, N * ldb, P(c), ldcg + 1, cg, P(bd), N, 0, st())
+            keep = torch.cat([c[:, q * cg:q * cg + N] for q in range(G)], 1).contiguous()
+            gaps = torch.cat([c[:, q * cg + N:(q + 1) * cg] for q in range(G)] + [c[:, G * cg:]], 1).contiguous()
+            def cgap(what):
+                assert bool((bits(gaps) == (0x7FC00000 if fill else 0)).all()), what + ": columns between the groups' outputs were written"
+            return rc, [keep], [chk, cgap]
+        for q in range(G): wantg[:, q * N:(q + 1) * N] = d(Ag)[:, q * K:(q + 1) * K] @ d(Bg[q]).T + bg[q]
+        run2(("gemm_bf16_nt_groups", M, N, K), build, want=wantg[:, :G * N])
+        # seg: the rows of one time chunk; rows outside it are don't-care in A and must survive in C
+        nclip = 3 if M % 3 == 0 else 1
+        sl = M // nclip; ss, so = sl + 2, 1
+        phys = np.array([(m // sl) * ss + so + m % sl for m in range(M)])
+        def build(fill):
+            Afull = np.full((nclip * ss, K), 0x7FC0 if fill else 0, np.uint16); Afull[phys] = A
+            a, _ = embed(T16(Afull), row_pad=8, fill=fill); b, _ = embed(T16(Bm), row_pad=8, fill=fill)
+            c, chk = embed_out((nclip * ss, N), F32, row_pad=3)
+            rc = hip.cruse_gemm_bf16_nt_seg(M, N, K, P(a), None, lda, P(b), None, ldb, 64, P(c), ldc, P(biasd), 0, sl, ss, so, st())
+            pc = torch.from_numpy(phys).cuda()
+            rest = torch.ones(nclip * ss, dtype=torch.bool, device="cuda"); rest[pc] = False
+            def crest(what):
+                assert bool((bits(c[rest]) == 0x7FC00000).all()), what + ": rows of C outside the segment were written"
+            return rc, [c[pc].contiguous()], [chk, crest]
+        run2(("gemm_bf16_nt_seg", M, N, K), build, want=want + bias)
+    # _slabs_cat: two products that share the time-major K-tiled A (made by cruse_transpose_bf16 on a poisoned buffer: K - 24 frames, the rest its zero
+    # pad) in one launch; "a product whose M_i is not a multiple of 128 still starts on a row tile of its own ... the rows that pad its last tile are
+    # computed and dropped": those rows lie behind the product inside the allocation (the image gets a trail of 128 rows), poisoned in the second run
+    cat_refused = 0
+    for (M, N, K) in ((3, 5, 64), (129, 127, 128), (17, 33, 320), (129, 128, 128), (17, 36, 320)):
+        Ms = (M, 3); Mt = M + 3; Kl = K - 24
+        Xa = rnd(Kl, Mt); B0, B1 = bf16(rnd(N, K)), bf16(rnd(N, K)); C0 = rnd(Mt, N)
+        At = f32_of(bf16(Xa)).astype(np.float64).T                                  # [Mt, Kl]
+        wantc = C0 + np.concatenate([At[:M] @ f32_of(B0).astype(np.float64)[:, :Kl].T, At[M:] @ f32_of(B1).astype(np.float64)[:, :Kl].T])
+        def build(fill):
+            x, _ = embed(torch.from_numpy(Xa), row_pad=4, fill=fill)
+            aT, c1 = embed(torch.zeros(K // 64, Mt, 64, dtype=BF), trail=128 * 64, fill=fill)
+            if fill: poison_(aT)
+            rc = hip.cruse_transpose_bf16(P(x), Kl, Mt, Mt + 4, P(aT), K, 0, st())
+            if rc: return rc, [], []
+            bs = [embed(T16(u), row_pad=8, fill=fill)[0] for u in (B0, B1)]
+            c, chk = embed(torch.from_numpy(C0), row_pad=3)
+            nb = hip.cruse_gemm_bf16_slab_bytes(Mt, N, 3)
+            ws, cws = embed(torch.zeros(nb // 4), fill=fill)
+            if fill: poison_(ws)
+            ms = (ctypes.c_int * 2)(*Ms); ar = (ctypes.c_longlong * 2)(0, M); bp = (ctypes.c_void_p * 2)(P(bs[0]), P(bs[1]))
+            rc = hip.cruse_gemm_bf16_nt_slabs_cat(2, ctypes.cast(ms, ctypes.c_void_p), N, K, P(aT), ctypes.cast(ar, ctypes.c_void_p), 64, Mt * 64,
+                                                  ctypes.cast(bp, ctypes.c_void_p), K + 8, 64, P(c), N + 3, 3, P(ws), nb, st())
+            return rc, [c], [chk, c1, cws]
+        if not run2(("gemm_bf16_nt_slabs_cat", M, N, K), build, want=wantc): cat_refused += 1
+    assert not L.bad, L.bad[:10]
+    # (_cat: the same two N as the slab form, and for the same reason)
+    assert slab_refused == 2 and cat_refused == 2 and L.refused == 4, (slab_refused, cat_refused, L.refused)
+    # issue shapes: 2 plain + x3 + f16 + f16x2 + K-tiled B + atr + groups + seg = 9 each; slabs: (3, 5, 64) and the two N % 4 shapes; _cat: the same three
+    assert L.n == 3 * 9 + 1 + 2 + 3, L.n
+
+
+def test_f32_gemm_with_row_gaps_in_all_four_layouts(hip):
+    """cruse_gemm: "C[M,N] (=|+=) op(A) * op(B) (+ bias[n]); op(A) is [M,K]: transA==0 -> A[m*lda+k], else A[k*lda+m]; op(B) is [K,N]: transB==0 ->
+    B[k*ldb+n], else B[n*ldb+k] ... b_shift_T > 0 (transB==0 only): row k of B is read from row k-1 and is zero when k % b_shift_T == 0" -- the row
+    gaps under lda / ldb are not read, C[m*ldc + n] is stored (accumulate == 0) and the gap under ldc is left alone.  P1, P2, P3; the product against
+    numpy in float64 within 2e-5 (test_gpu_abi_ref.py::test_gemm uses 2e-5 for CRUSE_PREC_F32).  Refusals expected: 0."""
+    rnd, L = rnd_(23), Log()
+    for (M, N, K) in ((5, 7, 9), (65, 33, 130)):
+        for tA in (0, 1):
+            for tB in (0, 1):
+                for shift in ((0, 3 if K == 9 else 13) if tB == 0 else (0,)):
+                    A = rnd(K, M) if tA else rnd(M, K); Bm = rnd(N, K) if tB else rnd(K, N); bias = rnd(N)
+                    opA = (A.T if tA else A).astype(np.float64); opB = (Bm.T if tB else Bm).astype(np.float64)
+                    if shift:
+                        sh = np.zeros_like(opB); sh[1:] = opB[:-1]; sh[0:K:shift] = 0; opB = sh
+                    want = opA @ opB + bias
+                    res = []
+                    tag = (M, N, K, tA, tB, shift)
+                    for fill in (False, True):
+                        a, _ = embed(torch.from_numpy(A), row_pad=3, fill=fill); b, _ = embed(torch.from_numpy(Bm), row_pad=3, fill=fill)
+                        c, chk = embed(torch.zeros(M, N), row_pad=3, fill=fill)
+                        if fill: poison_(c)
+                        bd = torch.from_numpy(bias).cuda()
+                        rc = hip.cruse_gemm(tA, tB, M, N, K, P(a), A.shape[1] + 3, P(b), Bm.shape[1] + 3, P(c), N + 3, P(bd), 0, 1, shift, 0, st())
+                        torch.cuda.synchronize()
+                        if rc: L.refused += 1; break
+                        if fill: L.guard(tag, chk); L.written(tag, c)
+                        res.append(c.clone())
+                    if len(res) == 2:
+                        L.n += 1; L.same(tag, res[0], res[1]); L.close(tag, res[1], want, 2e-5)
+    assert not L.bad, L.bad[:10]
+    assert L.refused == 0 and L.n == 2 * 6, (L.refused, L.n)
+
+
+# ======================================================================================================================
+# frame-major convolutions
+# ======================================================================================================================
+CONV_TOL = {-1: 1e-5, 0: 1e-4, 1: 2e-4, 2: 3e-2}      # test_gpu_abi_sweeps.py::test_fused_convolutions_equal_the_composed_twins, per prec
+WGRAD_TOL = {-1: 3e-5, 0: 1e-4, 2: 3e-2}               # test_gpu_abi_ref.py (twins, prec -1) / ::test_conv_wgrad_sweep_over_small_and_odd_widths
+# prec 1 (split bf16, three MFMAs: "~2^-17 relative" per product, cruse_hip.h; runs at Fin = 16) has no tolerance in an existing weight-gradient test.
+# Its products are at least as exact as 2^-17 = 7.6e-6 each and are summed in f32 like prec 0, whose bound allows for that summation: the prec-0 bound.
+WGRAD_TOL[1] = WGRAD_TOL[0]
+
+
+def test_convolutions_write_y_and_clear_their_sums_and_scratch_themselves(hip, ref):
+    """cruse_conv_gather / _scatter2: "y[b,t,co,fo] (+)= act(bias[co] + sum ...) ... accum != 0: y += result" -- y [B,T,Cout,Fout] is stored in full
+    (its prior content is don't-care) or, with accum, added to; nothing around it is written.   _bnstats / _bnbwd: "sums is
+    [CRUSE_BN_STAT_REPLICAS][2*Cout] doubles ... zeroed != 0: the caller has cleared sums (else cleared here, on `stream`)" -- with zeroed = 0 sums may
+    hold anything (P4) and all 16 replicas are written.   cruse_conv_wgrad: "dw[ca][cb][kt][kf] += ... ws: scratch of cruse_conv_wgrad_ws_bytes()
+    bytes" and ops._ws: "zero = False: a scratch whose user writes every byte it reads (weight-gradient / split-K slabs)" -- ws may hold anything (P4).
+    The sums are folded over the replicas and compared, like dw (f32 / f64 atomics, free order), with the float64 twin results within the tolerances of
+    the cited tests; y is bit-identical between the runs and within tolerance of the twin.
+    Refusals expected: 50.  18 from cruse_conv_wgrad at (Ca, Cb) = (40, 24): all four prec at Fin = 2 / 17 and prec -1 at Fin = 16: Fa is 1 or 9, odd, so neither MFMA kernel takes it ("odd widths
+    go to the exact VALU kernel"; the direct-read kernel wants Fb == S * Fa) and the VALU kernel refuses 60 output tiles ("do not divide the 256-thread
+    block"); at Fin = 16 (Fa = 8) prec 0 / 1 / 2 are served there by the slab kernels, which is how the test knows they ran.  32 from the scatter2
+    _bnstats / _bnbwd forms at (Cs, Cout) = (24, 40), Fg = 16 / 17, both T, all four prec: Cin = 24 is no power of two, so the VALU kernel runs, whose
+    statistics are a cruse_bn_stats / cruse_bn_act_bwd_reduce pass that refuses C*F = 40 * 32 = 1280 and 40 * 34 = 1360 > 768.
+    (8, 16) is added to the issue's channel pairs: it is the smallest pair the MFMA kernel takes."""
+    rnd, L = rnd_(24), Log()
+    NREP, B = 16, 2
+    wg_refused, sum_refused, mfma_fwd, wg_slab = [], [], set(), []
+    for prec in (-1, 0, 1, 2):
+        tol = CONV_TOL[prec]
+        for Cin, Cout in ((1, 16), (24, 40), (8, 16)):    # (8, 16): the MFMA kernel -- it wants Cin a power of two, so (24, 40) runs the VALU kernel at every prec
+            for Fin in (2, 16, 17):      # 16: even widths, 8 frames x 8 positions -- what the MFMA conv and both slab weight-gradient kernels want
+                for T in (1, 4):
+                    for scatter in (0, 1):
+                        KT, S, pad = (1, 2, 0) if scatter else (2, 2, 1)
+                        Fout = 2 * Fin if scatter else (Fin + 2 * pad - 3) // S + 1
+                        if prec >= 0:
+                            plan = (ctypes.c_int * 8)()
+                            hip.cruse_conv_plan(scatter, Cin, Fin, Cout, Fout, KT, S, pad, 0, B, T, prec, 0, 0, 0, 0, 0, ctypes.cast(plan, ctypes.c_void_p))
+                            if plan[0] == 1: mfma_fwd.add((Cin, Cout, Fin, scatter))
+                        x, bias, y0 = rnd(B, T, Cin, Fin), rnd(Cout), rnd(B, T, Cout, Fout)
+                        w = (rnd(Cin, Cout, KT, 3) if scatter else rnd(Cout, Cin, KT, 3)) * 0.3
+                        name = "cruse_conv_scatter2" if scatter else "cruse_conv_gather"
+                        geo = (B, T, Cin, Fin, Cout, Fout, KT) + ((pad,) if scatter else (S, pad))
+                        tag0 = (name, prec) + geo
+                        xd, wd, bd = [torch.from_numpy(a).cuda() for a in (x, w, bias)]
+                        ytw, ynb = np.zeros_like(y0), np.zeros_like(y0)
+                        tail = (0, 0, prec, 0, 0, None)
+                        R.call(ref, name, x, w, bias, ytw, *geo, *((0,) if not scatter else ()), *tail)
+                        R.call(ref, name, x, w, None, ynb, *geo, *((0,) if not scatter else ()), *tail)
+                        fn = getattr(hip, name)
+                        # forward (store) and accumulate
+                        for accum in (0, 1):
+                            res = []
+                            for fill in (False, True):
+                                y, chk = embed(torch.from_numpy(y0), fill=True if accum else fill)
+                                if fill and not accum: poison_(y)
+                                wl = () if scatter else (0,)
+                                rc = fn(P(xd), P(wd), P(bd), P(y), *geo, *wl, 0, accum, prec, 0, 0, st()); torch.cuda.synchronize()
+                                if rc: L.refused += 1; break
+                                if fill: L.guard(tag0 + (accum,), chk); L.written(tag0 + (accum,), y)
+                                res.append(y.clone())
+                            if len(res) == 2:
+                                L.n += 1; L.same(tag0 + (accum,), res[0], res[1]); L.close(tag0 + (accum,), res[1], ytw + (y0 if accum else 0), tol)
+                        # batch sums from the epilogue, sums not cleared by the caller
+                        s_tw = np.zeros(2 * Cout); R.call(ref, "cruse_bn_stats", ytw, LL(B * T), Cout, Fout, s_tw, 0, None)
+                        bn_y = rnd(B, T, Cout, Fout); mean, rstd = rnd(Cout) * 0.2, np.abs(rnd(Cout)) + 0.5; gamma, beta = rnd(Cout) * 0.3 + 1, rnd(Cout) * 0.2
+                        s_bw = np.zeros(2 * Cout)
+                        R.call(ref, "cruse_bn_act_bwd_reduce", ynb, bn_y, mean, rstd, gamma, beta, LL(B * T), Cout, Fout, 1, s_bw, 0, None)
+                        keep = [torch.from_numpy(a).cuda() for a in (bn_y, mean, rstd, gamma, beta)]
+                        for form, y_want, s_want, stol in (("_bnstats", ytw, s_tw, max(tol, 1e-5)), ("_bnbwd", ynb, s_bw, max(10 * tol, 1e-5))):
+                            res = []
+                            for fill in (False, True):
+                                y, chk = embed(torch.from_numpy(y0), fill=fill); sd, cs = embed(torch.zeros(NREP, 2 * Cout, dtype=F64), fill=fill)
+                                if fill: poison_(y); poison_(sd)
+                                if form == "_bnstats":
+                                    rc = getattr(hip, name + form)(P(xd), P(wd), P(bd), P(y), *geo, prec, P(sd), 0, st())
+                                else:
+                                    wl = () if scatter else (0,)
+                                    rc = getattr(hip, name + form)(P(xd), P(wd), P(y), *geo, *wl, 0, prec, *[P(k) for k in keep], 1, P(sd), 0, 0, 0, st())
+                                torch.cuda.synchronize()
+                                if rc: L.refused += 1; sum_refused.append((form, prec, Cin, Cout, Fout, scatter, hip.cruse_last_error().decode()[:60])); break
+                                if fill: L.guard(tag0 + (form,), chk, cs); L.written(tag0 + (form,), y, sd)
+                                res.append((y.clone(), sd.clone()))
+                            if len(res) == 2:
+                                L.n += 1; L.same(tag0 + (form,), res[0][0], res[1][0]); L.close(tag0 + (form, "y"), res[1][0], y_want, tol)
+                                for r in res: L.close(tag0 + (form, "sums"), r[1].sum(0), s_want, stol)
+                        # weight gradient: dw[Cout][Cin] += dy (x) x for the gather form (a = dy, bt = x); scratch not cleared
+                        if scatter: continue
+                        a, dw0 = rnd(B, T, Cout, Fout), rnd(Cout, Cin, KT, 3)
+                        want = dw0.copy()
+                        R.call(ref, "cruse_conv_wgrad", a, x, want, B, T, Cout, Fout, Cin, Fin, KT, S, pad, prec, 0, 0, None, None)
+                        ad = torch.from_numpy(a).cuda()
+                        nws = max(hip.cruse_conv_wgrad_ws_bytes(Cout, Cin, KT), 16)
+                        for fill in (False, True):
+                            dw, cdw = embed(torch.from_numpy(dw0)); ws, cws = embed(torch.zeros(nws, dtype=torch.uint8), lead=256, trail=256, fill=fill)
+                            if fill: poison_(ws)
+                            rc = hip.cruse_conv_wgrad(P(ad), P(xd), P(dw), B, T, Cout, Fout, Cin, Fin, KT, S, pad, prec, 0, 0, P(ws), st()); torch.cuda.synchronize()
+                            if rc: L.refused += 1; wg_refused.append((prec, Cout, Cin, Fin, T)); break
+                            if fill and (Cout, Cin) == (40, 24): wg_slab.append((prec, Fin, T))
+                            L.guard(("conv_wgrad", prec) + geo, cdw, cws)
+                            got = dw.double().cpu().numpy()
+                            err = np.abs(got - want).max() / np.abs(want).max() if np.isfinite(got).all() else float("inf")
+                            if not err <= WGRAD_TOL[prec]: L.bad.append(("P4 conv_wgrad", prec, fill) + geo + (err,))
+                            if fill: L.n += 1
+    print("conv_wgrad refused:", wg_refused)
+    assert not L.bad, L.bad[:10]
+    # weight gradient: refused at (40, 24) wherever the VALU kernel is what is left (odd Fa at every prec; prec -1 at Fa = 8) ...
+    assert all(r[1:3] == (40, 24) for r in wg_refused), wg_refused
+    assert sorted(r for r in wg_refused if r[3] != 16) == sorted((p_, 40, 24, f_, t_) for p_ in (-1, 0, 1, 2) for f_ in (2, 17) for t_ in (1, 4)), wg_refused
+    assert sorted(r for r in wg_refused if r[3] == 16) == [(-1, 40, 24, 16, 1), (-1, 40, 24, 16, 4)], wg_refused
+    # ... and SERVED there at Fin = 16 for prec 0, 1, 2: the VALU kernel refuses 60 output tiles, so these six ran a slab kernel (wgrad_mfma.hip for
+    # prec 0 / 1, wgrad_rd.hip for prec 2: Fa = 8 even, Fb == S * Fa) on the poisoned scratch; (16, 1) and (16, 8) at Fin = 16 pass the same checks
+    assert sorted(wg_slab) == sorted((p_, 16, t_) for p_ in (0, 1, 2) for t_ in (1, 4)), wg_slab
+    # forward forms: what cruse_conv_plan says ran the MFMA kernel at prec >= 0 (by reading: Cin a power of two >= 8, 8 frames x positions % 16 == 0)
+    assert mfma_fwd == {(8, 16, 2, 1), (8, 16, 16, 0), (8, 16, 16, 1)}, mfma_fwd
+    assert len(sum_refused) == 32 and L.refused == 32 + 18, (L.refused, wg_refused, sum_refused)
+    assert all(r[2:4] == (24, 40) and r[4] in (32, 34) and r[5] == 1 and ("1360" in r[6] or "1280" in r[6]) for r in sum_refused), sum_refused
+    # cases: 4 prec x 36 (pair, Fin, T, form of conv) x 4 (store, accum, _bnstats, _bnbwd) - 32 refused; weight gradient 4 prec x 18 - 18 refused
+    assert L.n == 4 * 36 * 4 - 32 + 4 * 18 - 18, L.n
+
+
+def test_data_gradient_convolutions_with_the_fused_batchnorm_backward_of_their_input(hip):
+    """cruse_conv_gather_bnbwd_in / _scatter2_bnbwd_in: "One call = cruse_bn_act_bwd_apply(dout -> dy_bf16; in_dgamma / in_dbeta / in_dbias += ...) followed
+    by cruse_conv_gather / _scatter2 [_bnbwd] (dy_bf16 -> y) ... writes dy_bf16 [B,T,Cin,Fin] ... Any other shape / dtype runs the two calls" -- y and
+    dy_bf16 are written in full (P2, P3), the output-side sums [16][2*Cout] are cleared by the callee with zeroed = 0 (P4), in_dgamma / in_dbeta /
+    in_dbias are added to (their prior content is input).  CRUSE_PREC_BF16 only: the second call reads a bf16 operand, which "need[s] the MFMA
+    kernels".  Refusals: the MFMA kernel's admission is a page of arithmetic (Cin a power of two, frames x positions a multiple of 16, even Fin ...),
+    so the expected set is taken from the library's own host-side statement of it, cruse_conv_plan(forms = BBI | BNB), case by case; by reading, the
+    issue's pairs (1, 16) and (24, 40) are refused everywhere (Cin no power of two >= 8) and (8, 16) is served where 8 * positions % 16 == 0 and Fin
+    is even (scatter2 at Fg = 2 and 16, gather at Fin = 16): 12 of the 72 cases below, asserted."""
+    rnd, L = rnd_(28), Log()
+    NREP, B, prec = 16, 2, 2
+    served = 0
+    for Cin, Cout in ((1, 16), (24, 40), (8, 16)):
+        for Fin in (2, 16, 17):
+            for T in (1, 4):
+                for scatter in (0, 1):
+                    for dout_bf16 in (0, 1):
+                        KT, S, pad = (1, 2, 0) if scatter else (2, 2, 1)
+                        Fout = 2 * Fin if scatter else (Fin + 2 * pad - 3) // S + 1
+                        geo = (B, T, Cin, Fin, Cout, Fout, KT) + ((pad,) if scatter else (S, pad, 0))
+                        tag = ("bnbwd_in", scatter, dout_bf16) + geo
+                        plan = (ctypes.c_int * 8)()
+                        rc_plan = hip.cruse_conv_plan(scatter, Cin, Fin, Cout, Fout, KT, S, pad, 0, B, T, prec, 2 if dout_bf16 else 0, 0, 0, 0, 8 | 2 | 1,
+                                                      ctypes.cast(plan, ctypes.c_void_p))
+                        dout = torch.from_numpy(rnd(B, T, Cin, Fin)).cuda()
+                        if dout_bf16: dout = dout.to(BF)
+                        in_y, w = torch.from_numpy(rnd(B, T, Cin, Fin)).cuda(), torch.from_numpy((rnd(Cin, Cout, KT, 3) if scatter else rnd(Cout, Cin, KT, 3)) * 0.3).cuda()
+                        im, ir, ig, ib = [torch.from_numpy(a).cuda() for a in (rnd(Cin) * 0.2, np.abs(rnd(Cin)) + 0.5, rnd(Cin) * 0.3 + 1, rnd(Cin) * 0.2)]
+                        isums = torch.zeros(NREP, 2 * Cin, dtype=F64).cuda(); isums[0] = torch.from_numpy(rnd(2 * Cin).astype(np.float64)).cuda()   # (as after the reduce pass)
+                        keep = [torch.from_numpy(a).cuda() for a in (rnd(B, T, Cout, Fout), rnd(Cout) * 0.2, np.abs(rnd(Cout)) + 0.5, rnd(Cout) * 0.3 + 1, rnd(Cout) * 0.2)]
+                        p0 = [rnd(Cin) for _ in range(3)]
+                        res = []
+                        for fill in (False, True):
+                            y, cy = embed(torch.zeros(B, T, Cout, Fout), fill=fill); dv, cdv = embed(torch.zeros(B, T, Cin, Fin, dtype=BF), fill=fill)
+                            sd, cs = embed(torch.zeros(NREP, 2 * Cout, dtype=F64), fill=fill)
+                            if fill: poison_(y); poison_(dv); poison_(sd)
+                            par = [embed(torch.from_numpy(a)) for a in p0]
+                            fn = hip.cruse_conv_scatter2_bnbwd_in if scatter else hip.cruse_conv_gather_bnbwd_in
+                            rc = fn(P(dout), 2 if dout_bf16 else 0, P(in_y), P(im), P(ir), P(ig), P(ib), P(isums), NREP, 1, 1, P(dv), P(par[0][0]), P(par[1][0]),
+                                    P(par[2][0]), P(w), P(y), *geo, 0, prec, *[P(k) for k in keep], 1, P(sd), 0, 0, st())
+                            torch.cuda.synchronize()
+                            if (rc != 0) != (rc_plan != 0): L.bad.append(("refusal differs from cruse_conv_plan", tag, rc, rc_plan))
+                            if rc: L.refused += 1; break
+                            if fill:
+                                L.guard(tag, cy, cdv, cs, *[q[1] for q in par]); L.written(tag, y, dv, sd)
+                            res.append([t_.clone() for t_ in (y, dv, sd.sum(0), par[0][0], par[1][0], par[2][0])])
+                        if len(res) == 2:
+                            served += 1; L.n += 1
+                            # the values: "One call = cruse_bn_act_bwd_apply(...) followed by cruse_conv_* _bnbwd" -- those two calls on plain buffers; every
+                            # result bit-identical, the folded sums within 1e-6 (test_gpu_conv_forms.py::test_bwd_in_is_the_batchnorm_backward_apply_...)
+                            dy2, y2, s2 = torch.zeros(B, T, Cin, Fin, dtype=BF).cuda(), torch.zeros(B, T, Cout, Fout).cuda(), torch.zeros(NREP, 2 * Cout, dtype=F64).cuda()
+                            par2 = [torch.from_numpy(a).cuda() for a in p0]
+                            rc1 = hip.cruse_bn_act_bwd_apply(P(dout), P(in_y), P(im), P(ir), P(ig), P(ib), P(isums), NREP, B * T, Cin, Fin, 1, 1, 2 if dout_bf16 else 0,
+                                                             P(dy2), 2, P(par2[0]), P(par2[1]), P(par2[2]), st())
+                            fn2 = hip.cruse_conv_scatter2_bnbwd if scatter else hip.cruse_conv_gather_bnbwd
+                            rc2 = fn2(P(dy2), P(w), P(y2), *geo, 0, prec, *[P(k) for k in keep], 1, P(s2), 0, 2, 0, st()); torch.cuda.synchronize()
+                            if rc1 or rc2: L.bad.append(("the two separate calls are refused", tag, rc1, rc2))
+                            else:
+                                for i, (a, b_) in enumerate(zip(res[1], (y2, dy2, None, par2[0], par2[1], par2[2]))):
+                                    if b_ is not None: L.same(tag + ("vs the two calls", i), a, b_, "P2")
+                                L.close(tag + ("sums vs the two calls",), res[1][2], s2.sum(0), 1e-6)
+                            for i, (a, b_) in enumerate(zip(*res)):
+                                # (sums: f64 atomics of f32-valued partial sums, "the result does not depend on their order" -- bit-identical too)
+                                L.same(tag + (i,), a, b_)
+                                if not bool(torch.isfinite(b_.double()).all()): L.bad.append(("not finite", tag, i))
+    print("bnbwd_in served / refused:", served, L.refused)
+    assert not L.bad, L.bad[:10]
+    assert served == 12 and L.refused == 72 - 12, (served, L.refused)
+
+
+# ======================================================================================================================
+# BatchNorm and LayerNorm
+# ======================================================================================================================
+def test_batchnorm_kernels_on_poisoned_outputs_and_sums(hip, ref):
+    """cruse_bn_stats: "sums[0..C) = sum y, sums[C..2C) = sum y^2 over rows x F (f64).  zeroed != 0: the caller hands over accumulators that are already
+    zero ... otherwise the callee clears them first" (P4).   cruse_bn_act_fwd: "out = [relu]((y-mean)*rstd*gamma+beta) [+ skip]" -- out [rows, C*F] in
+    full, skip nullable.   cruse_bn_finalize_act_fwd: "mean / rstd come from the batch sums inside the kernel, are also written out ... out_bf16
+    (nullable): also a bf16 copy of out".   cruse_bn_act_bwd_reduce: "`zeroed` as for cruse_bn_stats"; _apply: "dy = gamma*rstd*(...); dgamma += sum_gx;
+    dbeta += sum_g" -- dy in full, dgamma / dbeta added to.
+    The f64 sums against numpy in float64 within 1e-6 (test_gpu_abi_ref.py uses 1e-6 for cruse_bn_stats); everything else bit-identical between the
+    zero-filled and the poisoned run.  Refusals expected: 3 -- cruse_bn_stats, _bwd_reduce and _bwd_apply at (C, F) = (24, 40): "C*F=960 must be a
+    multiple of 4 and <= 768" (the model's widest BatchNorm row is 768); cruse_bn_act_fwd and _finalize_act_fwd have no such bound."""
+    rnd, L = rnd_(25), Log()
+    rows = 7
+    refused = []
+    for C, Fq in ((8, 5), (24, 40), (24, 32)):      # (24, 32): C*F = 768, the widest row the three bounded kernels take, more than one pass of a block
+        y, skip, dout = rnd(rows, C, Fq), rnd(rows, C, Fq), rnd(rows, C, Fq)
+        gamma, beta = rnd(C) * 0.3 + 1, rnd(C) * 0.2
+        y64 = y.astype(np.float64)
+        s_want = np.concatenate([y64.sum((0, 2)), (y64 * y64).sum((0, 2))])
+        mean = (s_want[:C] / (rows * Fq)).astype(np.float32); rstd = (1 / np.sqrt(s_want[C:] / (rows * Fq) - mean.astype(np.float64) ** 2 + 1e-5)).astype(np.float32)
+        yd, skd, dod, gd, btd, md, rd = [torch.from_numpy(a).cuda() for a in (y, skip, dout, gamma, beta, mean, rstd)]
+        out = {}
+        for fill in (False, True):
+            def buf(shape, dt=F32, init=None):
+                v, c = embed(torch.zeros(shape, dtype=dt) if init is None else torch.from_numpy(init), fill=True if init is not None else fill)
+                if fill and init is None: poison_(v)
+                return v, c
+            sums, cs = buf((2 * C,), F64)
+            rc = hip.cruse_bn_stats(P(yd), rows, C, Fq, P(sums), 0, st()); torch.cuda.synchronize()
+            if rc and fill: refused.append(("bn_stats", C, Fq))
+            if not rc:
+                L.guard(("bn_stats", C, Fq), cs); L.written(("bn_stats", C, Fq), sums); L.close(("bn_stats", C, Fq, fill), sums, s_want, 1e-6); L.n += fill
+            sums_in = torch.from_numpy(s_want).cuda()
+            for sk in (None, skd):
+                o, co = buf((rows, C, Fq))
+                rc = hip.cruse_bn_act_fwd(P(yd), P(md), P(rd), P(gd), P(btd), P(sk), P(o), rows, C, Fq, 1, st()); torch.cuda.synchronize()
+                if rc: refused.append(("bn_act_fwd", C, Fq)); continue
+                L.guard(("bn_act_fwd", C, Fq), co); L.written(("bn_act_fwd", C, Fq), o); out.setdefault(("fwd", sk is None), []).append(o.clone()); L.n += fill
+                o, co = buf((rows, C, Fq)); ob, cb = buf((rows, C, Fq), BF); mo, cm = buf((C,)); ro, cr = buf((C,))
+                rc = hip.cruse_bn_finalize_act_fwd(P(yd), P(sums_in), 1, rows * Fq, 1e-5, 0.1, P(gd), P(btd), P(sk), P(o), P(ob), P(mo), P(ro), None, None,
+                                                   rows, C, Fq, 1, st()); torch.cuda.synchronize()
+                if rc: refused.append(("bn_finalize_act_fwd", C, Fq)); continue
+                L.guard(("bn_finalize_act_fwd", C, Fq), co, cb, cm, cr); L.written(("bn_finalize_act_fwd", C, Fq), o, ob, mo, ro); L.n += fill
+                out.setdefault(("fin", sk is None), []).append([t_.clone() for t_ in (o, ob, mo, ro)])
+            bs, cbs = buf((2 * C,), F64)
+            rc = hip.cruse_bn_act_bwd_reduce(P(dod), P(yd), P(md), P(rd), P(gd), P(btd), rows, C, Fq, 1, P(bs), 0, st()); torch.cuda.synchronize()
+            if rc and fill: refused.append(("bn_act_bwd_reduce", C, Fq))
+            if not rc:
+                L.guard(("bwd_reduce", C, Fq), cbs); L.written(("bwd_reduce", C, Fq), bs); out.setdefault("red", []).append(bs.clone()); L.n += fill
+                dy, cdy = buf((rows, C, Fq)); dg, cdg = buf((C,), init=gamma); db, cdb = buf((C,), init=beta)
+                bs1 = out["red"][0]          # (the sums of the FIRST run for both: the reduce pass adds in free order, dy must not inherit that)
+                rc = hip.cruse_bn_act_bwd_apply(P(dod), P(yd), P(md), P(rd), P(gd), P(btd), P(bs1), 1, rows, C, Fq, 1, 1, 0, P(dy), 0, P(dg), P(db), None, st())
+                torch.cuda.synchronize()
+                if rc: refused.append(("bn_act_bwd_apply", C, Fq))
+                else:
+                    L.guard(("bwd_apply", C, Fq), cdy, cdg, cdb); L.written(("bwd_apply", C, Fq), dy, dg, db); L.n += fill
+                    out.setdefault("app", []).append([t_.clone() for t_ in (dy, dg, db)])
+            if rc and fill and ("bn_act_bwd_reduce", C, Fq) in refused:
+                t1, t2, t3 = torch.zeros(rows, C, Fq).cuda(), torch.zeros(C).cuda(), torch.zeros(C).cuda()       # (throwaway outputs)
+                rc2 = hip.cruse_bn_act_bwd_apply(P(dod), P(yd), P(md), P(rd), P(gd), P(btd), P(sums_in), 1, rows, C, Fq, 1, 1, 0, P(t1), 0, P(t2), P(t3), None, st())
+                if rc2: refused.append(("bn_act_bwd_apply", C, Fq))
+        for k, v in out.items():
+            a, b = v[0], v[1]
+            if k == "red":            # f64 atomics of per-block partial sums, free order: both runs against the CPU twin (1e-5, test_gpu_abi_ref.py)
+                s_bw = np.zeros(2 * C); R.call(ref, "cruse_bn_act_bwd_reduce", dout, y, mean, rstd, gamma, beta, LL(rows), C, Fq, 1, s_bw, 0, None)
+                L.close((k, C, Fq), a, s_bw, 1e-5); L.close((k, C, Fq), b, s_bw, 1e-5)
+            elif isinstance(a, list):
+                for p_, q_ in zip(a, b): L.same((k, C, Fq), p_, q_)
+            else: L.same((k, C, Fq), a, b)
+    assert not L.bad, L.bad[:10]
+    assert sorted(refused) == [("bn_act_bwd_apply", 24, 40), ("bn_act_bwd_reduce", 24, 40), ("bn_stats", 24, 40)], refused
+    # (8, 5) and (24, 32): stats, 2 act_fwd, 2 finalize_act_fwd, reduce, apply = 7; (24, 40): the 4 unbounded ones
+    assert L.n == 7 + 4 + 7, L.n
+
+
+def test_layernorm_rows_segments_and_parameter_sums(hip):
+    """cruse_ln_fwd: "y[row, P(c)] = (x[row,c]-mean)*rstd*gamma[P(c)] + beta[P(c)] (+ res[row,P(c)]) ... y_bf16 (nullable): also a bf16 copy of y
+    [rows, H] ... seg_len > 0 (interleave_g == 1): ROW SEGMENTS -- logical row r of every row-indexed array is physical row (r / seg_len) * seg_stride
+    + seg_off + r % seg_len" -- y, the copy, mean and rstd are written for the rows of the call and for no other row; x and res rows outside the segment
+    are not read.   cruse_ln_bwd: dx [rows, H] in full; dgamma / dbeta are added to (f32 atomics: compared with numpy in float64 within 2e-5, the
+    tolerance of test_gpu_abi_ref.py for cruse_ln_bwd).  Refusals expected: 0 (H <= 1024, 4 | H, 16-byte aligned rows)."""
+    rnd, L = rnd_(26), Log()
+    for H in (96, 160, 640):
+        for rows in (3, 70):
+            gamma, beta = rnd(H) * 0.3 + 1, rnd(H) * 0.2
+            gd, btd = torch.from_numpy(gamma).cuda(), torch.from_numpy(beta).cuda()
+            for ig, with_res, seg in ((1, False, False), (1, True, False), (4, False, False), (4, True, False), (1, True, True)):
+                nclip = 3 if rows == 3 else 10
+                sl = rows // nclip; ss, so = (sl + 2, 1) if seg else (sl, 0)
+                nphys = nclip * ss
+                phys = torch.tensor([(r // sl) * ss + so + r % sl for r in range(rows)]).cuda()
+                x, res = rnd(rows, H), rnd(rows, H)
+                tag = ("ln_fwd", rows, H, ig, with_res, seg)
+                outs = []
+                for fill in (False, True):
+                    def full(a):          # the physical tensor: the rows of the call inside, don't-care rows around them
+                        f = torch.zeros(nphys, H).cuda()
+                        if fill: poison_(f)
+                        f[phys] = torch.from_numpy(a).cuda()
+                        return f
+                    xd, rs = full(x), (full(res) if with_res else None)
+                    y, cy = embed_out((nphys, H)); yb, cb = embed_out((nphys, H), BF); mo, cm = embed_out((nphys,)); ro, cr = embed_out((nphys,))
+                    rc = hip.cruse_ln_fwd(P(xd), P(gd), P(btd), P(rs), P(y), P(yb), P(mo), P(ro), rows, H, ig, 1e-5, sl if seg else 0, ss, so, st())
+                    torch.cuda.synchronize()
+                    if rc: L.refused += 1; break
+                    L.guard(tag, cy, cb, cm, cr)
+                    got = [t_[phys].contiguous() for t_ in (y, yb, mo, ro)]
+                    L.written(tag, *got)
+                    rest = torch.ones(nphys, dtype=torch.bool, device="cuda"); rest[phys] = False
+                    for t_ in (y, yb, mo, ro):
+                        if rest.any() and not bool((bits(t_[rest]) == bits(poison_(t_[rest].clone()))).all()): L.bad.append(("P3 rows outside the segment written",) + tag)
+                    outs.append(got)
+                if len(outs) == 2:
+                    L.n += 1
+                    for a, b in zip(*outs): L.same(tag, a, b)
+                if seg or len(outs) != 2: continue
+                # backward of the same rows
+                _, _, mean, rstd = outs[1]
+                dyv, dg0, db0 = rnd(rows, H), rnd(H), rnd(H)
+                xd, dyd = torch.from_numpy(x).cuda(), torch.from_numpy(dyv).cuda()
+                perm = np.array([(c % (H // ig)) * ig + c // (H // ig) for c in range(H)])
+                xh = (x.astype(np.float64) - mean.double().cpu().numpy()[:, None]) * rstd.double().cpu().numpy()[:, None]
+                dyl = dyv.astype(np.float64)[:, perm]                                 # dy in the order of x's features
+                dg_w, db_w = dg0.astype(np.float64), db0.astype(np.float64)
+                np.add.at(dg_w, perm, (dyl * xh).sum(0)); np.add.at(db_w, perm, dyl.sum(0))
+                res2 = []
+                for fill in (False, True):
+                    dx, cdx = embed(torch.zeros(rows, H), fill=fill)
+                    if fill: poison_(dx)
+                    dg, cdg = embed(torch.from_numpy(dg0)); db, cdb = embed(torch.from_numpy(db0))
+                    rc = hip.cruse_ln_bwd(P(dyd), P(xd), P(mean), P(rstd), P(gd), rows, H, ig, P(dx), P(dg), P(db), st()); torch.cuda.synchronize()
+                    if rc: L.refused += 1; break
+                    tb = ("ln_bwd", rows, H, ig, fill)
+                    L.guard(tb, cdx, cdg, cdb); L.written(tb, dx); L.close(tb + ("dgamma",), dg, dg_w, 2e-5); L.close(tb + ("dbeta",), db, db_w, 2e-5)
+                    res2.append(dx.clone())
+                if len(res2) == 2: L.n += 1; L.same(("ln_bwd dx", rows, H, ig), res2[0], res2[1])
+    assert not L.bad, L.bad[:10]
+    assert L.refused == 0 and L.n == 6 * (5 + 4), (L.refused, L.n)
+
+
+# ======================================================================================================================
+# GRU sequence kernels
+# ======================================================================================================================
+def test_gru_sequence_tensors_are_written_in_full_and_only_inside_the_chunk():
+    bad = []
+    for prec in ("f32", "bf16"):
+        for (Hg, G, B, T) in ((128, 2, 3, 5), (160, 4, 9, 4)):
+            bad += [(prec, Hg, G, B, T) + tuple(b) for b in _gru_case(prec, Hg, G, B, T)]
+    assert not bad, bad[:10]
+
+
+def _gru_case(prec, Hg, G, B, T):
+    """cruse_gru_seq_fwd: "Output h [B,T,G*Hg] ... coef [B,T,G,3*Hg] ... (bf16 elements when prec == CRUSE_PREC_BF16, f32 otherwise), an [B,T,G*Hg],
+    z [B,T,G*Hg]"; _fwd_ex: "chunk [t0, t0+n) is (gi + t0*G*3*Hg, h + t0*G*Hg, ..., h0 = h + (t0-1)*G*Hg ...) -- the results are those of the single
+    launch"; cruse_gru_seq_bwd: "dout = dL/dh [B,T,G*Hg] -> dh [B,T,G*Hg]"; _bwd_on: "dgi != NULL (CRUSE_PREC_BF16, with the a_n rows `an`): also
+    writes the bf16 gate gradients dgi [B,T,G,3*Hg]" -- every tensor is written for the frames of the call, in full, and nowhere else; frames outside
+    the chunk are neither read (gi, dout, coef, z) nor written.  A chunk continuation is bit-identical to the single launch when the same kernels serve
+    both: in CRUSE_PREC_BF16 at Hg = 160 / 320 a launch from h0 = NULL runs gru_fwd_tf_kernel (every wave walks the whole K), a continuation (h0 given)
+    gru_fwd_lean_kernel (K split over four waves, summed through LDS) -- other f32 summation order, other last bits; cruse_hip.h now says so, and the
+    comparison with the single launch is made in the other three cases, where one kernel serves both (it held there).  (The issue's H is the group width Hg: 160 over 4 groups would not be a multiple of
+    32.)  The hand-off panels and the status header stay as ops.py hands them over: zeroed.  Refusals: none possible through ops (it raises)."""
+    from cruse_amd import ops
+    torch.manual_seed(7)
+    H = G * Hg
+    gi = torch.randn(B, T, 3 * H).cuda()
+    w = [(torch.randn(3 * Hg, Hg) / Hg ** 0.5).cuda() for _ in range(G)]
+    b = [(0.1 * torch.randn(3 * Hg)).cuda() for _ in range(G)]
+    dout = torch.randn(B, T, H).cuda()
+    cdt = BF if prec == "bf16" else F32
+    want_dgi = prec == "bf16"
+    L = Log()
+    ref_f = ops.gru_seq_fwd(gi, w, b, B, T, G, Hg, prec)                     # plain buffers: the reference of P2
+    ref_b = ops.gru_seq_bwd(dout, w, ref_f[1], ref_f[3], B, T, G, Hg, prec, an=ref_f[2] if want_dgi else None, want_dgi=want_dgi)
+    torch.cuda.synchronize()
+    assert ops.gru_status() == 0
+    # whole sequence into poisoned, embedded outputs
+    outs = [embed_out((B, T, H)), embed_out((B, T, 3 * H), cdt), embed_out((B, T, H)), embed_out((B, T, H))]
+    got = ops.gru_seq_fwd(gi, w, b, B, T, G, Hg, prec, out=tuple(o[0] for o in outs)); torch.cuda.synchronize()
+    assert ops.gru_status() == 0
+    L.guard(("fwd",), *[o[1] for o in outs]); L.written(("fwd",), *got)
+    for a, r in zip(got, ref_f): L.same(("fwd",), a, r, "P2")
+    dh, cdh = embed_out((B, T, H))
+    if want_dgi:
+        dgi, cdg = embed_out((B * T, G, 3, Hg), BF, trail=128)
+        gb = ops.gru_seq_bwd(dout, w, got[1], got[3], B, T, G, Hg, prec, an=got[2], want_dgi=True, out=(dh, dgi))
+    else:
+        cdg = lambda what: None
+        gb = (ops.gru_seq_bwd(dout, w, got[1], got[3], B, T, G, Hg, prec, out=dh),)
+    torch.cuda.synchronize()
+    assert ops.gru_status() == 0
+    L.guard(("bwd",), cdh, cdg); L.written(("bwd",), *gb)
+    for a, r in zip(gb, ref_b if want_dgi else (ref_b,)): L.same(("bwd",), a, r, "P2")
+    # one chunk split: frames [t0, T) only; everything before t0 is poison except h[:, t0 - 1], the chunk's initial state
+    t0 = 2
+    # (P1 as defined: the same chunk call with the don't-care frames zero, then poisoned)
+    runs = []
+    for fill in (False, True):
+        gi_p = gi.clone(); gi_p[:, :t0] = 0
+        outs = [embed(torch.zeros(B, T, H), fill=fill), embed(torch.zeros(B, T, 3 * H, dtype=cdt), fill=fill), embed(torch.zeros(B, T, H), fill=fill),
+                embed(torch.zeros(B, T, H), fill=fill)]
+        if fill:
+            poison_(gi_p[:, :t0])
+            for o in outs: poison_(o[0])
+        outs[0][0][:, t0 - 1] = ref_f[0][:, t0 - 1]
+        got = ops.gru_seq_fwd(gi_p, w, b, B, T, G, Hg, prec, out=tuple(o[0] for o in outs), chunk=(t0, T - t0)); torch.cuda.synchronize()
+        assert ops.gru_status() == 0
+        runs.append([a[:, t0:].clone() for a in got])
+        if not fill: continue
+        L.guard(("fwd chunk",), *[o[1] for o in outs]); L.written(("fwd chunk",), *runs[1])
+        for i, a in enumerate(got):
+            before = a[:, :t0 - 1] if i == 0 else a[:, :t0]
+            if before.numel() and not bool((bits(before) == bits(poison_(before.clone()))).all()): L.bad.append(("P3 frames before the chunk written", i))
+    for i, (a, r) in enumerate(zip(*runs)): L.same(("fwd chunk", i), a, r)
+    # (where a launch from h0 = NULL and its continuation run the same kernel -- every case here but bf16 at Hg = 160 -- the chunk is the single launch)
+    for i, (a, r) in enumerate(zip(runs[1], ref_f)):
+        if not (prec == "bf16" and Hg in (160, 320)): L.same(("fwd chunk vs single launch", i), a, r[:, t0:].contiguous(), "P2")
+        else: L.close(("fwd chunk vs single launch", i), a, r[:, t0:], 3e-2)      # (3e-2: test_gpu_kernels.py::test_gru_sequence_fwd_bwd, bf16)
+    # backward: the LAST chunk (no carry) with coef / z / dout of the frames before it poisoned
+    co_p, z_p, do_p, an_p = ref_f[1].clone(), ref_f[3].clone(), dout.clone(), ref_f[2].clone()
+    for t_ in (co_p, z_p, do_p, an_p): poison_(t_[:, :t0])
+    dh, cdh = embed_out((B, T, H))
+    if want_dgi:
+        dgi, cdg = embed_out((B * T, G, 3, Hg), BF, trail=128)
+        gb = ops.gru_seq_bwd(do_p, w, co_p, z_p, B, T, G, Hg, prec, an=an_p, want_dgi=True, out=(dh, dgi), chunk=(t0, T - t0))
+        gb = (gb[0], gb[1].view(B, T, 3 * H)); rb = (ref_b[0], ref_b[1].view(B, T, 3 * H))
+    else:
+        gb = (ops.gru_seq_bwd(do_p, w, co_p, z_p, B, T, G, Hg, prec, out=dh, chunk=(t0, T - t0)),); rb = (ref_b,)
+    torch.cuda.synchronize()
+    assert ops.gru_status() == 0
+    L.guard(("bwd chunk",), cdh, cdg)
+    for i, (a, r) in enumerate(zip(gb, rb)):
+        L.same(("bwd chunk", i), a[:, t0:].contiguous(), r[:, t0:].contiguous())
+        if not bool((bits(a[:, :t0]) == bits(poison_(a[:, :t0].clone()))).all()): L.bad.append(("P3 frames before the chunk written (bwd)", i))
+    return L.bad
+
+
+# ======================================================================================================================
+# STFT / iSTFT, mask, loss and pointwise kernels
+# ======================================================================================================================
+def test_frontend_mask_loss_and_pointwise_kernels(hip, ref):
+    """cruse_stft_fwd: "wave [B,L] -> re, im [B,T,n_fft/2+1] (either may be NULL), mag [B,T,mag_bins] ... for the first mag_bins bins"; cruse_istft_fwd:
+    "re, im [B,T,n_fft/2+1] -> wave [B,L]"; _bwd: "dwave [B,L] -> dre, dim [B,T,n_fft/2+1]".   cruse_mask_apply / _bwd / cruse_mask_loss_fwd (mask
+    [rows,Fn], spectra [rows,Fs]): est = mask * noisy for f < Fn and zero for Fn <= f < Fs (formed as 0 * noisy: a zero with the sign of
+    the noisy bin, so it is compared as a value, not as bits); the backward reads f < Fn of the Fs-wide gradients only.
+    cruse_sisnr_fwd / cruse_wave_l1_mse / cruse_sumsq(accumulate = 0) / cruse_mask_loss_fwd clear their accumulator words (mom, loss, out, loss_sum)
+    themselves (P4): ops.py hands them torch.empty.   cruse_axpby: out = a*x + b*y in full; cruse_adam_step: p, m, v updated in place, n elements.
+    Loss words are f64 atomics of per-block sums (free order): finite and within the tolerance of test_gpu_abi_ref.py of the CPU twin / numpy in float64;
+    everything else bit-identical.  Refusals expected: 1 -- cruse_stft_fwd at L = 1 ("reflect padding needs L > n_fft/2"; iSTFT runs at L = 1)."""
+    rnd, L = rnd_(27), Log()
+    refused = []
+    rows = 3
+
+    def two(tag, build, order_free={}):
+        """order_free: {output index: (reference or function of the run's outputs, tolerance) or None} -- outputs summed in free order; None: derived
+        from such sums, run against run"""
+        res = []
+        for fill in (False, True):
+            rc, outs, guards = build(fill); torch.cuda.synchronize()
+            if rc:
+                refused.append(tag)
+                return
+            if fill: L.guard(tag, *guards); L.written(tag, *outs)
+            res.append([o.clone() for o in outs])
+        L.n += 1
+        for i, (a, b) in enumerate(zip(*res)):
+            if i in order_free and order_free[i] is not None:
+                want, tol = order_free[i]
+                for run in res: L.close(tag + (i,), run[i], want(run) if callable(want) else want, tol)
+            elif i in order_free: L.close(tag + (i,), a, b, 2e-5); L.close(tag + (i,), b, a, 2e-5)
+            else: L.same(tag + (i,), a, b)
+
+    def out(fill, shape, dt=F32):
+        v, c = embed(torch.zeros(shape, dtype=dt), fill=fill)
+        if fill: poison_(v)
+        return v, c
+    n_fft, hop, Fq = 320, 160, 161
+    for Lw in (1, 4099):
+        wave = torch.from_numpy(rnd(rows, Lw) * 0.1).cuda()
+        T = 1 + Lw // hop
+        def build(fill):
+            o = [out(fill, (rows, T, Fq)), out(fill, (rows, T, Fq)), out(fill, (rows, T, Fq - 1))]
+            rc = hip.cruse_stft_fwd(P(wave), rows, Lw, n_fft, hop, P(o[0][0]), P(o[1][0]), P(o[2][0]), Fq - 1, 1e-8, st())
+            return rc, [x[0] for x in o], [x[1] for x in o]
+        two(("stft", Lw), build)
+        Ti = max(T, 2)
+        re, im = torch.from_numpy(rnd(rows, Ti, Fq)).cuda(), torch.from_numpy(rnd(rows, Ti, Fq)).cuda()
+        def build(fill):
+            o = out(fill, (rows, Lw))
+            return hip.cruse_istft_fwd(P(re), P(im), rows, Ti, n_fft, hop, Lw, P(o[0]), st()), [o[0]], [o[1]]
+        two(("istft", Lw), build)
+        def build(fill):
+            o = [out(fill, (rows, Ti, Fq)), out(fill, (rows, Ti, Fq))]
+            return hip.cruse_istft_bwd(P(wave), rows, Ti, n_fft, hop, Lw, P(o[0][0]), P(o[1][0]), st()), [x[0] for x in o], [x[1] for x in o]
+        two(("istft_bwd", Lw), build)
+        # time-domain losses and pointwise kernels on rows x Lw (n % 4 != 0 at both lengths: 3 and 12297)
+        xs, ss = torch.from_numpy(rnd(rows, Lw)).cuda(), torch.from_numpy(rnd(rows, Lw)).cuda()
+        def build(fill):
+            mom, loss, coef = out(fill, (rows, 5), F64), out(fill, (1,), F64), out(fill, (rows, 4))
+            rc = hip.cruse_sisnr_fwd(P(xs), P(ss), rows, Lw, 1e-8, P(mom[0]), P(loss[0]), P(coef[0]), st())
+            return rc, [loss[0], coef[0], mom[0]], [mom[1], loss[1], coef[1]]
+        mom_w, loss_w, coef_w = np.zeros((rows, 5)), np.zeros(1), np.zeros((rows, 4), np.float32)
+        R.call(ref, "cruse_sisnr_fwd", xs.cpu().numpy(), ss.cpu().numpy(), rows, Lw, 1e-8, mom_w, loss_w, coef_w, None)
+        # (1e-6 for loss and moments: test_gpu_abi_ref.py; the gradient scalars hang on |e| ~ 0 at L = 1 and are compared run against run, 2e-5 as there)
+        # At L = 1 the zero-mean clip is empty: <x,s>, |s|^2 and |e|^2 are differences of equal numbers, so the loss is a function of the rounding of
+        # the moments and no independent reference exists (the twin, which squares in double, differs from the kernel by 65 %).  There the moments
+        # are checked against the twin and the loss against the finalize formula (tdloss.hip, train_base/loss.py:7-25) on the kernel's OWN moments.
+        def sisnr_loss_of(mom, eps=1e-8):
+            n = float(Lw); sx, s1, sxx, sss, sxs = [mom[:, k] for k in range(5)]
+            mx, ms = sx / n, s1 / n
+            Pq = sxs - n * mx * ms; S2 = np.maximum(sss - n * ms * ms, 0); X2 = np.maximum(sxx - n * mx * mx, 0)
+            al = Pq / (S2 + eps); nt = np.abs(al) * np.sqrt(S2); ne = np.sqrt(np.maximum(X2 - 2 * al * Pq + al * al * S2, 0))
+            return np.array([(-20 * np.log10(eps + nt / (ne + eps)) / rows).sum()])
+        loss_ref = loss_w if Lw > 1 else (lambda outs: sisnr_loss_of(outs[2].double().cpu().numpy()))
+        two(("sisnr_fwd", Lw), build, order_free={0: (loss_ref, 1e-6), 1: None, 2: (mom_w, 1e-6)})
+
+        coef = torch.from_numpy(rnd(rows, 4)).cuda()
+        def build(fill):
+            dx = out(fill, (rows, Lw))
+            return hip.cruse_sisnr_bwd(P(xs), P(ss), P(coef), rows, Lw, 1.0, P(dx[0]), st()), [dx[0]], [dx[1]]
+        two(("sisnr_bwd", Lw), build)
+        n = rows * Lw
+        for mse in (0, 1):
+            def build(fill):
+                loss, dest = out(fill, (1,), F64), out(fill, (rows, Lw))
+                rc = hip.cruse_wave_l1_mse(P(xs), P(ss), n, mse, 1.0 / n, P(loss[0]), P(dest[0]), st())
+                return rc, [loss[0], dest[0]], [loss[1], dest[1]]
+            ls_w, d_w = np.zeros(1), np.zeros((rows, Lw), np.float32)
+            R.call(ref, "cruse_wave_l1_mse", xs.cpu().numpy(), ss.cpu().numpy(), LL(n), mse, 1.0 / n, ls_w, d_w, None)
+            two(("wave_l1_mse", Lw, mse), build, order_free={0: (ls_w, 2e-6)})
+        def build(fill):
+            o = out(fill, (1,), F64)
+            return hip.cruse_sumsq(P(xs), n, P(o[0]), 0, st()), [o[0]], [o[1]]
+        # (f32 partial sums added in f64, the scheme of cruse_wave_l1_mse: its 2e-6)
+        two(("sumsq", Lw), build, order_free={0: (np.array([(xs.double() ** 2).sum().item()]), 2e-6)})
+        def build(fill):
+            o = out(fill, (rows, Lw))
+            return hip.cruse_axpby(P(o[0]), P(xs), P(ss), 0.5, -2.0, n, st()), [o[0]], [o[1]]
+        two(("axpby", Lw), build)
+        def build(fill):
+            pmv = [embed(xs.cpu() * k, fill=fill) for k in (1.0, 0.1, 0.01)]
+            pmv[2][0].abs_()
+            rc = hip.cruse_adam_step(P(pmv[0][0]), P(ss), P(pmv[1][0]), P(pmv[2][0]), n, 1e-3, 0.9, 0.999, 1e-8, 0.01, 3, 1.0, st())
+            return rc, [x[0] for x in pmv], [x[1] for x in pmv]
+        two(("adam_step", Lw), build)
+    # mask kernels, Fs = Fn + 1
+    for Fn in (1, 160):
+        Fs = Fn + 1
+        mask = torch.from_numpy(1 / (1 + np.exp(-rnd(rows, Fn)))).cuda()
+        nre, nim, cmag = [torch.from_numpy(a).cuda() for a in (rnd(rows, Fs), rnd(rows, Fs), np.abs(rnd(rows, Fs)))]
+        def build(fill):
+            o = [out(fill, (rows, Fs)), out(fill, (rows, Fs))]
+            rc = hip.cruse_mask_apply(P(mask), P(nre), P(nim), rows, Fn, Fs, P(o[0][0]), P(o[1][0]), st())
+            if not rc and fill and not bool(((o[0][0][:, Fn:] == 0) & (o[1][0][:, Fn:] == 0)).all()): L.bad.append(("mask_apply: bins >= Fn not zero", Fn))
+            return rc, [x[0] for x in o], [x[1] for x in o]
+        two(("mask_apply", Fn), build)
+        dre, dim = rnd(rows, Fs), rnd(rows, Fs)
+        for sig in (0, 1):
+            def build(fill):
+                g = []
+                for a in (dre, dim):
+                    t_ = torch.from_numpy(a).cuda()
+                    if fill: poison_(t_[:, Fn:])
+                    else: t_[:, Fn:] = 0
+                    g.append(t_)
+                o = out(fill, (rows, Fn))
+                return hip.cruse_mask_apply_bwd(P(g[0]), P(g[1]), P(nre), P(nim), P(mask), rows, Fn, Fs, sig, P(o[0]), st()), [o[0]], [o[1]]
+            two(("mask_apply_bwd", Fn, sig), build)
+        def build(fill):
+            o = [out(fill, (1,), F64), out(fill, (rows, Fn)), out(fill, (rows, Fn)), out(fill, (rows, Fs)), out(fill, (rows, Fs))]
+            rc = hip.cruse_mask_loss_fwd(P(mask), P(nre), P(nim), P(cmag), rows, Fn, Fs, 2.0, 1.0, *[P(x[0]) for x in o], st())
+            if not rc and fill and not bool(((o[3][0][:, Fn:] == 0) & (o[4][0][:, Fn:] == 0)).all()): L.bad.append(("mask_loss: est bins >= Fn not zero", Fn))
+            return rc, [x[0] for x in o], [x[1] for x in o]
+        tw = [np.zeros(1), np.zeros((rows, Fn), np.float32), np.zeros((rows, Fn), np.float32), np.zeros((rows, Fs), np.float32), np.zeros((rows, Fs), np.float32)]
+        R.call(ref, "cruse_mask_loss_fwd", *[a.cpu().numpy() for a in (mask, nre, nim, cmag)], LL(rows), Fn, Fs, 2.0, 1.0, *tw, None)
+        two(("mask_loss", Fn), build, order_free={0: (tw[0], 1e-5)})       # (1e-5: test_gpu_abi_ref.py for the loss word)
+    assert not L.bad, L.bad[:10]
+    assert refused == [("stft", 1)], refused
+    assert L.n == 2 * 10 - 1 + 2 * 4, L.n
