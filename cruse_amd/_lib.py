@@ -87,6 +87,7 @@ SIGNATURES = {
     "cruse_gru_gate_grads": ("pppppqiiip", "i"),
     "cruse_gru_gate_grads_bf16": ("pppppqppqiip", "i"),
     "cruse_mask_loss_fwd": ("ppppqiiffpppppp", "i"),
+    "cruse_mask_head_fwd_bwd": ("ppiff" + "ppppp" + "ppp" + "iiiiiff" + "ppppp" + "pppp" + "i" + "pii" + "ip", "i"),
     "cruse_mask_apply": ("pppqiippp", "i"),
     "cruse_mask_apply_bwd": ("pppppqiiipp", "i"),
     "cruse_mask_sdnr_fwd": ("pppppqiiiffpppp", "i"),

@@ -60,6 +60,10 @@ class EngineConfig:
                                     # (98 MB per layer written and read).  Same products, same summation order (bit-identical GEMM: tests/test_gpu_kernels.py).
                                     # Round 4 measured it time-neutral and pruned it; round 6 (fixed stream conditions): 4.676 against 4.688 ms in four
                                     # interleaved A/B pairs of 100 steps, -0.2 GB of HBM traffic per step
+    fuse_mask_head: bool = True     # WO-MALE training step, transposed decoder with up to 16 channels at level 1: the last decoder BatchNorm (+ ReLU + skip),
+                                    # the 8 -> 1 mask conv + sigmoid, the loss with dL/dlogit and the decoder-1 data gradient with its BatchNorm-backward
+                                    # sums run as ONE kernel (cruse_mask_head_fwd_bwd) that keeps u_1 and dlogit of a tile of frames in LDS, instead of six
+                                    # launches that write and re-read them; the same bits in every tensor
     pick_launch_stream: bool = True # HIP-graph form: time the replay of a fresh capture from the current stream and three pool streams and
                                     # keep the fastest launcher (engine._pick_launch_stream: a graph's own side-branch streams may share
                                     # the launching stream's hardware queue, which serialises the branches -- +25..35 % per step)
@@ -73,7 +77,7 @@ class EngineConfig:
              
             "fuse_bn_fwd": ("CRUSE_FUSE_BN_FWD", lambda v: v != "0"), "fuse_bn_bwd_apply": ("CRUSE_FUSE_BN_BWD_APPLY", lambda v: v != "0"), "bf16_dy": ("CRUSE_BF16_DY", lambda v: v != "0"), "bf16_de": ("CRUSE_BF16_DE", lambda v: v != "0"),
             "pick_launch_stream": ("CRUSE_PICK_LAUNCH_STREAM", lambda v: v != "0"), "gi_store_f16": ("CRUSE_GI_STORE_F16", lambda v: v != "0"),
-            "dx_atr": ("CRUSE_DX_ATR", lambda v: v != "0")}
+            "dx_atr": ("CRUSE_DX_ATR", lambda v: v != "0"), "fuse_mask_head": ("CRUSE_FUSE_MASK_HEAD", lambda v: v != "0")}
     _LIB_ENV = {"CRUSE_GRU_BWD_RS": "gru_bwd_rs", "CRUSE_GRU_FWD_LEAN": "gru_fwd_lean", "CRUSE_GRU_WLO": "gru_wlo", "CRUSE_GRU_DBG": "gru_dbg",
                 "CRUSE_GRU_TF": "gru_tf", "CRUSE_GRU_POLL_FWD": "gru_poll_fwd", "CRUSE_GRU_POLL_BWD": "gru_poll_bwd", "CRUSE_CM_KINT": "cm_kint",
                 "CRUSE_CM_SWAP": "cm_swap", "CRUSE_CM_NW": "cm_nw", "CRUSE_PW_VALU": "pw_valu", "CRUSE_WG_DBG": "wg_dbg",

@@ -273,13 +273,17 @@ class TrainEngine:
                     cre = torch.empty(B, T, self.f_stft, device=clean.device, dtype=torch.float32)
                     cim = torch.empty_like(cre)
                 self.side.defer(lambda: ops.stft(clean, self.n_fft, self.hop, out=(cre, cim, None)), clean, cre, cim, kind=1, lane=0)
+        # EngineConfig.fuse_mask_head: the last decoder BatchNorm, the mask conv, WO-MALE and the first data gradient in one kernel
+        defer_head = training and self.loss == "wo_male" and bool(self.cfg.fuse_mask_head) and self.f_stft == self.f_net + 1
         mask, ctx = unet2_forward(mag.view(B, 1, T, self.f_net), self.flat.P, self.Bf, self.model.ch,
                                   self.model.rnn_groups, self.prec, training=training, save=training,
-                                  update_running=training)
-        self._last_mask = mask
+                                  update_running=training, defer_head=defer_head)
         rows = B * T
         dlogit = None
-        if self.loss == "wo_male":
+        if ctx.get("head") is not None:
+            mask, loss_sum, dlogit = _net.unet2_mask_head(ctx, self.flat.P, nre, nim, cmag, self.f_stft, self.loss_alpha, self.loss_beta)
+            self._norm = float(rows * self.f_stft)
+        elif self.loss == "wo_male":
             loss_sum, _, dlogit, _, _ = ops.mask_loss(mask, nre, nim, cmag, rows, self.f_net, self.f_stft,
                                                       self.loss_alpha, self.loss_beta, want_dlogit=training)
             self._norm = float(rows * self.f_stft)
@@ -304,6 +308,7 @@ class TrainEngine:
             if training:
                 dre, dim = ops.istft_bwd(dwave, T, self.n_fft, self.hop)
                 dlogit = ops.mask_apply_bwd(dre, dim, nre, nim, mask, rows, self.f_net, self.f_stft)
+        self._last_mask = mask
         return loss_sum, dlogit, ctx
 
     def _deepfilter_loss(self, mask, unp, ref, B, T, training):
@@ -556,7 +561,8 @@ class TrainEngine:
         return out
 
     def step(self, noisy: torch.Tensor, clean: torch.Tensor) -> torch.Tensor:
-        """One optimizer step; returns the (device, f64) loss sum -- divide by .loss_norm for the loss."""
+        """One optimizer step; returns the (device, f64) loss sum -- divide by .loss_norm for the loss.  The tensor is the step's own
+        accumulator (the replayed graph's, or a word of the per-step cleared arena): read or clone it before the next step."""
         if self._auto is not None:
             return self._auto_step(noisy, clean)
         self._works = []

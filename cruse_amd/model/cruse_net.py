@@ -644,8 +644,13 @@ def _bn_act(y, rows, C, F, P, Bf, name, training, update_running, skip=None, sum
 
 
 def unet2_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], Bf: Dict[str, torch.Tensor], ch, groups: int,
-                  prec, training: bool, save: bool = True, update_running: bool = True, dec_mode: str = "transposed"):
+                  prec, training: bool, save: bool = True, update_running: bool = True, dec_mode: str = "transposed",
+                  defer_head: bool = False):
     """x [B,1,T,F0] (== frame-major [B,T,1,F0]) -> (mask [B,1,T,F0], ctx).  cruse_net.py:147-165.
+
+    defer_head (the WO-MALE training step, EngineConfig.fuse_mask_head): where the shapes allow it the forward pass stops in front of the
+    last decoder BatchNorm -- u_1 stays virtual (ctx["head"], an ops.BnIn like `pend` below), the returned mask is None -- and
+    unet2_mask_head() runs that BatchNorm, the mask conv, the loss and the first data gradient of the backward pass in one kernel.
 
     dec_mode "upsample": the decoder of model/cruse.py:14 (CRUSE4MagAddSkipUpsample) -- cust_conv.convkxf(mode="upsample"),
     :159-167: nearest FreqUpsample(2) + Conv2d (1,3) pad (0,1) with weights conv{k}_t.weight [Cout][Cin][1][3] (no bias under a
@@ -732,6 +737,7 @@ def unet2_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], Bf: Dict[str, tor
         SIDE.run(fn, *keep, lane=2)
     us, vs, dstats, uus = {L: u}, {}, {}, {}
     pend = None
+    head = None
     for k in range(L, 1, -1):
         if ups:
             uus[k] = ops.upsample_w(u, rows * ch[k], Fk[k], 2).view(B, T, ch[k], Fk[k - 1])
@@ -755,12 +761,20 @@ def unet2_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], Bf: Dict[str, tor
             pend = virtual(v, sums, ch[k - 1], Fk[k - 1], f"bn{k}_t", add=ss[k - 1])
             u = torch.empty(B, T, ch[k - 1], Fk[k - 1], device=dev, dtype=torch.bfloat16)      # written by conv{k-1}_t while it stages
             mean, rstd = pend.mean, pend.rstd
+        elif (defer_head and k == 2 and training and save and not ups and sums is not None and config.get().fuse_bn_bwd_stats
+              and ops.mask_head_eligible(ch[1], Fk[1], Fk[0] + 1)):
+            pend = None
+            head = virtual(v, sums, ch[1], Fk[1], "bn2_t", add=ss[1])          # u_1 is written (f32) by the mask-head kernel
+            u = None
+            mean, rstd = head.mean, head.rstd
         else:
             pend = None
             u, mean, rstd = _bn_act(v, rows, ch[k - 1], Fk[k - 1], P, Bf, f"bn{k}_t", training, update_running, skip=ss[k - 1],
                                     sums=sums)
         vs[k] = v; dstats[k] = (mean, rstd); us[k - 1] = u
-    if ups:
+    if head is not None:
+        mask = None
+    elif ups:
         uus[1] = ops.upsample_w(u, rows * ch[1], Fk[1], 2).view(B, T, ch[1], Fk[0])
         mask = ops.conv_gather(uus[1], P["conv1_t.weight"], P.get("conv1_t.bias"), B, T, ch[1], Fk[0], ch[0], Fk[0], KT=1, S=1, pad=1,
                                act=1, prec=prec)
@@ -769,10 +783,22 @@ def unet2_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], Bf: Dict[str, tor
                                  prec=prec)
     _flush_counters()
     if save:
-        ctx.update(ys=ys, es=es, stats=stats, gctx=gctx, us=us, vs=vs, dstats=dstats, mask=mask, uus=uus, dec_mode=dec_mode)
+        ctx.update(ys=ys, es=es, stats=stats, gctx=gctx, us=us, vs=vs, dstats=dstats, mask=mask, uus=uus, dec_mode=dec_mode, head=head)
         if e_bf is not None and e_bf.dtype == torch.bfloat16:
             ctx["e_bf"] = e_bf.view(B, T, ch[L], Fk[L])        # RNE(e_L): the operand bits the bf16 weight gradient forms from e_L anyway
-    return mask.view(B, ch[0], T, F0), ctx
+    return (mask.view(B, ch[0], T, F0) if mask is not None else None), ctx
+
+
+def unet2_mask_head(ctx, P: Dict[str, torch.Tensor], nre, nim, cmag, Fs: int, alpha: float, beta: float):
+    """The deferred end of unet2_forward(defer_head=True) fused with WO-MALE and the start of unet2_backward (ops.mask_head):
+    -> (mask [B,1,T,F0], loss_sum, dlogit [B*T,F0]); u_1, the mask and (du_1, its BatchNorm-backward sums) are left in ctx."""
+    B, T, Fk, ch = ctx["B"], ctx["T"], ctx["F"], ctx["ch"]
+    u, mask, loss_sum, dlogit, du, du_sums = ops.mask_head(ctx["head"], P["conv1_t.weight"], P["conv1_t.bias"], nre, nim, cmag, B, T, ch[1], Fk[1],
+                                                           Fs, alpha, beta)
+    ctx["us"][1] = u
+    ctx["mask"] = mask
+    ctx["du1"] = (du, du_sums)
+    return mask.view(B, ch[0], T, Fk[0]), loss_sum, dlogit
 
 
 def bucket_of(name: str) -> int:
@@ -865,7 +891,10 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
 
     def lvl_bf16(k):
         return de_bf16 and 2 <= k < L
-    du, du_sums = dec_dgrad(1, dv, bn_of(2, True) if L >= 2 else None)
+    if ctx.get("du1") is not None:                      # unet2_mask_head has formed du_1 and the bn2_t backward sums with the loss
+        du, du_sums = ctx["du1"]
+    else:
+        du, du_sums = dec_dgrad(1, dv, bn_of(2, True) if L >= 2 else None)
     ds = {1: du}                                        # gradient wrt skip_{k} output = du_k
     # skip_k = conv1x3(e_k) is a leaf of the decoder: its data gradient W^T ds_k and its weight gradient ds_k (*) e_k
     # are issued here, on the side stream, into the buffer de_pre[k] that the encoder backward later ACCUMULATES its

@@ -951,6 +951,36 @@ def mask_loss(mask, nre, nim, cmag, rows, Fn, Fs, alpha=2.0, beta=1.0, want_dmas
     return loss_sum, dmask, dlogit, er, ei
 
 
+def mask_head_eligible(C, F1, Fs) -> bool:
+    """shapes cruse_mask_head_fwd_bwd takes: up to 16 channels in rows of at most 640 floats, whole float4 per channel"""
+    return 1 <= C <= 16 and F1 % 4 == 0 and C * F1 <= 640 and Fs == 2 * F1 + 1
+
+
+def mask_head(bn: BnIn, w, bias, nre, nim, cmag, B, T, C, F1, Fs, alpha=2.0, beta=1.0, bwd_replicas=None, max_blocks=0, out=None):
+    """The mask head of the training step in one launch (cruse_mask_head_fwd_bwd): bn_finalize_act_fwd of the VIRTUAL u = relu(bn(bn.y_pre))
+    + bn.add, conv_scatter2(u, w, bias, sigmoid), mask_loss and the data gradient conv_gather(dlogit, w, bn_bwd of that BatchNorm), with
+    the bits of those four calls.  bn.mean / bn.rstd and the running statistics are written as by the first of them.
+    -> (u [B,T,C,F1], mask [B*T, 2*F1], loss_sum [1] f64, dlogit [B*T, 2*F1], du [B,T,C,F1], backward sums [replicas][2*C] f64).
+    loss_sum and the sums come from the step's cleared arena when one is active: they are then valid until the next step begins.
+    out: (u, mask, dlogit, du) to write into (tests)."""
+    dev = bn.y_pre.device
+    rows = B * T
+    if out is None:
+        u = torch.empty(B, T, C, F1, device=dev, dtype=torch.float32)
+        mask = torch.empty(rows, 2 * F1, device=dev, dtype=torch.float32)
+        dlogit = torch.empty(rows, 2 * F1, device=dev, dtype=torch.float32)
+        du = torch.empty(B, T, C, F1, device=dev, dtype=torch.float32)
+    else:
+        u, mask, dlogit, du = out
+    nrep = BN_STAT_REPLICAS if bwd_replicas is None else int(bwd_replicas)
+    loss_sum, lz = ARENA.take(1, dev)
+    sums, sz = ARENA.take(2 * C * nrep, dev)
+    check(lib.cruse_mask_head_fwd_bwd(_p(bn.y_pre), _p(bn.sums), bn.nrep, bn.eps, bn.momentum, _p(bn.gamma), _p(bn.beta), _p(bn.add), _p(w), _p(bias),
+                                      _p(nre), _p(nim), _p(cmag), B, T, C, F1, Fs, alpha, beta, _p(u), _p(bn.mean), _p(bn.rstd), _p(bn.rm), _p(bn.rv),
+                                      _p(mask), _p(dlogit), _p(du), _p(loss_sum), lz, _p(sums), nrep, sz, max_blocks, _stream()))
+    return u, mask, loss_sum, dlogit, du, sums
+
+
 def mask_apply(mask, nre, nim, rows, Fn, Fs):
     er = torch.empty(rows, Fs, device=mask.device, dtype=torch.float32)
     ei = torch.empty_like(er)

@@ -534,6 +534,22 @@ int cruse_mask_loss_fwd(const float* mask, const float* nre, const float* nim, c
                         double* loss_sum, float* dmask, float* dlogit, float* est_re, float* est_im,
                         void* stream);
 
+/* The mask head of the training step in one launch (csrc/mask_head.hip; additive entry point):
+ *   cruse_bn_finalize_act_fwd(v, bn_sums, ..., skip)          -> u [B,T,C,F1], mean, rstd [C], running statistics (nullable pair)
+ *   cruse_conv_scatter2(u, w [C][1][1][3], bias, KT 1, pad 0, sigmoid)  -> mask [B*T, 2*F1]
+ *   cruse_mask_loss_fwd(mask, nre, nim, cmag [B*T, Fs], Fs = 2*F1 + 1)  -> loss_sum, dlogit [B*T, 2*F1]
+ *   cruse_conv_gather_bnbwd(dlogit, w, Cin 1, S 2, pad 0; bn_y = v)     -> du [B,T,C,F1], bwd_sums [bwd_replicas][2*C] (sum g, sum g*xhat)
+ * with the bits of those calls in every tensor; loss_sum and bwd_sums are f64 atomics (free order) and are ADDED to when
+ * loss_zeroed / bwd_zeroed != 0, cleared first otherwise.  C <= 16, F1 % 4 == 0, C * F1 <= 640; v, skip, u, du 16-byte aligned.
+ * max_blocks: 0, or a cap on the grid (a workgroup then walks several tiles of 8 frames). */
+int cruse_mask_head_fwd_bwd(const float* v, const double* bn_sums, int sum_replicas, float eps, float momentum,
+                            const float* gamma, const float* beta, const float* skip, const float* w, const float* bias,
+                            const float* nre, const float* nim, const float* cmag,
+                            int B, int T, int C, int F1, int Fs, float loss_alpha, float loss_beta,
+                            float* u, float* mean, float* rstd, float* running_mean, float* running_var,
+                            float* mask, float* dlogit, float* du, double* loss_sum, int loss_zeroed,
+                            double* bwd_sums, int bwd_replicas, int bwd_zeroed, int max_blocks, void* stream);
+
 /* ---- time-domain loss in the loop ---------------------------- */
 
 /* PreProcess.masking "mag_mapping" alone (utils/utils.py:418-420): est = mask * noisy spectrum on the first Fn

@@ -35,7 +35,7 @@ def main():
         losses = []
         for s in range(a.steps):
             noisy, clean = synth_batch(a.batch, L, "cuda", 7000 + s)
-            losses.append(eng.step(noisy, clean))
+            losses.append(eng.step(noisy, clean).clone())      # (the step's accumulator is reused by the next step)
         torch.cuda.synchronize()
         curves[prec] = [eng.loss_value(l) for l in losses]
         assert eng.skipped_steps() == 0
