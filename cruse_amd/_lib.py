@@ -96,6 +96,7 @@ SIGNATURES = {
     "cruse_wave_l1_mse": ("ppqifppp", "i"),
     "cruse_deepfilter_fwd": ("ppppiiiiippp", "i"),
     "cruse_deepfilter_bwd": ("ppppppiiiiippppp", "i"),
+    "cruse_df_head_apply": ("pppiiiiiippp", "i"),
     "cruse_sigmoid_bwd": ("pppqp", "i"),
     "cruse_axpby": ("pppffqp", "i"),
     "cruse_adam_step": ("ppppqfffffifp", "i"),

@@ -6,6 +6,10 @@ enhanced_mag * (cos, sin)(noisy phase) -> istft(length=noisy.shape[-1])) and `__
 rtf = elapsed / (len / sr), 0.8 * int16 peak scaling).  CRUSE's unet_2 returns a sigmoid MASK on the first
 `in_feat // 2 * 2` bins (model/cruse_net.py:164), so the enhanced magnitude is mask * |noisy| and
 mag * cos(phase) == mask * real: the phase is never formed (PreProcess.masking, utils/utils.py:418-420).
+
+head="df" is for a model trained with the DeepFilter loss (BASELINE config 4, TrainEngine(loss="wo_male_df")): its output is the real
+part of a DeepFilter(t_dim, f_dim) filter field, and the enhanced spectrum is the neighbourhood sum of mask * N
+(loss.deepfilter_spectrum, one kernel) instead of mask * N itself.
 """
 from __future__ import annotations
 
@@ -16,13 +20,21 @@ import numpy as np
 import torch
 
 from ..acoustics import feature
-from ..loss import enhanced_spectrum
+from ..loss import deepfilter_spectrum, enhanced_spectrum
+
+HEADS = ("mask", "df")
 
 
 class Inferencer:
     def __init__(self, model: torch.nn.Module, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
-                 sr: int = 16000, device="cuda", atten_lim_db=None):
+                 sr: int = 16000, device="cuda", atten_lim_db=None, head: str = "mask", df_dims=(1, 5)):
         from .. import ops
+        if head not in HEADS:
+            raise ValueError(f"Inferencer: head = {head!r}, expected one of {HEADS}")
+        t_dim, f_dim = (int(d) for d in df_dims)
+        if not (0 <= t_dim <= 8 and 0 <= f_dim <= 16):
+            raise ValueError(f"Inferencer: df_dims = {tuple(df_dims)!r}, expected (t_dim in 0..8, f_dim in 0..16)")
+        self.head, self.df_dims = head, (t_dim, f_dim)
         self.lim = ops.atten_lim_gain(atten_lim_db)       # DeepFilterNet's atten_lim_db as a gain; 0: no limit (the default)
         self.model = model.to(device).eval()
         self.n_fft, self.hop, self.win, self.sr = n_fft, hop_length, win_length, sr
@@ -36,7 +48,10 @@ class Inferencer:
             raise RuntimeError(f"Inferencer expects [B,L] waveforms, got {tuple(noisy.shape)}")
         spec = feature.pre_stft(noisy, self.n_fft, self.hop, self.win, f_net=self.f_net)
         mask = self.model(spec["mag_net"])                                   # [B,1,T,f_net]
-        est = enhanced_spectrum(mask, spec["real"].squeeze(1), spec["imag"].squeeze(1))   # [B,T,F,2]
+        if self.head == "df":
+            est = deepfilter_spectrum(mask, spec["real"].squeeze(1), spec["imag"].squeeze(1), *self.df_dims)
+        else:
+            est = enhanced_spectrum(mask, spec["real"].squeeze(1), spec["imag"].squeeze(1))   # [B,T,F,2]
         wave = feature.istft_ri(est[..., 0], est[..., 1], self.n_fft, self.hop, length=noisy.shape[-1])
         if self.lim == 0.0:
             return wave

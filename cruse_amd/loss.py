@@ -56,6 +56,22 @@ def enhanced_spectrum(mask, noisy_real, noisy_imag):
     return torch.stack([er.view(B, T, Fs), ei.view(B, T, Fs)], dim=-1)
 
 
+def deepfilter_spectrum(mask, noisy_real, noisy_imag, t_dim=1, f_dim=5):
+    """The DeepFilter(t_dim, f_dim) head of BASELINE config 4 (model/deep_filter.py:15-41 with unet_2's one real filter channel):
+    -> [B,T,Fs,2], the (2*t_dim+1) x (2*f_dim+1) neighbourhood sum of mask * N; bins >= Fn of the product are zero (R8).
+    Arguments as enhanced_spectrum; one kernel (cruse_df_head_apply), no gradient."""
+    if mask.dim() != 4:
+        raise RuntimeError(f"deepfilter_spectrum: mask must be [B,1,T,F], got {tuple(mask.shape)}")
+    B, _, T, Fn = mask.shape
+    Fs = noisy_real.shape[-1]
+    for name, t in (("noisy_real", noisy_real), ("noisy_imag", noisy_imag)):
+        if t.numel() != B * T * Fs:
+            raise RuntimeError(f"Dimension mismatch when applying the deep filter, {name} {tuple(t.shape)} vs mask {tuple(mask.shape)}")
+    er, ei = ops.df_head_apply(mask.detach().contiguous(), noisy_real.contiguous().view(B, T, Fs), noisy_imag.contiguous().view(B, T, Fs),
+                               t_dim, f_dim)
+    return torch.stack([er, ei], dim=-1)
+
+
 class _SiSnrFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, s, eps):

@@ -1052,6 +1052,32 @@ def deepfilter_bwd(dor, doi, xr, xi, hr, hi, f_dim, t_dim):
     return outs
 
 
+def df_head_apply(mask, nre, nim, t_dim=1, f_dim=5, out=None):
+    """The DeepFilter head of a trained config-4 model in one launch (cruse_df_head_apply): mask [B*T, Fn] (any shape with B*T*Fn
+    elements, such as unet_2's [B,1,T,Fn]), nre / nim [B,T,Fs] -> (ere, eim) [B,T,Fs], the (2*t_dim+1) x (2*f_dim+1) neighbourhood
+    sum of mask * N with bins Fn..Fs-1 of the product zero.  The bits of mask_apply(mask, ones, zeros) + deepfilter_fwd as
+    engine._deepfilter_loss composes them.  out: (ere, eim) to write into."""
+    if nre.dim() != 3 or nim.shape != nre.shape:
+        raise RuntimeError(f"df_head_apply: the spectrum planes must both be [B,T,Fs], got {tuple(nre.shape)} and {tuple(nim.shape)}")
+    B, T, Fs = nre.shape
+    rows = B * T
+    Fn = mask.numel() // rows if rows > 0 else 0
+    if rows <= 0 or Fn * rows != mask.numel():
+        raise RuntimeError(f"df_head_apply: mask {tuple(mask.shape)} is not [B*T, Fn] for the spectrum {tuple(nre.shape)}")
+    for name, t in (("mask", mask), ("nre", nre), ("nim", nim)):
+        _f32(t, f"df_head_apply {name}")
+    if out is None:
+        ere = torch.empty(B, T, Fs, device=nre.device, dtype=torch.float32)
+        eim = torch.empty_like(ere)
+    else:
+        ere, eim = out
+        for name, t in (("ere", ere), ("eim", eim)):
+            if _f32(t, f"df_head_apply {name}").numel() != rows * Fs:
+                raise RuntimeError(f"df_head_apply: {name} {tuple(t.shape)} is not [B,T,Fs] = {(B, T, Fs)}")
+    check(lib.cruse_df_head_apply(_p(mask), _p(nre), _p(nim), B, T, Fn, Fs, int(t_dim), int(f_dim), _p(ere), _p(eim), _stream()))
+    return ere, eim
+
+
 def sigmoid_bwd(dmask, mask):
     out = torch.empty_like(mask)
     check(lib.cruse_sigmoid_bwd(_p(dmask), _p(mask), _p(out), mask.numel(), _stream()))

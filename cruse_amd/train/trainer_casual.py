@@ -356,8 +356,10 @@ class Trainer:
             tag = ("l1" if isinstance(loss_function, torch.nn.L1Loss) else "mse", {})
         if tag is None:
             raise RuntimeError(f"loss_function {loss_function!r} has no fused HIP form: use l1_loss, mse_loss, wo_male_loss, "
-                               "si_snr_loss or sdnr_loss from train_base.loss (config [loss_function].name)")
+                               "wo_male_df_loss, si_snr_loss or sdnr_loss from train_base.loss (config [loss_function].name)")
         loss_name, loss_kwargs = tag
+        # how validation turns the network output into audio: a model trained on the DeepFilter(1, 5) head is scored through that head
+        self.validation_head = "df" if loss_name == "wo_male_df" else "mask"
         # meta.use_amp (base_trainer.py:41-42: GradScaler(enabled=use_amp)) has no autocast / scaler here; what mixed precision
         # means on this path is the bf16-operand MFMA mode (f32 storage, statistics and accumulation, no loss scaling needed).
         # meta.precision (this repo) wins; otherwise use_amp = true -> "bf16", false -> "f32" (the reference's arithmetic).
@@ -470,7 +472,7 @@ class Trainer:
             was_training = self.model.training
             ac = self.acoustics
             enhance = Inferencer(self.model, n_fft=ac["n_fft"], hop_length=ac["hop_length"], win_length=ac.get("win_length", ac["n_fft"]),
-                                 sr=ac.get("sr", 16000), device=self.device)            # puts the model in eval mode
+                                 sr=ac.get("sr", 16000), device=self.device, head=self.validation_head)     # puts the model in eval mode
             sums = torch.zeros(len(self.metric_names), 2, dtype=torch.float64, device=self.device)      # per metric: noisy, enhanced
         for noisy, clean in self.validation_dataloader:
             noisy = noisy.to(self.device).float().contiguous()

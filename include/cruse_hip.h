@@ -589,6 +589,16 @@ int cruse_deepfilter_bwd(const float* dout_r, const float* dout_i, const float* 
                          const float* hr, const float* hi, int B, int F, int T, int f_dim, int t_dim,
                          float* dxr, float* dxi, float* dhr, float* dhi, void* stream);
 
+/* The DeepFilter head at inference in one launch (csrc/df_head.hip; model/deep_filter.py:15-41 with the one real filter channel
+ * unet_2 emits; additive entry point).  mask [B*T, Fn] (sigmoid output), nre / nim / ere / eim [B, T, Fs] frame-major:
+ *   P = mask * N on [0,T) x [0,Fn), zero on bins Fn..Fs-1 (repair R8) and outside the spectrum
+ *   E[b,t,f] = sum_{dt=-t_dim..t_dim} sum_{df=-f_dim..f_dim} P[b,t+dt,f+df]      (real and imaginary plane separately)
+ * f32 adds from 0.0f, dt the outer and df the inner loop, both ascending: the bits of cruse_mask_apply(mask, ones, zeros) followed
+ * by cruse_deepfilter_fwd(nre, nim, hr, zeros, F = T, T = Fs, f_dim = t_dim, t_dim = f_dim) on finite data.  Fn <= Fs, t_dim <= 8,
+ * f_dim <= 16; no alignment is required, no workspace is used. */
+int cruse_df_head_apply(const float* mask, const float* nre, const float* nim, int B, int T, int Fn, int Fs, int t_dim, int f_dim,
+                        float* ere, float* eim, void* stream);
+
 /* backward of nn.Sigmoid (cruse_net.py:164): dlogit = dmask * mask * (1 - mask) */
 int cruse_sigmoid_bwd(const float* dmask, const float* mask, float* dlogit, long long n, void* stream);
 

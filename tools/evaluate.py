@@ -1,7 +1,7 @@
 """Score a checkpoint on a list of paired WAV files (cruse_amd.evaluate.evaluate_files):
 
     python tools/evaluate.py --config cfg.toml --checkpoint runs/cfg/checkpoints/best_model.tar \\
-        --clean-list clean.txt --noisy-list noisy.txt [--batch-size 16] [--metrics SI_SDR STOI ESTOI SDR] [--csv scores.csv]
+        --clean-list clean.txt --noisy-list noisy.txt [--batch-size 16] [--metrics SI_SDR STOI ESTOI SDR] [--head df] [--csv scores.csv]
 
 The model is built from the config's [model] section as tools/train_stand.py builds it; the checkpoint is a *.tar of the trainer
 (its "model" entry) or a bare state dict (model_NNNN.pth).  Prints one line per metric with the Noisy and Enhanced means."""
@@ -26,6 +26,9 @@ def main(argv=None):
     parser.add_argument("--noisy-list", required=True, help="List file: the noisy WAV of the same line.")
     parser.add_argument("--batch-size", type=int, default=16)
     parser.add_argument("--metrics", nargs="+", default=["SI_SDR", "STOI", "ESTOI"])
+    parser.add_argument("--head", choices=["mask", "df"], default="mask",
+                        help="How the network output is applied: mask (magnitude mask) or df (DeepFilter(1, 5) head: a model trained "
+                             "with wo_male_df_loss, configs/cruse_deepfilter.toml).")
     parser.add_argument("--csv", help="Write the per-file table here.")
     args = parser.parse_args(argv)
     from cruse_amd.evaluate import evaluate_files
@@ -34,7 +37,7 @@ def main(argv=None):
     ck = torch.load(os.path.abspath(os.path.expanduser(args.checkpoint)), map_location="cpu", weights_only=False)
     model.load_state_dict(ck["model"] if "model" in ck else ck)
     res = evaluate_files(model, args.clean_list, args.noisy_list, metrics=args.metrics, batch_size=args.batch_size,
-                         acoustics=config.get("acoustics"))
+                         acoustics=config.get("acoustics"), head=args.head)
     for name, m in res["mean"].items():
         print(f"{name}: Noisy {m['Noisy']!r}  Enhanced {m['Enhanced']!r}")
     if args.csv:

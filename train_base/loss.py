@@ -21,6 +21,20 @@ def wo_male_loss(alpha=2.0, beta=1.0):
     return fn
 
 
+def wo_male_df_loss(alpha=2.0, beta=1.0):
+    """WO-MALE on the output of the DeepFilter(1, 5) head (BASELINE config 4): unet_2's output is the real part of the filter
+    field, the estimate the 3 x 11 neighbourhood sum of mask * N.  Training runs through the engine (its tag below); stand-alone,
+    fn(mask [B,1,T,Fn], noisy [B,2,T,Fs], clean [B,2,T,Fs]) gives the loss VALUE only: the head's inference kernel has no backward."""
+    from cruse_amd.loss import deepfilter_spectrum
+    from cruse_amd.loss_func import wo_male
+
+    def fn(mask, noisy_spec, clean_spec):
+        est = deepfilter_spectrum(mask, noisy_spec[:, 0], noisy_spec[:, 1], 1, 5).permute(0, 3, 1, 2)      # -> [B,2,T,Fs]
+        return wo_male(clean_spec, est.contiguous(), noisy_spec, alpha, beta)
+    fn.cruse_loss = ("wo_male_df", dict(loss_alpha=float(alpha), loss_beta=float(beta)))
+    return fn
+
+
 def si_snr_loss():
     """train_base/loss.py:7-25 on the HIP path (the engine runs it through the iSTFT on the enhanced waveform)."""
     from cruse_amd.loss import si_snr_loss as _f
