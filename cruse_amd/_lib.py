@@ -158,6 +158,9 @@ SIGNATURES = {
     "cruse_stream_resample_out": ("piipppipipp", "i"),
     "cruse_stream_resample_in_n": ("piiiipippipp", "i"),
     "cruse_stream_resample_out_n": ("piiiipppipipp", "i"),
+    "cruse_stream_df_layout": ("p", "i"),
+    "cruse_stream_df_head": ("piipiiiippipipippiip", "i"),
+    "cruse_stream_df_head_n": ("piiiipiiiippipipippiip", "i"),
     "cruse_si_sdr": ("ppiipp", "i"),
     "cruse_stoi_layout": ("iip", "i"),
     "cruse_stoi_ws_bytes": ("ii", "z"),

@@ -881,7 +881,253 @@ int decode_n_any(const char* who, const char* name, const int* pk, int S, int ho
 #undef CRUSE_DECODE_N
 }
 
+// ---- the DeepFilter(1, 5) head on the stream (cruse_stream_df_head / _df_head_n) -------------------------------------------------
+// A config-4 model's output is the real filter field of DeepFilter(t_dim = 1, f_dim = 5): with P[t] = mask[t] * N[t] on bins 0..159
+// (bin 160 zero), the enhanced row is E[t] = sum_{dt = -1..1} sum_{df = -5..5} P[t + dt][f + df], zero outside the spectrum and the
+// clip.  E[t] needs frame t + 1, so this kernel runs one frame behind the chain: it follows decode, reads the mask and the noisy
+// spectrum decode / encode left in the frame's work row, and keeps in a state row of its own P[t-2], P[t-1], N[t-1] (the attenuation
+// limit mixes against it), an overlap-add tail and the count of rows taken since the clip began (saturating at 2).  A step takes row
+// t, emits E[t-1] (inspection row, inverse DFT, window, overlap-add with its own tail: the arithmetic of the decode kernels) and
+// shifts the rows.  The step of the clip's frame 0 starts from a zero history and emits nothing; the block of E[0] lies in front of the
+// clip (as the mask path's frame-0 block) and is neither stored nor counted; a drain step takes an all-zero row and so emits E[T-1].
+// One workgroup per slot, no communication between workgroups; the frame loop is bounded by the packet's frame count (<= hops + 1).
+//
+// Bit contract: the window sum runs in f32 from 0.0f, frame offset outer, bin offset inner, both ascending, over products formed by one
+// multiplication each: the order of df_head.hip, so E has the bits of cruse_df_head_apply on the stacked rows.
+constexpr int DF_FD = 5, DF_PW = NB + 2 * DF_FD;          // a product plane with its zero halo of f_dim bins on either side
+constexpr int DF_THREADS = 384;
+constexpr int DF_PLANE = (NB + 3) & ~3;                   // floats between the re and the im plane of a state row pair
+// the largest hops any channel set's packet layout admits (packet_max_frames with the smallest row and staging area) bounds `hops`
+constexpr int DF_MAX_HOPS = (PACKET_LDS_BYTES / (int)sizeof(float) - 2 * NFFT - (2 * NB + 2) - 64) / (2 * (2 * NB + 2)) - 1;
+
+// the layout of cruse_stream_df_layout(): all ints, in the order of the header's description
+struct DfLayout {
+    int p2, p1, n1, tail, count, plane, stride;
+};
+static_assert(sizeof(DfLayout) == CRUSE_STREAM_DF_LAYOUT_INTS * sizeof(int), "df layout size");
+
+void make_df_layout(DfLayout& D) {
+    int o = 0;
+    auto take = [&](int n) { const int at = o; o += (n + 3) & ~3; return at; };
+    D.plane = DF_PLANE;
+    D.p2 = take(2 * DF_PLANE);
+    D.p1 = take(2 * DF_PLANE);
+    D.n1 = take(2 * DF_PLANE);
+    D.tail = take(HOP);
+    D.count = take(1);
+    D.stride = o;
+}
+
+// floats of LDS: three product rows (re | im, with halo) | N[t-1] | N[t] | the spectrum into the inverse DFT | y | tail | cos, sin | red
+constexpr int DF_LDS = 3 * 2 * DF_PW + 3 * 2 * NB + NFFT + HOP + 2 * NFFT + DF_THREADS / 64;
+
+// where the work rows of a call lie, as the caller's layout says
+struct DfRows {
+    const float* work;      // the slot's first row (null: a drain step, the row is all zero)
+    int WS, re, im, mask;   // floats between two frames' rows; offsets of the noisy spectrum and the mask in a row
+};
+
+// E[t-1] from the three product rows: sp (the spectrum for the inverse DFT; with LIM lim * N[t-1] + (1 - lim) * E) and the inspection row
+template <bool LIM>
+__device__ __forceinline__ void df_window(const float* p2, const float* p1, const float* pc, const float* n1, float lm, float* sp,
+                                          float* __restrict__ dfw) {
+#pragma clang fp contract(off)
+    for (int i = threadIdx.x; i < 2 * NB; i += blockDim.x) {
+        const int pl = i >= NB, f = i - pl * NB;
+        const float* q[3] = {p2 + pl * DF_PW + f, p1 + pl * DF_PW + f, pc + pl * DF_PW + f};     // q[dt][df]: bin f - 5 + df
+        float acc = 0.f;
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt)
+#pragma unroll
+            for (int df = 0; df <= 2 * DF_FD; ++df) acc += q[dt][df];
+        dfw[i] = acc;
+        if constexpr (LIM) sp[i] = lm * n1[i] + (1.0f - lm) * acc;
+        else sp[i] = acc;
+    }
+}
+
+// nf frames of slot s from rows R: f0: the first one is frame 0 of the clip.  dfw: the slot's inspection rows (one per emitted E),
+// out + o_at: the slot's output blocks (one per emitted E but E[0]).  st: the slot's state row.
+template <typename OUT, bool LIM>
+__device__ __forceinline__ void df_frames(float* sm, int s, int nf, bool f0, const DfRows R, const float* __restrict__ tab,
+                                          float* __restrict__ st, const DfLayout D, float* __restrict__ dfw, OUT* __restrict__ out,
+                                          size_t o_at, const float* __restrict__ lim, int* __restrict__ clip) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    float* p2 = sm;
+    float* p1 = p2 + 2 * DF_PW;
+    float* pc = p1 + 2 * DF_PW;
+    float* n1 = pc + 2 * DF_PW;
+    float* nc = n1 + 2 * NB;
+    float* sp = nc + 2 * NB;
+    float* y = sp + 2 * NB;
+    float* tail = y + NFFT;
+    float* cs = tail + HOP;
+    float* red = cs + 2 * NFFT;
+    float lm = 0.f;
+    if constexpr (LIM) lm = lim[s];
+    int cnt = (int)st[D.count];                           // uniform: rows taken since the clip began, 2: two or more
+    for (int i = tid; i < 3 * 2 * DF_PW; i += nt) sm[i] = 0.f;          // the halos stay zero from here on
+    __syncthreads();
+    for (int i = tid; i < 2 * NB; i += nt) {
+        const int pl = i >= NB, f = i - pl * NB;
+        p2[pl * DF_PW + DF_FD + f] = st[D.p2 + pl * D.plane + f];
+        p1[pl * DF_PW + DF_FD + f] = st[D.p1 + pl * D.plane + f];
+        n1[i] = st[D.n1 + pl * D.plane + f];
+    }
+    for (int i = tid; i < HOP; i += nt) tail[i] = st[D.tail + i];
+    for (int i = tid; i < 2 * NFFT; i += nt) cs[i] = tab[TB_COS + i];
+    int nclip = 0, e = 0, ob = 0;
+    for (int fr = 0; fr < nf; ++fr) {
+        if (fr == 0 && f0) {                              // frame 0 of the clip: the history is zero, whatever the state row held
+            __syncthreads();
+            for (int i = tid; i < 2 * NB; i += nt) {
+                const int pl = i >= NB, f = i - pl * NB;
+                p2[pl * DF_PW + DF_FD + f] = 0.f;
+                p1[pl * DF_PW + DF_FD + f] = 0.f;
+                n1[i] = 0.f;
+            }
+            for (int i = tid; i < HOP; i += nt) tail[i] = 0.f;
+            cnt = 0;
+        }
+        // row t: P[t] = mask * N[t] on bins 0..159, bin 160 zero
+        const float* row = R.work ? R.work + (size_t)fr * R.WS : nullptr;
+        for (int i = tid; i < 2 * NB; i += nt) {
+            const int pl = i >= NB, f = i - pl * NB;
+            const float n = row ? row[(pl ? R.im : R.re) + f] : 0.f;
+            nc[i] = n;
+            pc[pl * DF_PW + DF_FD + f] = row && f < F0 ? row[R.mask + f] * n : 0.f;
+        }
+        __syncthreads();
+        if (cnt >= 1) {                                   // E[t-1]
+            df_window<LIM>(p2, p1, pc, n1, lm, sp, dfw + (size_t)e * 2 * NB);
+            ++e;
+            __syncthreads();
+            for (int n = tid; n < NFFT; n += nt) y[n] = irdft320(sp, sp + NB, cs, n) * tab[TB_WIN + n];
+            __syncthreads();
+            const bool keep = cnt >= 2;                   // E[0]'s block lies in front of the clip
+            for (int i = tid; i < HOP; i += nt) {
+                const float o = (tail[i] + y[i]) * tab[TB_IENV + i];
+                if (keep) nclip += st_sample(out, o_at + (size_t)ob * HOP + i, o);
+                tail[i] = y[HOP + i];
+            }
+            ob += keep;
+            __syncthreads();
+        }
+        // shift the rows
+        float* t = p2; p2 = p1; p1 = pc; pc = t;
+        t = n1; n1 = nc; nc = t;
+        cnt = min(cnt + 1, 2);
+    }
+    for (int i = tid; i < 2 * NB; i += nt) {
+        const int pl = i >= NB, f = i - pl * NB;
+        st[D.p2 + pl * D.plane + f] = p2[pl * DF_PW + DF_FD + f];
+        st[D.p1 + pl * D.plane + f] = p1[pl * DF_PW + DF_FD + f];
+        st[D.n1 + pl * D.plane + f] = n1[i];
+    }
+    for (int i = tid; i < HOP; i += nt) st[D.tail + i] = tail[i];
+    if (tid == 0) st[D.count] = (float)cnt;
+    if constexpr (!std::is_same<OUT, float>::value) count_clipped(clip, s, nclip, red);
+}
+
+// drain: only slots whose mode is END step, on an all-zero row
+template <typename OUT, bool LIM>
+__global__ void __launch_bounds__(DF_THREADS) stream_df_head_kernel(const int* __restrict__ mode, int drain, DfRows R,
+                                                                   const float* __restrict__ tab, float* __restrict__ state, int SS,
+                                                                   DfLayout D, float* __restrict__ dfw, int DWS, OUT* __restrict__ out,
+                                                                   const float* __restrict__ lim, int* __restrict__ clip) {
+    __shared__ float sm[DF_LDS];
+    const int s = blockIdx.x, m = mode[s];
+    if (drain ? m != CRUSE_STREAM_MODE_END : !mode_computes_frame(m)) return;
+    R.work = drain ? nullptr : R.work + (size_t)s * R.WS;
+    df_frames<OUT, LIM>(sm, s, 1, !drain && m == CRUSE_STREAM_MODE_FRAME0, R, tab, state + (size_t)s * SS, D, dfw + (size_t)s * DWS, out,
+                        (size_t)s * HOP, lim, clip);
+}
+
+template <typename OUT, bool LIM>
+__global__ void __launch_bounds__(DF_THREADS) stream_df_head_n_kernel(const int* __restrict__ pk, int S, int hops, int out_hops, int NFW,
+                                                                     DfRows R, const float* __restrict__ tab, float* __restrict__ state,
+                                                                     int SS, DfLayout D, float* __restrict__ dfw, int DWF,
+                                                                     OUT* __restrict__ out, const float* __restrict__ lim,
+                                                                     int* __restrict__ clip) {
+    __shared__ float sm[DF_LDS];
+    const int s = blockIdx.x;
+    const Pkt p = packet_of(pk, S, s, hops);
+    if (p.nf == 0) return;
+    R.work += (size_t)s * NFW * R.WS;
+    // at most nf - f0 <= hops rows are emitted: dfw holds DWF >= hops rows per slot, out out_hops >= hops blocks
+    df_frames<OUT, LIM>(sm, s, p.nf, p.f0, R, tab, state + (size_t)s * SS, D, dfw + (size_t)s * DWF * 2 * NB, out,
+                        (size_t)s * out_hops * HOP, lim, clip);
+}
+
+// shared argument checks of the two entry points
+int df_head_args(const char* who, int S, const void* ctl, const float* work, int wk_stride, int wk_re, int wk_im, int wk_mask,
+                 const float* tab, const float* df_state, int st_stride, const float* df_work, const void* out, int out_fmt, const int* clip,
+                 int t_dim, int f_dim, DfLayout& D) {
+    CRUSE_REQUIRE(t_dim == 1 && f_dim == DF_FD, CRUSE_E_SHAPE, "%s: (t_dim, f_dim) = (%d, %d): only the DeepFilter(1, %d) instance is built", who,
+                  t_dim, f_dim, DF_FD);
+    CRUSE_REQUIRE(S >= 1, CRUSE_E_SHAPE, "%s: S = %d (need S >= 1)", who, S);
+    CRUSE_REQUIRE(ctl && work && tab && df_state && df_work && out, CRUSE_E_SHAPE, "%s: null buffer", who);
+    CRUSE_REQUIRE(wk_stride >= 2 * NB + F0 && wk_re >= 0 && wk_re + NB <= wk_stride && wk_im >= 0 && wk_im + NB <= wk_stride && wk_mask >= 0 &&
+                  wk_mask + F0 <= wk_stride, CRUSE_E_SHAPE,
+                  "%s: wk_re %d / wk_im %d (+ %d) / wk_mask %d (+ %d) do not lie in a work row of %d floats (>= %d)", who, wk_re, wk_im, NB,
+                  wk_mask, F0, wk_stride, 2 * NB + F0);
+    make_df_layout(D);
+    CRUSE_REQUIRE(st_stride >= D.stride, CRUSE_E_SHAPE, "%s: df_state rows of %d floats, the layout needs %d", who, st_stride, D.stride);
+    return out_args(who, out_fmt, clip);
+}
+
+#define CRUSE_DF_FORMS(LAUNCH)                                                                      \
+    if (out_fmt == FMT_S16) { if (lim) { LAUNCH(short, true); } else { LAUNCH(short, false); } }   \
+    else if (lim) { LAUNCH(float, true); } else { LAUNCH(float, false); }
+
 }  // namespace
+
+extern "C" int cruse_stream_df_layout(int* out) {
+    CRUSE_REQUIRE(out, CRUSE_E_SHAPE, "stream_df_layout: null output");
+    DfLayout D;
+    make_df_layout(D);
+    memcpy(out, &D, sizeof(D));
+    return CRUSE_OK;
+}
+
+extern "C" int cruse_stream_df_head(const int* mode, int S, int drain, const float* work, int wk_stride, int wk_re, int wk_im, int wk_mask,
+                                    const float* tab, float* df_state, int st_stride, float* df_work, int dw_stride, void* out, int out_fmt,
+                                    const float* lim, int* clip, int t_dim, int f_dim, void* stream) {
+    DfLayout D;
+    const int rc = df_head_args("stream_df_head", S, mode, work, wk_stride, wk_re, wk_im, wk_mask, tab, df_state, st_stride, df_work, out,
+                                out_fmt, clip, t_dim, f_dim, D);
+    if (rc) return rc;
+    CRUSE_REQUIRE(dw_stride >= 2 * NB, CRUSE_E_SHAPE, "stream_df_head: df_work rows of %d floats, need %d", dw_stride, 2 * NB);
+    const DfRows R = {work, wk_stride, wk_re, wk_im, wk_mask};
+#define CRUSE_DF_HEAD(OUT, LIM)                                                                                                        \
+    hipLaunchKernelGGL((stream_df_head_kernel<OUT, LIM>), dim3(S), dim3(DF_THREADS), 0, (hipStream_t)stream, mode, drain != 0, R, tab, \
+                       df_state, st_stride, D, df_work, dw_stride, (OUT*)out, lim, clip)
+    CRUSE_DF_FORMS(CRUSE_DF_HEAD)
+#undef CRUSE_DF_HEAD
+    CRUSE_LAUNCH_CHECK("cruse_stream_df_head");
+    return CRUSE_OK;
+}
+
+extern "C" int cruse_stream_df_head_n(const int* pk, int S, int hops, int out_hops, int work_frames, const float* work, int wk_stride,
+                                      int wk_re, int wk_im, int wk_mask, const float* tab, float* df_state, int st_stride, float* df_work,
+                                      int dw_frames, void* out, int out_fmt, const float* lim, int* clip, int t_dim, int f_dim,
+                                      void* stream) {
+    DfLayout D;
+    const int rc = df_head_args("stream_df_head_n", S, pk, work, wk_stride, wk_re, wk_im, wk_mask, tab, df_state, st_stride, df_work, out,
+                                out_fmt, clip, t_dim, f_dim, D);
+    if (rc) return rc;
+    CRUSE_REQUIRE(hops >= 1 && hops <= DF_MAX_HOPS && work_frames >= hops + 1 && out_hops >= hops && dw_frames >= hops, CRUSE_E_SHAPE,
+                  "stream_df_head_n: hops = %d (1..%d), work_frames = %d (>= hops + 1), out_hops = %d, dw_frames = %d (>= hops)", hops,
+                  DF_MAX_HOPS, work_frames, out_hops, dw_frames);
+    const DfRows R = {work, wk_stride, wk_re, wk_im, wk_mask};
+#define CRUSE_DF_HEAD_N(OUT, LIM)                                                                                                       \
+    hipLaunchKernelGGL((stream_df_head_n_kernel<OUT, LIM>), dim3(S), dim3(DF_THREADS), 0, (hipStream_t)stream, pk, S, hops, out_hops,  \
+                       work_frames, R, tab, df_state, st_stride, D, df_work, dw_frames, (OUT*)out, lim, clip)
+    CRUSE_DF_FORMS(CRUSE_DF_HEAD_N)
+#undef CRUSE_DF_HEAD_N
+    CRUSE_LAUNCH_CHECK("cruse_stream_df_head_n");
+    return CRUSE_OK;
+}
 
 extern "C" int cruse_stream_layout(int c0, int c1, int c2, int c3, int c4, int* out) {
     CRUSE_REQUIRE(out, CRUSE_E_SHAPE, "stream_layout: null output");

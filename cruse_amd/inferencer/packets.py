@@ -41,6 +41,20 @@ def flush_plan(b: int) -> PacketPlan:
     return PacketPlan(b, 1, b - 1, 1, 2)
 
 
+def df_packet_plan(b: int, c: int) -> PacketPlan:
+    """packet_plan for the DeepFilter head (StreamingInferencer(head="df")): the same frames, but the head's row t needs frame t + 1,
+    so a slot that has consumed b >= 2 blocks has returned b - 2 of them (30 ms behind instead of 20)."""
+    p = packet_plan(b, c)
+    first_out = max(b - 2, 0)
+    return PacketPlan(p.first_frame, p.n_frames, first_out, max(b + c - 2, 0) - first_out, p.start)
+
+
+def df_flush_plan(b: int) -> PacketPlan:
+    """The end frame of a clip of `b >= 2` blocks and the drain step of the head: output blocks b-2 and b-1."""
+    p = flush_plan(b)
+    return PacketPlan(p.first_frame, p.n_frames, b - 2, 2, p.start)
+
+
 def padded_blocks(L: int) -> int:
     """Blocks of a clip of L samples, its last block zero-padded to 160."""
     return (L + HOP - 1) // HOP

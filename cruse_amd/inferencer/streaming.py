@@ -28,7 +28,7 @@ import torch
 
 from .. import ops
 from . import resample
-from .packets import packet_plan
+from .packets import df_packet_plan, packet_plan
 
 
 def _bn_fold(bn):
@@ -65,15 +65,34 @@ class StreamingInferencer:
     today's 16 kHz enhancement of a whole clip, pushes + flush, packets + flush and enhance return Out(E(In(u))) truncated to the
     input's length: the converters delay the signal by io_delay samples at io_rate (64 / 96 at 32 / 48 kHz = 2 ms; 32 at 8 kHz = 4 ms)
     on top of the chain's 20 ms, and the last io_delay samples of the filters' tail are dropped.
+
+    head = "df" (default "mask": nothing changes): the model's output is the real filter field of DeepFilter(1, 5) (a unet_2 trained
+    with wo_male_df_loss; a checkpoint does not say so, the server must be told) and is applied as Inferencer(head="df") applies it:
+    E[t] = the 3 x 11 neighbourhood sum of mask * noisy.  E[t] needs frame t + 1, so one more kernel (cruse_stream_df_head / _n) ends
+    every chain, one frame behind decode, with a state row of its own (`df_state`): the output is 30 ms behind instead of 20.  push is
+    valid from the slot's third block on (push #b returns block b-2), push_packet follows packets.df_packet_plan, flush returns the last
+    TWO blocks [len(slots), 320] (the end frame's, then a drain step's), enhance still returns [n, L].  atten_lim, pcm_out and clipped()
+    work through the new kernel (limit 0 dB: the input, 30 ms late); precision and pcm_in are untouched.  stage_df(slot) shows the rows E.
+    On an instance with max_hops > 1 a push runs as a packet of one block: pushes and packets of any split then give one set of bits
+    (the single-hop chain, which max_hops = 1 and every flush's end frame use, rounds its GRU sums differently).
+    Only df_dims = (1, 5) is built, and head="df" needs io_rate = 16000.
     """
 
     HOP = 160
 
     def __init__(self, model: torch.nn.Module, n_slots: int, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
                  device="cuda", use_graph: bool = True, max_hops: int = 1, precision: str = "f32", atten_lim: bool = False,
-                 pcm_in: bool = False, pcm_out: bool = False, io_rate: int = 16000):
+                 pcm_in: bool = False, pcm_out: bool = False, io_rate: int = 16000, head: str = "mask", df_dims=(1, 5)):
         from ..model.cruse_net import unet_2
         io_rate = resample.check_rate(io_rate)
+        if head not in ("mask", "df"):
+            raise ValueError(f"StreamingInferencer head must be \"mask\" or \"df\", got {head!r}")
+        if tuple(df_dims) != ops.STREAM_DF_DIMS:
+            raise ValueError(f"StreamingInferencer streams the DeepFilter{ops.STREAM_DF_DIMS} head only (the one instance the kernels are "
+                             f"built for), got df_dims = {tuple(df_dims)}")
+        if head == "df" and io_rate != resample.MODEL_RATE:
+            raise ValueError(f"StreamingInferencer(head=\"df\") runs at io_rate = {resample.MODEL_RATE} only (the output converter follows the "
+                             f"main chain's modes, which are one block ahead of the head), got io_rate = {io_rate}")
         if (n_fft, hop_length, win_length) != (320, 160, 320):
             raise ValueError(f"StreamingInferencer supports n_fft = win_length = 320, hop_length = 160 only "
                              f"(got n_fft={n_fft}, hop_length={hop_length}, win_length={win_length})")
@@ -89,6 +108,8 @@ class StreamingInferencer:
             raise ValueError(f"n_slots must be >= 1, got {n_slots}")
         self.model = model
         self.precision = precision
+        self.head = head
+        self._df = head == "df"
         self.S = int(n_slots)
         self.device = torch.device(device)
         self.ch = tuple(model.ch)
@@ -119,6 +140,15 @@ class StreamingInferencer:
             self.io_out = torch.zeros(S, self.io_block, device=dev, dtype=self.out_dtype)
             self.rs_taps = ops.stream_resample_taps(io_rate, dev)
             self.rs_state = torch.zeros(S, sum(resample.history(io_rate)), device=dev)      # [in-side history | out-side history]
+        if self._df:
+            # the head's own rows: state (P[t-2], P[t-1], N[t-1], tail, count), the E rows of the last call (row 1: the drain step of a
+            # flush), the drain step's block, and the block decode's mask path still computes (not returned)
+            self.df_lay = ops.stream_df_layout()
+            self.df_state = torch.zeros(S, self.df_lay["stride"], device=dev)
+            self.df_work = torch.zeros(S, 2, ops.STREAM_DF_ROW, device=dev)
+            self.out_drain = torch.zeros(S, self.HOP, device=dev, dtype=self.out_dtype)
+            self._mask_out = torch.zeros(S, self.HOP, device=dev)
+            self._df_rows = np.zeros(S, dtype=np.int64)                         # E rows the slot's last call wrote
         self.lim = torch.zeros(S, device=dev) if self.atten_lim else None       # per-slot gains 10^(-dB/20); 0: no limit
         self.clip = torch.zeros(S, device=dev, dtype=torch.int32) if self.pcm_out else None     # clamped samples per slot
         self.mode = torch.zeros(2, S, device=dev, dtype=torch.int32)            # row 0: the frame-0 chain, row 1: the main chain
@@ -142,6 +172,9 @@ class StreamingInferencer:
             if self._rs:
                 self.io_pblocks = torch.zeros(S, K, self.io_block, device=dev, dtype=self.in_dtype)
                 self.io_pout = torch.zeros(S, K, self.io_block, device=dev, dtype=self.out_dtype)
+            if self._df:
+                self._mask_pout = torch.zeros(S, K, self.HOP, device=dev)
+                self.df_pwork = torch.zeros(S, K, ops.STREAM_DF_ROW, device=dev)    # one E row per frame a packet emits
             self.pwork = torch.zeros(S, K + 1, play["wk_stride"], device=dev)   # one work row per frame of a packet
             self.gi = torch.zeros(S, K + 1, 3 * self.H, device=dev)             # GRU input products of the layer in flight
             self.pk = torch.zeros(2, S, device=dev, dtype=torch.int32)          # row 0: min(blocks held, 2), row 1: counts
@@ -226,6 +259,10 @@ class StreamingInferencer:
         ops.stream_encode(mode, self.ch, self.blocks, self.tab, self.w, self.state, self.work)
         for layer, x_off, st_off, h_off, pack, pack16, ln1 in self._layers:
             ops.stream_gru(mode, layer, g, Hg, self.work, x_off, self.state, st_off, pack, self.work, h_off, pack16=pack16, **ln1)
+        if self._df:        # decode leaves the mask in the work row; the head, one frame behind, writes the block
+            ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self._mask_out)
+            ops.stream_df_head(mode, self.work, self.lay, self.tab, self.df_state, self.df_work[:, 0], self.out, lim=self.lim, clip=self.clip)
+            return
         ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out, lim=self.lim,
                           clip=None if self._rs else self.clip)             # behind the converters, resample_out counts
 
@@ -243,7 +280,7 @@ class StreamingInferencer:
             self._graphs[key] = gr
         gr.replay()
 
-    def _launch(self, passes: int) -> None:
+    def _launch(self, passes: int, drain: bool = False) -> None:
         rows = (0, 1) if passes == 2 else (1,)
 
         def hop():
@@ -253,10 +290,13 @@ class StreamingInferencer:
                 self._chain(r)
             if self._rs:
                 ops.stream_resample_out(self.mode[1], self.io_rate, self.out, self.rs_taps, self.rs_state, self.io_out, clip=self.clip)
+            if drain:                                                           # head="df": the END slots' last row, on a zero row
+                ops.stream_df_head(self.mode[1], self.work, self.lay, self.tab, self.df_state, self.df_work[:, 1], self.out_drain,
+                                   lim=self.lim, clip=self.clip, drain=True)
 
-        self._replay(passes, hop)
+        self._replay(("drain", passes) if drain else passes, hop)
 
-    def _run(self, m0: np.ndarray, m1: np.ndarray) -> None:
+    def _run(self, m0: np.ndarray, m1: np.ndarray, drain: bool = False) -> None:
         if self._host_free is not None:
             self._host_free.synchronize()
         hm = self._mode_host.numpy()
@@ -265,7 +305,7 @@ class StreamingInferencer:
         ev = torch.cuda.Event()
         ev.record()
         self._host_free = ev
-        self._launch(2 if m0.any() else 1)
+        self._launch(2 if m0.any() else 1, drain)
 
     def _samples(self, t: torch.Tensor, who: str) -> torch.Tensor:
         """the input samples in the instance's input format: float32 (converted, as always), or int16 and nothing else with pcm_in"""
@@ -290,11 +330,18 @@ class StreamingInferencer:
             act = (active.cpu().numpy() if torch.is_tensor(active) else np.asarray(active)).astype(bool).reshape(-1)
             if act.size != S:
                 raise ValueError(f"active must have {S} entries, got {act.size}")
+        if self._df and self.max_hops != 1:
+            # an instance built for packets: a push is a packet of one block, so that a slot's output does not depend on how its blocks
+            # were grouped into calls (the packet chain's GRU sums round differently from the single-hop chain's)
+            out, n_out = self.push_packet(blocks.unsqueeze(1), act.astype(np.int64))
+            return out[:, 0], n_out > 0
         (self.io_blocks if self._rs else self.blocks).copy_(blocks, non_blocking=True)
         b = self.nblk
         m0 = np.where(act & (b == 1), ops.STREAM_FRAME0, ops.STREAM_SKIP).astype(np.int32)
         m1 = np.where(act, np.where(b == 0, ops.STREAM_STORE, ops.STREAM_FRAME), ops.STREAM_SKIP).astype(np.int32)
-        valid = act & (b >= 1)
+        valid = act & (b >= (2 if self._df else 1))
+        if self._df:
+            self._df_rows[act] = (b >= 1)[act]
         self.nblk += act
         self._last_frames[act] = 0
         self._run(m0, m1)
@@ -303,7 +350,7 @@ class StreamingInferencer:
     @torch.no_grad()
     def flush(self, slots) -> torch.Tensor:
         """End the clip of each slot in `slots`: computes its end frame and returns its last output block ([len(slots), 160],
-        device), then resets the slot.  A slot must hold at least two blocks."""
+        device), then resets the slot.  A slot must hold at least two blocks.  head="df": the last two blocks, [len(slots), 320]."""
         slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
         for s in slots:
             if not 0 <= s < self.S:
@@ -313,10 +360,14 @@ class StreamingInferencer:
         m1 = np.zeros(self.S, dtype=np.int32)
         m1[slots] = ops.STREAM_END
         self._last_frames[slots] = 0
-        self._run(np.zeros(self.S, dtype=np.int32), m1)
+        self._run(np.zeros(self.S, dtype=np.int32), m1, drain=self._df)
         idx = torch.tensor(slots, device=self.device, dtype=torch.long)
         last = (self.io_out if self._rs else self.out).index_select(0, idx)
+        if self._df:                                                            # the end frame's block, then the drain step's
+            last = torch.cat([last, self.out_drain.index_select(0, idx)], dim=1)
         self.reset(slots)
+        if self._df:
+            self._df_rows[slots] = 2
         return last
 
     @torch.no_grad()
@@ -330,6 +381,8 @@ class StreamingInferencer:
             self.state.index_fill_(0, idx, 0.0)
             if self._rs:
                 self.rs_state.index_fill_(0, idx, 0.0)
+            if self._df:
+                self.df_state.index_fill_(0, idx, 0.0)
         self.nblk[slots] = 0
         self._last_frames[slots] = 0
 
@@ -388,6 +441,10 @@ class StreamingInferencer:
             ops.stream_gru_proj_n(pk, hops, layer, g, Hg, wk, x_off, pack, self.gi, pack16=pack16, **ln1)
             for f in range(nf):
                 ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, st_off, pack, wk, h_off, pack16=pack16)
+        if self._df:
+            ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self._mask_pout)
+            ops.stream_df_head_n(pk, hops, wk, self.lay, self.tab, self.df_state, self.df_pwork, self.pout, lim=self.lim, clip=self.clip)
+            return
         ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout, lim=self.lim,
                             clip=None if self._rs else self.clip)
         if self._rs:
@@ -423,7 +480,8 @@ class StreamingInferencer:
         if self.max_hops == 1:                                                  # one block per call: the single-hop chain
             out, valid = self.push(blocks[:, 0], cnt > 0)
             return out.unsqueeze(1), valid.to(torch.int64)
-        plans = [packet_plan(int(b), int(c)) for b, c in zip(self.nblk, cnt)]
+        plan = df_packet_plan if self._df else packet_plan
+        plans = [plan(int(b), int(c)) for b, c in zip(self.nblk, cnt)]
         n_out = np.array([p.n_out for p in plans], dtype=np.int64)
         frames = np.array([p.n_frames for p in plans], dtype=np.int64)
         hops = int(cnt.max())
@@ -442,6 +500,8 @@ class StreamingInferencer:
         act = cnt > 0
         self._last_frames[act] = frames[act]
         self._last_f0[act] = np.array([p.first_frame == 0 for p in plans])[act]
+        if self._df:                                                            # every frame but a clip's frame 0 emits a row
+            self._df_rows[act] = (frames - (self._last_f0 & (frames > 0)))[act]
         nf = int(frames.max())
         self._replay(("packet", hops, nf), lambda: self._packet_chain(hops, nf))
         return (self.io_pout if self._rs else self.pout)[:, :K].clone(), torch.from_numpy(n_out)
@@ -514,8 +574,19 @@ class StreamingInferencer:
             out[f"skip{k}"] = wk[lay[f"wk_skip{k}"]:lay[f"wk_skip{k}"] + n]
             if k < 4:
                 out[f"e{k}"] = e[eoff[k]:eoff[k] + n]
-        if nfr > 0:
+        if nfr > 0 and not self._df:                                            # (head="df": pout holds the head's blocks, a frame behind)
             first = int(self._last_f0[slot])                                    # frame 0 of a clip yields no output block
             if f - first >= 0:
                 out["block"] = self.pout[slot, f - first]
         return out
+
+    def stage_df(self, slot: int) -> torch.Tensor:
+        """head="df": the rows E (re[161] | im[161]) the head emitted for slot `slot` in its last call, [rows, 322] in frame order: one
+        after a push that computed a frame (E[t-1] for frame t; none after the push of block 0), one per frame but a clip's frame 0 after
+        push_packet, two after flush (the end frame's E[T-2] and the drain step's E[T-1])."""
+        if not self._df:
+            raise ValueError("stage_df: this StreamingInferencer was built with head=\"mask\" (there is no DeepFilter head to inspect)")
+        if not 0 <= slot < self.S:
+            raise ValueError(f"slot {slot} out of range [0, {self.S})")
+        rows = self.df_pwork if self._last_frames[slot] > 0 else self.df_work
+        return rows[slot, :int(self._df_rows[slot])]

@@ -1297,7 +1297,56 @@ def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out, lim=None, cl
                                            _p(w), float(ln_eps), _p(state), _p(work), _p(out), *io, _stream()))
 
 
-# 8 / 32 / 48 kHz I/O around the 16 kHz chains (cruse_stream_resample_*).  taps: stream_resample_taps(io_rate); rs_state [S, >= the two
+# the DeepFilter(1, 5) head at the end of a chain (cruse_stream_df_head / _df_head_n): one frame behind decode, state rows of its own
+STREAM_DF_LAYOUT_NAMES = ("p2", "p1", "n1", "tail", "count", "plane", "stride")
+STREAM_DF_DIMS = (1, 5)     # the (t_dim, f_dim) instance the streaming kernels are built for
+STREAM_DF_ROW = 2 * 161     # floats of an inspection row: E re | im
+
+
+def stream_df_layout() -> Dict[str, int]:
+    """Offsets (floats) in a df_state row: P[t-2], P[t-1], N[t-1] (re plane, im plane `plane` floats on), the overlap-add tail, the
+    count of rows taken; `stride`: floats of a row."""
+    arr = (ctypes.c_int * len(STREAM_DF_LAYOUT_NAMES))()
+    check(lib.cruse_stream_df_layout(arr))
+    return dict(zip(STREAM_DF_LAYOUT_NAMES, list(arr)))
+
+
+def _df_head_io(out, lim, clip, name):
+    io = _stream_io(out, lim, clip, name)
+    return (STREAM_FMT_F32, None, None) if io is None else io
+
+
+def stream_df_head(mode, work, lay, tab, df_state, df_work, out, lim=None, clip=None, drain=False, df_dims=STREAM_DF_DIMS) -> None:
+    """After stream_decode: every slot whose mode computes a frame takes the mask and the noisy spectrum of its row of work [S, wk_stride]
+    (lay: wk_re / wk_im / wk_mask of stream_layout), writes E[t-1] to df_work [S, >= 322] and its block to out [S, 160] (float32 or
+    int16; lim / clip as stream_decode).  drain: slots whose mode is END take a zero row instead (the clip's last E).  df_state
+    [S, >= stream_df_layout()["stride"]] f32."""
+    fmt, plim, pclip = _df_head_io(out, lim, clip, "stream_df_head")
+    _f32(df_work, "df_work")
+    # rows may be a strided view (one row of several per slot): the kernel takes the row stride
+    if not df_work.is_cuda or df_work.dim() != 2 or df_work.shape[0] != mode.numel() or df_work.shape[1] < STREAM_DF_ROW or df_work.stride(1) != 1:
+        raise RuntimeError(f"stream_df_head: df_work must be [{mode.numel()}, >= {STREAM_DF_ROW}] rows of contiguous floats on the device, got "
+                           f"{tuple(df_work.shape)} with strides {df_work.stride()}")
+    check(lib.cruse_stream_df_head(_p(mode), mode.numel(), int(bool(drain)), _p(_f32(work, "work")), work.shape[1], int(lay["wk_re"]),
+                                   int(lay["wk_im"]), int(lay["wk_mask"]), _p(tab), _p(_f32(df_state, "df_state")), df_state.shape[1],
+                                   df_work.data_ptr(), df_work.stride(0), _p(out), fmt, plim, pclip, int(df_dims[0]), int(df_dims[1]),
+                                   _stream()))
+
+
+def stream_df_head_n(pk, hops, work, lay, tab, df_state, df_work, out, lim=None, clip=None, df_dims=STREAM_DF_DIMS) -> None:
+    """After stream_decode_n: the same step for the frames of every slot's packet, in order.  work [S, work_frames, wk_stride];
+    df_work [S, >= hops, 322]: one row per emitted E; out [S, out_hops, 160]: the emitted blocks from index 0."""
+    fmt, plim, pclip = _df_head_io(out, lim, clip, "stream_df_head_n")
+    if df_work.dim() != 3 or df_work.shape[0] != pk.shape[1] or df_work.shape[2] != STREAM_DF_ROW or work.dim() != 3 or out.dim() != 3:
+        raise RuntimeError(f"stream_df_head_n: expected work [S, frames, stride], out [S, hops, 160] and df_work [{pk.shape[1]}, rows, "
+                           f"{STREAM_DF_ROW}], got {tuple(work.shape)}, {tuple(out.shape)}, {tuple(df_work.shape)}")
+    check(lib.cruse_stream_df_head_n(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], _p(_f32(work, "work")), work.shape[2],
+                                     int(lay["wk_re"]), int(lay["wk_im"]), int(lay["wk_mask"]), _p(tab), _p(_f32(df_state, "df_state")),
+                                     df_state.shape[1], _p(_f32(df_work, "df_work")), df_work.shape[1], _p(out), fmt, plim, pclip,
+                                     int(df_dims[0]), int(df_dims[1]), _stream()))
+
+
+# 8 / 32 / 48 kHz I/O around the 16 kHz chains (cruse_stream_resample_*). taps: stream_resample_taps(io_rate); rs_state [S, >= the two
 # history sizes of inferencer.resample.history(io_rate)] f32: the slots' converter histories, zero at the start of a clip.
 def stream_resample_taps(io_rate: int, device) -> torch.Tensor:
     """the f32 device table of the converters' low-pass (inferencer.resample.design, float64 rounded once)"""

@@ -968,6 +968,41 @@ int cruse_stream_resample_in_n(const int* pk, int S, int hops, int in_hops, int 
 int cruse_stream_resample_out_n(const int* pk, int S, int hops, int out_hops, int io_rate, const float* out16, const float* taps,
                                 float* rs_state, int rs_stride, void* out, int out_fmt, int* clip, void* stream);
 
+/* ---- the DeepFilter(1, 5) head on the stream (additive; nothing above changes, the kernels above launch as before) ---------------
+ * A model trained against the DeepFilter loss emits the real filter field of DeepFilter(t_dim = 1, f_dim = 5), not a mask: with
+ * P[t][f] = mask[t][f] * N[t][f] on bins 0..159 and P[t][160] = 0, the enhanced row is E[t][f] = sum_{dt=-1..1} sum_{df=-5..5}
+ * P[t+dt][f+df] on all 161 bins, terms outside the spectrum or the clip zero (cruse_df_head_apply, bit for bit: f32 from 0.0f, frame
+ * offset outer, bin offset inner, ascending).  These kernels follow cruse_stream_decode / _decode_n in a chain and read nothing but
+ * what the chain leaves in the frame's work row: the mask (160 floats at wk_mask) and the noisy spectrum (161 at wk_re, 161 at
+ * wk_im), rows wk_stride floats apart -- the offsets of cruse_stream_layout, with the stride of cruse_stream_packet_layout for packets.
+ * E[t] needs frame t + 1: a step takes row t, emits E[t-1] (written to df_work, then inverse DFT, window, overlap-add and envelope
+ * as cruse_stream_decode, with a tail of its own) and shifts the rows.  The step of a clip's frame 0 (mode FRAME0; a packet's first
+ * frame where pk says the slot held at most one block) starts from a zero history and emits nothing.  The block of E[0] lies in front
+ * of the clip: it is neither stored nor counted.  df_state[S][st_stride] (device, f32; zero at the start of a clip; st_stride >= the
+ * stride of cruse_stream_df_layout) holds P[t-2], P[t-1], N[t-1] (re | im planes), the tail and the count of rows taken (0, 1, 2 = two
+ * or more).  out / out_fmt / lim / clip are those of the _io entry points; with lim the spectrum that is inverted is
+ * lim * N[t-1] + (1 - lim) * E[t-1] on all 161 bins.  One workgroup per slot.  Refused with CRUSE_E_SHAPE before any launch: a null
+ * buffer (lim and clip may be null), S < 1, wk_re / wk_im / wk_mask that do not lie in a row of wk_stride floats or a row shorter than
+ * 161 + 161 + 160, st_stride or the df_work rows too small, an unknown format, a clip counter with f32 output, hops outside
+ * [1, 47] (the largest any packet layout admits), work_frames < hops + 1, out_hops or dw_frames < hops, and (t_dim, f_dim) other than
+ * (1, 5): only that instance is built. */
+#define CRUSE_STREAM_DF_LAYOUT_INTS 7
+/* out[CRUSE_STREAM_DF_LAYOUT_INTS] (HOST array): offsets in a df_state row of P[t-2], P[t-1], N[t-1] (each re plane, then the im
+ * plane `plane` floats on), the tail (160), the count (one float); floats between the planes of a pair; the row stride */
+int cruse_stream_df_layout(int* out);
+/* after cruse_stream_decode: drain = 0: every slot whose mode computes a frame (FRAME, FRAME0, END) takes its work row; drain = 1:
+ * every slot whose mode is END takes an all-zero row, which emits the clip's last row E[T-1].  df_work[S][dw_stride] (dw_stride >=
+ * 322): E re | im of the slot's step; out[S][160] */
+int cruse_stream_df_head(const int* mode, int S, int drain, const float* work, int wk_stride, int wk_re, int wk_im, int wk_mask,
+                         const float* tab, float* df_state, int st_stride, float* df_work, int dw_stride, void* out, int out_fmt,
+                         const float* lim, int* clip, int t_dim, int f_dim, void* stream);
+/* after cruse_stream_decode_n: the same step for the frames of the slot's packet, in order (the frame set cruse_stream_decode_n
+ * derives from pk).  df_work[S][dw_frames][322]: one row per emitted E, from index 0; out[S][out_hops][160]: the emitted blocks in
+ * order from index 0 (E[0]'s is not among them) */
+int cruse_stream_df_head_n(const int* pk, int S, int hops, int out_hops, int work_frames, const float* work, int wk_stride, int wk_re,
+                           int wk_im, int wk_mask, const float* tab, float* df_state, int st_stride, float* df_work, int dw_frames,
+                           void* out, int out_fmt, const float* lim, int* clip, int t_dim, int f_dim, void* stream);
+
 /* ---- validation metrics on the device (ABI 13, additive; csrc/metrics.hip) -------------------------------------------------------
  * The two closed-form metrics of train_base/metrics.py, scored per clip of a batch ref[B][L], est[B][L] (f32) into out[B] (f32).
  * Every sum runs in a fixed order and there are no atomics: a result is bit-identical from run to run, and a clip scores the same

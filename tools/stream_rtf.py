@@ -20,8 +20,12 @@ With --io-rate 16000,48000,... every cell is measured once per rate (StreamingIn
 through the rate-conversion kernels; a hop is still 10 ms) and every row carries "io_rate"; without it nothing changes (DESIGN 12d,
 profiles/stream_rs_rtf.json).
 
+With --head mask,df every (n_slots, hops) cell is measured for both heads of StreamingInferencer in one run: one instance
+each, in alternating slices of the measuring time; every row carries "head", the df row "vs_mask" (p50 wall time per hop over the mask
+row's) and "device_vs_mask" (profiles/stream_df_rtf.json).
+
     python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--precision f32,f16] [--pcm]
-                               [--atten-lim DB] [--io-rate 16000,8000,48000] [--out FILE]
+                               [--atten-lim DB] [--io-rate 16000,8000,48000] [--head mask,df] [--out FILE]
 """
 from __future__ import annotations
 
@@ -127,6 +131,46 @@ def measure_packets(model, S: int, hops: int, seconds: float, precision: str = "
             "device_us_per_hop": r(d.mean() / hops), "rtf": round(float(w.mean()) / (10000.0 * hops), 5)}
 
 
+def measure_heads(model, S: int, hops: int, seconds: float, heads, precision: str = "f32", rounds: int = 8):
+    """one (n_slots, hops) cell for every head in `heads`, side by side: one instance per head, measured in `rounds` alternating slices of
+    seconds / rounds each, so that clock and machine drift hit both alike.  Rows as measure_packets, plus "head" and, on the "df" row,
+    "vs_mask" = its wall time per hop over the mask row's."""
+    infs = {h: _inferencer(model, S, precision, max_hops=hops, head=h) for h in heads}
+    blocks = _blocks(S, hops, 160)
+    calls = {h: ((lambda i=i: i.push(blocks[:, 0])) if hops == 1 else (lambda i=i: i.push_packet(blocks))) for h, i in infs.items()}
+    for call in calls.values():
+        for _ in range(50):
+            call()
+    torch.cuda.synchronize()
+    walls, devs = {h: [] for h in heads}, {h: [] for h in heads}
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(rounds):
+        for h in heads:
+            t_end = time.perf_counter() + seconds / rounds
+            n0 = len(walls[h])
+            while time.perf_counter() < t_end or len(walls[h]) - n0 < 50:
+                t0 = time.perf_counter()
+                ev0.record()
+                calls[h]()
+                ev1.record()
+                torch.cuda.synchronize()
+                walls[h].append(time.perf_counter() - t0)
+                devs[h].append(ev0.elapsed_time(ev1) * 1e-3)
+    r = lambda v: round(float(v), 2)
+    rows = []
+    for h in heads:
+        w, d = np.array(walls[h]) * 1e6, np.array(devs[h]) * 1e6
+        rows.append({"n_slots": S, "hops": hops, "head": h, "path": "push" if hops == 1 else "push_packet", "calls": len(w),
+                     "wall_us_per_hop": {"mean": r(w.mean() / hops), "p50": r(np.median(w) / hops), "p99": r(np.percentile(w, 99) / hops)},
+                     "device_us_per_hop": r(d.mean() / hops), "rtf": round(float(w.mean()) / (10000.0 * hops), 5)})
+    base = {row["head"]: row for row in rows}.get("mask")
+    for row in rows:
+        if base is not None and row["head"] != "mask":
+            row["vs_mask"] = round(row["wall_us_per_hop"]["p50"] / base["wall_us_per_hop"]["p50"], 3)
+            row["device_vs_mask"] = round(row["device_us_per_hop"] / base["device_us_per_hop"], 3)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--slots", default="1,16,64,256,1024")
@@ -137,6 +181,7 @@ def main():
     ap.add_argument("--pcm", action="store_true", help="int16 PCM blocks in and out (pcm_in = pcm_out = True)")
     ap.add_argument("--atten-lim", type=float, default=None, metavar="DB", help="every slot limited to DB dB of attenuation (atten_lim = True)")
     ap.add_argument("--io-rate", default=None, help="comma-separated I/O sample rates (8000, 16000, 32000, 48000): measure every cell at each")
+    ap.add_argument("--head", default=None, help="mask, df or mask,df: the heads to measure side by side, alternating, in every cell")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()
     IO.update(pcm=a.pcm, atten_lim=a.atten_lim)
@@ -150,6 +195,19 @@ def main():
     if any(p not in ("f32", "f16") for p in precs):
         ap.error(f"--precision takes f32, f16 or f32,f16, got {a.precision}")
     rows = []
+    heads = None if a.head is None else a.head.split(",")
+    if heads is not None:
+        if any(h not in ("mask", "df") for h in heads):
+            ap.error(f"--head takes mask, df or mask,df, got {a.head}")
+        for prec in precs:
+            for s in a.slots.split(","):
+                for h in (a.hops or "1").split(","):
+                    part = measure_heads(m, int(s), int(h), a.seconds, heads, prec)
+                    for r in part:
+                        if precs != ["f32"]:
+                            r["precision"] = prec
+                    rows += part
+        rates = []
     for rate in rates:
         IO.update(io_rate=rate)
         for prec in precs:
