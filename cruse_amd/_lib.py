@@ -154,6 +154,9 @@ SIGNATURES = {
     "cruse_stream_decode_io": ("piiiiiippfpppippp", "i"),
     "cruse_stream_encode_n_io": ("piiiiiiiiipippppp", "i"),
     "cruse_stream_decode_n_io": ("piiiiiiiiippfpppippp", "i"),
+    "cruse_stream_decode_pf": ("piiiiiippfpppippipp", "i"),
+    "cruse_stream_decode_n_pf": ("piiiiiiiiippfpppippipp", "i"),
+    "cruse_mask_postfilter": ("ipqqpqpp", "i"),
     "cruse_stream_resample_in": ("piipippipp", "i"),
     "cruse_stream_resample_out": ("piipppipipp", "i"),
     "cruse_stream_resample_in_n": ("piiiipippipp", "i"),

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <type_traits>
+#include "postfilter.h"
 #include "stream_common.h"
 
 namespace {
@@ -412,11 +413,14 @@ __global__ void __launch_bounds__(256) stream_gru_f32_kernel(GruArgs a) {
 
 // lim[s] (LIM): the slot's attenuation limit as a gain, the output is lim * noisy + (1 - lim) * enhanced, mixed on the spectrum;
 // clip[s] (PCM out, may be null): the count of clamped samples
-template <typename OUT, bool LIM>
+// pf_tau[s], pf_kind (PF): the slot's perceptual post-filter (postfilter.h), applied to the mask value before the limit's mix:
+// gain = lim + (1 - lim) * pf(mask); pf_tau[s] == 0 is the bypass.  The wk_mask row keeps the raw mask.  PF = false reads neither.
+template <typename OUT, bool LIM, bool PF>
 __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restrict__ mode, Layout L, const float* __restrict__ tab,
                                                             const float* __restrict__ w, float ln_eps, float* __restrict__ state,
                                                             float* __restrict__ work, OUT* __restrict__ out,
-                                                            const float* __restrict__ lim, int* __restrict__ clip) {
+                                                            const float* __restrict__ lim, int* __restrict__ clip, int pf_kind,
+                                                            const float* __restrict__ pf_tau) {
     extern __shared__ float sm[];
     const int s = blockIdx.x, m = mode[s];
     if (!mode_computes_frame(m)) return;
@@ -456,13 +460,26 @@ __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restri
     // mask on bins 0..159 (bin 160 zero), 320-point inverse real DFT (imaginary parts of bins 0 and 160 ignored, as irfft)
     if constexpr (LIM) {                                  // gain = lim + (1 - lim) * mask; bin 160 keeps lim of the input
         const float lm = lim[s];
+        [[maybe_unused]] float tau = 0.f;
+        if constexpr (PF) tau = pf_tau[s];
         for (int i = tid; i < F0; i += blockDim.x) {
             wk[L.wk_mask + i] = row[0][i];
-            const float gain = fmaf(1.0f - lm, row[0][i], lm);
+            float g = row[0][i];
+            if constexpr (PF) g = cruse_pf::post_filter(g, tau, pf_kind);
+            const float gain = fmaf(1.0f - lm, g, lm);
             re[i] *= gain;
             im[i] *= gain;
         }
         if (tid == 0) { re[F0] *= lm; im[F0] *= lm; }
+    } else if constexpr (PF) {
+        const float tau = pf_tau[s];
+        for (int i = tid; i < F0; i += blockDim.x) {
+            wk[L.wk_mask + i] = row[0][i];
+            const float g = cruse_pf::post_filter(row[0][i], tau, pf_kind);
+            re[i] *= g;
+            im[i] *= g;
+        }
+        if (tid == 0) { re[F0] = 0.f; im[F0] = 0.f; }
     } else {
         for (int i = tid; i < F0; i += blockDim.x) {
             wk[L.wk_mask + i] = row[0][i];
@@ -637,12 +654,13 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
     }
 }
 
-template <typename OUT, bool LIM>
+template <typename OUT, bool LIM, bool PF>
 __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __restrict__ pk, int S, int hops, int out_hops, int NFW,
                                                               Layout L, int WS, int rowmax, int wcap, const float* __restrict__ tab,
                                                               const float* __restrict__ w, float ln_eps, float* __restrict__ state,
                                                               float* __restrict__ work, OUT* __restrict__ out,
-                                                              const float* __restrict__ lim, int* __restrict__ clip) {
+                                                              const float* __restrict__ lim, int* __restrict__ clip, int pf_kind,
+                                                              const float* __restrict__ pf_tau) {
     extern __shared__ float sm[];
     const int s = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const Pkt p = packet_of(pk, S, s, hops);
@@ -693,21 +711,27 @@ __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __rest
     // src: the masks.  Masked spectrum re[161] | im[161] of every frame into dst (bin 160 zero), cos / sin tables into Wb
     if constexpr (LIM) {                                  // gain = lim + (1 - lim) * mask; bin 160 keeps lim of the input
         const float lm = lim[s];
+        [[maybe_unused]] float tau = 0.f;
+        if constexpr (PF) tau = pf_tau[s];
         for (int idx = tid; idx < nf * NB; idx += nt) {
             const int f = idx / NB, k = idx - f * NB;
             float* row = wk + (size_t)f * WS;
-            const float m = k < F0 ? src[f * rowmax + k] : 0.f;
+            float m = k < F0 ? src[f * rowmax + k] : 0.f;
             if (k < F0) row[L.wk_mask + k] = m;
+            if constexpr (PF) m = cruse_pf::post_filter(m, tau, pf_kind);       // (bin 160: pf(0) = 0, and the gain below is lim)
             const float gain = k < F0 ? fmaf(1.0f - lm, m, lm) : lm;
             dst[f * rowmax + k] = row[L.wk_re + k] * gain;
             dst[f * rowmax + NB + k] = row[L.wk_im + k] * gain;
         }
     } else {
+        [[maybe_unused]] float tau = 0.f;
+        if constexpr (PF) tau = pf_tau[s];
         for (int idx = tid; idx < nf * NB; idx += nt) {
             const int f = idx / NB, k = idx - f * NB;
             float* row = wk + (size_t)f * WS;
-            const float m = k < F0 ? src[f * rowmax + k] : 0.f;
+            float m = k < F0 ? src[f * rowmax + k] : 0.f;
             if (k < F0) row[L.wk_mask + k] = m;
+            if constexpr (PF) m = cruse_pf::post_filter(m, tau, pf_kind);       // (bin 160: pf(0) = 0)
             dst[f * rowmax + k] = row[L.wk_re + k] * m;
             dst[f * rowmax + NB + k] = row[L.wk_im + k] * m;
         }
@@ -783,13 +807,13 @@ int encode_any(const char* who, const char* name, const int* mode, int S, int c0
                              : launch_encode<float>(name, mode, S, L, lds, in, tab, w, state, work, stream);
 }
 
-template <typename OUT, bool LIM>
+template <typename OUT, bool LIM, bool PF>
 int launch_decode(const char* name, const int* mode, int S, const Layout& L, size_t lds, const float* tab, const float* w, float ln_eps,
-                  float* state, float* work, void* out, const float* lim, int* clip, void* stream) {
-    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_kernel<OUT, LIM>, lds, name);
+                  float* state, float* work, void* out, const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream) {
+    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_kernel<OUT, LIM, PF>, lds, name);
     if (rc) return rc;
-    hipLaunchKernelGGL((stream_decode_kernel<OUT, LIM>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, tab, w, ln_eps, state,
-                       work, (OUT*)out, lim, clip);
+    hipLaunchKernelGGL((stream_decode_kernel<OUT, LIM, PF>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, tab, w, ln_eps,
+                       state, work, (OUT*)out, lim, clip, pf_kind, pf_tau);
     CRUSE_LAUNCH_CHECK(name);
     return CRUSE_OK;
 }
@@ -803,17 +827,21 @@ int out_args(const char* who, int out_fmt, const int* clip) {
 }
 
 int decode_any(const char* who, const char* name, const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab,
-               const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip, void* stream) {
+               const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip, void* stream,
+               int pf_kind = 0, const float* pf_tau = nullptr) {
     Layout L;
     int rc = make_layout(c0, c1, c2, c3, c4, L);
     if (rc) return rc;
     CRUSE_REQUIRE(S > 0 && mode && tab && w && state && work && out, CRUSE_E_SHAPE, "%s: S = %d or a null buffer", who, S);
     rc = out_args(who, out_fmt, clip);
     if (rc) return rc;
+    const bool pf = pf_kind != 0;                         // the _pf entry points have refused kind 0 and a null pf_tau
     int n = 2 * NB + NFFT + FRAME_THREADS / 64;
     for (int k = 0; k < 5; ++k) n += L.ch[k] * L.F[k];
     const size_t lds = (size_t)n * sizeof(float);
-#define CRUSE_DECODE(OUT, LIM) launch_decode<OUT, LIM>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, stream)
+#define CRUSE_DECODE(OUT, LIM) \
+    (pf ? launch_decode<OUT, LIM, true>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, pf_kind, pf_tau, stream) \
+        : launch_decode<OUT, LIM, false>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, 0, nullptr, stream))
     if (out_fmt == FMT_S16) return lim ? CRUSE_DECODE(short, true) : CRUSE_DECODE(short, false);
     return lim ? CRUSE_DECODE(float, true) : CRUSE_DECODE(float, false);
 #undef CRUSE_DECODE
@@ -849,33 +877,38 @@ int encode_n_any(const char* who, const char* name, const int* pk, int S, int ho
                              : launch_encode_n<float>(name, pk, S, hops, in_hops, work_frames, L, in, tab, w, state, work, stream);
 }
 
-template <typename OUT, bool LIM>
+template <typename OUT, bool LIM, bool PF>
 int launch_decode_n(const char* name, const int* pk, int S, int hops, int out_hops, int NFW, const Layout& L, const float* tab, const float* w,
-                    float ln_eps, float* state, float* work, void* out, const float* lim, int* clip, void* stream) {
+                    float ln_eps, float* state, float* work, void* out, const float* lim, int* clip, int pf_kind, const float* pf_tau,
+                    void* stream) {
     const int rowmax = packet_row_max(L), wcap = packet_wcap(L), WS = packet_work_stride(L, nullptr);
     const size_t lds = (size_t)(2 * NFW * rowmax + wcap + 2 * NFW) * sizeof(float);
-    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_n_kernel<OUT, LIM>, lds, name);
+    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_n_kernel<OUT, LIM, PF>, lds, name);
     if (rc) return rc;
-    hipLaunchKernelGGL((stream_decode_n_kernel<OUT, LIM>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, out_hops, NFW, L,
-                       WS, rowmax, wcap, tab, w, ln_eps, state, work, (OUT*)out, lim, clip);
+    hipLaunchKernelGGL((stream_decode_n_kernel<OUT, LIM, PF>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, out_hops, NFW,
+                       L, WS, rowmax, wcap, tab, w, ln_eps, state, work, (OUT*)out, lim, clip, pf_kind, pf_tau);
     CRUSE_LAUNCH_CHECK(name);
     return CRUSE_OK;
 }
 
 int decode_n_any(const char* who, const char* name, const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2,
                  int c3, int c4, const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
-                 const float* lim, int* clip, void* stream) {
+                 const float* lim, int* clip, void* stream, int pf_kind = 0, const float* pf_tau = nullptr) {
     Layout L;
     int rc = make_layout(c0, c1, c2, c3, c4, L);
     if (rc) return rc;
     CRUSE_REQUIRE(pk && tab && w && state && work && out, CRUSE_E_SHAPE, "%s: null buffer", who);
+    const bool pf = pf_kind != 0;
     rc = packet_args(who, S, hops, work_frames, L);
     if (rc) return rc;
     CRUSE_REQUIRE(out_hops >= hops, CRUSE_E_SHAPE, "%s: out_hops = %d < hops = %d", who, out_hops, hops);
     rc = out_args(who, out_fmt, clip);
     if (rc) return rc;
-#define CRUSE_DECODE_N(OUT, LIM) \
-    launch_decode_n<OUT, LIM>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, stream)
+#define CRUSE_DECODE_N(OUT, LIM)                                                                                                              \
+    (pf ? launch_decode_n<OUT, LIM, true>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, pf_kind, \
+                                          pf_tau, stream)                                                                                    \
+        : launch_decode_n<OUT, LIM, false>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, 0,      \
+                                           nullptr, stream))
     if (out_fmt == FMT_S16) return lim ? CRUSE_DECODE_N(short, true) : CRUSE_DECODE_N(short, false);
     return lim ? CRUSE_DECODE_N(float, true) : CRUSE_DECODE_N(float, false);
 #undef CRUSE_DECODE_N
@@ -1192,6 +1225,23 @@ extern "C" int cruse_stream_decode_io(const int* mode, int S, int c0, int c1, in
                       lim, clip, stream);
 }
 
+// the perceptual post-filter in the gain line (utils/utils.py:345-362): the _io arguments plus the kind and the per-slot tau
+static int pf_args(const char* who, int pf_kind, const float* pf_tau) {
+    const int rc = cruse_pf::kind_args(who, pf_kind);
+    if (rc) return rc;
+    CRUSE_REQUIRE(pf_tau != nullptr, CRUSE_E_SHAPE, "%s: null pf_tau", who);
+    return CRUSE_OK;
+}
+
+extern "C" int cruse_stream_decode_pf(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
+                                      float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
+                                      int pf_kind, const float* pf_tau, void* stream) {
+    const int rc = pf_args("cruse_stream_decode_pf", pf_kind, pf_tau);
+    if (rc) return rc;
+    return decode_any("stream_decode_pf", "cruse_stream_decode_pf", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out, out_fmt,
+                      lim, clip, stream, pf_kind, pf_tau);
+}
+
 extern "C" int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4, int* out) {
     CRUSE_REQUIRE(out, CRUSE_E_SHAPE, "stream_packet_layout: null output");
     Layout L;
@@ -1246,4 +1296,13 @@ extern "C" int cruse_stream_decode_n_io(const int* pk, int S, int hops, int out_
                                         const float* lim, int* clip, void* stream) {
     return decode_n_any("stream_decode_n_io", "cruse_stream_decode_n_io", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w,
                         ln_eps, state, work, out, out_fmt, lim, clip, stream);
+}
+
+extern "C" int cruse_stream_decode_n_pf(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                                        const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
+                                        const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream) {
+    const int rc = pf_args("cruse_stream_decode_n_pf", pf_kind, pf_tau);
+    if (rc) return rc;
+    return decode_n_any("stream_decode_n_pf", "cruse_stream_decode_n_pf", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w,
+                        ln_eps, state, work, out, out_fmt, lim, clip, stream, pf_kind, pf_tau);
 }

@@ -42,11 +42,12 @@ def read_pairs(clean_list, noisy_list):
 @torch.no_grad()
 def evaluate_files(model, clean_list, noisy_list, metrics: Sequence[str] = ("SI_SDR", "STOI", "ESTOI"), batch_size: int = 16,
                    device="cuda", atten_lim_db=None, acoustics: Optional[dict] = None, head: str = "mask",
-                   df_dims=(1, 5)) -> Dict[str, object]:
+                   df_dims=(1, 5), post_filter=None, pf_tau: float = 0.02) -> Dict[str, object]:
     """Score `model` on the pairs (clean_list[i], noisy_list[i]); each list a list file (one WAV path per line, wavio.read_list) or a
     Python list of paths; 16-bit PCM at any rate, channel 0 of multi-channel files.  acoustics: the [acoustics] table of a config
     (n_fft, hop_length, win_length), the Inferencer's defaults without it.  head / df_dims: the Inferencer's ("df" for a model trained
-    with the DeepFilter loss, BASELINE config 4).
+    with the DeepFilter loss, BASELINE config 4).  post_filter / pf_tau: the Inferencer's ("iam" or "envelope": the perceptual post-filter
+    on the mask).
     -> {"names": the clean files' base names, "lengths": int64 [n] samples at 16 kHz,
         "scores": {metric: {"Noisy": f32 [n], "Enhanced": f32 [n]}}, "mean": {metric: {"Noisy": float, "Enhanced": float}}}, in LIST order.
     One read-back per batch."""
@@ -64,7 +65,7 @@ def evaluate_files(model, clean_list, noisy_list, metrics: Sequence[str] = ("SI_
     ac = acoustics or {}
     enhance = Inferencer(model, n_fft=ac.get("n_fft", 320), hop_length=ac.get("hop_length", 160),
                          win_length=ac.get("win_length", ac.get("n_fft", 320)), sr=SR, device=device, atten_lim_db=atten_lim_db,
-                         head=head, df_dims=df_dims)
+                         head=head, df_dims=df_dims, post_filter=post_filter, pf_tau=pf_tau)
     with torch.cuda.device(device):
         # one flat pool for both sides: one ragged resampler launch per distinct (rate, channels), int16 read in the kernel
         pool, start, lens, _ = load_pool(clean + noisy, device, SR, files=fc + fn)

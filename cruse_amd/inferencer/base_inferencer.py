@@ -10,6 +10,9 @@ mag * cos(phase) == mask * real: the phase is never formed (PreProcess.masking, 
 head="df" is for a model trained with the DeepFilter loss (BASELINE config 4, TrainEngine(loss="wo_male_df")): its output is the real
 part of a DeepFilter(t_dim, f_dim) filter field, and the enhanced spectrum is the neighbourhood sum of mask * N
 (loss.deepfilter_spectrum, one kernel) instead of mask * N itself.
+
+post_filter="iam" / "envelope" applies the reference's perceptual post-filter (utils/utils.py:345-362, ops.post_filter, one pointwise
+kernel) to the mask before it meets the spectrum; None (the default) launches nothing new.
 """
 from __future__ import annotations
 
@@ -27,10 +30,16 @@ HEADS = ("mask", "df")
 
 class Inferencer:
     def __init__(self, model: torch.nn.Module, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
-                 sr: int = 16000, device="cuda", atten_lim_db=None, head: str = "mask", df_dims=(1, 5)):
+                 sr: int = 16000, device="cuda", atten_lim_db=None, head: str = "mask", df_dims=(1, 5), post_filter=None,
+                 pf_tau: float = 0.02):
         from .. import ops
         if head not in HEADS:
             raise ValueError(f"Inferencer: head = {head!r}, expected one of {HEADS}")
+        if post_filter is not None:
+            ops.post_filter_kind(post_filter)
+            if head == "df":
+                raise ValueError("Inferencer(head=\"df\") takes no post_filter: the model's output is a filter field, not a gain")
+        self.post_filter, self.pf_tau = post_filter, ops.post_filter_tau(pf_tau)
         t_dim, f_dim = (int(d) for d in df_dims)
         if not (0 <= t_dim <= 8 and 0 <= f_dim <= 16):
             raise ValueError(f"Inferencer: df_dims = {tuple(df_dims)!r}, expected (t_dim in 0..8, f_dim in 0..16)")
@@ -51,6 +60,9 @@ class Inferencer:
         if self.head == "df":
             est = deepfilter_spectrum(mask, spec["real"].squeeze(1), spec["imag"].squeeze(1), *self.df_dims)
         else:
+            if self.post_filter is not None:
+                from .. import ops
+                mask = ops.post_filter(mask.contiguous(), self.pf_tau, self.post_filter)
             est = enhanced_spectrum(mask, spec["real"].squeeze(1), spec["imag"].squeeze(1))   # [B,T,F,2]
         wave = feature.istft_ri(est[..., 0], est[..., 1], self.n_fft, self.hop, length=noisy.shape[-1])
         if self.lim == 0.0:

@@ -76,17 +76,29 @@ class StreamingInferencer:
     On an instance with max_hops > 1 a push runs as a packet of one block: pushes and packets of any split then give one set of bits
     (the single-hop chain, which max_hops = 1 and every flush's end frame use, rounds its GRU sums differently).
     Only df_dims = (1, 5) is built, and head="df" needs io_rate = 16000.
+
+    post_filter = "iam" or "envelope" (default None: nothing changes): the reference's perceptual post-filter of the mask (postfiltering /
+    envelope_postfiltering, utils/utils.py:345-362; the closed forms and their two repairs: DESIGN 12e), applied inside the decode kernels
+    before the attenuation limit: gain = lim + (1 - lim) * pf(mask).  Every slot has a tau, set_post_filter(tau, slots), in the device
+    tensor `pf` [n_slots] (zeros: off, the plain server's output to the bit) that the kernels read, so a change is a copy into it and never
+    re-captures a graph; like a limit it belongs to the slot: reset() and flush() leave it alone.  push, push_packet, flush and enhance
+    honour it, with either precision, atten_lim, pcm_in / pcm_out and every io_rate; stage()["mask"] keeps the raw mask.  head="df" refuses
+    it: that model's output is a filter field, not a gain.
     """
 
     HOP = 160
 
     def __init__(self, model: torch.nn.Module, n_slots: int, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
                  device="cuda", use_graph: bool = True, max_hops: int = 1, precision: str = "f32", atten_lim: bool = False,
-                 pcm_in: bool = False, pcm_out: bool = False, io_rate: int = 16000, head: str = "mask", df_dims=(1, 5)):
+                 pcm_in: bool = False, pcm_out: bool = False, io_rate: int = 16000, head: str = "mask", df_dims=(1, 5),
+                 post_filter=None):
         from ..model.cruse_net import unet_2
         io_rate = resample.check_rate(io_rate)
         if head not in ("mask", "df"):
             raise ValueError(f"StreamingInferencer head must be \"mask\" or \"df\", got {head!r}")
+        pf_kind = None if post_filter is None else ops.post_filter_kind(post_filter)
+        if pf_kind is not None and head == "df":
+            raise ValueError("StreamingInferencer(head=\"df\") takes no post_filter: the model's output is a filter field, not a gain")
         if tuple(df_dims) != ops.STREAM_DF_DIMS:
             raise ValueError(f"StreamingInferencer streams the DeepFilter{ops.STREAM_DF_DIMS} head only (the one instance the kernels are "
                              f"built for), got df_dims = {tuple(df_dims)}")
@@ -150,6 +162,9 @@ class StreamingInferencer:
             self._mask_out = torch.zeros(S, self.HOP, device=dev)
             self._df_rows = np.zeros(S, dtype=np.int64)                         # E rows the slot's last call wrote
         self.lim = torch.zeros(S, device=dev) if self.atten_lim else None       # per-slot gains 10^(-dB/20); 0: no limit
+        self.post_filter = post_filter
+        self.pf = torch.zeros(S, device=dev) if pf_kind is not None else None   # per-slot tau of the post-filter; 0: off
+        self._pf_kind = pf_kind
         self.clip = torch.zeros(S, device=dev, dtype=torch.int32) if self.pcm_out else None     # clamped samples per slot
         self.mode = torch.zeros(2, S, device=dev, dtype=torch.int32)            # row 0: the frame-0 chain, row 1: the main chain
         self._mode_host = torch.zeros(2, S, dtype=torch.int32).pin_memory()
@@ -264,7 +279,8 @@ class StreamingInferencer:
             ops.stream_df_head(mode, self.work, self.lay, self.tab, self.df_state, self.df_work[:, 0], self.out, lim=self.lim, clip=self.clip)
             return
         ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out, lim=self.lim,
-                          clip=None if self._rs else self.clip)             # behind the converters, resample_out counts
+                          clip=None if self._rs else self.clip,             # behind the converters, resample_out counts
+                          pf=self._pf())
 
     def _replay(self, key, fn) -> None:
         """run fn(): directly, or as the graph captured from it on the first call with this key"""
@@ -415,6 +431,29 @@ class StreamingInferencer:
             idx = torch.tensor(slots, device=self.device, dtype=torch.long)
             self.lim.index_copy_(0, idx, torch.tensor(gains, dtype=torch.float32).to(self.device))
 
+    def _pf(self):
+        """the pf argument of the decode calls: None without a post-filter (the calls are then today's)"""
+        return None if self.pf is None else (self._pf_kind, self.pf)
+
+    @torch.no_grad()
+    def set_post_filter(self, tau, slots=None) -> None:
+        """The post-filter's tau of `slots` (None: all): a scalar for all of them, or one value per listed slot.  0: off (the slot's
+        output is the unfiltered one, to the bit); the reference's default is 0.02.  Takes effect with the next frame of the slot and
+        stays until it is set again (reset and flush keep it).  Needs post_filter="iam" or "envelope" at construction."""
+        if self.pf is None:
+            raise ValueError("set_post_filter: this StreamingInferencer was built without post_filter (its kernels read no tau)")
+        slots = self._slot_list(slots)
+        if np.ndim(tau) == 0:
+            vals = [tau] * len(slots)
+        else:
+            vals = list(tau.tolist() if torch.is_tensor(tau) or isinstance(tau, np.ndarray) else tau)
+            if len(vals) != len(slots):
+                raise ValueError(f"set_post_filter: {len(vals)} values for {len(slots)} slots")
+        vals = [ops.post_filter_tau(v) for v in vals]                           # refuses negative and NaN before anything is copied
+        if slots:
+            idx = torch.tensor(slots, device=self.device, dtype=torch.long)
+            self.pf.index_copy_(0, idx, torch.tensor(vals, dtype=torch.float32).to(self.device))
+
     @torch.no_grad()
     def clipped(self, slots=None, reset: bool = False) -> np.ndarray:
         """int64 host array: the output samples of each slot in `slots` (None: all) that were clamped to the int16 range since the
@@ -446,7 +485,7 @@ class StreamingInferencer:
             ops.stream_df_head_n(pk, hops, wk, self.lay, self.tab, self.df_state, self.df_pwork, self.pout, lim=self.lim, clip=self.clip)
             return
         ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout, lim=self.lim,
-                            clip=None if self._rs else self.clip)
+                            clip=None if self._rs else self.clip, pf=self._pf())
         if self._rs:
             ops.stream_resample_out_n(pk, hops, self.io_rate, self.pout, self.rs_taps, self.rs_state, self.io_pout, clip=self.clip)
 

@@ -1240,9 +1240,75 @@ def stream_gru(mode, layer, groups, Hg, x, x_off, hprev, h_off, pack, hout, o_of
              hprev.shape[1], h_off, _p(pack), *p16, _p(hout), hout.shape[1], o_off, _stream()))
 
 
-def stream_decode(mode, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None) -> None:
+# the perceptual post-filter (cruse_mask_postfilter, cruse_stream_decode_pf / _n_pf; the reference's utils/utils.py:345-362)
+POST_FILTER_KINDS = {"iam": 1, "envelope": 2}
+
+
+def post_filter_kind(kind) -> int:
+    """the pf_kind of the header for "iam" / "envelope"; anything else raises ValueError"""
+    if kind not in POST_FILTER_KINDS:
+        raise ValueError(f"post-filter kind must be one of {tuple(POST_FILTER_KINDS)}, got {kind!r}")
+    return POST_FILTER_KINDS[kind]
+
+
+def post_filter_tau(tau) -> float:
+    """tau as a float; negative or NaN raises ValueError (0: the filter is off)"""
+    tau = float(tau)
+    if tau != tau or tau < 0.0 or tau == float("inf"):
+        raise ValueError(f"post-filter tau must be a finite non-negative number, got {tau}")
+    return tau
+
+
+def post_filter(mask: torch.Tensor, tau=0.02, kind: str = "iam", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's postfiltering ("iam", utils/utils.py:345-349) / envelope_postfiltering ("envelope", :352-362) of a mask with values
+    in [0, 1], in closed form, one pointwise kernel: float32, contiguous, any shape.  tau: a number (checked: >= 0), or a
+    float32 device tensor [B] for a mask [B, ...] (one tau per clip; its values must be >= 0, which is not checked: no synchronisation).
+    tau == 0 returns the mask's bits.  out: a contiguous float32 tensor of the mask's shape to write (it may be the mask).
+    Inference only: a mask that requires grad raises."""
+    k = post_filter_kind(kind)
+    if mask.requires_grad:
+        raise RuntimeError("post_filter is inference-only (no backward kernel): the mask requires grad")
+    if mask.dtype != torch.float32 or not mask.is_contiguous() or mask.numel() < 1:
+        raise RuntimeError(f"post_filter: mask must be a non-empty contiguous float32 tensor, got {mask.dtype} {tuple(mask.shape)}")
+    if torch.is_tensor(tau):
+        if tau.dtype != torch.float32 or tau.device != mask.device or tau.dim() != 1 or not tau.is_contiguous() or mask.dim() < 1 \
+                or tau.numel() != mask.shape[0]:
+            raise RuntimeError(f"post_filter: a tensor tau must be float32 [{mask.shape[0] if mask.dim() else 1}] on the mask's device, got "
+                               f"{tau.dtype} {tuple(tau.shape)} on {tau.device}")
+        F = mask.numel() // mask.shape[0]
+        rows, per = mask.shape[0], 1
+        if F < 1:
+            raise RuntimeError(f"post_filter: empty mask {tuple(mask.shape)}")
+    else:
+        tau = torch.full((1,), post_filter_tau(tau), dtype=torch.float32, device=mask.device)
+        rows, F, per = 1, mask.numel(), 0
+    if out is None:
+        out = torch.empty_like(mask)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != mask.shape or out.device != mask.device:
+        raise RuntimeError(f"post_filter: out must be contiguous float32 {tuple(mask.shape)} on the mask's device, got {out.dtype} "
+                           f"{tuple(out.shape)}")
+    check(lib.cruse_mask_postfilter(k, _p(mask), rows, F, _p(tau), per, _p(out), _stream()))
+    return out
+
+
+def _stream_pf(pf, out: torch.Tensor, name: str):
+    """(pf_kind, pf_tau) of a decode call from pf = (kind, tau [S] f32)"""
+    kind, tau = pf
+    if tau.dtype != torch.float32 or tau.numel() != out.shape[0] or not tau.is_contiguous():
+        raise RuntimeError(f"{name}: pf tau must be float32 with one entry per slot ({out.shape[0]}), got {tau.dtype} x {tau.numel()}")
+    return int(kind), _p(tau)
+
+
+def stream_decode(mode, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None, pf=None) -> None:
     """out [S, 160]: float32, or int16 PCM (clamp(rint(y * 32768))); lim [S] f32: per-slot attenuation-limit gains (atten_lim_gain);
-    clip [S] int32: += the clamped samples per slot (int16 out only).  Any of them selects cruse_stream_decode_io."""
+    clip [S] int32: += the clamped samples per slot (int16 out only).  Any of them selects cruse_stream_decode_io.
+    pf = (pf_kind, tau [S] f32): the perceptual post-filter on the mask before the limit (cruse_stream_decode_pf)."""
+    if pf is not None:
+        fmt = _stream_fmt(out, "stream_decode")
+        io = _stream_io(out, lim, clip, "stream_decode") or (fmt, None, None)
+        check(lib.cruse_stream_decode_pf(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state),
+                                         _p(work), _p(out), *io, *_stream_pf(pf, out, "stream_decode"), _stream()))
+        return
     io = _stream_io(out, lim, clip, "stream_decode")
     if io is None:
         check(lib.cruse_stream_decode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state), _p(work),
@@ -1286,8 +1352,16 @@ def stream_gru_rec_n(pk, hops, frame, groups, Hg, gi, state, st_off, pack, work,
              *p16, _p(work), work.shape[2], h_off, _stream()))
 
 
-def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None) -> None:
-    """out [S, out_hops, 160]: float32 or int16 PCM; lim / clip as stream_decode (cruse_stream_decode_n_io)"""
+def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None, pf=None) -> None:
+    """out [S, out_hops, 160]: float32 or int16 PCM; lim / clip as stream_decode (cruse_stream_decode_n_io); pf as stream_decode
+    (cruse_stream_decode_n_pf)"""
+    if pf is not None:
+        fmt = _stream_fmt(out, "stream_decode_n")
+        io = _stream_io(out, lim, clip, "stream_decode_n") or (fmt, None, None)
+        check(lib.cruse_stream_decode_n_pf(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab),
+                                           _p(w), float(ln_eps), _p(state), _p(work), _p(out), *io,
+                                           *_stream_pf(pf, out, "stream_decode_n"), _stream()))
+        return
     io = _stream_io(out, lim, clip, "stream_decode_n")
     if io is None:
         check(lib.cruse_stream_decode_n(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab), _p(w),

@@ -921,6 +921,32 @@ int cruse_stream_decode_n_io(const int* pk, int S, int hops, int out_hops, int w
                              const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
                              const float* lim, int* clip, void* stream);
 
+/* ---- the perceptual post-filter (additive; every entry point above is unchanged and launches the same kernels with the same
+ * arguments) ------------------------------------------------------------------------------------------------------------------------
+ * The reference's numpy post-filters of a mask value g in [0, 1] (utils/utils.py:345-362), in closed form; s = sin(pi g / 2), tau >= 0:
+ *   pf_kind 1, "iam"      (postfiltering, utils/utils.py:345-349):           pf = g (1 + tau) s^2 / (s^2 + tau)
+ *   pf_kind 2, "envelope" (envelope_postfiltering, utils/utils.py:352-362):  pf = g s sqrt((1 + tau) s / (s^2 + tau))
+ * pf(0) = 0 (the reference's "iam" form is 0 / 0 there), pf(1) = 1; the "envelope" form's eps term, its only use of the unprocessed
+ * magnitude, is dropped.  tau == 0 is a bypass: pf = g to the bit.
+ * cruse_stream_decode_pf / _n_pf (utils/utils.py:345-362): the _io sibling's arguments plus pf_kind and pf_tau[S] (device; the slot's
+ * tau, 0: off).  The gain of bins 0..159 is pf(mask) without a limit and fmaf(1 - lim, pf(mask), lim) with one (DeepFilterNet's order);
+ * bin 160 as in the sibling; the mask row of the work buffer keeps the model's mask.  With every pf_tau 0 the output is the sibling's.
+ * Refused with CRUSE_E_SHAPE before any launch: what the sibling refuses, pf_kind outside {1, 2}, a null pf_tau. */
+int cruse_stream_decode_pf(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
+                           float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
+                           int pf_kind, const float* pf_tau, void* stream);
+int cruse_stream_decode_n_pf(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                             const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
+                             const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream);
+/* the same function on a whole mask tensor (utils/utils.py:345-362), one pointwise launch: out[r][f] = pf(mask[r][f], tau[r /
+ * rows_per_tau]) for r < rows, f < F; rows_per_tau = 0: tau[0] serves every row (a scalar tau), else tau holds ceil(rows /
+ * rows_per_tau) values (a [B,1,T,F] mask with a tau per clip: rows = B * T, rows_per_tau = T).  tau is device memory; its values must
+ * be >= 0 (not checked: the call does not synchronise).  out may be mask.  16-byte accesses where mask and out are 16-byte aligned,
+ * scalar over the last rows * F % 4 elements and everywhere else; deterministic, capturable.  Refused with CRUSE_E_SHAPE before the
+ * launch: kind outside {1, 2}, rows < 1, F < 1, rows_per_tau outside [0, rows], a null pointer. */
+int cruse_mask_postfilter(int kind, const float* mask, long long rows, long long F, const float* tau, long long rows_per_tau,
+                          float* out, void* stream);
+
 /* ---- f16-operand MFMA GRU of the streaming chains (additive; rows, mode / pk semantics and the f32 pack are those above, so these
  * may replace their f32 counterparts call by call) ------------------------------------------------------------------------------
  * pack16 (device, f16): the layer's weights as MFMA A fragments, [W_ih | W_hh][g][gate r,z,n][UT][KS][64 lanes][8], UT =

@@ -1,7 +1,8 @@
 """Score a checkpoint on a list of paired WAV files (cruse_amd.evaluate.evaluate_files):
 
     python tools/evaluate.py --config cfg.toml --checkpoint runs/cfg/checkpoints/best_model.tar \\
-        --clean-list clean.txt --noisy-list noisy.txt [--batch-size 16] [--metrics SI_SDR STOI ESTOI SDR] [--head df] [--csv scores.csv]
+        --clean-list clean.txt --noisy-list noisy.txt [--batch-size 16] [--metrics SI_SDR STOI ESTOI SDR] [--head df] [--post-filter iam] [--pf-tau 0.02]
+        [--csv scores.csv]
 
 The model is built from the config's [model] section as tools/train_stand.py builds it; the checkpoint is a *.tar of the trainer
 (its "model" entry) or a bare state dict (model_NNNN.pth).  Prints one line per metric with the Noisy and Enhanced means."""
@@ -29,6 +30,9 @@ def main(argv=None):
     parser.add_argument("--head", choices=["mask", "df"], default="mask",
                         help="How the network output is applied: mask (magnitude mask) or df (DeepFilter(1, 5) head: a model trained "
                              "with wo_male_df_loss, configs/cruse_deepfilter.toml).")
+    parser.add_argument("--post-filter", choices=["iam", "envelope"], default=None,
+                        help="The reference's perceptual post-filter on the mask (postfiltering / envelope_postfiltering); off by default.")
+    parser.add_argument("--pf-tau", type=float, default=0.02, help="The post-filter's tau (the reference's default 0.02).")
     parser.add_argument("--csv", help="Write the per-file table here.")
     args = parser.parse_args(argv)
     from cruse_amd.evaluate import evaluate_files
@@ -37,7 +41,7 @@ def main(argv=None):
     ck = torch.load(os.path.abspath(os.path.expanduser(args.checkpoint)), map_location="cpu", weights_only=False)
     model.load_state_dict(ck["model"] if "model" in ck else ck)
     res = evaluate_files(model, args.clean_list, args.noisy_list, metrics=args.metrics, batch_size=args.batch_size,
-                         acoustics=config.get("acoustics"), head=args.head)
+                         acoustics=config.get("acoustics"), head=args.head, post_filter=args.post_filter, pf_tau=args.pf_tau)
     for name, m in res["mean"].items():
         print(f"{name}: Noisy {m['Noisy']!r}  Enhanced {m['Enhanced']!r}")
     if args.csv:

@@ -24,8 +24,13 @@ With --head mask,df every (n_slots, hops) cell is measured for both heads of Str
 each, in alternating slices of the measuring time; every row carries "head", the df row "vs_mask" (p50 wall time per hop over the mask
 row's) and "device_vs_mask" (profiles/stream_df_rtf.json).
 
+With --post-filter none,iam every (n_slots, hops) cell is measured with and without the perceptual post-filter in one
+run, in the style of --head: one instance each (the filtered one with every slot's tau = --pf-tau, default 0.02), alternating slices;
+every row carries "post_filter", the filtered rows "vs_none" and "device_vs_none".
+
     python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--precision f32,f16] [--pcm]
-                               [--atten-lim DB] [--io-rate 16000,8000,48000] [--head mask,df] [--out FILE]
+                               [--atten-lim DB] [--io-rate 16000,8000,48000] [--head mask,df]
+                               [--post-filter none,iam] [--pf-tau 0.02] [--out FILE]
 """
 from __future__ import annotations
 
@@ -131,11 +136,22 @@ def measure_packets(model, S: int, hops: int, seconds: float, precision: str = "
             "device_us_per_hop": r(d.mean() / hops), "rtf": round(float(w.mean()) / (10000.0 * hops), 5)}
 
 
-def measure_heads(model, S: int, hops: int, seconds: float, heads, precision: str = "f32", rounds: int = 8):
+def _variant(model, S, precision, hops, key, h, pf_tau):
+    """the instance of one side-by-side variant: a head, or a post-filter setting ("none": the plain server)"""
+    if key == "head":
+        return _inferencer(model, S, precision, max_hops=hops, head=h)
+    inf = _inferencer(model, S, precision, max_hops=hops, post_filter=None if h == "none" else h)
+    if h != "none":
+        inf.set_post_filter(pf_tau)
+    return inf
+
+
+def measure_heads(model, S: int, hops: int, seconds: float, heads, precision: str = "f32", rounds: int = 8, key: str = "head",
+                  base_name: str = "mask", pf_tau: float = 0.02):
     """one (n_slots, hops) cell for every head in `heads`, side by side: one instance per head, measured in `rounds` alternating slices of
     seconds / rounds each, so that clock and machine drift hit both alike.  Rows as measure_packets, plus "head" and, on the "df" row,
-    "vs_mask" = its wall time per hop over the mask row's."""
-    infs = {h: _inferencer(model, S, precision, max_hops=hops, head=h) for h in heads}
+    "vs_mask" = its wall time per hop over the mask row's.  key = "post_filter", base_name = "none": the same for the post-filter settings."""
+    infs = {h: _variant(model, S, precision, hops, key, h, pf_tau) for h in heads}
     blocks = _blocks(S, hops, 160)
     calls = {h: ((lambda i=i: i.push(blocks[:, 0])) if hops == 1 else (lambda i=i: i.push_packet(blocks))) for h, i in infs.items()}
     for call in calls.values():
@@ -160,14 +176,14 @@ def measure_heads(model, S: int, hops: int, seconds: float, heads, precision: st
     rows = []
     for h in heads:
         w, d = np.array(walls[h]) * 1e6, np.array(devs[h]) * 1e6
-        rows.append({"n_slots": S, "hops": hops, "head": h, "path": "push" if hops == 1 else "push_packet", "calls": len(w),
+        rows.append({"n_slots": S, "hops": hops, key: h, "path": "push" if hops == 1 else "push_packet", "calls": len(w),
                      "wall_us_per_hop": {"mean": r(w.mean() / hops), "p50": r(np.median(w) / hops), "p99": r(np.percentile(w, 99) / hops)},
                      "device_us_per_hop": r(d.mean() / hops), "rtf": round(float(w.mean()) / (10000.0 * hops), 5)})
-    base = {row["head"]: row for row in rows}.get("mask")
+    base = {row[key]: row for row in rows}.get(base_name)
     for row in rows:
-        if base is not None and row["head"] != "mask":
-            row["vs_mask"] = round(row["wall_us_per_hop"]["p50"] / base["wall_us_per_hop"]["p50"], 3)
-            row["device_vs_mask"] = round(row["device_us_per_hop"] / base["device_us_per_hop"], 3)
+        if base is not None and row[key] != base_name:
+            row[f"vs_{base_name}"] = round(row["wall_us_per_hop"]["p50"] / base["wall_us_per_hop"]["p50"], 3)
+            row[f"device_vs_{base_name}"] = round(row["device_us_per_hop"] / base["device_us_per_hop"], 3)
     return rows
 
 
@@ -182,6 +198,8 @@ def main():
     ap.add_argument("--atten-lim", type=float, default=None, metavar="DB", help="every slot limited to DB dB of attenuation (atten_lim = True)")
     ap.add_argument("--io-rate", default=None, help="comma-separated I/O sample rates (8000, 16000, 32000, 48000): measure every cell at each")
     ap.add_argument("--head", default=None, help="mask, df or mask,df: the heads to measure side by side, alternating, in every cell")
+    ap.add_argument("--post-filter", default=None, help="none, iam, envelope or a list (none,iam): measured side by side like --head")
+    ap.add_argument("--pf-tau", type=float, default=0.02, help="tau of every slot of the post-filter instances")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()
     IO.update(pcm=a.pcm, atten_lim=a.atten_lim)
@@ -196,13 +214,21 @@ def main():
         ap.error(f"--precision takes f32, f16 or f32,f16, got {a.precision}")
     rows = []
     heads = None if a.head is None else a.head.split(",")
+    side = dict(key="head", base_name="mask")
+    if a.post_filter is not None:
+        if heads is not None:
+            ap.error("--head and --post-filter are measured in runs of their own")
+        heads = a.post_filter.split(",")
+        if any(h not in ("none", "iam", "envelope") for h in heads):
+            ap.error(f"--post-filter takes none, iam, envelope or a list of them, got {a.post_filter}")
+        side = dict(key="post_filter", base_name="none", pf_tau=a.pf_tau)
+    elif heads is not None and any(h not in ("mask", "df") for h in heads):
+        ap.error(f"--head takes mask, df or mask,df, got {a.head}")
     if heads is not None:
-        if any(h not in ("mask", "df") for h in heads):
-            ap.error(f"--head takes mask, df or mask,df, got {a.head}")
         for prec in precs:
             for s in a.slots.split(","):
                 for h in (a.hops or "1").split(","):
-                    part = measure_heads(m, int(s), int(h), a.seconds, heads, prec)
+                    part = measure_heads(m, int(s), int(h), a.seconds, heads, prec, **side)
                     for r in part:
                         if precs != ["f32"]:
                             r["precision"] = prec
