@@ -78,17 +78,27 @@ __device__ __forceinline__ void fft320(float (&xr)[5], float (&xi)[5], const flo
     }
 }
 
+// INVERSE = false: the analysis window as 0.5 - 0.5 cos(2 pi n / N), the bits the forward STFT has always used.
+// INVERSE = true (iSTFT and its adjoint): the same window as sin^2(pi n / N), the argument folded to n <= N/2.  The difference form is
+// off by 1e-4 relative next to n = 0 and n = N - 1, and the inverse divides by the window there: at a clip's last samples, which only the
+// last frame covers, and wherever frames do not overlap.
+template <bool INVERSE>
 __device__ __forceinline__ void init_tables(float* win, float2* tw, int tid, int nthreads) {
     for (int n = tid; n < NFFT; n += nthreads) {
         float s, c;
         sincospif((float)n / 160.0f, &s, &c);
         tw[n] = make_float2(c, s);
-        win[n] = 0.5f - 0.5f * c;          // periodic Hann: 0.5 - 0.5 cos(2 pi n / N)
+        if (INVERSE) {
+            const float h = sinpif((float)(n <= NFFT / 2 ? n : NFFT - n) / (float)NFFT);
+            win[n] = h * h;
+        } else {
+            win[n] = 0.5f - 0.5f * c;      // periodic Hann: 0.5 - 0.5 cos(2 pi n / N)
+        }
     }
 }
 
 // MODE 0: STFT (reflect padding).  MODE 1: adjoint of iSTFT (input = dwave, zero padding,
-// pre-divided by the window-square envelope, outputs scaled by c_k / N).
+// pre-divided by the window-square envelope -- 0 where istft320_kernel writes 0, envelope <= 1e-11 --, outputs scaled by c_k / N).
 template <int MODE>
 __global__ __launch_bounds__(256) void stft320_kernel(const float* __restrict__ wave, int B, int L, int hop, int T,
                                                       float* re, float* im, float* mag, int mag_bins, float mag_eps) {
@@ -101,7 +111,7 @@ __global__ __launch_bounds__(256) void stft320_kernel(const float* __restrict__ 
     const int b = blockIdx.x / ntile;
     const int t0 = (blockIdx.x % ntile) * FPB;
     const int nf = min(FPB, T - t0);
-    init_tables(s_win, s_tw, tid, 256);
+    init_tables<MODE == 1>(s_win, s_tw, tid, 256);
     __syncthreads();
     const int span = (nf - 1) * hop + NFFT;
     const int p0 = t0 * hop;
@@ -119,7 +129,7 @@ __global__ __launch_bounds__(256) void stft320_kernel(const float* __restrict__ 
                 float env = 0.f;
                 const int tlo = max(0, (p - NFFT + hop) / hop), thi = min(T - 1, p / hop);
                 for (int t = tlo; t <= thi; ++t) { const float w = s_win[p - t * hop]; env += w * w; }
-                v = wave[(long long)b * L + o] / env;
+                v = env > 1e-11f ? wave[(long long)b * L + o] / env : 0.f;      // the forward's rule: that sample is 0 for any spectrum
             }
         }
         s_x[i] = v;
@@ -178,7 +188,7 @@ __global__ __launch_bounds__(256) void istft320_kernel(const float* __restrict__
     const int b = blockIdx.x / ntile;
     const int s0 = NFFT / 2 + (blockIdx.x % ntile) * TS;  // first padded sample of this tile
     const int s1 = min(s0 + TS, total);
-    init_tables(s_win, s_tw, tid, 256);
+    init_tables<true>(s_win, s_tw, tid, 256);
     for (int i = tid; i < TS; i += 256) { s_y[i] = 0.f; s_w[i] = 0.f; }
     __syncthreads();
     // frames t with [t*hop, t*hop+NFFT) intersecting [s0, s1)
@@ -286,6 +296,7 @@ extern "C" int cruse_istft_bwd(const float* dwave, int B, int T, int n_fft, int 
                                float* dre, float* dim, void* stream) {
     CRUSE_REQUIRE(B > 0 && T > 0 && L > 0, CRUSE_E_SHAPE, "istft_bwd: bad shape");
     CRUSE_REQUIRE(n_fft == NFFT && hop > 0 && hop <= NFFT, CRUSE_E_SHAPE, "istft_bwd: only n_fft=320, hop<=320");
+    CRUSE_REQUIRE(L <= n_fft + hop * (T - 1) - n_fft / 2, CRUSE_E_SHAPE, "istft: length %d exceeds the %d frames", L, T);
     hipLaunchKernelGGL(stft320_kernel<1>, dim3(B * cdiv(T, FPB)), dim3(256), 0, (hipStream_t)stream, dwave, B, L, hop, T,
                        dre, dim, (float*)nullptr, 0, 0.f);
     CRUSE_LAUNCH_CHECK("istft_bwd");

@@ -86,7 +86,9 @@ int cruse_stft_fwd(const float* wave, int B, int L, int n_fft, int hop,
  * at feature.py:53-61 / utils/utils.py:448-454.  re, im [B,T,n_fft/2+1] -> wave [B,L]. */
 int cruse_istft_fwd(const float* re, const float* im, int B, int T, int n_fft, int hop, int L,
                     float* wave, void* stream);
-/* adjoint of cruse_istft_fwd: dwave [B,L] -> dre, dim [B,T,n_fft/2+1] */
+/* adjoint of cruse_istft_fwd: dwave [B,L] -> dre, dim [B,T,n_fft/2+1].  A sample whose window-square envelope is <= 1e-11 (every sample
+ * hop * t at hop = n_fft, where the Hann window is 0) is 0 in the forward for any spectrum and so contributes 0 here: the outputs are
+ * finite.  L > hop * (T - 1) + n_fft/2 is refused (CRUSE_E_SHAPE) as the forward refuses it.  dim of bins 0 and n_fft/2 is 0. */
 int cruse_istft_bwd(const float* dwave, int B, int T, int n_fft, int hop, int L,
                     float* dre, float* dim, void* stream);
 
