@@ -156,6 +156,8 @@ SIGNATURES = {
     "cruse_stream_decode_n_io": ("piiiiiiiiippfpppippp", "i"),
     "cruse_stream_decode_pf": ("piiiiiippfpppippipp", "i"),
     "cruse_stream_decode_n_pf": ("piiiiiiiiippfpppippipp", "i"),
+    "cruse_stream_decode_up": ("piiiiiippfpppippipp", "i"),
+    "cruse_stream_decode_n_up": ("piiiiiiiiippfpppippipp", "i"),
     "cruse_mask_postfilter": ("ipqqpqpp", "i"),
     "cruse_stream_resample_in": ("piipippipp", "i"),
     "cruse_stream_resample_out": ("piipppipipp", "i"),

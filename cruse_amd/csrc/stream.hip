@@ -182,6 +182,41 @@ __device__ __forceinline__ void dec_convt(const float* __restrict__ W, const flo
     }
 }
 
+// nearest x2 FreqUpsample + Conv2d (1,3), padding (0,1) (cust_conv.py:163-166,177-184): [Cin][Fin] -> [Cout][2*Fin]; W packed
+// [Cout][Cin][3], the Conv2d order (BN folded).  With u[i] = in[i >> 1] the taps of column fo are u[fo-1], u[fo], u[fo+1]: rows
+// (j-1, j, j) of `in` for fo = 2j and (j, j, j+1) for fo = 2j+1; u[-1] and u[2*Fin] are the zero padding.  Three FMAs per input
+// channel in tap order, the order of the conv on the upsampled row.  act as dec_convt
+__device__ __forceinline__ void dec_upconv(const float* __restrict__ W, const float* __restrict__ b, const float* src, float* dst, int fs,
+                                           const float* __restrict__ add, size_t as,
+                                           int nf, int Cin, int Fin, int Cout, int act) {
+    const int Fout = 2 * Fin, per = Cout * Fout;
+    for (int idx = threadIdx.x; idx < nf * per; idx += blockDim.x) {
+        const int f = nf == 1 ? 0 : idx / per, r = idx - f * per, co = r / Fout, fo = r - co * Fout;
+        const float* in = src + f * fs;
+        const float* w = W + co * Cin * 3;
+        const bool left = fo >= 1, right = fo + 1 < Fout;
+        const int lo = left ? (fo - 1) >> 1 : 0, mid = fo >> 1, hi = right ? (fo + 1) >> 1 : 0;
+        float acc = b[co];
+        for (int ci = 0; ci < Cin; ++ci) {
+            const float* x = in + ci * Fin;
+            if (left) acc = fmaf(w[ci * 3 + 0], x[lo], acc);
+            acc = fmaf(w[ci * 3 + 1], x[mid], acc);
+            if (right) acc = fmaf(w[ci * 3 + 2], x[hi], acc);
+        }
+        dst[f * fs + r] = act == 0 ? fmaxf(acc, 0.f) + add[f * as + r] : 1.0f / (1.0f + expf(-acc));
+    }
+}
+
+// the decoder of the decode kernels: the ConvTranspose levels of unet_2 or the upsample levels of CRUSE4MagAddSkipUpsample
+enum { DEC_CONVT = 0, DEC_UPCONV = 1 };
+
+template <int DEC>
+__device__ __forceinline__ void dec_level(const float* __restrict__ W, const float* __restrict__ b, const float* src, float* dst, int fs,
+                                          const float* __restrict__ add, size_t as, int nf, int Cin, int Fin, int Cout, int act) {
+    if constexpr (DEC == DEC_UPCONV) dec_upconv(W, b, src, dst, fs, add, as, nf, Cin, Fin, Cout, act);
+    else dec_convt(W, b, src, dst, fs, add, as, nf, Cin, Fin, Cout, act);
+}
+
 // tables: [0,320) periodic Hann, [320,640) cos(2 pi j / 320), [640,960) sin(2 pi j / 320), [960,1120) 1 / (w^2(m) + w^2(m+160))
 constexpr int TB_WIN = 0, TB_COS = 320, TB_SIN = 640, TB_IENV = 960, TB_TOTAL = 1120;
 
@@ -415,7 +450,8 @@ __global__ void __launch_bounds__(256) stream_gru_f32_kernel(GruArgs a) {
 // clip[s] (PCM out, may be null): the count of clamped samples
 // pf_tau[s], pf_kind (PF): the slot's perceptual post-filter (postfilter.h), applied to the mask value before the limit's mix:
 // gain = lim + (1 - lim) * pf(mask); pf_tau[s] == 0 is the bypass.  The wk_mask row keeps the raw mask.  PF = false reads neither.
-template <typename OUT, bool LIM, bool PF>
+// DEC: the decoder's four levels (dec_level); everything around them is the same code for both kinds.
+template <int DEC, typename OUT, bool LIM, bool PF>
 __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restrict__ mode, Layout L, const float* __restrict__ tab,
                                                             const float* __restrict__ w, float ln_eps, float* __restrict__ state,
                                                             float* __restrict__ work, OUT* __restrict__ out,
@@ -453,8 +489,8 @@ __global__ void __launch_bounds__(1024) stream_decode_kernel(const int* __restri
     }
     __syncthreads();
     for (int k = 4; k >= 1; --k) {
-        dec_convt(w + L.decW[k], w + L.decB[k], row[k], row[k - 1], 0, k > 1 ? wk + L.wk_skip[k - 1] : nullptr, 0, 1, L.ch[k], L.F[k],
-                  L.ch[k - 1], k > 1 ? 0 : 1);
+        dec_level<DEC>(w + L.decW[k], w + L.decB[k], row[k], row[k - 1], 0, k > 1 ? wk + L.wk_skip[k - 1] : nullptr, 0, 1, L.ch[k], L.F[k],
+                       L.ch[k - 1], k > 1 ? 0 : 1);
         __syncthreads();
     }
     // mask on bins 0..159 (bin 160 zero), 320-point inverse real DFT (imaginary parts of bins 0 and 160 ignored, as irfft)
@@ -654,7 +690,7 @@ __global__ void __launch_bounds__(1024) stream_encode_n_kernel(const int* __rest
     }
 }
 
-template <typename OUT, bool LIM, bool PF>
+template <int DEC, typename OUT, bool LIM, bool PF>
 __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __restrict__ pk, int S, int hops, int out_hops, int NFW,
                                                               Layout L, int WS, int rowmax, int wcap, const float* __restrict__ tab,
                                                               const float* __restrict__ w, float ln_eps, float* __restrict__ state,
@@ -704,7 +740,8 @@ __global__ void __launch_bounds__(1024) stream_decode_n_kernel(const int* __rest
         for (int i = tid; i < nwf; i += nt) Wb[i] = w[L.decW[k] + i];
         for (int i = tid; i < L.ch[k - 1]; i += nt) Wb[nwf + i] = w[L.decB[k] + i];
         __syncthreads();
-        dec_convt(Wb, Wb + nwf, src, dst, rowmax, wk + (k > 1 ? L.wk_skip[k - 1] : 0), WS, nf, L.ch[k], L.F[k], L.ch[k - 1], k > 1 ? 0 : 1);
+        dec_level<DEC>(Wb, Wb + nwf, src, dst, rowmax, wk + (k > 1 ? L.wk_skip[k - 1] : 0), WS, nf, L.ch[k], L.F[k], L.ch[k - 1],
+                       k > 1 ? 0 : 1);
         __syncthreads();
         float* t = src; src = dst; dst = t;
     }
@@ -807,13 +844,13 @@ int encode_any(const char* who, const char* name, const int* mode, int S, int c0
                              : launch_encode<float>(name, mode, S, L, lds, in, tab, w, state, work, stream);
 }
 
-template <typename OUT, bool LIM, bool PF>
+template <int DEC, typename OUT, bool LIM, bool PF>
 int launch_decode(const char* name, const int* mode, int S, const Layout& L, size_t lds, const float* tab, const float* w, float ln_eps,
                   float* state, float* work, void* out, const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream) {
-    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_kernel<OUT, LIM, PF>, lds, name);
+    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_kernel<DEC, OUT, LIM, PF>, lds, name);
     if (rc) return rc;
-    hipLaunchKernelGGL((stream_decode_kernel<OUT, LIM, PF>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, tab, w, ln_eps,
-                       state, work, (OUT*)out, lim, clip, pf_kind, pf_tau);
+    hipLaunchKernelGGL((stream_decode_kernel<DEC, OUT, LIM, PF>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, tab, w,
+                       ln_eps, state, work, (OUT*)out, lim, clip, pf_kind, pf_tau);
     CRUSE_LAUNCH_CHECK(name);
     return CRUSE_OK;
 }
@@ -826,6 +863,7 @@ int out_args(const char* who, int out_fmt, const int* clip) {
     return CRUSE_OK;
 }
 
+template <int DEC>
 int decode_any(const char* who, const char* name, const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab,
                const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip, void* stream,
                int pf_kind = 0, const float* pf_tau = nullptr) {
@@ -840,8 +878,8 @@ int decode_any(const char* who, const char* name, const int* mode, int S, int c0
     for (int k = 0; k < 5; ++k) n += L.ch[k] * L.F[k];
     const size_t lds = (size_t)n * sizeof(float);
 #define CRUSE_DECODE(OUT, LIM) \
-    (pf ? launch_decode<OUT, LIM, true>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, pf_kind, pf_tau, stream) \
-        : launch_decode<OUT, LIM, false>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, 0, nullptr, stream))
+    (pf ? launch_decode<DEC, OUT, LIM, true>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, pf_kind, pf_tau, stream) \
+        : launch_decode<DEC, OUT, LIM, false>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, 0, nullptr, stream))
     if (out_fmt == FMT_S16) return lim ? CRUSE_DECODE(short, true) : CRUSE_DECODE(short, false);
     return lim ? CRUSE_DECODE(float, true) : CRUSE_DECODE(float, false);
 #undef CRUSE_DECODE
@@ -877,20 +915,21 @@ int encode_n_any(const char* who, const char* name, const int* pk, int S, int ho
                              : launch_encode_n<float>(name, pk, S, hops, in_hops, work_frames, L, in, tab, w, state, work, stream);
 }
 
-template <typename OUT, bool LIM, bool PF>
+template <int DEC, typename OUT, bool LIM, bool PF>
 int launch_decode_n(const char* name, const int* pk, int S, int hops, int out_hops, int NFW, const Layout& L, const float* tab, const float* w,
                     float ln_eps, float* state, float* work, void* out, const float* lim, int* clip, int pf_kind, const float* pf_tau,
                     void* stream) {
     const int rowmax = packet_row_max(L), wcap = packet_wcap(L), WS = packet_work_stride(L, nullptr);
     const size_t lds = (size_t)(2 * NFW * rowmax + wcap + 2 * NFW) * sizeof(float);
-    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_n_kernel<OUT, LIM, PF>, lds, name);
+    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_n_kernel<DEC, OUT, LIM, PF>, lds, name);
     if (rc) return rc;
-    hipLaunchKernelGGL((stream_decode_n_kernel<OUT, LIM, PF>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, out_hops, NFW,
-                       L, WS, rowmax, wcap, tab, w, ln_eps, state, work, (OUT*)out, lim, clip, pf_kind, pf_tau);
+    hipLaunchKernelGGL((stream_decode_n_kernel<DEC, OUT, LIM, PF>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, out_hops,
+                       NFW, L, WS, rowmax, wcap, tab, w, ln_eps, state, work, (OUT*)out, lim, clip, pf_kind, pf_tau);
     CRUSE_LAUNCH_CHECK(name);
     return CRUSE_OK;
 }
 
+template <int DEC>
 int decode_n_any(const char* who, const char* name, const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2,
                  int c3, int c4, const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
                  const float* lim, int* clip, void* stream, int pf_kind = 0, const float* pf_tau = nullptr) {
@@ -904,11 +943,11 @@ int decode_n_any(const char* who, const char* name, const int* pk, int S, int ho
     CRUSE_REQUIRE(out_hops >= hops, CRUSE_E_SHAPE, "%s: out_hops = %d < hops = %d", who, out_hops, hops);
     rc = out_args(who, out_fmt, clip);
     if (rc) return rc;
-#define CRUSE_DECODE_N(OUT, LIM)                                                                                                              \
-    (pf ? launch_decode_n<OUT, LIM, true>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, pf_kind, \
-                                          pf_tau, stream)                                                                                    \
-        : launch_decode_n<OUT, LIM, false>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, 0,      \
-                                           nullptr, stream))
+#define CRUSE_DECODE_N(OUT, LIM)                                                                                                          \
+    (pf ? launch_decode_n<DEC, OUT, LIM, true>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, \
+                                               pf_kind, pf_tau, stream)                                                                   \
+        : launch_decode_n<DEC, OUT, LIM, false>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, \
+                                                0, nullptr, stream))
     if (out_fmt == FMT_S16) return lim ? CRUSE_DECODE_N(short, true) : CRUSE_DECODE_N(short, false);
     return lim ? CRUSE_DECODE_N(float, true) : CRUSE_DECODE_N(float, false);
 #undef CRUSE_DECODE_N
@@ -1214,15 +1253,15 @@ extern "C" int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg
 
 extern "C" int cruse_stream_decode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
                                    float ln_eps, float* state, float* work, float* out, void* stream) {
-    return decode_any("stream_decode", "cruse_stream_decode", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out, FMT_F32, nullptr,
-                      nullptr, stream);
+    return decode_any<DEC_CONVT>("stream_decode", "cruse_stream_decode", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out, FMT_F32,
+                                 nullptr, nullptr, stream);
 }
 
 extern "C" int cruse_stream_decode_io(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
                                       float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
                                       void* stream) {
-    return decode_any("stream_decode_io", "cruse_stream_decode_io", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out, out_fmt,
-                      lim, clip, stream);
+    return decode_any<DEC_CONVT>("stream_decode_io", "cruse_stream_decode_io", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out,
+                                 out_fmt, lim, clip, stream);
 }
 
 // the perceptual post-filter in the gain line (utils/utils.py:345-362): the _io arguments plus the kind and the per-slot tau
@@ -1238,8 +1277,8 @@ extern "C" int cruse_stream_decode_pf(const int* mode, int S, int c0, int c1, in
                                       int pf_kind, const float* pf_tau, void* stream) {
     const int rc = pf_args("cruse_stream_decode_pf", pf_kind, pf_tau);
     if (rc) return rc;
-    return decode_any("stream_decode_pf", "cruse_stream_decode_pf", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out, out_fmt,
-                      lim, clip, stream, pf_kind, pf_tau);
+    return decode_any<DEC_CONVT>("stream_decode_pf", "cruse_stream_decode_pf", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out,
+                                 out_fmt, lim, clip, stream, pf_kind, pf_tau);
 }
 
 extern "C" int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4, int* out) {
@@ -1287,15 +1326,15 @@ extern "C" int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_f
 
 extern "C" int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                      const float* tab, const float* w, float ln_eps, float* state, float* work, float* out, void* stream) {
-    return decode_n_any("stream_decode_n", "cruse_stream_decode_n", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w, ln_eps,
-                        state, work, out, FMT_F32, nullptr, nullptr, stream);
+    return decode_n_any<DEC_CONVT>("stream_decode_n", "cruse_stream_decode_n", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w,
+                                   ln_eps, state, work, out, FMT_F32, nullptr, nullptr, stream);
 }
 
 extern "C" int cruse_stream_decode_n_io(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                         const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
                                         const float* lim, int* clip, void* stream) {
-    return decode_n_any("stream_decode_n_io", "cruse_stream_decode_n_io", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w,
-                        ln_eps, state, work, out, out_fmt, lim, clip, stream);
+    return decode_n_any<DEC_CONVT>("stream_decode_n_io", "cruse_stream_decode_n_io", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab,
+                                   w, ln_eps, state, work, out, out_fmt, lim, clip, stream);
 }
 
 extern "C" int cruse_stream_decode_n_pf(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
@@ -1303,6 +1342,28 @@ extern "C" int cruse_stream_decode_n_pf(const int* pk, int S, int hops, int out_
                                         const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream) {
     const int rc = pf_args("cruse_stream_decode_n_pf", pf_kind, pf_tau);
     if (rc) return rc;
-    return decode_n_any("stream_decode_n_pf", "cruse_stream_decode_n_pf", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w,
-                        ln_eps, state, work, out, out_fmt, lim, clip, stream, pf_kind, pf_tau);
+    return decode_n_any<DEC_CONVT>("stream_decode_n_pf", "cruse_stream_decode_n_pf", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab,
+                                   w, ln_eps, state, work, out, out_fmt, lim, clip, stream, pf_kind, pf_tau);
+}
+
+// ---- the upsample decoder of CRUSE4MagAddSkipUpsample (cust_conv.py:163-166,177-184): the _pf argument lists, every form in one pair.
+// pf_kind 0: no post-filter, pf_tau is not read; out_fmt 0, null lim and null clip: the plain form.
+static int up_pf_args(const char* who, int pf_kind, const float* pf_tau) { return pf_kind == 0 ? CRUSE_OK : pf_args(who, pf_kind, pf_tau); }
+
+extern "C" int cruse_stream_decode_up(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
+                                      float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
+                                      int pf_kind, const float* pf_tau, void* stream) {
+    const int rc = up_pf_args("cruse_stream_decode_up", pf_kind, pf_tau);
+    if (rc) return rc;
+    return decode_any<DEC_UPCONV>("stream_decode_up", "cruse_stream_decode_up", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out,
+                                  out_fmt, lim, clip, stream, pf_kind, pf_kind ? pf_tau : nullptr);
+}
+
+extern "C" int cruse_stream_decode_n_up(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                                        const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
+                                        const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream) {
+    const int rc = up_pf_args("cruse_stream_decode_n_up", pf_kind, pf_tau);
+    if (rc) return rc;
+    return decode_n_any<DEC_UPCONV>("stream_decode_n_up", "cruse_stream_decode_n_up", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab,
+                                    w, ln_eps, state, work, out, out_fmt, lim, clip, stream, pf_kind, pf_kind ? pf_tau : nullptr);
 }

@@ -39,8 +39,52 @@ def _bn_fold(bn):
     return s, beta - mean * s
 
 
+DECODERS = ops.STREAM_DECODERS
+
+
+def pack_weights(model, lay, decoder: str = "transposed") -> torch.Tensor:
+    """The conv and LayerNorm weights of `model` as the streaming kernels read them: a float64 host vector of lay["wtotal"] floats at the
+    offsets of lay = ops.stream_layout(ch), eval-mode BatchNorm folded in float64 (running statistics, bn.eps).  Needs no device.
+    decoder = "transposed": unet_2's children (conv{k} / bn{k}, skip_connect_{k}, conv{k}_t / bn{k}_t); decW{k} is ConvTranspose2d's
+    [Cin][Cout][3].  decoder = "upsample": CRUSE4MagAddSkipUpsample's (enc{k}.1 / enc{k}.2, skip_connect_{k}, dec{k}.sconv / dec{k}.norm);
+    decW{k} is Conv2d's [Cout][Cin][3]; dec2..4 have no conv bias (the folded shift is the bias), dec1 has a bias and no norm."""
+    if decoder not in DECODERS:
+        raise ValueError(f"pack_weights: decoder must be one of {DECODERS}, got {decoder!r}")
+    m = model
+    w = torch.zeros(lay["wtotal"], dtype=torch.float64)
+    d = lambda t: t.detach().double().cpu()
+
+    def put(name, t):
+        t = d(t).reshape(-1)
+        w[lay[name]:lay[name] + t.numel()] = t
+
+    for k in range(1, 5):
+        if decoder == "upsample":
+            enc, dec = getattr(m, f"enc{k}"), getattr(m, f"dec{k}")
+            conv, bn, sconv, norm = enc[1], enc[2], dec.sconv, getattr(dec, "norm", None)
+        else:
+            conv, bn, sconv, norm = getattr(m, f"conv{k}"), getattr(m, f"bn{k}"), getattr(m, f"conv{k}_t"), getattr(m, f"bn{k}_t", None)
+        s, sh = _bn_fold(bn)
+        put(f"encW{k}", d(conv.weight) * s.view(-1, 1, 1, 1))
+        put(f"encB{k}", d(conv.bias) * s + sh)
+        put(f"skW{k}", getattr(m, f"skip_connect_{k}").weight)
+        if k > 1:
+            s, sh = _bn_fold(norm)
+            # the output channels: dim 0 of a Conv2d weight, dim 1 of a ConvTranspose2d weight
+            put(f"decW{k}", d(sconv.weight) * (s.view(-1, 1, 1, 1) if decoder == "upsample" else s.view(1, -1, 1, 1)))
+            put(f"decB{k}", sh if sconv.bias is None else d(sconv.bias) * s + sh)
+        else:
+            put(f"decW{k}", sconv.weight)
+            put(f"decB{k}", sconv.bias)
+    put("ln1g", m.gru.ln1.weight)
+    put("ln1b", m.gru.ln1.bias)
+    put("ln2g", m.gru.ln2.weight)
+    put("ln2b", m.gru.ln2.bias)
+    return w
+
+
 class StreamingInferencer:
-    """Streaming unet_2 over `n_slots` independent streams.
+    """Streaming unet_2 (or, with decoder="upsample", CRUSE4MagAddSkipUpsample) over `n_slots` independent streams.
 
     precision = "f32" (default): f32 operands, f32 accumulation throughout.  precision = "f16": the two GRU layers run on f16-operand
     MFMA kernels (cruse_stream_gru*_f16) -- the operand copies of x, h and the GRU weights are rounded to f16; accumulation, biases,
@@ -84,6 +128,11 @@ class StreamingInferencer:
     re-captures a graph; like a limit it belongs to the slot: reset() and flush() leave it alone.  push, push_packet, flush and enhance
     honour it, with either precision, atten_lim, pcm_in / pcm_out and every io_rate; stage()["mask"] keeps the raw mask.  head="df" refuses
     it: that model's output is a filter field, not a gain.
+
+    decoder = "upsample" (default "transposed": nothing changes; the names are convkxf's modes): the model is model/cruse.py's
+    CRUSE4MagAddSkipUpsample, whose decoder levels are nearest FreqUpsample + Conv2d (1,3) (cust_conv.py:163-166,177-184) in place of
+    ConvTranspose2d.  Encoder, skips and GGRU are unet_2's, the decoder has time extent 1 and so no state of its own: the chains are the
+    same but for their decode call (cruse_stream_decode_up / _n_up), and every option above composes as for unet_2.
     """
 
     HOP = 160
@@ -91,7 +140,8 @@ class StreamingInferencer:
     def __init__(self, model: torch.nn.Module, n_slots: int, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
                  device="cuda", use_graph: bool = True, max_hops: int = 1, precision: str = "f32", atten_lim: bool = False,
                  pcm_in: bool = False, pcm_out: bool = False, io_rate: int = 16000, head: str = "mask", df_dims=(1, 5),
-                 post_filter=None):
+                 post_filter=None, decoder: str = "transposed"):
+        from ..model.cruse import CRUSE4MagAddSkipUpsample
         from ..model.cruse_net import unet_2
         io_rate = resample.check_rate(io_rate)
         if head not in ("mask", "df"):
@@ -110,12 +160,27 @@ class StreamingInferencer:
                              f"(got n_fft={n_fft}, hop_length={hop_length}, win_length={win_length})")
         if precision not in ("f32", "f16"):
             raise ValueError(f"StreamingInferencer precision must be \"f32\" or \"f16\", got {precision!r}")
-        if type(model) is not unet_2:
-            raise ValueError(f"StreamingInferencer streams cruse_net.unet_2 only (the upsample decoder of "
-                             f"{type(model).__name__} is not supported)")
-        if tuple(model.stride) != (1, 2) or len(model.ch) != 5 or model.ch[0] != 1 or model.in_feat != 161:
-            raise ValueError(f"StreamingInferencer needs unet_2 with stride (1,2), four levels, ch[0] == 1 and in_feat 161 "
-                             f"(got stride {tuple(model.stride)}, ch {model.ch}, in_feat {model.in_feat})")
+        if decoder not in DECODERS:
+            raise ValueError(f"StreamingInferencer decoder must be one of {DECODERS}, got {decoder!r}")
+        if decoder == "upsample":
+            if type(model) is not CRUSE4MagAddSkipUpsample:
+                raise ValueError(f"StreamingInferencer(decoder=\"upsample\") streams cruse.CRUSE4MagAddSkipUpsample only, got "
+                                 f"{type(model).__name__} (unet_2 takes decoder=\"transposed\", the default)")
+            # (the class has no stride or in_feat attribute: its blocks are built with fstride 2, and f_net = in_feat // 16 * 16)
+            if len(model.ch) != 5 or model.ch[0] != 1 or model.f_net != 160:
+                raise ValueError(f"StreamingInferencer needs CRUSE4MagAddSkipUpsample with four levels, ch[0] == 1 and in_feat 161 "
+                                 f"(got ch {model.ch}, {model.f_net} network bins)")
+            self.g, self.H = model.gru.groups, model.gru.hidden_size
+        else:
+            if type(model) is not unet_2:
+                raise ValueError(f"StreamingInferencer(decoder=\"transposed\") streams cruse_net.unet_2 only (the upsample decoder of "
+                                 f"{type(model).__name__} is not supported"
+                                 + (": pass decoder=\"upsample\")" if type(model) is CRUSE4MagAddSkipUpsample else ")"))
+            if tuple(model.stride) != (1, 2) or len(model.ch) != 5 or model.ch[0] != 1 or model.in_feat != 161:
+                raise ValueError(f"StreamingInferencer needs unet_2 with stride (1,2), four levels, ch[0] == 1 and in_feat 161 "
+                                 f"(got stride {tuple(model.stride)}, ch {model.ch}, in_feat {model.in_feat})")
+            self.g, self.H = model.rnn_groups, model.hidden_size
+        self.decoder = decoder
         if n_slots < 1:
             raise ValueError(f"n_slots must be >= 1, got {n_slots}")
         self.model = model
@@ -125,8 +190,6 @@ class StreamingInferencer:
         self.S = int(n_slots)
         self.device = torch.device(device)
         self.ch = tuple(model.ch)
-        self.g = model.rnn_groups
-        self.H = model.hidden_size
         if self.H % self.g or (self.H // self.g) % 4:
             raise ValueError(f"StreamingInferencer needs hidden_size / rnn_groups divisible by 4 (hidden {self.H}, groups {self.g})")
         self.Hg = self.H // self.g
@@ -214,33 +277,10 @@ class StreamingInferencer:
     # -- weights ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def refresh(self) -> None:
-        """Re-pack the module's weights: BatchNorm folded into the convs (running statistics, bn.eps), GRU weights per layer as
+        """Re-pack the module's weights: pack_weights (BatchNorm folded into the convs; running statistics, bn.eps), GRU weights per layer as
         W_ih [g][3Hg][Hg] | W_hh | b_ih [g][3Hg] | b_hh; in f16 mode also each layer's weights as f16 MFMA fragments (ops.stream_pack_f16)."""
-        m, lay, ch = self.model, self.lay, self.ch
-        w = torch.zeros(lay["wtotal"], dtype=torch.float64)
-
-        def put(name, t):
-            t = t.detach().double().cpu().reshape(-1)
-            w[lay[name]:lay[name] + t.numel()] = t
-
-        for k in range(1, 5):
-            s, sh = _bn_fold(getattr(m, f"bn{k}"))
-            conv = getattr(m, f"conv{k}")
-            put(f"encW{k}", conv.weight.detach().double().cpu() * s.view(-1, 1, 1, 1))
-            put(f"encB{k}", conv.bias.detach().double().cpu() * s + sh)
-            put(f"skW{k}", getattr(m, f"skip_connect_{k}").weight)
-            convt = getattr(m, f"conv{k}_t")
-            if k > 1:
-                s, sh = _bn_fold(getattr(m, f"bn{k}_t"))
-                put(f"decW{k}", convt.weight.detach().double().cpu() * s.view(1, -1, 1, 1))
-                put(f"decB{k}", convt.bias.detach().double().cpu() * s + sh)
-            else:
-                put(f"decW{k}", convt.weight)
-                put(f"decB{k}", convt.bias)
-        put("ln1g", m.gru.ln1.weight)
-        put("ln1b", m.gru.ln1.bias)
-        put("ln2g", m.gru.ln2.weight)
-        put("ln2b", m.gru.ln2.bias)
+        m, lay = self.model, self.lay
+        w = pack_weights(m, lay, self.decoder)
         self.ln1_eps, self.ln2_eps = float(m.gru.ln1.eps), float(m.gru.ln2.eps)
         w = w.float().to(self.device)
         packs, packs16 = [], []
@@ -275,12 +315,12 @@ class StreamingInferencer:
         for layer, x_off, st_off, h_off, pack, pack16, ln1 in self._layers:
             ops.stream_gru(mode, layer, g, Hg, self.work, x_off, self.state, st_off, pack, self.work, h_off, pack16=pack16, **ln1)
         if self._df:        # decode leaves the mask in the work row; the head, one frame behind, writes the block
-            ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self._mask_out)
+            ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self._mask_out, decoder=self.decoder)
             ops.stream_df_head(mode, self.work, self.lay, self.tab, self.df_state, self.df_work[:, 0], self.out, lim=self.lim, clip=self.clip)
             return
         ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out, lim=self.lim,
                           clip=None if self._rs else self.clip,             # behind the converters, resample_out counts
-                          pf=self._pf())
+                          pf=self._pf(), decoder=self.decoder)
 
     def _replay(self, key, fn) -> None:
         """run fn(): directly, or as the graph captured from it on the first call with this key"""
@@ -481,11 +521,11 @@ class StreamingInferencer:
             for f in range(nf):
                 ops.stream_gru_rec_n(pk, hops, f, g, Hg, self.gi, self.state, st_off, pack, wk, h_off, pack16=pack16)
         if self._df:
-            ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self._mask_pout)
+            ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self._mask_pout, decoder=self.decoder)
             ops.stream_df_head_n(pk, hops, wk, self.lay, self.tab, self.df_state, self.df_pwork, self.pout, lim=self.lim, clip=self.clip)
             return
         ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout, lim=self.lim,
-                            clip=None if self._rs else self.clip, pf=self._pf())
+                            clip=None if self._rs else self.clip, pf=self._pf(), decoder=self.decoder)
         if self._rs:
             ops.stream_resample_out_n(pk, hops, self.io_rate, self.pout, self.rs_taps, self.rs_state, self.io_pout, clip=self.clip)
 

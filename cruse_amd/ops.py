@@ -1299,10 +1299,29 @@ def _stream_pf(pf, out: torch.Tensor, name: str):
     return int(kind), _p(tau)
 
 
-def stream_decode(mode, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None, pf=None) -> None:
+STREAM_DECODERS = ("transposed", "upsample")     # convkxf's modes: ConvTranspose2d levels (unet_2), FreqUpsample + Conv2d levels
+
+
+def _stream_up(decoder, out: torch.Tensor, lim, clip, pf, name: str):
+    """None for the ConvTranspose decoder, else the tail (out_fmt, lim, clip, pf_kind, pf_tau) of a cruse_stream_decode_up / _n_up call"""
+    if decoder not in STREAM_DECODERS:
+        raise ValueError(f"{name}: decoder must be one of {STREAM_DECODERS}, got {decoder!r}")
+    if decoder == "transposed":
+        return None
+    io = _stream_io(out, lim, clip, name) or (_stream_fmt(out, name), None, None)
+    return (*io, *(_stream_pf(pf, out, name) if pf is not None else (0, None)))
+
+
+def stream_decode(mode, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None, pf=None, decoder="transposed") -> None:
     """out [S, 160]: float32, or int16 PCM (clamp(rint(y * 32768))); lim [S] f32: per-slot attenuation-limit gains (atten_lim_gain);
     clip [S] int32: += the clamped samples per slot (int16 out only).  Any of them selects cruse_stream_decode_io.
-    pf = (pf_kind, tau [S] f32): the perceptual post-filter on the mask before the limit (cruse_stream_decode_pf)."""
+    pf = (pf_kind, tau [S] f32): the perceptual post-filter on the mask before the limit (cruse_stream_decode_pf).
+    decoder = "upsample": w holds the [Cout][Cin][3] decoder weights of CRUSE4MagAddSkipUpsample; every form is cruse_stream_decode_up."""
+    up = _stream_up(decoder, out, lim, clip, pf, "stream_decode")
+    if up is not None:
+        check(lib.cruse_stream_decode_up(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state),
+                                         _p(work), _p(out), *up, _stream()))
+        return
     if pf is not None:
         fmt = _stream_fmt(out, "stream_decode")
         io = _stream_io(out, lim, clip, "stream_decode") or (fmt, None, None)
@@ -1352,9 +1371,14 @@ def stream_gru_rec_n(pk, hops, frame, groups, Hg, gi, state, st_off, pack, work,
              *p16, _p(work), work.shape[2], h_off, _stream()))
 
 
-def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None, pf=None) -> None:
+def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None, pf=None, decoder="transposed") -> None:
     """out [S, out_hops, 160]: float32 or int16 PCM; lim / clip as stream_decode (cruse_stream_decode_n_io); pf as stream_decode
-    (cruse_stream_decode_n_pf)"""
+    (cruse_stream_decode_n_pf); decoder as stream_decode (cruse_stream_decode_n_up)"""
+    up = _stream_up(decoder, out, lim, clip, pf, "stream_decode_n")
+    if up is not None:
+        check(lib.cruse_stream_decode_n_up(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab),
+                                           _p(w), float(ln_eps), _p(state), _p(work), _p(out), *up, _stream()))
+        return
     if pf is not None:
         fmt = _stream_fmt(out, "stream_decode_n")
         io = _stream_io(out, lim, clip, "stream_decode_n") or (fmt, None, None)

@@ -949,6 +949,26 @@ int cruse_stream_decode_n_pf(const int* pk, int S, int hops, int out_hops, int w
 int cruse_mask_postfilter(int kind, const float* mask, long long rows, long long F, const float* tau, long long rows_per_tau,
                           float* out, void* stream);
 
+/* ---- the upsample decoder (additive; every entry point above is unchanged) ---------------------------------------------------------
+ * cruse_stream_decode_up / _n_up: cruse_stream_decode_pf / _n_pf for model/cruse.py's CRUSE4MagAddSkipUpsample, whose decoder levels are
+ * convkxf(mode="upsample") (model/based_model/cust_conv.py:163-166,177-184): nearest x2 FreqUpsample along frequency, then Conv2d (1,3),
+ * padding (0,1), [Cin][Fin] -> [Cout][2*Fin].  With u[i] = in[i >> 1] for 0 <= i < 2*Fin and zero outside,
+ *   out[co][fo] = b[co] + sum_ci sum_kw W[co][ci][kw] * u[fo - 1 + kw]
+ * (fo = 2j reads in[j-1], in[j], in[j]; fo = 2j+1 reads in[j], in[j], in[j+1]), BatchNorm folded into W and b, ReLU then + skip on
+ * levels 4..2, sigmoid on level 1.  The weights at decW[k] are packed [Cout][Cin][3], the Conv2d order (cruse_stream_decode's are
+ * ConvTranspose2d's [Cin][Cout][3]); the float counts are equal, so cruse_stream_layout and cruse_stream_packet_layout serve both
+ * decoders.  Encode, the GRU layers, the resamplers and the DeepFilter head are the same calls for both models.  Everything of the
+ * kernels but the four decoder levels is cruse_stream_decode's code.
+ * One pair covers every form: out_fmt 0 with null lim and clip is the plain form, out_fmt / lim / clip as in the _io siblings, pf_kind
+ * 0: no post-filter (pf_tau is not read), pf_kind 1 / 2 with pf_tau[S] as in the _pf siblings.  Refused with CRUSE_E_SHAPE before any
+ * launch: what the _io siblings refuse, pf_kind outside {0, 1, 2}, pf_kind != 0 with a null pf_tau. */
+int cruse_stream_decode_up(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
+                           float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
+                           int pf_kind, const float* pf_tau, void* stream);
+int cruse_stream_decode_n_up(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
+                             const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
+                             const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream);
+
 /* ---- f16-operand MFMA GRU of the streaming chains (additive; rows, mode / pk semantics and the f32 pack are those above, so these
  * may replace their f32 counterparts call by call) ------------------------------------------------------------------------------
  * pack16 (device, f16): the layer's weights as MFMA A fragments, [W_ih | W_hh][g][gate r,z,n][UT][KS][64 lanes][8], UT =

@@ -28,9 +28,14 @@ With --post-filter none,iam every (n_slots, hops) cell is measured with and with
 run, in the style of --head: one instance each (the filtered one with every slot's tau = --pf-tau, default 0.02), alternating slices;
 every row carries "post_filter", the filtered rows "vs_none" and "device_vs_none".
 
+With --model unet_2,cruse4 every (n_slots, hops) cell is measured for both decoders in one run, in the style of --head: unet_2 (ConvTranspose
+levels, decoder="transposed") and CRUSE4MagAddSkipUpsample with the same channels and groups (FreqUpsample + Conv2d levels,
+decoder="upsample"), one instance each, alternating slices; every row carries "model", the cruse4 row "vs_unet_2" and
+"device_vs_unet_2" (profiles/stream_up_rtf.json).  --model cruse4 alone measures that model through every other option.
+
     python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--precision f32,f16] [--pcm]
                                [--atten-lim DB] [--io-rate 16000,8000,48000] [--head mask,df]
-                               [--post-filter none,iam] [--pf-tau 0.02] [--out FILE]
+                               [--post-filter none,iam] [--pf-tau 0.02] [--model unet_2,cruse4] [--out FILE]
 """
 from __future__ import annotations
 
@@ -53,7 +58,7 @@ def closed_form(model):
         for i, (name, p) in enumerate(model.named_parameters()):
             j = torch.arange(p.numel(), dtype=torch.float64)
             s = torch.sin(0.37 * j + 1.3 * i + 0.1)
-            is_norm = ".ln" in name or "bn" in name
+            is_norm = ".ln" in name or "bn" in name or ".norm." in name or (name.startswith("enc") and ".2." in name)
             if is_norm:
                 v = 1.0 + 0.1 * s if name.endswith("weight") else 0.05 * s
             else:
@@ -62,10 +67,25 @@ def closed_form(model):
 
 
 IO = {"pcm": False, "atten_lim": None, "io_rate": None}      # --pcm / --atten-lim / --io-rate: the I/O mode of every instance measured
+MODELS = {"unet_2": "transposed", "cruse4": "upsample"}      # --model: the StreamingInferencer decoder each name runs on
+
+
+def build_model(name: str, groups: int):
+    """the product module of --model `name` with deterministic weights, on the device"""
+    if name == "cruse4":
+        from cruse_amd.model.cruse import CRUSE4MagAddSkipUpsample
+        m = CRUSE4MagAddSkipUpsample(rnn_groups=groups, precision="f32")
+    else:
+        from cruse_amd.model.cruse_net import unet_2
+        m = unet_2(rnn_groups=groups, precision="f32")
+    closed_form(m)
+    return m.cuda().eval()
 
 
 def _inferencer(model, S: int, precision: str, **kw):
     from cruse_amd.inferencer import StreamingInferencer
+    if type(model).__name__ == "CRUSE4MagAddSkipUpsample":
+        kw.update(decoder="upsample")
     if IO["pcm"]:
         kw.update(pcm_in=True, pcm_out=True)
     if IO["atten_lim"] is not None:
@@ -140,6 +160,8 @@ def _variant(model, S, precision, hops, key, h, pf_tau):
     """the instance of one side-by-side variant: a head, or a post-filter setting ("none": the plain server)"""
     if key == "head":
         return _inferencer(model, S, precision, max_hops=hops, head=h)
+    if key == "model":
+        return _inferencer(model[h], S, precision, max_hops=hops)
     inf = _inferencer(model, S, precision, max_hops=hops, post_filter=None if h == "none" else h)
     if h != "none":
         inf.set_post_filter(pf_tau)
@@ -200,15 +222,17 @@ def main():
     ap.add_argument("--head", default=None, help="mask, df or mask,df: the heads to measure side by side, alternating, in every cell")
     ap.add_argument("--post-filter", default=None, help="none, iam, envelope or a list (none,iam): measured side by side like --head")
     ap.add_argument("--pf-tau", type=float, default=0.02, help="tau of every slot of the post-filter instances")
+    ap.add_argument("--model", default="unet_2", help="unet_2 (default), cruse4, or unet_2,cruse4: the two decoders side by side like --head")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()
     IO.update(pcm=a.pcm, atten_lim=a.atten_lim)
     rates = [None] if a.io_rate is None else [int(r) for r in a.io_rate.split(",")]
-    from cruse_amd.model.cruse_net import unet_2
+    names = a.model.split(",")
+    if any(n not in MODELS for n in names) or len(set(names)) != len(names):
+        ap.error(f"--model takes unet_2, cruse4 or unet_2,cruse4, got {a.model}")
     torch.manual_seed(0)
-    m = unet_2(rnn_groups=a.groups, precision="f32")
-    closed_form(m)
-    m = m.cuda().eval()
+    built = {n: build_model(n, a.groups) for n in names}
+    m = built[names[0]]
     precs = a.precision.split(",")
     if any(p not in ("f32", "f16") for p in precs):
         ap.error(f"--precision takes f32, f16 or f32,f16, got {a.precision}")
@@ -224,6 +248,10 @@ def main():
         side = dict(key="post_filter", base_name="none", pf_tau=a.pf_tau)
     elif heads is not None and any(h not in ("mask", "df") for h in heads):
         ap.error(f"--head takes mask, df or mask,df, got {a.head}")
+    if len(names) > 1:
+        if heads is not None:
+            ap.error("--model with two models is measured in a run of its own (no --head / --post-filter)")
+        heads, side, m = names, dict(key="model", base_name="unet_2"), built
     if heads is not None:
         for prec in precs:
             for s in a.slots.split(","):
@@ -258,7 +286,7 @@ def main():
         for r in rows:
             if r["precision"] == "f16":
                 r["vs_f32"] = round(per_hop(r) / f32[cell(r)], 3)
-    res = {"model": f"unet_2 ch={m.ch} rnn_groups={a.groups}", "device": torch.cuda.get_device_name(0), "rows": rows}
+    res = {"model": f"{'+'.join(names)} ch={built[names[0]].ch} rnn_groups={a.groups}", "device": torch.cuda.get_device_name(0), "rows": rows}
     if a.pcm or a.atten_lim is not None:
         res["io"] = {"pcm": a.pcm, "atten_lim_db": a.atten_lim}
     if a.out:
