@@ -166,6 +166,7 @@ SIGNATURES = {
     "cruse_stream_df_layout": ("p", "i"),
     "cruse_stream_df_head": ("piipiiiippipipippiip", "i"),
     "cruse_stream_df_head_n": ("piiiipiiiippipipippiip", "i"),
+    "cruse_stream_boundary_plan": ("ipip", "i"),
     "cruse_si_sdr": ("ppiipp", "i"),
     "cruse_stoi_layout": ("iip", "i"),
     "cruse_stoi_ws_bytes": ("ii", "z"),

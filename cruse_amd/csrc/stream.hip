@@ -7,9 +7,11 @@
 // All arithmetic is f32 with f32 accumulation.  Every kernel reads the per-slot mode (CRUSE_STREAM_MODE_*) from device
 // memory; a slot whose mode is SKIP is not touched.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <mutex>
+#include <tuple>
 #include <type_traits>
 #include "postfilter.h"
 #include "stream_common.h"
@@ -808,149 +810,132 @@ int packet_args(const char* who, int S, int hops, int NFW, const Layout& L) {
     return CRUSE_OK;
 }
 
-// ---- host side of the boundary kernels: the plain entry point and its _io form share one function (`who` names the entry point in
-// the messages); fmt 0 = f32, 1 = s16.  Plain: fmt 0, no limit, no counter -> the <float> / <float, false> kernels.
-enum { FMT_F32 = 0, FMT_S16 = 1 };
+// ---- host side of the boundary kernels (encode, decode, the DeepFilter head).  Each of the 14 entry points lists its arguments by group
+// into a BoundaryArgs and calls its family's function, which checks and launches, single hop or packet.  A group an entry point has no
+// arguments for stays zero: f32 samples, no limit, no counter, no post-filter -> the <float> / <float, false, false> kernels.
+struct Slots { const char* name; const int* ctl; int S; };      // the entry point's name ("cruse_stream_..."); mode[S], packets: pk[2][S]
+struct Packet { bool packet; int hops, io_hops, work_frames; };
+struct Net { std::array<int, 5> ch; const float *tab, *w; float ln_eps, *state, *work; };
+struct Samples { const void* io; int fmt; const float* lim; int* clip; };       // io: encode's in, decode's and the head's out
+struct PostFilter { bool pf_required; int pf_kind; const float* pf_tau; int dec; };      // pf_required: pf_kind 0 is refused; dec: DEC_*
+// the head's work rows (DfRows), state rows and inspection rows (dw, single hop: floats between two rows; packets: rows per slot), instance
+struct Head { int drain; const float* rows; int wk_stride, wk_re, wk_im, wk_mask; float* df_state; int st_stride;
+              float* df_work; int dw, t_dim, f_dim; };
+struct BoundaryArgs : Slots, Packet, Net, Samples, PostFilter, Head { Layout L; };       // L: of ch, by chain_args
 
-int fmt_args(const char* who, int fmt) {
-    CRUSE_REQUIRE(fmt == FMT_F32 || fmt == FMT_S16, CRUSE_E_SHAPE, "%s: unknown sample format %d (0: f32, 1: s16)", who, fmt);
+const char* who_of(const BoundaryArgs& a) { return a.name + 6; }        // the family's messages leave out the "cruse_"
+
+// cruse_stream_boundary_plan calls the entry point itself with plan_out set: launch_* then write what they were about to launch (family:
+// 0 encode, 2 decode, 4 head, + 1 for packets) and return
+thread_local int* plan_out = nullptr;
+struct Plan { int family, dec, s16, lim, pf, grid, block, lds, WS, rowmax, wcap; };
+static_assert(sizeof(Plan) == CRUSE_STREAM_PLAN_INTS * sizeof(int), "plan size");
+
+int planned(const Plan& p) { return memcpy(plan_out, &p, sizeof(p)), CRUSE_OK; }
+
+// (fmt, lim, pf_kind) -> f(OUT(), LIM, PF) with LIM, PF as std::true_type / false_type: the one place the kernel instance is chosen.
+// WITH_PF false: the kernels have no PF axis
+template <bool WITH_PF, typename F>
+int with_form(const BoundaryArgs& a, F&& f) {
+    auto pf = [&](auto out, auto lim) {
+        if (WITH_PF && a.pf_kind != 0) return f(out, lim, std::bool_constant<WITH_PF>());
+        return f(out, lim, std::false_type());
+    };
+    auto lim = [&](auto out) { return a.lim ? pf(out, std::true_type()) : pf(out, std::false_type()); };
+    return a.fmt == FMT_S16 ? lim(short()) : lim(float());
+}
+
+// the perceptual post-filter in the gain line (utils/utils.py:345-362): the kind and the per-slot tau.  allow_none (every entry point
+// but the _pf ones): pf_kind 0 is no post-filter, and pf_tau is not read
+int pf_args(const char* who, int pf_kind, const float* pf_tau, bool allow_none) {
+    if (allow_none && pf_kind == 0) return CRUSE_OK;
+    const int rc = cruse_pf::kind_args(who, pf_kind);
+    if (rc) return rc;
+    CRUSE_REQUIRE(pf_tau != nullptr, CRUSE_E_SHAPE, "%s: null pf_tau", who);
+    return CRUSE_OK;
+}
+
+// the layout and the checks encode and decode share; io_hops: what the entry point calls the block stride of its samples
+int chain_args(BoundaryArgs& a, const char* io_hops) {
+    const char* who = who_of(a);
+    int rc = make_layout(a.ch[0], a.ch[1], a.ch[2], a.ch[3], a.ch[4], a.L);
+    if (rc) return rc;
+    const bool bufs = a.ctl && a.io && a.tab && a.w && a.state && a.work;
+    CRUSE_REQUIRE(a.packet || (a.S > 0 && bufs), CRUSE_E_SHAPE, "%s: S = %d or a null buffer", who, a.S);
+    if (!a.packet) return CRUSE_OK;
+    CRUSE_REQUIRE(bufs, CRUSE_E_SHAPE, "%s: null buffer", who);
+    rc = packet_args(who, a.S, a.hops, a.work_frames, a.L);
+    if (rc) return rc;
+    CRUSE_REQUIRE(a.io_hops >= a.hops, CRUSE_E_SHAPE, "%s: %s = %d < hops = %d", who, io_hops, a.io_hops, a.hops);
     return CRUSE_OK;
 }
 
 template <typename IN>
-int launch_encode(const char* name, const int* mode, int S, const Layout& L, size_t lds, const void* in, const float* tab, const float* w,
-                  float* state, float* work, void* stream) {
-    const int rc = cruse_ensure_dyn_lds((const void*)stream_encode_kernel<IN>, lds, name);
+int launch_encode(const BoundaryArgs& a, hipStream_t st) {
+    const Layout& L = a.L;
+    int rows = NFFT + 2 * NB;                             // single hop: frame | rows of levels 0..4 | previous rows 0..3 | re | im
+    for (int k = 0; k < 5; ++k) rows += L.ch[k] * L.F[k];
+    for (int k = 0; k < 4; ++k) rows += L.ch[k] * L.F[k];
+    const int rowmax = a.packet ? packet_row_max(L) : 0, wcap = a.packet ? packet_wcap(L) : 0;
+    int eoff[4] = {0, 0, 0, 0};
+    const int WS = a.packet ? packet_work_stride(L, eoff) : 0;
+    const size_t lds = (size_t)(a.packet ? (2 * a.work_frames + 1) * rowmax + wcap : rows) * sizeof(float);
+    if (plan_out) return planned({0 + a.packet, 0, std::is_same<IN, short>::value, 0, 0, a.S, FRAME_THREADS, (int)lds, WS, rowmax, wcap});
+    const void* fn = a.packet ? (const void*)stream_encode_n_kernel<IN> : (const void*)stream_encode_kernel<IN>;
+    const int rc = cruse_ensure_dyn_lds(fn, lds, a.name);
     if (rc) return rc;
-    hipLaunchKernelGGL(stream_encode_kernel<IN>, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, (const IN*)in, tab, w, state,
-                       work);
-    CRUSE_LAUNCH_CHECK(name);
+    if (a.packet)
+        hipLaunchKernelGGL(stream_encode_n_kernel<IN>, dim3(a.S), dim3(FRAME_THREADS), lds, st, a.ctl, a.S, a.hops, a.io_hops,
+                           a.work_frames, L, WS, eoff[1], eoff[2], eoff[3], rowmax, wcap, (const IN*)a.io, a.tab, a.w, a.state, a.work);
+    else
+        hipLaunchKernelGGL(stream_encode_kernel<IN>, dim3(a.S), dim3(FRAME_THREADS), lds, st, a.ctl, L, (const IN*)a.io, a.tab, a.w, a.state, a.work);
+    CRUSE_LAUNCH_CHECK(a.name);
     return CRUSE_OK;
 }
 
-int encode_any(const char* who, const char* name, const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const void* in, int in_fmt,
-               const float* tab, const float* w, float* state, float* work, void* stream) {
-    Layout L;
-    int rc = make_layout(c0, c1, c2, c3, c4, L);
+int encode_any(BoundaryArgs a, void* stream) {
+    int rc = chain_args(a, "in_hops");
     if (rc) return rc;
-    CRUSE_REQUIRE(S > 0 && mode && in && tab && w && state && work, CRUSE_E_SHAPE, "%s: S = %d or a null buffer", who, S);
-    rc = fmt_args(who, in_fmt);
+    rc = fmt_args(who_of(a), a.fmt);
     if (rc) return rc;
-    int n = NFFT + 2 * NB;
-    for (int k = 0; k < 5; ++k) n += L.ch[k] * L.F[k];
-    for (int k = 0; k < 4; ++k) n += L.ch[k] * L.F[k];
-    const size_t lds = (size_t)n * sizeof(float);
-    return in_fmt == FMT_S16 ? launch_encode<short>(name, mode, S, L, lds, in, tab, w, state, work, stream)
-                             : launch_encode<float>(name, mode, S, L, lds, in, tab, w, state, work, stream);
+    return a.fmt == FMT_S16 ? launch_encode<short>(a, (hipStream_t)stream) : launch_encode<float>(a, (hipStream_t)stream);
 }
 
 template <int DEC, typename OUT, bool LIM, bool PF>
-int launch_decode(const char* name, const int* mode, int S, const Layout& L, size_t lds, const float* tab, const float* w, float ln_eps,
-                  float* state, float* work, void* out, const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream) {
-    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_kernel<DEC, OUT, LIM, PF>, lds, name);
+int launch_decode(const BoundaryArgs& a, hipStream_t st) {
+    const Layout& L = a.L;
+    int rows = 2 * NB + NFFT + FRAME_THREADS / 64;        // single hop: rows of levels 4..0 | re | im | y | red
+    for (int k = 0; k < 5; ++k) rows += L.ch[k] * L.F[k];
+    const int rowmax = a.packet ? packet_row_max(L) : 0, wcap = a.packet ? packet_wcap(L) : 0, WS = a.packet ? packet_work_stride(L, nullptr) : 0;
+    const size_t lds = (size_t)(a.packet ? 2 * a.work_frames * rowmax + wcap + 2 * a.work_frames : rows) * sizeof(float);
+    if (plan_out) return planned({2 + a.packet, DEC, std::is_same<OUT, short>::value, LIM, PF, a.S, FRAME_THREADS, (int)lds, WS, rowmax, wcap});
+    const void* fn = a.packet ? (const void*)stream_decode_n_kernel<DEC, OUT, LIM, PF> : (const void*)stream_decode_kernel<DEC, OUT, LIM, PF>;
+    const int rc = cruse_ensure_dyn_lds(fn, lds, a.name);
     if (rc) return rc;
-    hipLaunchKernelGGL((stream_decode_kernel<DEC, OUT, LIM, PF>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, mode, L, tab, w,
-                       ln_eps, state, work, (OUT*)out, lim, clip, pf_kind, pf_tau);
-    CRUSE_LAUNCH_CHECK(name);
+    const int pf_kind = PF ? a.pf_kind : 0;               // an instance without PF reads neither
+    const float* pf_tau = PF ? a.pf_tau : nullptr;
+    if (a.packet)
+        hipLaunchKernelGGL((stream_decode_n_kernel<DEC, OUT, LIM, PF>), dim3(a.S), dim3(FRAME_THREADS), lds, st, a.ctl, a.S, a.hops, a.io_hops,
+                           a.work_frames, L, WS, rowmax, wcap, a.tab, a.w, a.ln_eps, a.state, a.work, (OUT*)a.io, a.lim, a.clip, pf_kind, pf_tau);
+    else
+        hipLaunchKernelGGL((stream_decode_kernel<DEC, OUT, LIM, PF>), dim3(a.S), dim3(FRAME_THREADS), lds, st, a.ctl, L, a.tab, a.w, a.ln_eps, a.state,
+                           a.work, (OUT*)a.io, a.lim, a.clip, pf_kind, pf_tau);
+    CRUSE_LAUNCH_CHECK(a.name);
     return CRUSE_OK;
 }
 
-// the clamp counter belongs to PCM output: f32 output is never clamped
-int out_args(const char* who, int out_fmt, const int* clip) {
-    const int rc = fmt_args(who, out_fmt);
+int decode_any(BoundaryArgs a, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    int rc = pf_args(a.name, a.pf_kind, a.pf_tau, !a.pf_required);      // comes first, and names the entry point in full
     if (rc) return rc;
-    CRUSE_REQUIRE(out_fmt == FMT_S16 || clip == nullptr, CRUSE_E_SHAPE, "%s: a clip counter needs s16 output (out_fmt 1), got out_fmt %d", who, out_fmt);
-    return CRUSE_OK;
-}
-
-template <int DEC>
-int decode_any(const char* who, const char* name, const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab,
-               const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip, void* stream,
-               int pf_kind = 0, const float* pf_tau = nullptr) {
-    Layout L;
-    int rc = make_layout(c0, c1, c2, c3, c4, L);
+    rc = chain_args(a, "out_hops");
     if (rc) return rc;
-    CRUSE_REQUIRE(S > 0 && mode && tab && w && state && work && out, CRUSE_E_SHAPE, "%s: S = %d or a null buffer", who, S);
-    rc = out_args(who, out_fmt, clip);
+    rc = out_args(who_of(a), a.fmt, a.clip);
     if (rc) return rc;
-    const bool pf = pf_kind != 0;                         // the _pf entry points have refused kind 0 and a null pf_tau
-    int n = 2 * NB + NFFT + FRAME_THREADS / 64;
-    for (int k = 0; k < 5; ++k) n += L.ch[k] * L.F[k];
-    const size_t lds = (size_t)n * sizeof(float);
-#define CRUSE_DECODE(OUT, LIM) \
-    (pf ? launch_decode<DEC, OUT, LIM, true>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, pf_kind, pf_tau, stream) \
-        : launch_decode<DEC, OUT, LIM, false>(name, mode, S, L, lds, tab, w, ln_eps, state, work, out, lim, clip, 0, nullptr, stream))
-    if (out_fmt == FMT_S16) return lim ? CRUSE_DECODE(short, true) : CRUSE_DECODE(short, false);
-    return lim ? CRUSE_DECODE(float, true) : CRUSE_DECODE(float, false);
-#undef CRUSE_DECODE
-}
-
-template <typename IN>
-int launch_encode_n(const char* name, const int* pk, int S, int hops, int in_hops, int NFW, const Layout& L, const void* in, const float* tab,
-                    const float* w, float* state, float* work, void* stream) {
-    const int rowmax = packet_row_max(L), wcap = packet_wcap(L);
-    int eoff[4];
-    const int WS = packet_work_stride(L, eoff);
-    const size_t lds = (size_t)((2 * NFW + 1) * rowmax + wcap) * sizeof(float);
-    const int rc = cruse_ensure_dyn_lds((const void*)stream_encode_n_kernel<IN>, lds, name);
-    if (rc) return rc;
-    hipLaunchKernelGGL(stream_encode_n_kernel<IN>, dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, in_hops, NFW, L, WS,
-                       eoff[1], eoff[2], eoff[3], rowmax, wcap, (const IN*)in, tab, w, state, work);
-    CRUSE_LAUNCH_CHECK(name);
-    return CRUSE_OK;
-}
-
-int encode_n_any(const char* who, const char* name, const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2,
-                 int c3, int c4, const void* in, int in_fmt, const float* tab, const float* w, float* state, float* work, void* stream) {
-    Layout L;
-    int rc = make_layout(c0, c1, c2, c3, c4, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(pk && in && tab && w && state && work, CRUSE_E_SHAPE, "%s: null buffer", who);
-    rc = packet_args(who, S, hops, work_frames, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(in_hops >= hops, CRUSE_E_SHAPE, "%s: in_hops = %d < hops = %d", who, in_hops, hops);
-    rc = fmt_args(who, in_fmt);
-    if (rc) return rc;
-    return in_fmt == FMT_S16 ? launch_encode_n<short>(name, pk, S, hops, in_hops, work_frames, L, in, tab, w, state, work, stream)
-                             : launch_encode_n<float>(name, pk, S, hops, in_hops, work_frames, L, in, tab, w, state, work, stream);
-}
-
-template <int DEC, typename OUT, bool LIM, bool PF>
-int launch_decode_n(const char* name, const int* pk, int S, int hops, int out_hops, int NFW, const Layout& L, const float* tab, const float* w,
-                    float ln_eps, float* state, float* work, void* out, const float* lim, int* clip, int pf_kind, const float* pf_tau,
-                    void* stream) {
-    const int rowmax = packet_row_max(L), wcap = packet_wcap(L), WS = packet_work_stride(L, nullptr);
-    const size_t lds = (size_t)(2 * NFW * rowmax + wcap + 2 * NFW) * sizeof(float);
-    const int rc = cruse_ensure_dyn_lds((const void*)stream_decode_n_kernel<DEC, OUT, LIM, PF>, lds, name);
-    if (rc) return rc;
-    hipLaunchKernelGGL((stream_decode_n_kernel<DEC, OUT, LIM, PF>), dim3(S), dim3(FRAME_THREADS), lds, (hipStream_t)stream, pk, S, hops, out_hops,
-                       NFW, L, WS, rowmax, wcap, tab, w, ln_eps, state, work, (OUT*)out, lim, clip, pf_kind, pf_tau);
-    CRUSE_LAUNCH_CHECK(name);
-    return CRUSE_OK;
-}
-
-template <int DEC>
-int decode_n_any(const char* who, const char* name, const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2,
-                 int c3, int c4, const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
-                 const float* lim, int* clip, void* stream, int pf_kind = 0, const float* pf_tau = nullptr) {
-    Layout L;
-    int rc = make_layout(c0, c1, c2, c3, c4, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(pk && tab && w && state && work && out, CRUSE_E_SHAPE, "%s: null buffer", who);
-    const bool pf = pf_kind != 0;
-    rc = packet_args(who, S, hops, work_frames, L);
-    if (rc) return rc;
-    CRUSE_REQUIRE(out_hops >= hops, CRUSE_E_SHAPE, "%s: out_hops = %d < hops = %d", who, out_hops, hops);
-    rc = out_args(who, out_fmt, clip);
-    if (rc) return rc;
-#define CRUSE_DECODE_N(OUT, LIM)                                                                                                          \
-    (pf ? launch_decode_n<DEC, OUT, LIM, true>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, \
-                                               pf_kind, pf_tau, stream)                                                                   \
-        : launch_decode_n<DEC, OUT, LIM, false>(name, pk, S, hops, out_hops, work_frames, L, tab, w, ln_eps, state, work, out, lim, clip, \
-                                                0, nullptr, stream))
-    if (out_fmt == FMT_S16) return lim ? CRUSE_DECODE_N(short, true) : CRUSE_DECODE_N(short, false);
-    return lim ? CRUSE_DECODE_N(float, true) : CRUSE_DECODE_N(float, false);
-#undef CRUSE_DECODE_N
+    return with_form<true>(a, [&](auto out, auto lim, auto pf) {
+        constexpr bool LIM = decltype(lim)::value, PF = decltype(pf)::value;
+        return a.dec == DEC_UPCONV ? launch_decode<DEC_UPCONV, decltype(out), LIM, PF>(a, st) : launch_decode<DEC_CONVT, decltype(out), LIM, PF>(a, st);
+    });
 }
 
 // ---- the DeepFilter(1, 5) head on the stream (cruse_stream_df_head / _df_head_n) -------------------------------------------------
@@ -1131,26 +1116,44 @@ __global__ void __launch_bounds__(DF_THREADS) stream_df_head_n_kernel(const int*
                         (size_t)s * out_hops * HOP, lim, clip);
 }
 
-// shared argument checks of the two entry points
-int df_head_args(const char* who, int S, const void* ctl, const float* work, int wk_stride, int wk_re, int wk_im, int wk_mask,
-                 const float* tab, const float* df_state, int st_stride, const float* df_work, const void* out, int out_fmt, const int* clip,
-                 int t_dim, int f_dim, DfLayout& D) {
-    CRUSE_REQUIRE(t_dim == 1 && f_dim == DF_FD, CRUSE_E_SHAPE, "%s: (t_dim, f_dim) = (%d, %d): only the DeepFilter(1, %d) instance is built", who,
-                  t_dim, f_dim, DF_FD);
-    CRUSE_REQUIRE(S >= 1, CRUSE_E_SHAPE, "%s: S = %d (need S >= 1)", who, S);
-    CRUSE_REQUIRE(ctl && work && tab && df_state && df_work && out, CRUSE_E_SHAPE, "%s: null buffer", who);
-    CRUSE_REQUIRE(wk_stride >= 2 * NB + F0 && wk_re >= 0 && wk_re + NB <= wk_stride && wk_im >= 0 && wk_im + NB <= wk_stride && wk_mask >= 0 &&
-                  wk_mask + F0 <= wk_stride, CRUSE_E_SHAPE,
-                  "%s: wk_re %d / wk_im %d (+ %d) / wk_mask %d (+ %d) do not lie in a work row of %d floats (>= %d)", who, wk_re, wk_im, NB,
-                  wk_mask, F0, wk_stride, 2 * NB + F0);
-    make_df_layout(D);
-    CRUSE_REQUIRE(st_stride >= D.stride, CRUSE_E_SHAPE, "%s: df_state rows of %d floats, the layout needs %d", who, st_stride, D.stride);
-    return out_args(who, out_fmt, clip);
+template <typename OUT, bool LIM>
+int launch_df_head(const BoundaryArgs& a, const DfLayout& D, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (plan_out) return planned({4 + a.packet, 0, std::is_same<OUT, short>::value, LIM, 0, a.S, DF_THREADS, 0, 0, 0, 0});
+    const DfRows R = {a.rows, a.wk_stride, a.wk_re, a.wk_im, a.wk_mask};
+    if (a.packet)
+        hipLaunchKernelGGL((stream_df_head_n_kernel<OUT, LIM>), dim3(a.S), dim3(DF_THREADS), 0, st, a.ctl, a.S, a.hops, a.io_hops, a.work_frames, R,
+                           a.tab, a.df_state, a.st_stride, D, a.df_work, a.dw, (OUT*)a.io, a.lim, a.clip);
+    else
+        hipLaunchKernelGGL((stream_df_head_kernel<OUT, LIM>), dim3(a.S), dim3(DF_THREADS), 0, st, a.ctl, a.drain != 0, R, a.tab, a.df_state,
+                           a.st_stride, D, a.df_work, a.dw, (OUT*)a.io, a.lim, a.clip);
+    CRUSE_LAUNCH_CHECK(a.name);
+    return CRUSE_OK;
 }
 
-#define CRUSE_DF_FORMS(LAUNCH)                                                                      \
-    if (out_fmt == FMT_S16) { if (lim) { LAUNCH(short, true); } else { LAUNCH(short, false); } }   \
-    else if (lim) { LAUNCH(float, true); } else { LAUNCH(float, false); }
+int df_head_any(const BoundaryArgs& a, void* stream) {
+    const char* who = who_of(a);
+    CRUSE_REQUIRE(a.t_dim == 1 && a.f_dim == DF_FD, CRUSE_E_SHAPE, "%s: (t_dim, f_dim) = (%d, %d): only the DeepFilter(1, %d) instance is built", who,
+                  a.t_dim, a.f_dim, DF_FD);
+    CRUSE_REQUIRE(a.S >= 1, CRUSE_E_SHAPE, "%s: S = %d (need S >= 1)", who, a.S);
+    CRUSE_REQUIRE(a.ctl && a.rows && a.tab && a.df_state && a.df_work && a.io, CRUSE_E_SHAPE, "%s: null buffer", who);
+    CRUSE_REQUIRE(a.wk_stride >= 2 * NB + F0 && a.wk_re >= 0 && a.wk_re + NB <= a.wk_stride && a.wk_im >= 0 && a.wk_im + NB <= a.wk_stride &&
+                  a.wk_mask >= 0 && a.wk_mask + F0 <= a.wk_stride, CRUSE_E_SHAPE,
+                  "%s: wk_re %d / wk_im %d (+ %d) / wk_mask %d (+ %d) do not lie in a work row of %d floats (>= %d)", who, a.wk_re, a.wk_im, NB,
+                  a.wk_mask, F0, a.wk_stride, 2 * NB + F0);
+    DfLayout D;
+    make_df_layout(D);
+    CRUSE_REQUIRE(a.st_stride >= D.stride, CRUSE_E_SHAPE, "%s: df_state rows of %d floats, the layout needs %d", who, a.st_stride, D.stride);
+    const int rc = out_args(who, a.fmt, a.clip);
+    if (rc) return rc;
+    if (a.packet)
+        CRUSE_REQUIRE(a.hops >= 1 && a.hops <= DF_MAX_HOPS && a.work_frames >= a.hops + 1 && a.io_hops >= a.hops && a.dw >= a.hops, CRUSE_E_SHAPE,
+                      "%s: hops = %d (1..%d), work_frames = %d (>= hops + 1), out_hops = %d, dw_frames = %d (>= hops)", who, a.hops, DF_MAX_HOPS,
+                      a.work_frames, a.io_hops, a.dw);
+    else
+        CRUSE_REQUIRE(a.dw >= 2 * NB, CRUSE_E_SHAPE, "%s: df_work rows of %d floats, need %d", who, a.dw, 2 * NB);
+    return with_form<false>(a, [&](auto out, auto lim, auto) { return launch_df_head<decltype(out), decltype(lim)::value>(a, D, stream); });
+}
 
 }  // namespace
 
@@ -1165,40 +1168,16 @@ extern "C" int cruse_stream_df_layout(int* out) {
 extern "C" int cruse_stream_df_head(const int* mode, int S, int drain, const float* work, int wk_stride, int wk_re, int wk_im, int wk_mask,
                                     const float* tab, float* df_state, int st_stride, float* df_work, int dw_stride, void* out, int out_fmt,
                                     const float* lim, int* clip, int t_dim, int f_dim, void* stream) {
-    DfLayout D;
-    const int rc = df_head_args("stream_df_head", S, mode, work, wk_stride, wk_re, wk_im, wk_mask, tab, df_state, st_stride, df_work, out,
-                                out_fmt, clip, t_dim, f_dim, D);
-    if (rc) return rc;
-    CRUSE_REQUIRE(dw_stride >= 2 * NB, CRUSE_E_SHAPE, "stream_df_head: df_work rows of %d floats, need %d", dw_stride, 2 * NB);
-    const DfRows R = {work, wk_stride, wk_re, wk_im, wk_mask};
-#define CRUSE_DF_HEAD(OUT, LIM)                                                                                                        \
-    hipLaunchKernelGGL((stream_df_head_kernel<OUT, LIM>), dim3(S), dim3(DF_THREADS), 0, (hipStream_t)stream, mode, drain != 0, R, tab, \
-                       df_state, st_stride, D, df_work, dw_stride, (OUT*)out, lim, clip)
-    CRUSE_DF_FORMS(CRUSE_DF_HEAD)
-#undef CRUSE_DF_HEAD
-    CRUSE_LAUNCH_CHECK("cruse_stream_df_head");
-    return CRUSE_OK;
+    return df_head_any({{"cruse_stream_df_head", mode, S}, {}, {{}, tab}, {out, out_fmt, lim, clip}, {},
+                        {drain, work, wk_stride, wk_re, wk_im, wk_mask, df_state, st_stride, df_work, dw_stride, t_dim, f_dim}}, stream);
 }
 
 extern "C" int cruse_stream_df_head_n(const int* pk, int S, int hops, int out_hops, int work_frames, const float* work, int wk_stride,
                                       int wk_re, int wk_im, int wk_mask, const float* tab, float* df_state, int st_stride, float* df_work,
                                       int dw_frames, void* out, int out_fmt, const float* lim, int* clip, int t_dim, int f_dim,
                                       void* stream) {
-    DfLayout D;
-    const int rc = df_head_args("stream_df_head_n", S, pk, work, wk_stride, wk_re, wk_im, wk_mask, tab, df_state, st_stride, df_work, out,
-                                out_fmt, clip, t_dim, f_dim, D);
-    if (rc) return rc;
-    CRUSE_REQUIRE(hops >= 1 && hops <= DF_MAX_HOPS && work_frames >= hops + 1 && out_hops >= hops && dw_frames >= hops, CRUSE_E_SHAPE,
-                  "stream_df_head_n: hops = %d (1..%d), work_frames = %d (>= hops + 1), out_hops = %d, dw_frames = %d (>= hops)", hops,
-                  DF_MAX_HOPS, work_frames, out_hops, dw_frames);
-    const DfRows R = {work, wk_stride, wk_re, wk_im, wk_mask};
-#define CRUSE_DF_HEAD_N(OUT, LIM)                                                                                                       \
-    hipLaunchKernelGGL((stream_df_head_n_kernel<OUT, LIM>), dim3(S), dim3(DF_THREADS), 0, (hipStream_t)stream, pk, S, hops, out_hops,  \
-                       work_frames, R, tab, df_state, st_stride, D, df_work, dw_frames, (OUT*)out, lim, clip)
-    CRUSE_DF_FORMS(CRUSE_DF_HEAD_N)
-#undef CRUSE_DF_HEAD_N
-    CRUSE_LAUNCH_CHECK("cruse_stream_df_head_n");
-    return CRUSE_OK;
+    return df_head_any({{"cruse_stream_df_head_n", pk, S}, {true, hops, out_hops, work_frames}, {{}, tab}, {out, out_fmt, lim, clip}, {},
+                        {0, work, wk_stride, wk_re, wk_im, wk_mask, df_state, st_stride, df_work, dw_frames, t_dim, f_dim}}, stream);
 }
 
 extern "C" int cruse_stream_layout(int c0, int c1, int c2, int c3, int c4, int* out) {
@@ -1234,12 +1213,12 @@ extern "C" int cruse_stream_tables(float* tab, void* stream) {
 
 extern "C" int cruse_stream_encode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* in, const float* tab,
                                    const float* w, float* state, float* work, void* stream) {
-    return encode_any("stream_encode", "cruse_stream_encode", mode, S, c0, c1, c2, c3, c4, in, FMT_F32, tab, w, state, work, stream);
+    return encode_any({{"cruse_stream_encode", mode, S}, {}, {{c0, c1, c2, c3, c4}, tab, w, 0.f, state, work}, {in}}, stream);
 }
 
 extern "C" int cruse_stream_encode_io(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const void* in, int in_fmt,
                                       const float* tab, const float* w, float* state, float* work, void* stream) {
-    return encode_any("stream_encode_io", "cruse_stream_encode_io", mode, S, c0, c1, c2, c3, c4, in, in_fmt, tab, w, state, work, stream);
+    return encode_any({{"cruse_stream_encode_io", mode, S}, {}, {{c0, c1, c2, c3, c4}, tab, w, 0.f, state, work}, {in, in_fmt}}, stream);
 }
 
 extern "C" int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg, const float* x, int x_stride, int x_off,
@@ -1253,32 +1232,22 @@ extern "C" int cruse_stream_gru(const int* mode, int S, int layer, int g, int Hg
 
 extern "C" int cruse_stream_decode(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
                                    float ln_eps, float* state, float* work, float* out, void* stream) {
-    return decode_any<DEC_CONVT>("stream_decode", "cruse_stream_decode", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out, FMT_F32,
-                                 nullptr, nullptr, stream);
+    return decode_any({{"cruse_stream_decode", mode, S}, {}, {{c0, c1, c2, c3, c4}, tab, w, ln_eps, state, work}, {out}}, stream);
 }
 
 extern "C" int cruse_stream_decode_io(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
                                       float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
                                       void* stream) {
-    return decode_any<DEC_CONVT>("stream_decode_io", "cruse_stream_decode_io", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out,
-                                 out_fmt, lim, clip, stream);
+    return decode_any({{"cruse_stream_decode_io", mode, S}, {}, {{c0, c1, c2, c3, c4}, tab, w, ln_eps, state, work},
+                       {out, out_fmt, lim, clip}}, stream);
 }
 
 // the perceptual post-filter in the gain line (utils/utils.py:345-362): the _io arguments plus the kind and the per-slot tau
-static int pf_args(const char* who, int pf_kind, const float* pf_tau) {
-    const int rc = cruse_pf::kind_args(who, pf_kind);
-    if (rc) return rc;
-    CRUSE_REQUIRE(pf_tau != nullptr, CRUSE_E_SHAPE, "%s: null pf_tau", who);
-    return CRUSE_OK;
-}
-
 extern "C" int cruse_stream_decode_pf(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
                                       float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
                                       int pf_kind, const float* pf_tau, void* stream) {
-    const int rc = pf_args("cruse_stream_decode_pf", pf_kind, pf_tau);
-    if (rc) return rc;
-    return decode_any<DEC_CONVT>("stream_decode_pf", "cruse_stream_decode_pf", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out,
-                                 out_fmt, lim, clip, stream, pf_kind, pf_tau);
+    return decode_any({{"cruse_stream_decode_pf", mode, S}, {}, {{c0, c1, c2, c3, c4}, tab, w, ln_eps, state, work}, {out, out_fmt, lim, clip},
+                       {true, pf_kind, pf_tau}}, stream);
 }
 
 extern "C" int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4, int* out) {
@@ -1295,15 +1264,15 @@ extern "C" int cruse_stream_packet_layout(int c0, int c1, int c2, int c3, int c4
 
 extern "C" int cruse_stream_encode_n(const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                      const float* in, const float* tab, const float* w, float* state, float* work, void* stream) {
-    return encode_n_any("stream_encode_n", "cruse_stream_encode_n", pk, S, hops, in_hops, work_frames, c0, c1, c2, c3, c4, in, FMT_F32, tab, w,
-                        state, work, stream);
+    return encode_any({{"cruse_stream_encode_n", pk, S}, {true, hops, in_hops, work_frames},
+                       {{c0, c1, c2, c3, c4}, tab, w, 0.f, state, work}, {in}}, stream);
 }
 
 extern "C" int cruse_stream_encode_n_io(const int* pk, int S, int hops, int in_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                         const void* in, int in_fmt, const float* tab, const float* w, float* state, float* work,
                                         void* stream) {
-    return encode_n_any("stream_encode_n_io", "cruse_stream_encode_n_io", pk, S, hops, in_hops, work_frames, c0, c1, c2, c3, c4, in, in_fmt,
-                        tab, w, state, work, stream);
+    return encode_any({{"cruse_stream_encode_n_io", pk, S}, {true, hops, in_hops, work_frames},
+                       {{c0, c1, c2, c3, c4}, tab, w, 0.f, state, work}, {in, in_fmt}}, stream);
 }
 
 extern "C" int cruse_stream_gru_proj_n(const int* pk, int S, int hops, int work_frames, int layer, int g, int Hg, const float* work,
@@ -1326,44 +1295,70 @@ extern "C" int cruse_stream_gru_rec_n(const int* pk, int S, int hops, int work_f
 
 extern "C" int cruse_stream_decode_n(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                      const float* tab, const float* w, float ln_eps, float* state, float* work, float* out, void* stream) {
-    return decode_n_any<DEC_CONVT>("stream_decode_n", "cruse_stream_decode_n", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab, w,
-                                   ln_eps, state, work, out, FMT_F32, nullptr, nullptr, stream);
+    return decode_any({{"cruse_stream_decode_n", pk, S}, {true, hops, out_hops, work_frames},
+                       {{c0, c1, c2, c3, c4}, tab, w, ln_eps, state, work}, {out}}, stream);
 }
 
 extern "C" int cruse_stream_decode_n_io(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                         const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
                                         const float* lim, int* clip, void* stream) {
-    return decode_n_any<DEC_CONVT>("stream_decode_n_io", "cruse_stream_decode_n_io", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab,
-                                   w, ln_eps, state, work, out, out_fmt, lim, clip, stream);
+    return decode_any({{"cruse_stream_decode_n_io", pk, S}, {true, hops, out_hops, work_frames},
+                       {{c0, c1, c2, c3, c4}, tab, w, ln_eps, state, work}, {out, out_fmt, lim, clip}}, stream);
 }
 
 extern "C" int cruse_stream_decode_n_pf(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                         const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
                                         const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream) {
-    const int rc = pf_args("cruse_stream_decode_n_pf", pf_kind, pf_tau);
-    if (rc) return rc;
-    return decode_n_any<DEC_CONVT>("stream_decode_n_pf", "cruse_stream_decode_n_pf", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab,
-                                   w, ln_eps, state, work, out, out_fmt, lim, clip, stream, pf_kind, pf_tau);
+    return decode_any({{"cruse_stream_decode_n_pf", pk, S}, {true, hops, out_hops, work_frames},
+                       {{c0, c1, c2, c3, c4}, tab, w, ln_eps, state, work}, {out, out_fmt, lim, clip}, {true, pf_kind, pf_tau}}, stream);
 }
 
 // ---- the upsample decoder of CRUSE4MagAddSkipUpsample (cust_conv.py:163-166,177-184): the _pf argument lists, every form in one pair.
 // pf_kind 0: no post-filter, pf_tau is not read; out_fmt 0, null lim and null clip: the plain form.
-static int up_pf_args(const char* who, int pf_kind, const float* pf_tau) { return pf_kind == 0 ? CRUSE_OK : pf_args(who, pf_kind, pf_tau); }
-
 extern "C" int cruse_stream_decode_up(const int* mode, int S, int c0, int c1, int c2, int c3, int c4, const float* tab, const float* w,
                                       float ln_eps, float* state, float* work, void* out, int out_fmt, const float* lim, int* clip,
                                       int pf_kind, const float* pf_tau, void* stream) {
-    const int rc = up_pf_args("cruse_stream_decode_up", pf_kind, pf_tau);
-    if (rc) return rc;
-    return decode_any<DEC_UPCONV>("stream_decode_up", "cruse_stream_decode_up", mode, S, c0, c1, c2, c3, c4, tab, w, ln_eps, state, work, out,
-                                  out_fmt, lim, clip, stream, pf_kind, pf_kind ? pf_tau : nullptr);
+    return decode_any({{"cruse_stream_decode_up", mode, S}, {}, {{c0, c1, c2, c3, c4}, tab, w, ln_eps, state, work}, {out, out_fmt, lim, clip},
+                       {false, pf_kind, pf_tau, DEC_UPCONV}}, stream);
 }
 
 extern "C" int cruse_stream_decode_n_up(const int* pk, int S, int hops, int out_hops, int work_frames, int c0, int c1, int c2, int c3, int c4,
                                         const float* tab, const float* w, float ln_eps, float* state, float* work, void* out, int out_fmt,
                                         const float* lim, int* clip, int pf_kind, const float* pf_tau, void* stream) {
-    const int rc = up_pf_args("cruse_stream_decode_n_up", pf_kind, pf_tau);
-    if (rc) return rc;
-    return decode_n_any<DEC_UPCONV>("stream_decode_n_up", "cruse_stream_decode_n_up", pk, S, hops, out_hops, work_frames, c0, c1, c2, c3, c4, tab,
-                                    w, ln_eps, state, work, out, out_fmt, lim, clip, stream, pf_kind, pf_kind ? pf_tau : nullptr);
+    return decode_any({{"cruse_stream_decode_n_up", pk, S}, {true, hops, out_hops, work_frames},
+                       {{c0, c1, c2, c3, c4}, tab, w, ln_eps, state, work}, {out, out_fmt, lim, clip}, {false, pf_kind, pf_tau, DEC_UPCONV}}, stream);
+}
+
+// What a call of an entry point launches: calls fn itself, with plan_out set, on its ints from v in their order, 0 for a float (ln_eps)
+// and the null stream.  Bit i of null_mask: its i-th pointer argument is null; the others get a stand-in, which nothing on the host
+// reads through.
+template <typename... A>
+static int plan_call(int (*fn)(A...), const int* v, int null_mask, int* out) {
+    static float standin[4];
+    int bit = 0;
+    auto arg = [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        if constexpr (std::is_pointer<T>::value) return (T)((null_mask >> bit++ & 1) ? nullptr : standin);
+        else return std::is_floating_point<T>::value ? T(0) : T(*v++);
+    };
+    std::tuple<A...> args{arg((A*)nullptr)...};           // a braced list: evaluated left to right
+    std::get<sizeof...(A) - 1>(args) = nullptr;           // the stream
+    plan_out = out;
+    const int rc = std::apply(fn, args);
+    plan_out = nullptr;
+    return rc;
+}
+
+template <auto FN>
+static int plan_of(const int* v, int null_mask, int* out) { return plan_call(FN, v, null_mask, out); }
+
+extern "C" int cruse_stream_boundary_plan(int entry, const int* v, int null_mask, int* out) {
+    static int (*const entries[])(const int*, int, int*) = {       // in the order of CRUSE_STREAM_ENTRY_*
+        plan_of<cruse_stream_encode>, plan_of<cruse_stream_encode_io>, plan_of<cruse_stream_decode>, plan_of<cruse_stream_decode_io>,
+        plan_of<cruse_stream_decode_pf>, plan_of<cruse_stream_decode_up>, plan_of<cruse_stream_encode_n>, plan_of<cruse_stream_encode_n_io>,
+        plan_of<cruse_stream_decode_n>, plan_of<cruse_stream_decode_n_io>, plan_of<cruse_stream_decode_n_pf>, plan_of<cruse_stream_decode_n_up>,
+        plan_of<cruse_stream_df_head>, plan_of<cruse_stream_df_head_n>};
+    static_assert(sizeof(entries) / sizeof(*entries) == CRUSE_STREAM_ENTRY_N, "one per entry point");
+    CRUSE_REQUIRE(entry >= 0 && entry < CRUSE_STREAM_ENTRY_N && v && out, CRUSE_E_SHAPE, "stream_boundary_plan: entry %d or a null array", entry);
+    return entries[entry](v, null_mask, out);
 }

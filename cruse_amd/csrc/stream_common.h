@@ -1,5 +1,6 @@
 // Shared pieces of the streaming kernels (stream.hip: f32 chain; stream_f16.hip: f16-operand MFMA GRU): the packet schedule, the
-// "does this slot compute a frame" test, and the launch arguments / row addressing / argument checks of the GRU entry points.
+// "does this slot compute a frame" test, the launch arguments / row addressing / argument checks of the GRU entry points, and the
+// sample-format checks of the boundary kernels and the resamplers (stream_rs.hip).
 #pragma once
 #include "common.h"
 
@@ -142,6 +143,23 @@ inline int gru_rec_args(const char* who, const int* pk, int S, int hops, int wor
     a.pack = pack;
     a.out = work + (size_t)frame * wk_stride; a.o_stride = slot; a.o_off = h_off;
     a.gi = const_cast<float*>(gi) + (size_t)frame * 3 * g * Hg; a.gi_stride = (long long)work_frames * 3 * g * Hg;
+    return CRUSE_OK;
+}
+
+// ---- host: the sample formats of the I/O forms (in_fmt / out_fmt of the header: the boundary kernels of stream.hip, the resamplers of
+// stream_rs.hip) and their checks
+enum { FMT_F32 = 0, FMT_S16 = 1 };
+
+inline int fmt_args(const char* who, int fmt) {
+    CRUSE_REQUIRE(fmt == FMT_F32 || fmt == FMT_S16, CRUSE_E_SHAPE, "%s: unknown sample format %d (0: f32, 1: s16)", who, fmt);
+    return CRUSE_OK;
+}
+
+// the clamp counter belongs to PCM output: f32 output is never clamped
+inline int out_args(const char* who, int out_fmt, const int* clip) {
+    const int rc = fmt_args(who, out_fmt);
+    if (rc) return rc;
+    CRUSE_REQUIRE(out_fmt == FMT_S16 || clip == nullptr, CRUSE_E_SHAPE, "%s: a clip counter needs s16 output (out_fmt 1), got out_fmt %d", who, out_fmt);
     return CRUSE_OK;
 }
 

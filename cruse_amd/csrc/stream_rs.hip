@@ -20,7 +20,6 @@ constexpr int RS_THREADS = 256;
 constexpr int TAPS_PAD = 100;             // N = 97 at q = 3, padded
 constexpr int MAX_HIST = 96;              // N - 1 at q = 3
 constexpr int MAX_BLOCK = 480;            // 10 ms at 48 kHz
-enum { FMT_F32 = 0, FMT_S16 = 1 };
 enum { SIDE_IN = 0, SIDE_OUT = 1 };
 
 // The sample formats of DESIGN 12c.  ld_sample / st_sample live in stream.hip, which stays as it is: the two one-liners are restated.
@@ -130,9 +129,8 @@ int resample_any(const char* who, const char* name, int side, const int* ctl, in
     CRUSE_REQUIRE(S > 0 && ctl && in && taps && rs_state && out, CRUSE_E_SHAPE, "%s: S = %d or a null buffer", who, S);
     CRUSE_REQUIRE(io_rate == 8000 || io_rate == 32000 || io_rate == 48000, CRUSE_E_SHAPE,
                   "%s: unknown io_rate %d (8000, 32000 or 48000; 16000 needs no resampling)", who, io_rate);
-    CRUSE_REQUIRE(fmt == FMT_F32 || fmt == FMT_S16, CRUSE_E_SHAPE, "%s: unknown sample format %d (0: f32, 1: s16)", who, fmt);
-    if (side == SIDE_OUT)
-        CRUSE_REQUIRE(fmt == FMT_S16 || clip == nullptr, CRUSE_E_SHAPE, "%s: a clip counter needs s16 output (out_fmt 1), got out_fmt %d", who, fmt);
+    const int rc = side == SIDE_OUT ? out_args(who, fmt, clip) : fmt_args(who, fmt);
+    if (rc) return rc;
     if (hops != 0) {
         CRUSE_REQUIRE(hops >= 1, CRUSE_E_SHAPE, "%s: hops = %d", who, hops);
         CRUSE_REQUIRE(stride_blocks >= hops, CRUSE_E_SHAPE, "%s: %s = %d < hops = %d", who, side == SIDE_IN ? "in_hops" : "out_hops",

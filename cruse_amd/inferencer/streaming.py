@@ -230,8 +230,7 @@ class StreamingInferencer:
         self._pf_kind = pf_kind
         self.clip = torch.zeros(S, device=dev, dtype=torch.int32) if self.pcm_out else None     # clamped samples per slot
         self.mode = torch.zeros(2, S, device=dev, dtype=torch.int32)            # row 0: the frame-0 chain, row 1: the main chain
-        self._mode_host = torch.zeros(2, S, dtype=torch.int32).pin_memory()
-        self._host_free = None                                                  # event: the last copy out of _mode_host is done
+        self._mode_host = [torch.zeros(2, S, dtype=torch.int32).pin_memory(), None]     # pinned twin, event: the last copy out of it is done
         self.tab = ops.stream_tables(dev)
         self.nblk = np.zeros(S, dtype=np.int64)                                 # blocks pushed per slot since its last reset
         self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
@@ -256,8 +255,7 @@ class StreamingInferencer:
             self.pwork = torch.zeros(S, K + 1, play["wk_stride"], device=dev)   # one work row per frame of a packet
             self.gi = torch.zeros(S, K + 1, 3 * self.H, device=dev)             # GRU input products of the layer in flight
             self.pk = torch.zeros(2, S, device=dev, dtype=torch.int32)          # row 0: min(blocks held, 2), row 1: counts
-            self._pk_host = torch.zeros(2, S, dtype=torch.int32).pin_memory()
-            self._pk_free = None
+            self._pk_host = [torch.zeros(2, S, dtype=torch.int32).pin_memory(), None]
         self.refresh()
 
     @property
@@ -352,15 +350,20 @@ class StreamingInferencer:
 
         self._replay(("drain", passes) if drain else passes, hop)
 
+    @staticmethod
+    def _upload(dev: torch.Tensor, twin: list, row0, row1) -> None:
+        """Rows 0 and 1 of the [2, S] device tensor dev (mode, pk) through twin = [pinned host tensor, event]: wait until the previous copy
+        out of the host tensor is done, fill it, copy without blocking, record the event the next upload waits for."""
+        if twin[1] is not None:
+            twin[1].synchronize()
+        h = twin[0].numpy()
+        h[0], h[1] = row0, row1
+        dev.copy_(twin[0], non_blocking=True)
+        twin[1] = torch.cuda.Event()
+        twin[1].record()
+
     def _run(self, m0: np.ndarray, m1: np.ndarray, drain: bool = False) -> None:
-        if self._host_free is not None:
-            self._host_free.synchronize()
-        hm = self._mode_host.numpy()
-        hm[0], hm[1] = m0, m1
-        self.mode.copy_(self._mode_host, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._host_free = ev
+        self._upload(self.mode, self._mode_host, m0, m1)
         self._launch(2 if m0.any() else 1, drain)
 
     def _samples(self, t: torch.Tensor, who: str) -> torch.Tensor:
@@ -407,10 +410,10 @@ class StreamingInferencer:
     def flush(self, slots) -> torch.Tensor:
         """End the clip of each slot in `slots`: computes its end frame and returns its last output block ([len(slots), 160],
         device), then resets the slot.  A slot must hold at least two blocks.  head="df": the last two blocks, [len(slots), 320]."""
-        slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
+        if slots is None:
+            raise TypeError("flush: slots is None (a flush names its slots)")
+        slots = self._slot_list(slots)
         for s in slots:
-            if not 0 <= s < self.S:
-                raise ValueError(f"slot {s} out of range [0, {self.S})")
             if self.nblk[s] < 2:
                 raise ValueError(f"cannot flush slot {s}: it holds {self.nblk[s]} block(s), a clip needs at least 2 (L >= 320)")
         m1 = np.zeros(self.S, dtype=np.int32)
@@ -429,9 +432,7 @@ class StreamingInferencer:
     @torch.no_grad()
     def reset(self, slots=None) -> None:
         """Zero the state of `slots` (None: all): the next push to such a slot is block 0 of a new clip."""
-        if slots is None:
-            slots = list(range(self.S))
-        slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
+        slots = self._slot_list(slots, in_range=False)                          # (as ever, reset leaves the range to the indexing)
         if slots:
             idx = torch.tensor(slots, device=self.device, dtype=torch.long)
             self.state.index_fill_(0, idx, 0.0)
@@ -443,14 +444,28 @@ class StreamingInferencer:
         self._last_frames[slots] = 0
 
     # -- attenuation limit, clip counters -----------------------------------------------------------------------------------
-    def _slot_list(self, slots):
+    def _slot_list(self, slots, in_range: bool = True):
         if slots is None:
             return list(range(self.S))
         slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
         for s in slots:
-            if not 0 <= s < self.S:
+            if in_range and not 0 <= s < self.S:
                 raise ValueError(f"slot {s} out of range [0, {self.S})")
         return slots
+
+    def _set_per_slot(self, tensor: torch.Tensor, values, slots, convert, who: str) -> None:
+        """tensor[slots] = convert(values): a scalar (or None) for all of `slots` (None: all), or one value per listed slot"""
+        slots = self._slot_list(slots)
+        if values is None or np.ndim(values) == 0:
+            vals = [values] * len(slots)
+        else:
+            vals = list(values.tolist() if torch.is_tensor(values) or isinstance(values, np.ndarray) else values)
+            if len(vals) != len(slots):
+                raise ValueError(f"{who}: {len(vals)} values for {len(slots)} slots")
+        vals = [convert(v) for v in vals]                                       # refuses negative and NaN before anything is copied
+        if slots:
+            idx = torch.tensor(slots, device=self.device, dtype=torch.long)
+            tensor.index_copy_(0, idx, torch.tensor(vals, dtype=torch.float32).to(self.device))
 
     @torch.no_grad()
     def set_atten_lim(self, db, slots=None) -> None:
@@ -459,17 +474,7 @@ class StreamingInferencer:
         stays until it is set again (reset and flush keep it).  Needs atten_lim=True at construction."""
         if not self.atten_lim:
             raise ValueError("set_atten_lim: this StreamingInferencer was built without atten_lim=True (its kernels read no limits)")
-        slots = self._slot_list(slots)
-        if db is None or np.ndim(db) == 0:
-            vals = [db] * len(slots)
-        else:
-            vals = list(db.tolist() if torch.is_tensor(db) or isinstance(db, np.ndarray) else db)
-            if len(vals) != len(slots):
-                raise ValueError(f"set_atten_lim: {len(vals)} values for {len(slots)} slots")
-        gains = [ops.atten_lim_gain(v) for v in vals]                          # refuses negative and NaN before anything is copied
-        if slots:
-            idx = torch.tensor(slots, device=self.device, dtype=torch.long)
-            self.lim.index_copy_(0, idx, torch.tensor(gains, dtype=torch.float32).to(self.device))
+        self._set_per_slot(self.lim, db, slots, ops.atten_lim_gain, "set_atten_lim")
 
     def _pf(self):
         """the pf argument of the decode calls: None without a post-filter (the calls are then today's)"""
@@ -482,17 +487,7 @@ class StreamingInferencer:
         stays until it is set again (reset and flush keep it).  Needs post_filter="iam" or "envelope" at construction."""
         if self.pf is None:
             raise ValueError("set_post_filter: this StreamingInferencer was built without post_filter (its kernels read no tau)")
-        slots = self._slot_list(slots)
-        if np.ndim(tau) == 0:
-            vals = [tau] * len(slots)
-        else:
-            vals = list(tau.tolist() if torch.is_tensor(tau) or isinstance(tau, np.ndarray) else tau)
-            if len(vals) != len(slots):
-                raise ValueError(f"set_post_filter: {len(vals)} values for {len(slots)} slots")
-        vals = [ops.post_filter_tau(v) for v in vals]                           # refuses negative and NaN before anything is copied
-        if slots:
-            idx = torch.tensor(slots, device=self.device, dtype=torch.long)
-            self.pf.index_copy_(0, idx, torch.tensor(vals, dtype=torch.float32).to(self.device))
+        self._set_per_slot(self.pf, tau, slots, ops.post_filter_tau, "set_post_filter")
 
     @torch.no_grad()
     def clipped(self, slots=None, reset: bool = False) -> np.ndarray:
@@ -567,14 +562,7 @@ class StreamingInferencer:
         if hops == 0:
             return torch.zeros(S, K, HOP, device=self.device, dtype=self.out_dtype), torch.from_numpy(n_out)
         (self.io_pblocks if self._rs else self.pblocks)[:, :K].copy_(blocks, non_blocking=True)
-        if self._pk_free is not None:
-            self._pk_free.synchronize()
-        hp = self._pk_host.numpy()
-        hp[0], hp[1] = [p.start for p in plans], cnt
-        self.pk.copy_(self._pk_host, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._pk_free = ev
+        self._upload(self.pk, self._pk_host, [p.start for p in plans], cnt)
         self.nblk += cnt
         act = cnt > 0
         self._last_frames[act] = frames[act]

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from ._lib import PREC_BF16, PREC_BF16X3, PREC_BY_NAME, PREC_F32, check, lib  # noqa: F401
+from ._lib import PREC_BF16, PREC_BF16X3, PREC_BY_NAME, PREC_F32, SIGNATURES, check, lib  # noqa: F401
 
 
 def _stream() -> int:
@@ -1192,11 +1192,9 @@ def _stream_fmt(t: torch.Tensor, name: str) -> int:
     raise RuntimeError(f"{name}: expected float32 or int16 samples, got {t.dtype}")
 
 
-def _stream_io(out: torch.Tensor, lim, clip, name: str):
-    """(out_fmt, lim, clip) of a decode call, or None where the plain entry point serves it"""
+def _stream_out(out: torch.Tensor, lim, clip, name: str):
+    """(out_fmt, lim, clip) of a decode or head call; (STREAM_FMT_F32, None, None) is what the plain entry points serve"""
     fmt = _stream_fmt(out, name)
-    if fmt == STREAM_FMT_F32 and lim is None and clip is None:
-        return None
     if lim is not None and (lim.dtype != torch.float32 or lim.numel() != out.shape[0]):
         raise RuntimeError(f"{name}: lim must be float32 with one entry per slot ({out.shape[0]}), got {lim.dtype} x {lim.numel()}")
     if clip is not None and (clip.dtype != torch.int32 or clip.numel() != out.shape[0]):
@@ -1215,15 +1213,22 @@ def atten_lim_gain(db) -> float:
     return 0.0 if db == float("inf") else 10.0 ** (-db / 20.0)
 
 
+def _stream_dims(ctl, hops, io, work):
+    """the int arguments in front of the channels: S, or (hops given: a packet call) S, hops, the block stride of io, work_frames"""
+    return (ctl.numel(),) if hops is None else (ctl.shape[1], int(hops), io.shape[1], work.shape[1])
+
+
+def _stream_encode(name, ctl, hops, ch, blocks, tab, w, state, work) -> None:
+    """cruse_<name> for float32 blocks, cruse_<name>_io for int16; hops: None for the single hop"""
+    fmt = _stream_fmt(blocks, name)
+    fn, io = (getattr(lib, f"cruse_{name}"), ()) if fmt == STREAM_FMT_F32 else (getattr(lib, f"cruse_{name}_io"), (fmt,))
+    dims = _stream_dims(ctl, hops, blocks, work)
+    check(fn(_p(ctl), *dims, *[int(c) for c in ch], _p(blocks), *io, _p(tab), _p(w), _p(state), _p(work), _stream()))
+
+
 def stream_encode(mode, ch, blocks, tab, w, state, work) -> None:
     """blocks [S, 160]: float32, or int16 PCM (read as v / 32768, cruse_stream_encode_io)"""
-    fmt = _stream_fmt(blocks, "stream_encode")
-    if fmt == STREAM_FMT_F32:
-        check(lib.cruse_stream_encode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(blocks), _p(tab), _p(w), _p(state), _p(work),
-                                      _stream()))
-    else:
-        check(lib.cruse_stream_encode_io(_p(mode), mode.numel(), *[int(c) for c in ch], _p(blocks), fmt, _p(tab), _p(w), _p(state),
-                                         _p(work), _stream()))
+    _stream_encode("stream_encode", mode, None, ch, blocks, tab, w, state, work)
 
 
 def _f16_args(name, pack16):
@@ -1291,25 +1296,32 @@ def post_filter(mask: torch.Tensor, tau=0.02, kind: str = "iam", out: Optional[t
     return out
 
 
-def _stream_pf(pf, out: torch.Tensor, name: str):
-    """(pf_kind, pf_tau) of a decode call from pf = (kind, tau [S] f32)"""
-    kind, tau = pf
-    if tau.dtype != torch.float32 or tau.numel() != out.shape[0] or not tau.is_contiguous():
-        raise RuntimeError(f"{name}: pf tau must be float32 with one entry per slot ({out.shape[0]}), got {tau.dtype} x {tau.numel()}")
-    return int(kind), _p(tau)
-
-
 STREAM_DECODERS = ("transposed", "upsample")     # convkxf's modes: ConvTranspose2d levels (unet_2), FreqUpsample + Conv2d levels
 
 
-def _stream_up(decoder, out: torch.Tensor, lim, clip, pf, name: str):
-    """None for the ConvTranspose decoder, else the tail (out_fmt, lim, clip, pf_kind, pf_tau) of a cruse_stream_decode_up / _n_up call"""
+def _stream_decode(name, ctl, hops, ch, tab, w, ln_eps, state, work, out, lim, clip, pf, decoder) -> None:
+    """The decode call of stream_decode / stream_decode_n: "upsample" is cruse_<name>_up in every form; else a post-filter selects _pf, else
+    int16 output, a limit or a counter _io, else the plain entry point.  hops: None for the single hop"""
     if decoder not in STREAM_DECODERS:
         raise ValueError(f"{name}: decoder must be one of {STREAM_DECODERS}, got {decoder!r}")
-    if decoder == "transposed":
-        return None
-    io = _stream_io(out, lim, clip, name) or (_stream_fmt(out, name), None, None)
-    return (*io, *(_stream_pf(pf, out, name) if pf is not None else (0, None)))
+    io = _stream_out(out, lim, clip, name)
+    pfa = (0, None)
+    if pf is not None:                                    # (pf_kind, tau [S] f32)
+        kind, tau = pf
+        if tau.dtype != torch.float32 or tau.numel() != out.shape[0] or not tau.is_contiguous():
+            raise RuntimeError(f"{name}: pf tau must be float32 with one entry per slot ({out.shape[0]}), got {tau.dtype} x {tau.numel()}")
+        pfa = (int(kind), _p(tau))
+    if decoder == "upsample":
+        suffix, tail = "_up", (*io, *pfa)
+    elif pf is not None:
+        suffix, tail = "_pf", (*io, *pfa)
+    elif out.dtype != torch.float32 or lim is not None or clip is not None:
+        suffix, tail = "_io", io
+    else:
+        suffix, tail = "", ()
+    fn = getattr(lib, f"cruse_{name}{suffix}")
+    check(fn(_p(ctl), *_stream_dims(ctl, hops, out, work), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state), _p(work),
+             _p(out), *tail, _stream()))
 
 
 def stream_decode(mode, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None, pf=None, decoder="transposed") -> None:
@@ -1317,24 +1329,7 @@ def stream_decode(mode, ch, tab, w, ln_eps, state, work, out, lim=None, clip=Non
     clip [S] int32: += the clamped samples per slot (int16 out only).  Any of them selects cruse_stream_decode_io.
     pf = (pf_kind, tau [S] f32): the perceptual post-filter on the mask before the limit (cruse_stream_decode_pf).
     decoder = "upsample": w holds the [Cout][Cin][3] decoder weights of CRUSE4MagAddSkipUpsample; every form is cruse_stream_decode_up."""
-    up = _stream_up(decoder, out, lim, clip, pf, "stream_decode")
-    if up is not None:
-        check(lib.cruse_stream_decode_up(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state),
-                                         _p(work), _p(out), *up, _stream()))
-        return
-    if pf is not None:
-        fmt = _stream_fmt(out, "stream_decode")
-        io = _stream_io(out, lim, clip, "stream_decode") or (fmt, None, None)
-        check(lib.cruse_stream_decode_pf(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state),
-                                         _p(work), _p(out), *io, *_stream_pf(pf, out, "stream_decode"), _stream()))
-        return
-    io = _stream_io(out, lim, clip, "stream_decode")
-    if io is None:
-        check(lib.cruse_stream_decode(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state), _p(work),
-                                      _p(out), _stream()))
-    else:
-        check(lib.cruse_stream_decode_io(_p(mode), mode.numel(), *[int(c) for c in ch], _p(tab), _p(w), float(ln_eps), _p(state),
-                                         _p(work), _p(out), *io, _stream()))
+    _stream_decode("stream_decode", mode, None, ch, tab, w, ln_eps, state, work, out, lim, clip, pf, decoder)
 
 
 # packets: up to `hops` blocks per slot in one chain (cruse_stream_*_n).  pk is the [2, S] int32 device tensor of the header
@@ -1349,13 +1344,7 @@ def stream_packet_layout(ch) -> Dict[str, int]:
 
 def stream_encode_n(pk, hops, ch, blocks, tab, w, state, work) -> None:
     """blocks [S, in_hops, 160]: float32, or int16 PCM (cruse_stream_encode_n_io)"""
-    fmt = _stream_fmt(blocks, "stream_encode_n")
-    if fmt == STREAM_FMT_F32:
-        check(lib.cruse_stream_encode_n(_p(pk), pk.shape[1], int(hops), blocks.shape[1], work.shape[1], *[int(c) for c in ch], _p(blocks),
-                                        _p(tab), _p(w), _p(state), _p(work), _stream()))
-    else:
-        check(lib.cruse_stream_encode_n_io(_p(pk), pk.shape[1], int(hops), blocks.shape[1], work.shape[1], *[int(c) for c in ch],
-                                           _p(blocks), fmt, _p(tab), _p(w), _p(state), _p(work), _stream()))
+    _stream_encode("stream_encode_n", pk, hops, ch, blocks, tab, w, state, work)
 
 
 def stream_gru_proj_n(pk, hops, layer, groups, Hg, work, x_off, pack, gi, ln_g=None, ln_b=None, ln_eps=1e-5, pack16=None) -> None:
@@ -1374,25 +1363,26 @@ def stream_gru_rec_n(pk, hops, frame, groups, Hg, gi, state, st_off, pack, work,
 def stream_decode_n(pk, hops, ch, tab, w, ln_eps, state, work, out, lim=None, clip=None, pf=None, decoder="transposed") -> None:
     """out [S, out_hops, 160]: float32 or int16 PCM; lim / clip as stream_decode (cruse_stream_decode_n_io); pf as stream_decode
     (cruse_stream_decode_n_pf); decoder as stream_decode (cruse_stream_decode_n_up)"""
-    up = _stream_up(decoder, out, lim, clip, pf, "stream_decode_n")
-    if up is not None:
-        check(lib.cruse_stream_decode_n_up(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab),
-                                           _p(w), float(ln_eps), _p(state), _p(work), _p(out), *up, _stream()))
-        return
-    if pf is not None:
-        fmt = _stream_fmt(out, "stream_decode_n")
-        io = _stream_io(out, lim, clip, "stream_decode_n") or (fmt, None, None)
-        check(lib.cruse_stream_decode_n_pf(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab),
-                                           _p(w), float(ln_eps), _p(state), _p(work), _p(out), *io,
-                                           *_stream_pf(pf, out, "stream_decode_n"), _stream()))
-        return
-    io = _stream_io(out, lim, clip, "stream_decode_n")
-    if io is None:
-        check(lib.cruse_stream_decode_n(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab), _p(w),
-                                        float(ln_eps), _p(state), _p(work), _p(out), _stream()))
-    else:
-        check(lib.cruse_stream_decode_n_io(_p(pk), pk.shape[1], int(hops), out.shape[1], work.shape[1], *[int(c) for c in ch], _p(tab),
-                                           _p(w), float(ln_eps), _p(state), _p(work), _p(out), *io, _stream()))
+    _stream_decode("stream_decode_n", pk, hops, ch, tab, w, ln_eps, state, work, out, lim, clip, pf, decoder)
+
+
+STREAM_BOUNDARY_ENTRIES = ("encode", "encode_io", "decode", "decode_io", "decode_pf", "decode_up", "encode_n", "encode_n_io", "decode_n",
+                           "decode_n_io", "decode_n_pf", "decode_n_up", "df_head", "df_head_n")        # CRUSE_STREAM_ENTRY_*
+_STREAM_PLAN_KEYS = ("family", "dec", "s16", "lim", "pf", "grid", "block", "lds_bytes", "wk_stride", "rowmax", "wcap")
+
+
+def stream_boundary_plan(entry: str, *args) -> dict:
+    """what cruse_stream_<entry>(*args, stream) launches (cruse_stream_boundary_plan; host-only): the kernel family and template instance,
+    grid, block, dynamic LDS bytes and the packet geometry, "raw" the array as the library wrote it.  entry: one of STREAM_BOUNDARY_ENTRIES;
+    args: of a pointer only "is it None (or 0)" counts, ln_eps is not looked at.  A call the entry point refuses raises its RuntimeError."""
+    sig = SIGNATURES[f"cruse_stream_{entry}"][0][:-1]
+    if len(args) != len(sig):
+        raise ValueError(f"stream_boundary_plan: cruse_stream_{entry} takes {len(sig)} arguments in front of the stream, got {len(args)}")
+    ints = [int(v) for c, v in zip(sig, args) if c == "i"]
+    nulls = sum(1 << i for i, v in enumerate(v for c, v in zip(sig, args) if c == "p") if not v)
+    out = (ctypes.c_int * len(_STREAM_PLAN_KEYS))()
+    check(lib.cruse_stream_boundary_plan(STREAM_BOUNDARY_ENTRIES.index(entry), (ctypes.c_int * len(ints))(*ints), nulls, out))
+    return dict(zip(_STREAM_PLAN_KEYS, out), raw=list(out))
 
 
 # the DeepFilter(1, 5) head at the end of a chain (cruse_stream_df_head / _df_head_n): one frame behind decode, state rows of its own
@@ -1409,17 +1399,12 @@ def stream_df_layout() -> Dict[str, int]:
     return dict(zip(STREAM_DF_LAYOUT_NAMES, list(arr)))
 
 
-def _df_head_io(out, lim, clip, name):
-    io = _stream_io(out, lim, clip, name)
-    return (STREAM_FMT_F32, None, None) if io is None else io
-
-
 def stream_df_head(mode, work, lay, tab, df_state, df_work, out, lim=None, clip=None, drain=False, df_dims=STREAM_DF_DIMS) -> None:
     """After stream_decode: every slot whose mode computes a frame takes the mask and the noisy spectrum of its row of work [S, wk_stride]
     (lay: wk_re / wk_im / wk_mask of stream_layout), writes E[t-1] to df_work [S, >= 322] and its block to out [S, 160] (float32 or
     int16; lim / clip as stream_decode).  drain: slots whose mode is END take a zero row instead (the clip's last E).  df_state
     [S, >= stream_df_layout()["stride"]] f32."""
-    fmt, plim, pclip = _df_head_io(out, lim, clip, "stream_df_head")
+    fmt, plim, pclip = _stream_out(out, lim, clip, "stream_df_head")
     _f32(df_work, "df_work")
     # rows may be a strided view (one row of several per slot): the kernel takes the row stride
     if not df_work.is_cuda or df_work.dim() != 2 or df_work.shape[0] != mode.numel() or df_work.shape[1] < STREAM_DF_ROW or df_work.stride(1) != 1:
@@ -1434,7 +1419,7 @@ def stream_df_head(mode, work, lay, tab, df_state, df_work, out, lim=None, clip=
 def stream_df_head_n(pk, hops, work, lay, tab, df_state, df_work, out, lim=None, clip=None, df_dims=STREAM_DF_DIMS) -> None:
     """After stream_decode_n: the same step for the frames of every slot's packet, in order.  work [S, work_frames, wk_stride];
     df_work [S, >= hops, 322]: one row per emitted E; out [S, out_hops, 160]: the emitted blocks from index 0."""
-    fmt, plim, pclip = _df_head_io(out, lim, clip, "stream_df_head_n")
+    fmt, plim, pclip = _stream_out(out, lim, clip, "stream_df_head_n")
     if df_work.dim() != 3 or df_work.shape[0] != pk.shape[1] or df_work.shape[2] != STREAM_DF_ROW or work.dim() != 3 or out.dim() != 3:
         raise RuntimeError(f"stream_df_head_n: expected work [S, frames, stride], out [S, hops, 160] and df_work [{pk.shape[1]}, rows, "
                            f"{STREAM_DF_ROW}], got {tuple(work.shape)}, {tuple(out.shape)}, {tuple(df_work.shape)}")

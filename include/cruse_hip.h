@@ -1051,6 +1051,19 @@ int cruse_stream_df_head_n(const int* pk, int S, int hops, int out_hops, int wor
                            int wk_im, int wk_mask, const float* tab, float* df_state, int st_stride, float* df_work, int dw_frames,
                            void* out, int out_fmt, const float* lim, int* clip, int t_dim, int f_dim, void* stream);
 
+/* ---- what a boundary entry point launches (additive; host-only: nothing is launched) ---------------------------------------------
+ * Runs entry point `entry` (encode, decode, the DeepFilter head: 14 in all) up to its launch.  ints (HOST): its int arguments in its own
+ * order; bit i of null_mask: its i-th pointer argument is null (pointers are only compared with null).  Returns the entry point's refusal
+ * (code and cruse_last_error()), else CRUSE_OK and out[CRUSE_STREAM_PLAN_INTS] (HOST): [0] kernel family (0 encode, 2 decode, 4 df_head;
+ * + 1 for _n)  [1] DEC (1: upsample levels)  [2] s16  [3] LIM  [4] PF  [5] grid x  [6] block x  [7] dynamic LDS bytes  [8] floats of a
+ * frame's work row, [9] of an LDS row, [10] of the LDS staging area (the last three: 0 for a single hop and for the head) */
+enum { CRUSE_STREAM_ENTRY_ENCODE, CRUSE_STREAM_ENTRY_ENCODE_IO, CRUSE_STREAM_ENTRY_DECODE, CRUSE_STREAM_ENTRY_DECODE_IO,
+       CRUSE_STREAM_ENTRY_DECODE_PF, CRUSE_STREAM_ENTRY_DECODE_UP, CRUSE_STREAM_ENTRY_ENCODE_N, CRUSE_STREAM_ENTRY_ENCODE_N_IO,
+       CRUSE_STREAM_ENTRY_DECODE_N, CRUSE_STREAM_ENTRY_DECODE_N_IO, CRUSE_STREAM_ENTRY_DECODE_N_PF, CRUSE_STREAM_ENTRY_DECODE_N_UP,
+       CRUSE_STREAM_ENTRY_DF_HEAD, CRUSE_STREAM_ENTRY_DF_HEAD_N, CRUSE_STREAM_ENTRY_N };
+#define CRUSE_STREAM_PLAN_INTS 11
+int cruse_stream_boundary_plan(int entry, const int* ints, int null_mask, int* out);
+
 /* ---- validation metrics on the device (ABI 13, additive; csrc/metrics.hip) -------------------------------------------------------
  * The two closed-form metrics of train_base/metrics.py, scored per clip of a batch ref[B][L], est[B][L] (f32) into out[B] (f32).
  * Every sum runs in a fixed order and there are no atomics: a result is bit-identical from run to run, and a clip scores the same
