@@ -167,6 +167,9 @@ SIGNATURES = {
     "cruse_stream_df_head": ("piipiiiippipipippiip", "i"),
     "cruse_stream_df_head_n": ("piiiipiiiippipipippiip", "i"),
     "cruse_stream_boundary_plan": ("ipip", "i"),
+    "cruse_stream_meter_layout": ("p", "i"),
+    "cruse_stream_meter": ("pipiiiippipppippip", "i"),
+    "cruse_stream_meter_n": ("piiiipiiiippipppippip", "i"),
     "cruse_si_sdr": ("ppiipp", "i"),
     "cruse_stoi_layout": ("iip", "i"),
     "cruse_stoi_ws_bytes": ("ii", "z"),

@@ -412,12 +412,17 @@ __global__ void wgrad_reduce_kernel(const float* partial, int nblk, int nout, fl
 
 // ---------------------------------------------------------------------------
 // channel sum: out[c] += sum_{rows,f} g[row,c,f]
+// ORDERED (a grid of one workgroup, few rows): no sum depends on the order in which atomics land -- a thread's column sum runs over
+// the rows in ascending order, a channel's columns are added in ascending order by one thread, and out[c] receives one addend --
+// so the result has the same bits from run to run.  Otherwise f32 atomics in LDS and across the grid's workgroups: the order is free.
 // ---------------------------------------------------------------------------
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void channel_sum_kernel(const float* g, long long rows, int C, int F, int ld,
                                                           float* out) {
     // grid.x strides over rows; each thread owns a fixed column j of the C*F-wide row (row stride ld);
     // 4 independent accumulators keep 4 loads in flight per thread
     __shared__ float sacc[2048];
+    [[maybe_unused]] __shared__ float scol[256];
     const int CF = C * F;
     const int tid = threadIdx.x;
     for (int c = tid; c < C; c += 256) sacc[c] = 0.f;
@@ -432,12 +437,25 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const float* g, long l
                 s0 += g[r * ld + j]; s1 += g[(r + G) * ld + j]; s2 += g[(r + 2 * G) * ld + j]; s3 += g[(r + 3 * G) * ld + j];
             }
             for (; r < rows; r += G) s0 += g[r * ld + j];
-            atomicAdd(&sacc[j / F], (s0 + s1) + (s2 + s3));
+            if constexpr (ORDERED) scol[tid] = (s0 + s1) + (s2 + s3);
+            else atomicAdd(&sacc[j / F], (s0 + s1) + (s2 + s3));
+        }
+        if constexpr (ORDERED) {                // thread t: channel c_lo + t of the <= 256 channels that have columns in this chunk
+            __syncthreads();
+            const int j1 = min(j0 + 256, CF), c = j0 / F + tid;
+            if (c <= (j1 - 1) / F) {
+                float a = sacc[c];
+                for (int k = max(c * F, j0); k < min((c + 1) * F, j1); ++k) a += scol[k - j0];
+                sacc[c] = a;
+            }
+            __syncthreads();
         }
     }
     __syncthreads();
     for (int c = tid; c < C; c += 256) atomicAdd(&out[c], sacc[c]);
 }
+
+constexpr long long CHANNEL_SUM_ORDERED_ROWS = 64;      // cruse_channel_sum: at most this many rows run as one ordered workgroup
 
 template <typename K>
 int set_smem(K kern, size_t bytes, const char* name) {
@@ -761,8 +779,13 @@ extern "C" int cruse_conv_wgrad(const float* a, const float* bt, float* dw,
 extern "C" int cruse_channel_sum(const float* g, long long rows, int C, int F, float* out, void* stream) {
     CRUSE_REQUIRE(rows > 0 && C > 0 && F > 0 && C <= 2048, CRUSE_E_SHAPE,
                   "channel_sum: bad shape rows=%lld C=%d F=%d (C <= 2048)", rows, C, F);
-    long long nb = rows < 512 ? rows : 512;
-    hipLaunchKernelGGL(channel_sum_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, g, rows, C, F, C * F, out);
+    // few rows (a training step of a few short clips): one workgroup walks them all, in a fixed order; there is no parallelism to lose
+    if (rows <= CHANNEL_SUM_ORDERED_ROWS) {
+        hipLaunchKernelGGL(channel_sum_kernel<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, g, rows, C, F, C * F, out);
+    } else {
+        long long nb = rows < 512 ? rows : 512;
+        hipLaunchKernelGGL(channel_sum_kernel<false>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, g, rows, C, F, C * F, out);
+    }
     CRUSE_LAUNCH_CHECK("channel_sum");
     return CRUSE_OK;
 }
@@ -771,7 +794,7 @@ extern "C" int cruse_col_sum(const float* g, long long rows, int ncol, int ld, f
     CRUSE_REQUIRE(rows > 0 && ncol > 0 && ncol <= 2048 && ld >= ncol, CRUSE_E_SHAPE,
                   "col_sum: bad shape rows=%lld ncol=%d ld=%d (ncol <= 2048)", rows, ncol, ld);
     long long nb = rows < 512 ? rows : 512;
-    hipLaunchKernelGGL(channel_sum_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, g, rows, ncol, 1, ld, out);
+    hipLaunchKernelGGL(channel_sum_kernel<false>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, g, rows, ncol, 1, ld, out);
     CRUSE_LAUNCH_CHECK("col_sum");
     return CRUSE_OK;
 }

@@ -133,6 +133,19 @@ class StreamingInferencer:
     CRUSE4MagAddSkipUpsample, whose decoder levels are nearest FreqUpsample + Conv2d (1,3) (cust_conv.py:163-166,177-184) in place of
     ConvTranspose2d.  Encoder, skips and GGRU are unet_2's, the decoder has time extent 1 and so no state of its own: the chains are the
     same but for their decode call (cruse_stream_decode_up / _n_up), and every option above composes as for unet_2.
+
+    meters = True (default False: nothing is allocated, captured or launched that was not before): one more kernel ends every chain
+    (cruse_stream_meter / _n) and tells, per slot and frame, what the server heard without a block being read back: a meter row
+    [L_in dBFS, L_out dBFS, p, vad] for every output block -- the level of the input frame, the level of the enhanced frame (both by
+    Parseval on the windowed frame, 10 log10(P + 1e-12): silence reads -120), the smoothed speech probability and the decision p > threshold
+    of an energy detector on the ENHANCED frame (the reference's activitydetector, utils/utils.py:143-183, with three repairs: the
+    recursion runs on the smoothed value, level_db is absolute and per slot instead of a whole-clip normalisation, and the constants are
+    converted from 50 ms windows to the 10 ms hop).  last_meters() is the device tensor of the last call's rows, activity() reads the
+    per-slot accumulators (frames, active frames, the level of the input and of the output over active frames: the reference's active_rms)
+    and set_vad() changes a slot's detector; like a limit the detector's parameters belong to the slot, and no graph is captured again.
+    L_out is the level of what decode put out: atten_lim and post_filter enter through the gain; precision, pcm_in / pcm_out and decoder do
+    not reach the kernel.  At another io_rate the levels are those of the model's 16 kHz side, before the output converter.  head="df"
+    refuses meters: that head's output is not mask * noisy and runs a frame behind.
     """
 
     HOP = 160
@@ -140,7 +153,7 @@ class StreamingInferencer:
     def __init__(self, model: torch.nn.Module, n_slots: int, n_fft: int = 320, hop_length: int = 160, win_length: int = 320,
                  device="cuda", use_graph: bool = True, max_hops: int = 1, precision: str = "f32", atten_lim: bool = False,
                  pcm_in: bool = False, pcm_out: bool = False, io_rate: int = 16000, head: str = "mask", df_dims=(1, 5),
-                 post_filter=None, decoder: str = "transposed"):
+                 post_filter=None, decoder: str = "transposed", meters: bool = False):
         from ..model.cruse import CRUSE4MagAddSkipUpsample
         from ..model.cruse_net import unet_2
         io_rate = resample.check_rate(io_rate)
@@ -155,6 +168,9 @@ class StreamingInferencer:
         if head == "df" and io_rate != resample.MODEL_RATE:
             raise ValueError(f"StreamingInferencer(head=\"df\") runs at io_rate = {resample.MODEL_RATE} only (the output converter follows the "
                              f"main chain's modes, which are one block ahead of the head), got io_rate = {io_rate}")
+        if meters and head == "df":
+            raise ValueError("StreamingInferencer(head=\"df\") takes no meters: the head's output is not mask * noisy and its rows run one "
+                             "frame behind the chain the meter reads")
         if (n_fft, hop_length, win_length) != (320, 160, 320):
             raise ValueError(f"StreamingInferencer supports n_fft = win_length = 320, hop_length = 160 only "
                              f"(got n_fft={n_fft}, hop_length={hop_length}, win_length={win_length})")
@@ -229,6 +245,16 @@ class StreamingInferencer:
         self.pf = torch.zeros(S, device=dev) if pf_kind is not None else None   # per-slot tau of the post-filter; 0: off
         self._pf_kind = pf_kind
         self.clip = torch.zeros(S, device=dev, dtype=torch.int32) if self.pcm_out else None     # clamped samples per slot
+        self.meters = bool(meters)
+        if self.meters:
+            # the detector's parameters (level_db, threshold, attack, release), p_prev, the f64 accumulators, the last call's rows
+            mlay = ops.stream_meter_layout()
+            d = ops.stream_vad_defaults()
+            self.vad_par = torch.tensor([[d["level_db"], d["threshold"], d["attack"], d["release"]]], dtype=torch.float64) \
+                .to(torch.float32).repeat(S, 1).to(dev)
+            self.meter_state = torch.zeros(S, mlay["stride"], device=dev)
+            self.meter_acc = torch.zeros(S, mlay["acc"], device=dev, dtype=torch.float64)
+            self.meter_out = torch.zeros(S, max(int(max_hops), 1), ops.STREAM_METER_ROW, device=dev)
         self.mode = torch.zeros(2, S, device=dev, dtype=torch.int32)            # row 0: the frame-0 chain, row 1: the main chain
         self._mode_host = [torch.zeros(2, S, dtype=torch.int32).pin_memory(), None]     # pinned twin, event: the last copy out of it is done
         self.tab = ops.stream_tables(dev)
@@ -319,6 +345,9 @@ class StreamingInferencer:
         ops.stream_decode(mode, self.ch, self.tab, self.w, self.ln2_eps, self.state, self.work, self.out, lim=self.lim,
                           clip=None if self._rs else self.clip,             # behind the converters, resample_out counts
                           pf=self._pf(), decoder=self.decoder)
+        if self.meters:
+            ops.stream_meter(mode, self.work, self.lay, self.tab, self.vad_par, self.meter_state, self.meter_acc, self.meter_out[:, 0],
+                             lim=self.lim, pf=self._pf())
 
     def _replay(self, key, fn) -> None:
         """run fn(): directly, or as the graph captured from it on the first call with this key"""
@@ -424,14 +453,19 @@ class StreamingInferencer:
         last = (self.io_out if self._rs else self.out).index_select(0, idx)
         if self._df:                                                            # the end frame's block, then the drain step's
             last = torch.cat([last, self.out_drain.index_select(0, idx)], dim=1)
-        self.reset(slots)
+        self._reset(slots, keep_activity=True)
         if self._df:
             self._df_rows[slots] = 2
         return last
 
     @torch.no_grad()
     def reset(self, slots=None) -> None:
-        """Zero the state of `slots` (None: all): the next push to such a slot is block 0 of a new clip."""
+        """Zero the state of `slots` (None: all): the next push to such a slot is block 0 of a new clip.  meters=True: the detector's
+        state and the slot's activity() accumulators are zeroed too (flush keeps the accumulators: they describe the clip just ended
+        until the slot's next clip begins)."""
+        self._reset(slots)
+
+    def _reset(self, slots, keep_activity: bool = False) -> None:
         slots = self._slot_list(slots, in_range=False)                          # (as ever, reset leaves the range to the indexing)
         if slots:
             idx = torch.tensor(slots, device=self.device, dtype=torch.long)
@@ -440,6 +474,10 @@ class StreamingInferencer:
                 self.rs_state.index_fill_(0, idx, 0.0)
             if self._df:
                 self.df_state.index_fill_(0, idx, 0.0)
+            if self.meters:
+                self.meter_state.index_fill_(0, idx, 0.0)
+                if not keep_activity:
+                    self.meter_acc.index_fill_(0, idx, 0.0)
         self.nblk[slots] = 0
         self._last_frames[slots] = 0
 
@@ -502,6 +540,58 @@ class StreamingInferencer:
             self.clip.index_fill_(0, idx, 0)
         return n
 
+    # -- level meters, voice activity -------------------------------------------------------------------------------------------
+    def _need_meters(self, who: str) -> None:
+        if not self.meters:
+            raise ValueError(f"{who}: this StreamingInferencer was built without meters=True (no meter kernel runs in its chains)")
+
+    def last_meters(self) -> torch.Tensor:
+        """The meter rows of the last call, [n_slots, max_hops, 4] on the device (the tensor the kernels write: no copy, no
+        synchronisation; clone it to keep it past the next call): row [s, j] = [L_in dBFS, L_out dBFS, p, vad] belongs to the j-th block
+        that call returned for slot s, and only as many rows as blocks are valid (push: row 0 where valid[s]; push_packet: n_out[s] rows;
+        flush: row 0 of each flushed slot).  Needs meters=True."""
+        self._need_meters("last_meters")
+        return self.meter_out
+
+    @torch.no_grad()
+    def activity(self, slots=None, reset: bool = False) -> np.ndarray:
+        """float64 host array [len(slots), 4] (slots None: all): frames metered, active frames (vad = 1), the level in dBFS of the input
+        and of the enhanced output over the active frames only (10 log10(mean P + 1e-12): the reference's active_rms on the detector's
+        own decisions; -120 without an active frame).  The accumulators start with a slot's clip (its frame 0 zeroes them), survive flush
+        and are zeroed by reset() or reset=True.  A host read-back, like clipped().  Needs meters=True."""
+        self._need_meters("activity")
+        slots = self._slot_list(slots)
+        idx = torch.tensor(slots, device=self.device, dtype=torch.long)
+        acc = self.meter_acc.index_select(0, idx).cpu().numpy().astype(np.float64).reshape(len(slots), 4)
+        if reset and slots:
+            self.meter_acc.index_fill_(0, idx, 0.0)
+        n = np.maximum(acc[:, 1], 1.0)
+        out = acc.copy()
+        out[:, 2:] = 10.0 * np.log10(acc[:, 2:] / n[:, None] + 1e-12)
+        return out
+
+    @torch.no_grad()
+    def set_vad(self, level_db=None, threshold=None, attack=None, release=None, slots=None) -> None:
+        """The detector of `slots` (None: all); every argument a scalar for all of them or one value per listed slot, None: unchanged.
+        level_db: the output level in dBFS at which the raw speech probability is 1/2 (default -28.23, ops.stream_vad_defaults);
+        threshold: vad = p > threshold (0.13); attack / release: the per-hop smoothing constants in (0, 1] towards a higher / lower
+        probability.  Takes effect with the slot's next frame and stays (reset and flush keep it).  Needs meters=True."""
+        self._need_meters("set_vad")
+
+        def finite(name, lo=None, hi=None):
+            def conv(v):
+                v = float(v)
+                if v != v or v in (float("inf"), float("-inf")) or (lo is not None and not v > lo) or (hi is not None and not v <= hi):
+                    raise ValueError(f"set_vad: {name} must be a finite number" + (f" in ({lo}, {hi}]" if lo is not None else "") + f", got {v}")
+                return v
+            return conv
+
+        for k, (name, val, conv) in enumerate((("level_db", level_db, finite("level_db")), ("threshold", threshold, finite("threshold")),
+                                               ("attack", attack, finite("attack", 0.0, 1.0)),
+                                               ("release", release, finite("release", 0.0, 1.0)))):
+            if val is not None:
+                self._set_per_slot(self.vad_par[:, k], val, slots, conv, f"set_vad({name})")
+
     # -- packets ----------------------------------------------------------------------------------------------------------
     def _packet_chain(self, hops: int, nf: int) -> None:
         """One linear chain for packets of up to `hops` blocks of which the longest slot computes `nf` frames."""
@@ -521,6 +611,9 @@ class StreamingInferencer:
             return
         ops.stream_decode_n(pk, hops, self.ch, self.tab, self.w, self.ln2_eps, self.state, wk, self.pout, lim=self.lim,
                             clip=None if self._rs else self.clip, pf=self._pf(), decoder=self.decoder)
+        if self.meters:
+            ops.stream_meter_n(pk, hops, wk, self.lay, self.tab, self.vad_par, self.meter_state, self.meter_acc, self.meter_out,
+                               lim=self.lim, pf=self._pf())
         if self._rs:
             ops.stream_resample_out_n(pk, hops, self.io_rate, self.pout, self.rs_taps, self.rs_state, self.io_pout, clip=self.clip)
 
@@ -574,13 +667,16 @@ class StreamingInferencer:
         return (self.io_pout if self._rs else self.pout)[:, :K].clone(), torch.from_numpy(n_out)
 
     @torch.no_grad()
-    def enhance(self, waves: torch.Tensor, hops=None) -> torch.Tensor:
+    def enhance(self, waves: torch.Tensor, hops=None, with_meters: bool = False):
         """Whole clips waves [n, L] (n <= n_slots, L >= 320, device or host) through push_packet with `hops` (default max_hops)
         blocks per call, then flush; -> [n, L] on the device.  Uses slots 0..n-1: resets them first and leaves them reset.  When L
         is not a multiple of 160 the clip is zero-padded to the next multiple and the result trimmed to L, so it equals the
         offline result OF THE PADDED CLIP (the end reflection then mirrors the padding).  Only one packet of the clip is on the
         device's work buffers at a time: memory beyond the input and output waveforms does not grow with L.  At another io_rate
-        320 and 160 read 2 * io_block and io_block."""
+        320 and 160 read 2 * io_block and io_block.  with_meters=True (needs meters=True): -> (waves [n, L], meters [n, frames - 1, 4]),
+        one meter row per block of the padded clip."""
+        if with_meters:
+            self._need_meters("enhance(with_meters=True)")
         if waves.dim() != 2:
             raise ValueError(f"enhance expects waves of shape (n, L), got {tuple(waves.shape)}")
         if self.pcm_in:
@@ -598,6 +694,7 @@ class StreamingInferencer:
         slots = list(range(n))
         self.reset(slots)
         res = torch.empty(n, nb * HOP, device=self.device, dtype=self.out_dtype)
+        met = torch.empty(n, nb, ops.STREAM_METER_ROW, device=self.device) if with_meters else None
         pkt = torch.zeros(S, hops * HOP, device=self.device, dtype=self.in_dtype)
         counts = np.zeros(S, dtype=np.int64)
         done = 0                                                                # output blocks written
@@ -611,8 +708,13 @@ class StreamingInferencer:
             out, n_out = self.push_packet(pkt, counts)
             k = int(n_out[0])
             res[:, done * HOP:(done + k) * HOP] = out[:n, :k].reshape(n, k * HOP)
+            if with_meters:
+                met[:, done:done + k] = self.meter_out[:n, :k]
             done += k
         res[:, done * HOP:] = self.flush(slots)
+        if with_meters:
+            met[:, done] = self.meter_out[:n, 0]
+            return res[:, :L], met
         return res[:, :L]
 
     # -- inspection ---------------------------------------------------------------------------------------------------------

@@ -1429,6 +1429,79 @@ def stream_df_head_n(pk, hops, work, lay, tab, df_state, df_work, out, lim=None,
                                      int(df_dims[0]), int(df_dims[1]), _stream()))
 
 
+# level meters and voice activity at the end of a chain (cruse_stream_meter / _meter_n): rows [L_in dBFS, L_out dBFS, p, vad]
+STREAM_METER_LAYOUT_NAMES = ("p", "stride", "acc", "row")
+STREAM_METER_ROW = 4        # floats of a meter row
+# the reference's activitydetector constants (utils/utils.py:143-154): 50 ms windows, logistic of a + b + 10 log10(sum of squares)
+_VAD_REF = dict(a=-1.0, b=0.2, window_samples=800, alpha_att=0.8, alpha_rel=0.05, target_level=-25.0, threshold=0.13, hops_per_window=5)
+
+
+def stream_vad_defaults() -> Dict[str, float]:
+    """The per-hop constants that reproduce the reference's activitydetector for a clip at its -25 dBFS target, in float64.
+    The reference normalises the clip to target_level = -25 dBFS and takes x = a + b + 10 log10(sum of 800 squared samples)
+    = a + b + 10 log10(800) + L, L the window's mean-square level in dB.  Here x = L_out - level_db on absolute levels, so for a clip that
+    already sits at the target, level_db = -25 - (a + b + 10 log10(800)) - (-25) = -(a + b + 10 log10(800)) = -28.23 with a = -1, b = 0.2.
+    One 50 ms window is five 10 ms hops: the per-hop attack 1 - (1 - 0.8)^(1/5) and release 1 - (1 - 0.05)^(1/5) reach, after five hops
+    towards a constant p_raw, what the reference's constants reach in one window."""
+    import math
+    r = _VAD_REF
+    n = r["hops_per_window"]
+    level = r["target_level"] - (r["a"] + r["b"] + 10.0 * math.log10(r["window_samples"])) - r["target_level"]
+    return {"level_db": level, "threshold": r["threshold"], "attack": 1.0 - (1.0 - r["alpha_att"]) ** (1.0 / n),
+            "release": 1.0 - (1.0 - r["alpha_rel"]) ** (1.0 / n)}
+
+
+def stream_meter_layout() -> Dict[str, int]:
+    """p: the offset of p_prev in a meter_state row; stride: floats of that row; acc: doubles of a meter_acc row; row: floats of a meter row"""
+    arr = (ctypes.c_int * len(STREAM_METER_LAYOUT_NAMES))()
+    check(lib.cruse_stream_meter_layout(arr))
+    return dict(zip(STREAM_METER_LAYOUT_NAMES, list(arr)))
+
+
+def _stream_meter_args(name, S, vad_par, meter_state, meter_acc, out, lim, pf):
+    """the checked tail of a meter call: (lim, pf_kind, pf_tau, vad_par, meter_state, st_stride, meter_acc, out, out_stride)"""
+    if vad_par.dtype != torch.float32 or tuple(vad_par.shape) != (S, 4):
+        raise RuntimeError(f"{name}: vad_par must be float32 [{S}, 4], got {vad_par.dtype} {tuple(vad_par.shape)}")
+    if meter_acc.dtype != torch.float64 or tuple(meter_acc.shape) != (S, 4):
+        raise RuntimeError(f"{name}: meter_acc must be float64 [{S}, 4], got {meter_acc.dtype} {tuple(meter_acc.shape)}")
+    if lim is not None and (lim.dtype != torch.float32 or lim.numel() != S):
+        raise RuntimeError(f"{name}: lim must be float32 with one entry per slot ({S}), got {lim.dtype} x {lim.numel()}")
+    kind, tau = (0, None) if pf is None else pf
+    if tau is not None and (tau.dtype != torch.float32 or tau.numel() != S):
+        raise RuntimeError(f"{name}: pf tau must be float32 with one entry per slot ({S}), got {tau.dtype} x {tau.numel()}")
+    # the rows of a slot may be a strided view (one row of several per slot): the kernel takes the slot stride
+    if out.dtype != torch.float32 or not out.is_cuda or out.dim() not in (2, 3) or out.shape[0] != S or out.shape[-1] != STREAM_METER_ROW \
+            or out.stride(-1) != 1 or (out.dim() == 3 and out.stride(1) != STREAM_METER_ROW):
+        raise RuntimeError(f"{name}: out must be float32 [{S}, {STREAM_METER_ROW}] or [{S}, rows, {STREAM_METER_ROW}] meter rows on the "
+                           f"device, got {out.dtype} {tuple(out.shape)} with strides {out.stride()}")
+    return (_p(lim), int(kind), _p(tau), _p(vad_par), _p(_f32(meter_state, "meter_state")), meter_state.shape[1], _p(meter_acc),
+            out.data_ptr(), out.stride(0))
+
+
+def stream_meter(mode, work, lay, tab, vad_par, meter_state, meter_acc, out, lim=None, pf=None) -> None:
+    """After stream_decode: every slot whose mode computes a frame reads the noisy spectrum and the mask of its row of work [S, wk_stride]
+    (lay: wk_re / wk_im / wk_mask of stream_layout) and writes [L_in dBFS, L_out dBFS, p, vad] to out[s] (out [S, 4], possibly a strided
+    view), p_prev to meter_state [S, >= stream_meter_layout()["stride"]] and its counts and sums to meter_acc [S, 4] f64; a FRAME0 slot
+    resets both and writes no row.  vad_par [S, 4] f32: level_db, threshold, attack, release.  lim / pf: those of the stream_decode call,
+    so that L_out is the level of what decode put out."""
+    S = mode.numel()
+    tail = _stream_meter_args("stream_meter", S, vad_par, meter_state, meter_acc, out, lim, pf)
+    check(lib.cruse_stream_meter(_p(mode), S, _p(_f32(work, "work")), work.shape[1], int(lay["wk_re"]), int(lay["wk_im"]),
+                                 int(lay["wk_mask"]), _p(tab), *tail, _stream()))
+
+
+def stream_meter_n(pk, hops, work, lay, tab, vad_par, meter_state, meter_acc, out, lim=None, pf=None) -> None:
+    """After stream_decode_n: the same for the frames of every slot's packet, in order.  work [S, work_frames, wk_stride]; out
+    [S, out_hops, 4]: one row per output block of the slot, from index 0 (a clip's frame 0 yields neither)."""
+    S = pk.shape[1]
+    if work.dim() != 3 or out.dim() != 3:
+        raise RuntimeError(f"stream_meter_n: expected work [S, frames, stride] and out [S, out_hops, {STREAM_METER_ROW}], got "
+                           f"{tuple(work.shape)}, {tuple(out.shape)}")
+    tail = _stream_meter_args("stream_meter_n", S, vad_par, meter_state, meter_acc, out, lim, pf)
+    check(lib.cruse_stream_meter_n(_p(pk), S, int(hops), out.shape[1], work.shape[1], _p(_f32(work, "work")), work.shape[2],
+                                   int(lay["wk_re"]), int(lay["wk_im"]), int(lay["wk_mask"]), _p(tab), *tail, _stream()))
+
+
 # 8 / 32 / 48 kHz I/O around the 16 kHz chains (cruse_stream_resample_*). taps: stream_resample_taps(io_rate); rs_state [S, >= the two
 # history sizes of inferencer.resample.history(io_rate)] f32: the slots' converter histories, zero at the start of a clip.
 def stream_resample_taps(io_rate: int, device) -> torch.Tensor:

@@ -1051,6 +1051,46 @@ int cruse_stream_df_head_n(const int* pk, int S, int hops, int out_hops, int wor
                            int wk_im, int wk_mask, const float* tab, float* df_state, int st_stride, float* df_work, int dw_frames,
                            void* out, int out_fmt, const float* lim, int* clip, int t_dim, int f_dim, void* stream);
 
+/* ---- per-slot level meters and voice activity on the stream (additive; csrc/stream_meter.hip) ---------------
+ * One more kernel at the end of a chain tells the caller what the server heard, frame by frame, without reading a block back: the level
+ * of the input, the level of the enhanced output and an energy voice-activity decision on the enhanced frame.  On the device they
+ * replace the reference's host numpy code utils/utils.py:143-183 (activitydetector: log-energy -> logistic -> attack / release smoothing
+ * -> threshold), :82-103 (active_rms: the level over active windows only) and :37-41 (normalize, which a stream cannot do: level_db is
+ * absolute and per slot).  The kernels follow cruse_stream_decode / _decode_n and read nothing but what the chain leaves in a frame's
+ * work row: the noisy spectrum N (161 floats at wk_re, 161 at wk_im) and the raw mask m (160 at wk_mask), rows wk_stride floats apart.
+ * Per computed frame:
+ *   G_f    the decode kernels' gain: pf(m_f) on bins 0..159 and 0 on bin 160; with lim: lim[s] + (1 - lim[s]) pf(m_f), and lim[s] on bin
+ *          160.  pf is the post-filter pf_kind (1 iam, 2 envelope) with tau pf_tau[s]; the identity where pf_kind == 0 or tau == 0.
+ *   P_in   (|N_0|^2 + 2 sum_{f=1..159} |N_f|^2 + |N_160|^2) / (320 W2), W2 the sum of the squared window of tab (cruse_stream_tables);
+ *          P_out the same of G_f N_f;  L = 10 log10(P + 1e-12) dBFS
+ *   p      p_prev + alpha (p_raw - p_prev), p_raw = 1 / (1 + exp(-(L_out - level_db))), alpha = attack where p_raw > p_prev else release
+ *   vad    p > threshold
+ * vad_par[S][4] (device, f32): level_db, threshold, attack, release per slot.  A frame writes the meter row [L_in, L_out, p, vad] (f32;
+ * vad 0.0 / 1.0) and adds to meter_acc[S][4] (device, f64): frames, active frames (vad = 1), the sums of P_in and of P_out over active
+ * frames.  meter_state[S][st_stride] (device, f32; st_stride >= the stride of cruse_stream_meter_layout) holds p_prev.  The frame 0 of a
+ * clip (mode FRAME0; a packet's first frame where pk says the slot held at most one block) resets p_prev and the accumulators whatever
+ * they held, takes part in the recursion and writes no row and no count: its block lies in front of the clip.  A slot that computes no
+ * frame leaves its rows, state and accumulators untouched.  One workgroup per slot, f32 sums in one fixed order in both forms, no
+ * atomics: a frame has the same bits from either entry point.  Refused with CRUSE_E_SHAPE before any launch: S < 1, a null buffer
+ * (lim may be null; pf_tau may be null where pf_kind == 0), wk_re / wk_im / wk_mask that do not lie in a row of wk_stride floats or a row
+ * shorter than 161 + 161 + 160, a pf_kind other than 0, 1, 2, st_stride or the out rows too small, hops outside [1, 64],
+ * work_frames < hops + 1, out_hops < hops. */
+#define CRUSE_STREAM_METER_LAYOUT_INTS 4
+/* out[CRUSE_STREAM_METER_LAYOUT_INTS] (HOST array): the offset of p_prev in a meter_state row, the row stride (floats), the doubles of a
+ * meter_acc row, the floats of a meter row */
+int cruse_stream_meter_layout(int* out);
+/* after cruse_stream_decode: every slot whose mode computes a frame (FRAME, FRAME0, END) takes its work row; the row of slot s goes to
+ * out + s * out_stride (out_stride >= 4 floats) */
+int cruse_stream_meter(const int* mode, int S, const float* work, int wk_stride, int wk_re, int wk_im, int wk_mask, const float* tab,
+                       const float* lim, int pf_kind, const float* pf_tau, const float* vad_par, float* meter_state, int st_stride,
+                       double* meter_acc, float* out, int out_stride, void* stream);
+/* after cruse_stream_decode_n: the same for the frames of the slot's packet, in order (the frame set cruse_stream_decode_n derives from
+ * pk); the rows of slot s go to out + s * out_stride from index 0, aligned with its output blocks (out_stride >= 4 out_hops floats) */
+int cruse_stream_meter_n(const int* pk, int S, int hops, int out_hops, int work_frames, const float* work, int wk_stride, int wk_re,
+                         int wk_im, int wk_mask, const float* tab, const float* lim, int pf_kind, const float* pf_tau,
+                         const float* vad_par, float* meter_state, int st_stride, double* meter_acc, float* out, int out_stride,
+                         void* stream);
+
 /* ---- what a boundary entry point launches (additive; host-only: nothing is launched) ---------------------------------------------
  * Runs entry point `entry` (encode, decode, the DeepFilter head: 14 in all) up to its launch.  ints (HOST): its int arguments in its own
  * order; bit i of null_mask: its i-th pointer argument is null (pointers are only compared with null).  Returns the entry point's refusal

@@ -33,9 +33,13 @@ levels, decoder="transposed") and CRUSE4MagAddSkipUpsample with the same channel
 decoder="upsample"), one instance each, alternating slices; every row carries "model", the cruse4 row "vs_unet_2" and
 "device_vs_unet_2" (profiles/stream_up_rtf.json).  --model cruse4 alone measures that model through every other option.
 
+With --meters off,on every (n_slots, hops) cell is measured without and with the level meters and voice-activity detector (meters=True:
+one more kernel per chain) in one run, in the style of --head: one instance each, alternating slices; every row carries
+"meters", the "on" row "vs_off" and "device_vs_off" (profiles/stream_meter_rtf.json).
+
     python tools/stream_rtf.py [--slots 1,16,64,256,1024] [--seconds 2] [--groups 4] [--hops 1,2,4,8] [--precision f32,f16] [--pcm]
                                [--atten-lim DB] [--io-rate 16000,8000,48000] [--head mask,df]
-                               [--post-filter none,iam] [--pf-tau 0.02] [--model unet_2,cruse4] [--out FILE]
+                               [--post-filter none,iam] [--pf-tau 0.02] [--model unet_2,cruse4] [--meters off,on] [--out FILE]
 """
 from __future__ import annotations
 
@@ -162,6 +166,8 @@ def _variant(model, S, precision, hops, key, h, pf_tau):
         return _inferencer(model, S, precision, max_hops=hops, head=h)
     if key == "model":
         return _inferencer(model[h], S, precision, max_hops=hops)
+    if key == "meters":
+        return _inferencer(model, S, precision, max_hops=hops, **({"meters": True} if h == "on" else {}))
     inf = _inferencer(model, S, precision, max_hops=hops, post_filter=None if h == "none" else h)
     if h != "none":
         inf.set_post_filter(pf_tau)
@@ -223,6 +229,7 @@ def main():
     ap.add_argument("--post-filter", default=None, help="none, iam, envelope or a list (none,iam): measured side by side like --head")
     ap.add_argument("--pf-tau", type=float, default=0.02, help="tau of every slot of the post-filter instances")
     ap.add_argument("--model", default="unet_2", help="unet_2 (default), cruse4, or unet_2,cruse4: the two decoders side by side like --head")
+    ap.add_argument("--meters", default=None, help="off, on or off,on: without / with the level meters, side by side like --head")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     a = ap.parse_args()
     IO.update(pcm=a.pcm, atten_lim=a.atten_lim)
@@ -248,9 +255,16 @@ def main():
         side = dict(key="post_filter", base_name="none", pf_tau=a.pf_tau)
     elif heads is not None and any(h not in ("mask", "df") for h in heads):
         ap.error(f"--head takes mask, df or mask,df, got {a.head}")
+    if a.meters is not None:
+        if heads is not None:
+            ap.error("--meters is measured in a run of its own (no --head / --post-filter)")
+        heads = a.meters.split(",")
+        if any(h not in ("off", "on") for h in heads):
+            ap.error(f"--meters takes off, on or off,on, got {a.meters}")
+        side = dict(key="meters", base_name="off")
     if len(names) > 1:
         if heads is not None:
-            ap.error("--model with two models is measured in a run of its own (no --head / --post-filter)")
+            ap.error("--model with two models is measured in a run of its own (no --head / --post-filter / --meters)")
         heads, side, m = names, dict(key="model", base_name="unet_2"), built
     if heads is not None:
         for prec in precs:
