@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import config, ops, streams
+from .step_plan import ggru_plan, unet_plan
 
 DEFAULT_PREC = "f32"
 
@@ -199,12 +200,6 @@ def _splitk_bf16(M: int, N: int, K: int) -> int:
     return max(1, min(256 // tiles, K // 1024))
 
 
-def _bf16_gemm_path(prec, Hg: int) -> bool:
-    """bf16-operand GEMMs: K = Hg and K = 3*Hg are rounded up to whole 64-deep tiles -- the weight operand is zero
-    padded (K-tiled), the activation operand reads on into the next group / row (finite values, zero weights)."""
-    return ops.prec_code(prec) == ops.PREC_BF16 and Hg % 32 == 0
-
-
 class _StepScratch:
     """Recurrence panel scratches of ONE training step: the engine clears the four slots with one launch at the top of the step
     (ops.gru_step_ws_clear) and every recurrence launch of the step then takes the next slot with zeroed=True -- the memset in
@@ -236,48 +231,6 @@ class _StepScratch:
 STEP_SCRATCH = _StepScratch()
 
 
-def _gi_x3_knob(Hg: int) -> int:
-    knob = config.get().gi_x3
-    return int(knob) if knob is not None else (7 if Hg <= 320 else 3)
-
-
-def _gi_takes_bf16_copy(prec, Hg: int) -> bool:
-    """The gate projections read ONE bf16 plane of their activation operand, unpadded: the producer (BatchNorm / LayerNorm
-    kernel) can then write that copy itself instead of a separate cast pass."""
-    return _bf16_gemm_path(prec, Hg) and Hg % 64 == 0 and not (_gi_x3_knob(Hg) & 4)
-
-
-def _gi_f16(prec, Hg: int, layer: int) -> bool:
-    """Forward gate projections as ONE pass on IEEE-f16 operands (EngineConfig.gi_f16, cruse_gemm_f16_nt): 11 significant bits on x
-    and W_ih, where the split-bf16 form keeps x at 8 bits and spends a second (Hg <= 320: and a third) pass on low planes.  The
-    producers' operand copies are then f16 tensors (g = 1; with g > 1 the interleaving LayerNorm has no fused copy and a cast pass
-    makes it) and W_ih is K-tiled as f16.  The operands are BatchNorm + ReLU / LayerNorm outputs and |W_ih| ~ 1 / sqrt(Hg): inside
-    f16's range; a value past 65504 would surface as a non-finite loss and the guarded optimizer step skips (engine.step_health).
-    Not with the row-major TN weight gradients or the time-chunk pipeline, which read the bf16 copies.
-    Only where the split-bf16 form does NOT split x as well (Hg > 320 by default, i.e. g = 1 at H = 640): the three-pass form of the
-    grouped configurations carries ~16 bits on both operands and measured BETTER than f16 there (enhanced spectrum at T = 401, closed-form
-    init, g = 4: 3.1e-4 against 1.7e-3; g = 2: 9e-5 against 5.5e-4), so those keep it."""
-    c = config.get()
-    return (bool((int(c.gi_f16) * 3 if isinstance(c.gi_f16, bool) else int(c.gi_f16 or 0)) >> layer & 1) and _bf16_gemm_path(prec, Hg) and not (_gi_x3_knob(Hg) & 4))
-
-
-_GI16_PLAN: Dict[tuple, bool] = {}
-
-
-def _gi16_served(B: int, Hg: int, prec: int) -> bool:
-    """does the forward recurrence read f16 gi rows at this shape (cruse_gru_seq_fwd_gi16: chains of 8 on the tag-free lean kernel)?  The plan is a
-    pure function of the shape (cached: two ctypes round trips per layer and step otherwise); the three library options that select another
-    kernel are A/B switches of probes and tests, looked up only when one is set."""
-    key = (B, Hg, prec)
-    ok = _GI16_PLAN.get(key)
-    if ok is None:
-        ok = _GI16_PLAN[key] = ops.gru_plan(B, 1, Hg, prec)["clips_per_chain"] == 8
-    if ok and config.get().lib_options:
-        lo = config.get().lib_options
-        ok = lo.get("gru_tf", 1) == 1 and lo.get("gru_wlo", 0) == 0 and lo.get("gru_fwd_lean", 1) == 1
-    return ok
-
-
 def _splitk(M: int, N: int, K: int) -> int:
     tiles = ((M + 127) // 128) * ((N + 127) // 128)
     sk = max(1, (512 + tiles - 1) // tiles)
@@ -289,142 +242,105 @@ def _splitk(M: int, N: int, K: int) -> int:
 # ======================================================================================
 def ggru_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], prefix: str, groups: int, prec,
                  residual: Optional[torch.Tensor] = None, save: bool = True, residual_ready=None, late_leaves=None,
-                 x_bf16=None):
-    """x [B,T,H] -> (ln2(gru2(ln1(interleave(gru1(x))))) [+ residual], ctx).  cruse_net.py:37-55."""
-    return _ggru_forward_one(x, P, prefix, groups, prec, residual, save, residual_ready=residual_ready,
-                             late_leaves=late_leaves, x_bf16=x_bf16)
-
-
-def _ggru_forward_one(x, P, prefix, groups, prec, residual=None, save=True, out=None, slot=0, xcd_rot=0, pre_done=None,
-                      residual_ready=None, late_leaves=None, x_bf16=None):
-    """residual_ready(): called right before the residual is read (the last layer norm) -- the caller may still be
+                 x_bf16=None, plan=None):
+    """x [B,T,H] -> (ln2(gru2(ln1(interleave(gru1(x))))) [+ residual], ctx).  cruse_net.py:37-55.
+    plan: the step_plan.GgruPlan of the caller's step (unet2_forward), with x_bf16 the operand copy it promises for layer 1;
+    None: the stand-alone block plans for itself from the active configuration.
+    residual_ready(): called right before the residual is read (the last layer norm) -- the caller may still be
     producing it on a side stream while the recurrences run."""
     B, T, H = x.shape
     g = groups
     Hg = H // g
     rows = B * T
-    ctx = dict(B=B, T=T, H=H, g=g, prec=prec, x=x, prefix=prefix, has_res=residual is not None, slot=slot, xcd_rot=xcd_rot)
-    hooks = [pre_done] if pre_done is not None else []
+    if plan is None:
+        plan = ggru_plan(B, T, H, g, prec, config.get(), False, save)
+    assert (x_bf16 is not None) == plan.layers[0].fused_copy, "the plan and the caller disagree about layer 1's operand copy"
+    ctx = dict(B=B, T=T, H=H, g=g, prec=prec, x=x, prefix=prefix, has_res=residual is not None, plan=plan)
+    pad, kp, fwd_T = plan.pad, plan.kp, plan.fwd_T and SIDE.enabled      # (the scheduler in force is run-time state, not configuration)
 
-    fast = _bf16_gemm_path(prec, Hg)
-
-
-    def layer(inp, lname, inp_bf=None):
-        # gi rows: f32, or IEEE f16 where the recurrence reads them (EngineConfig.gi_store_f16: bf16 mode, one group of 640, chains of 8 clips
-        # -- cruse_gru_seq_fwd_gi16): the largest tensor of the forward pass, written once and read once -- 197 -> 98 MB per layer at the bench shape
-        gi16 = bool(config.get().gi_store_f16) and fast and g == 1 and Hg == 640 and slot == 0 and _gi16_served(B, Hg, ops.prec_code(prec))
-        gi = torch.empty(B, T, g * 3 * Hg, device=x.device, dtype=torch.float16 if gi16 else torch.float32)
-        # The forward projection corrects the bf16 rounding of W_ih (a second pass with its low plane): that rounding
-        # dominates the forward error of the bf16 mode (enhanced spectrum 1.25e-3 -> 5.1e-4 rel-L2 on fixture G6;
-        # correcting x too only reaches 4.8e-4).  CRUSE_GI_X3: bit 0 / 1 = layer 1 / 2 corrected, bit 2 = also split x.
-        # Default: W_ih split on both layers; x split as well when Hg <= 320 (K is then short enough that the third pass
-        # costs < 0.04 ms per step, and the grouped configurations need it for the 1e-3 bar at T = 401: DESIGN.md section 2)
-        knob = _gi_x3_knob(Hg)
-        x3 = (knob >> (0 if lname == "gru_list1" else 1)) & 1
-        split_x = bool(knob & 4) and x3
-        pad = 64 if Hg % 64 else 0
-        if _gi_f16(prec, Hg, 0 if lname == "gru_list1" else 1) and (inp_bf is None or inp_bf.dtype != torch.float16):
-            # (eval, g > 1 or Hg % 64 != 0: no fused copy -- the same f16 operand from a cast pass, zero tail for the K round-up)
-            inp_bf = torch.empty(rows * H + pad, device=x.device, dtype=torch.float16)
-            if pad:
-                inp_bf[rows * H:].zero_()
-            ops.check(ops.lib.cruse_cast_f16(ops._p(inp), ops._p(inp_bf), rows * H, 1, ops._stream()))
-        if inp_bf is not None:                   # written by the kernel that produced inp (_gi_takes_bf16_copy)
-            inp_hi, inp_lo = inp_bf, None
-        elif fast and split_x:
-            inp_hi, inp_lo = ops.cast_bf16_padded(inp, pad=pad, split=True)
-        else:
-            inp_hi, inp_lo = (ops.cast_bf16_padded(inp, pad=pad) if fast else None), None
-        kp = (Hg + 63) // 64 * 64
+    def _project(lp, lname, inp, op_hi, op_lo, gi):
+        """gi = inp W_ih^T + b_ih in the GEMM form the plan names; op_hi / op_lo: the 2-byte planes of inp it reads"""
+        w_ihs = [P[f"{prefix}{lname}.{i}.weight_ih_l0"] for i in range(g)]
         b_ihs = [P[f"{prefix}{lname}.{i}.bias_ih_l0"] for i in range(g)]
-        bstep = ops.uniform_stride(b_ihs)
-        if (fast and g > 1 and inp_hi is not None and inp_hi.dtype == torch.bfloat16
-                and bstep is not None):
+        # (not planned: whether the biases lie at ONE stride is a fact about their addresses)
+        bstep = ops.uniform_stride(b_ihs) if lp.grouped else None
+        if bstep is not None:
             # all groups of the layer in ONE launch: the K-tiled W_ih planes stacked [g][kp / 64][3 Hg][64], columns of x / gi per group
             W_hi = torch.empty(g, kp // 64, 3 * Hg, 64, device=x.device, dtype=torch.bfloat16)
-            W_lo = torch.empty_like(W_hi) if x3 else None
+            W_lo = torch.empty_like(W_hi) if lp.x3 else None
             for i in range(g):
-                ops.ktile_bf16(P[f"{prefix}{lname}.{i}.weight_ih_l0"], 3 * Hg, Hg, split=bool(x3), out=(W_hi[i], W_lo[i] if x3 else None))
-            ops.gemm_bf16_nt_groups(rows, 3 * Hg, kp, g, inp_hi, inp_lo if x3 else None, H, Hg, W_hi, W_lo, 64, W_hi[0].numel(), gi, 3 * H, 3 * Hg,
+                ops.ktile_bf16(w_ihs[i], 3 * Hg, Hg, split=lp.x3, out=(W_hi[i], W_lo[i] if lp.x3 else None))
+            ops.gemm_bf16_nt_groups(rows, 3 * Hg, kp, g, op_hi, op_lo, H, Hg, W_hi, W_lo, 64, W_hi[0].numel(), gi, 3 * H, 3 * Hg,
                                     bias=b_ihs[0], bias_gstep=bstep, b_kstride=3 * Hg * 64)
-            grouped = True
-        else:
-            grouped = False
-        for i in range(0 if not grouped else g, g):
-            w_ih, b_ih = P[f"{prefix}{lname}.{i}.weight_ih_l0"], P[f"{prefix}{lname}.{i}.bias_ih_l0"]
-            if inp_bf is not None and inp_bf.dtype == torch.float16 and x3 and lname == "gru_list1":   # layer 1 on f16 (gi_f16 bit 0) with its gi_x3 bit: f16 x against W_ih hi + lo planes
+            return
+        for i, (w_ih, b_ih) in enumerate(zip(w_ihs, b_ihs)):
+            tail = (gi, i * 3 * Hg, 3 * H)
+            if lp.form == "f16x2":               # layer 1 on f16 (gi_f16 bit 0) with its gi_x3 bit: f16 x against W_ih hi + lo planes
                 w_hi, w_lo = ops.ktile_f16(w_ih, 3 * Hg, Hg, split=True)
-                ops.gemm_f16_nt(rows, 3 * Hg, kp, inp_bf, i * Hg, H, w_hi, 0, 64, gi, i * 3 * Hg, 3 * H, bias=b_ih, b_kstride=3 * Hg * 64, B_lo=w_lo)
-            elif inp_bf is not None and inp_bf.dtype == torch.float16:        # _gi_f16: one pass, 11-bit operands
-                ops.gemm_f16_nt(rows, 3 * Hg, kp, inp_bf, i * Hg, H, ops.ktile_f16(w_ih, 3 * Hg, Hg), 0, 64, gi, i * 3 * Hg, 3 * H,
-                                bias=b_ih, b_kstride=3 * Hg * 64)
-            elif fast and x3:
+                ops.gemm_f16_nt(rows, 3 * Hg, kp, op_hi, i * Hg, H, w_hi, 0, 64, *tail, bias=b_ih, b_kstride=3 * Hg * 64, B_lo=w_lo)
+            elif lp.form == "f16":               # _gi_f16: one pass, 11-bit operands
+                ops.gemm_f16_nt(rows, 3 * Hg, kp, op_hi, i * Hg, H, ops.ktile_f16(w_ih, 3 * Hg, Hg), 0, 64, *tail, bias=b_ih, b_kstride=3 * Hg * 64)
+            elif lp.form in ("bf16x3", "bf16x3_splitx"):
                 w_hi, w_lo = ops.ktile_bf16(w_ih, 3 * Hg, Hg, split=True)
-                ops.gemm_bf16x3_nt(rows, 3 * Hg, kp, inp_hi, inp_lo, i * Hg, H, w_hi, w_lo, 0, 64, gi, i * 3 * Hg, 3 * H,
-                                   bias=b_ih, b_kstride=3 * Hg * 64)
-            elif fast:
-                ops.gemm_bf16_nt(rows, 3 * Hg, kp, inp_hi, i * Hg, H, ops.ktile_bf16(w_ih, 3 * Hg, Hg), 0, 64, gi,
-                                 i * 3 * Hg, 3 * H, bias=b_ih, b_kstride=3 * Hg * 64)
+                ops.gemm_bf16x3_nt(rows, 3 * Hg, kp, op_hi, op_lo, i * Hg, H, w_hi, w_lo, 0, 64, *tail, bias=b_ih, b_kstride=3 * Hg * 64)
+            elif lp.form == "bf16":
+                ops.gemm_bf16_nt(rows, 3 * Hg, kp, op_hi, i * Hg, H, ops.ktile_bf16(w_ih, 3 * Hg, Hg), 0, 64, *tail, bias=b_ih, b_kstride=3 * Hg * 64)
             else:
-                ops.gemm(False, True, rows, 3 * Hg, Hg, inp, i * Hg, H, w_ih, 0, Hg, gi, i * 3 * Hg, 3 * H, bias=b_ih,
-                         prec=prec)
+                ops.gemm(False, True, rows, 3 * Hg, Hg, inp, i * Hg, H, w_ih, 0, Hg, *tail, bias=b_ih, prec=prec)
+
+    def layer(inp, li, inp_bf=None):
+        lp, lname = plan.layers[li], ("gru_list1", "gru_list2")[li]
+        gi = torch.empty(B, T, g * 3 * Hg, device=x.device, dtype=lp.gi_dtype)
+        op_hi, op_lo = inp_bf, None              # fused_copy: written by the kernel that produced inp
+        if lp.needs_cast_pass and lp.operand_dtype == torch.float16:
+            # (eval, g > 1 or Hg % 64 != 0: no fused copy -- the same f16 operand from a cast pass, zero tail for the K round-up)
+            op_hi = torch.empty(rows * H + pad, device=x.device, dtype=torch.float16)
+            if pad:
+                op_hi[rows * H:].zero_()
+            ops.check(ops.lib.cruse_cast_f16(ops._p(inp), ops._p(op_hi), rows * H, 1, ops._stream()))
+        elif lp.needs_cast_pass:
+            op_hi, op_lo = ops.cast_bf16_padded(inp, pad=pad, split=True) if lp.split_x else (ops.cast_bf16_padded(inp, pad=pad), None)
+        _project(lp, lname, inp, op_hi, op_lo, gi)
         w_hh = [P[f"{prefix}{lname}.{i}.weight_hh_l0"] for i in range(g)]
         b_hh = [P[f"{prefix}{lname}.{i}.bias_hh_l0"] for i in range(g)]
-        if hooks:
-            hooks.pop()()                    # the pre-stage of this slice is issued: the next slice may start its own
-        slot_, zeroed = STEP_SCRATCH.take(B, g, Hg, slot)
-        return SIDE.release_around(lambda: ops.gru_seq_fwd(gi, w_hh, b_hh, B, T, g, Hg, prec, save=save, slot=slot_,
-                                                           xcd_rot=xcd_rot, zeroed=zeroed))
+        slot, zeroed = STEP_SCRATCH.take(B, g, Hg, 0)
+        return SIDE.release_around(lambda: ops.gru_seq_fwd(gi, w_hh, b_hh, B, T, g, Hg, prec, save=save, slot=slot, zeroed=zeroed))
 
     # The K-tiled time-major bf16 copies of x, h1, l1, h2 -- the K operands of the four weight-gradient GEMMs -- depend on
     # the forward pass only.  From the first backward recurrence on, the side streams' queue is what the optimizer step
     # waits for, while in the forward pass they idle: three of the copies are made beside the second forward recurrence,
     # the fourth beside the decoder (late_leaves: the caller issues it after it has joined the side streams).
-    fwd_T = save and fast and SIDE.enabled and slot == 0
-    tt = {}
-
-    def queue_layer1_leaves(h1, l1, l1_bf):
-        """queued for the launch of the second forward recurrence"""
-        if not fwd_T:
-            return
+    h1, c1, a1, z1 = layer(x, 0, x_bf16)
+    l1_bf = torch.empty(rows * H, device=x.device, dtype=plan.layers[1].operand_dtype) if plan.layers[1].fused_copy else None
+    l1, m1, s1 = ops.ln_fwd(h1, P[prefix + "ln1.weight"], P[prefix + "ln1.bias"], None, rows, H, g, save=save, out_bf16=l1_bf)
+    if fwd_T:                                    # queued for the launch of the second forward recurrence
         ldT = (rows + 63) // 64 * 64
-        tt["xT"], tt["h1T"], tt["l1T"], tt["h2T"] = (torch.empty(ldT // 64, H, 64, device=x.device, dtype=torch.bfloat16)
-                                                     for _ in range(4))
-        w_ts = {}                                # K-tiled W_ih^T of both layers: the B operand of the backward dX GEMMs
+        xT, h1T, l1T, h2T = (torch.empty(ldT // 64, H, 64, device=x.device, dtype=torch.bfloat16) for _ in range(4))
+        w_ts = ctx["w_ts"] = {}                  # K-tiled W_ih^T of both layers: the B operand of the backward dX GEMMs
 
-        def t_layer1(x=x, h1=h1, l1=l1):
-            ops.transpose_bf16(x, rows, H, out=tt["xT"])
-            ops.transpose_bf16(h1, rows, H, shift_T=T, out=tt["h1T"])
-            ops.transpose_bf16(l1, rows, H, out=tt["l1T"])
+        def t_layer1():
+            ops.transpose_bf16(x, rows, H, out=xT)
+            ops.transpose_bf16(h1, rows, H, shift_T=T, out=h1T)
+            ops.transpose_bf16(l1, rows, H, out=l1T)
             for lname in ("gru_list1", "gru_list2"):
                 # (one stacked tensor per layer [g][ceil(3 Hg / 64)][Hg][64]: the grouped dX launch walks it with a group stride)
                 stack = torch.empty(g, (3 * Hg + 63) // 64, Hg, 64, device=x.device, dtype=torch.bfloat16)
                 for i in range(g):
                     w_ts[(lname, i)] = ops.transpose_bf16(P[f"{prefix}{lname}.{i}.weight_ih_l0"], 3 * Hg, Hg, out=stack[i])
                 w_ts[(lname, "stack")] = stack
-        ctx["w_ts"] = w_ts
-        SIDE.defer(t_layer1, x, h1, l1, tt["xT"], tt["h1T"], tt["l1T"], kind=1, lane=2)
-
-    h1, c1, a1, z1 = layer(x, "gru_list1", x_bf16)
-    f16 = _gi_f16(prec, Hg, 1)
-    l1_bf = (torch.empty(rows * H, device=x.device, dtype=torch.float16 if f16 else torch.bfloat16)
-             if _gi_takes_bf16_copy(prec, Hg) and not (f16 and g > 1) else None)
-    l1, m1, s1 = ops.ln_fwd(h1, P[prefix + "ln1.weight"], P[prefix + "ln1.bias"], None, rows, H, g, save=save, out_bf16=l1_bf)
-    queue_layer1_leaves(h1, l1, l1_bf)
-    h2, c2, a2, z2 = layer(l1, "gru_list2", l1_bf)
+        SIDE.defer(t_layer1, x, h1, l1, xT, h1T, l1T, kind=1, lane=2)
+    h2, c2, a2, z2 = layer(l1, 1, l1_bf)
     if residual_ready is not None:
         residual_ready()
-    out, m2, s2 = ops.ln_fwd(h2, P[prefix + "ln2.weight"], P[prefix + "ln2.bias"], residual, rows, H, 1, save=save, out=out)
+    out, m2, s2 = ops.ln_fwd(h2, P[prefix + "ln2.weight"], P[prefix + "ln2.bias"], residual, rows, H, 1, save=save)
     if fwd_T:
-        h2T = tt["h2T"]
-
-        def t_h2(h2=h2):
+        def t_h2():
             ops.transpose_bf16(h2, rows, H, shift_T=T, out=h2T)
         if late_leaves is not None:
             late_leaves.append((t_h2, (h2, h2T)))
         else:
             SIDE.defer(t_h2, h2, h2T, kind=1, lane=2)
-        ctx.update(T1=(tt["xT"], tt["h1T"]), T2=(tt["l1T"], h2T))
+        ctx.update(T1=(xT, h1T), T2=(l1T, h2T))
     if save:
         ctx.update(h1=h1, c1=c1, a1=a1, z1=z1, l1=l1, m1=m1, s1=s1,
                    h2=h2, c2=c2, a2=a2, z2=z2, m2=m2, s2=s2)
@@ -438,35 +354,24 @@ def ggru_backward(ctx, dout: torch.Tensor, P: Dict[str, torch.Tensor], G: Dict[s
     gradient is ADDED to (and returned) instead of a fresh one; dx_ready() is called right before it is touched.
     defer_last: queue layer 1's weight-gradient leaf (SIDE.defer) instead of issuing it -- the caller ends a segment
     right after this function and issues it with SIDE.flush() at the start of the next one."""
-    B, T, H, g, prec, prefix = ctx["B"], ctx["T"], ctx["H"], ctx["g"], ctx["prec"], ctx["prefix"]
-    dx = None
+    B, T, H, g, prec, prefix, plan = ctx["B"], ctx["T"], ctx["H"], ctx["g"], ctx["prec"], ctx["prefix"], ctx["plan"]
+    dx, dx_accum = None, dx_init is not None
     if need_dx:
-        if dx_init is not None:
-            dx = dx_init.view(B, T, H)
-        else:
-            dx = torch.empty(B, T, H, device=dout.device, dtype=torch.float32)
-    _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_init is not None, dx_ready, defer_last)
-    if join:
-        SIDE.join()
-    return dx
-
-
-def _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_accum, dx_ready, defer_last, pre_done=None):
-    """One batch slice of ggru_backward on the current stream; dx: the [B,T,H] rows its input gradient is written to
-    (added to when dx_accum)."""
-    B, T, H, g, prec, prefix = ctx["B"], ctx["T"], ctx["H"], ctx["g"], ctx["prec"], ctx["prefix"]
-    slot, xcd_rot = ctx.get("slot", 0), ctx.get("xcd_rot", 0)
+        dx = dx_init.view(B, T, H) if dx_accum else torch.empty(B, T, H, device=dout.device, dtype=torch.float32)
     Hg = H // g
     rows = B * T
-    hooks = [pre_done] if pre_done is not None else []
+
+    def _queue_weight_grads(fn, tensors, last):
+        """the weight-gradient leaf of a layer: beside the next recurrence, or (last: none follows) at once -- unless defer_last"""
+        if last and not defer_last:
+            SIDE.run(fn, *tensors, lane=2)
+        else:
+            SIDE.defer(fn, *tensors, kind=0xffff if last else 4, lane=2)
 
     def run_bwd(dout_h, w_hh, coef, z, an=None, dg_slabs=3):
-        if hooks:
-            hooks.pop()()
-        slot_, zeroed = STEP_SCRATCH.take(B, g, Hg, slot)
-        return SIDE.release_around(lambda: ops.gru_seq_bwd(dout_h, w_hh, coef, z, B, T, g, Hg, prec, slot=slot_,
-                                                           xcd_rot=xcd_rot, an=an, want_dgi=an is not None, dg_slabs=dg_slabs,
-                                                           zeroed=zeroed))
+        slot, zeroed = STEP_SCRATCH.take(B, g, Hg, 0)
+        return SIDE.release_around(lambda: ops.gru_seq_bwd(dout_h, w_hh, coef, z, B, T, g, Hg, prec, slot=slot, an=an,
+                                                           want_dgi=an is not None, dg_slabs=dg_slabs, zeroed=zeroed))
 
     def dinp_buffer(dout_h, need_dinp, last):
         if not need_dinp:
@@ -486,7 +391,7 @@ def _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_accum, dx_ready, defer_l
         ldT = (rows + 63) // 64 * 64
         dh = run_bwd(dout_h, w_hh, coef, z)
         # EngineConfig.dx_atr: dX reads the time-major tensor dgT through transposing LDS reads (cruse_gemm_bf16_nt_atr) -- no row-major dgi is written
-        dx_atr = bool(config.get().dx_atr) and Hg % 64 == 0 and need_dinp and g == 1
+        dx_atr = plan.dx_atr and need_dinp
         dgi, dgT, ldT = ops.gru_gate_grads_bf16(dh, coef, an, rows, g, Hg, bias_ih, bias_hh, want_dgi=not dx_atr)
         early = early_T.pop(lname, None)         # layer 1: transposed by a leaf of the FIRST recurrence (see below)
         if early is not None:
@@ -505,6 +410,7 @@ def _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_accum, dx_ready, defer_l
                 a0, b0 = 4 * i * Hg * 64, i * Hg * 64
                 g_ih, g_hh = G[nm + "weight_ih_l0"], G[nm + "weight_hh_l0"]
                 sk = _splitk_bf16(6 * Hg, Hg, ldT)       # (k-slices for the 6 Hg x Hg concatenated output)
+                # (not planned: whether dW_hh follows dW_ih in memory is a fact about the caller's gradient buffers)
                 if (abs(sk) > 1
                         and g_hh.data_ptr() == g_ih.data_ptr() + 4 * 3 * Hg * Hg):
                     # the three products as ONE launch on the concatenated output [dW_ih ; dW_hh] (back to back in the flat gradient buffer)
@@ -523,7 +429,7 @@ def _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_accum, dx_ready, defer_l
         # gate-gradient pass, not the GEMM, and the three dW products start ~150 us earlier (5.40 vs 5.46 ms).
         early_leaf = last and not defer_last
         if early_leaf:
-            SIDE.run(weight_grads, dgT, h, inp, inpT, hpT, dh, lane=2)
+            _queue_weight_grads(weight_grads, (dgT, h, inp, inpT, hpT, dh), last)
         dinp, acc_dx = dinp_buffer(dout_h, need_dinp, last)
         stack = ctx.get("w_ts", {}).get((lname, "stack"))
         if need_dinp and g > 1 and stack is not None:
@@ -541,19 +447,13 @@ def _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_accum, dx_ready, defer_l
                     continue
                 ops.gemm_bf16_nt(rows, Hg, w_t.shape[0] * 64, dgi, i * 3 * Hg, 3 * H, w_t, 0, 64, dinp, i * Hg, H,
                                  accumulate=acc_dx, b_kstride=Hg * 64)
-        if early_leaf:
-            pass
-        elif last and defer_last:
-            SIDE.defer(weight_grads, dgT, h, inp, inpT, hpT, dh, kind=0xffff, lane=2)
-        elif last:
-            SIDE.run(weight_grads, dgT, h, inp, inpT, hpT, dh, lane=2)
-        else:
-            SIDE.defer(weight_grads, dgT, h, inp, inpT, hpT, dh, kind=4, lane=2)
+        if not early_leaf:
+            _queue_weight_grads(weight_grads, (dgT, h, inp, inpT, hpT, dh), last)
         return dinp
 
     def layer_bwd(dout_h, lname, inp, h, coef, an, z, need_dinp, last):
         """last: no recurrence follows, so the weight-gradient leaves start at once instead of with the next one."""
-        if _bf16_gemm_path(prec, Hg):
+        if plan.fast:
             return layer_bwd_bf16(dout_h, lname, inp, h, coef, an, z, need_dinp, last)
         w_hh = [P[f"{prefix}{lname}.{i}.weight_hh_l0"] for i in range(g)]
         dh = run_bwd(dout_h, w_hh, coef, z)
@@ -577,12 +477,7 @@ def _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_accum, dx_ready, defer_l
             for i in range(g):
                 ops.gemm(False, False, rows, Hg, 3 * Hg, dgi, i * 3 * Hg, 3 * H,
                          P[f"{prefix}{lname}.{i}.weight_ih_l0"], 0, Hg, dinp, i * Hg, H, accumulate=acc_dx, prec=prec)
-        if last and defer_last:
-            SIDE.defer(weight_grads, dgi, dgh, h, inp, kind=0xffff, lane=2)
-        elif last:
-            SIDE.run(weight_grads, dgi, dgh, h, inp, lane=2)
-        else:
-            SIDE.defer(weight_grads, dgi, dgh, h, inp, kind=4, lane=2)
+        _queue_weight_grads(weight_grads, (dgi, dgh, h, inp), last)
         return dinp
 
     # The time-major bf16 copies of layer 1's x and h_{t-1} (the K operands of its weight-gradient GEMMs) depend on the
@@ -590,9 +485,9 @@ def _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_accum, dx_ready, defer_l
     # fill -- not after the second one, where the side streams' queue (layer 1's GEMMs, the encoder's weight gradients)
     # is what the optimizer step waits for.
     early_T = {}
-    if "T1" in ctx:                                      # made in the forward pass (_ggru_forward_one)
+    if "T1" in ctx:                                      # made in the forward pass (ggru_forward)
         early_T["gru_list1"], early_T["gru_list2"] = ctx["T1"], ctx["T2"]
-    elif _bf16_gemm_path(prec, Hg) and SIDE.enabled:
+    elif plan.fast and SIDE.enabled:
         ldT1 = (rows + 63) // 64 * 64
         x1T = torch.empty(ldT1 // 64, H, 64, device=dout.device, dtype=torch.bfloat16)
         h1T = torch.empty(ldT1 // 64, H, 64, device=dout.device, dtype=torch.bfloat16)
@@ -608,6 +503,9 @@ def _ggru_backward_one(ctx, dout, P, G, need_dx, dx, dx_accum, dx_ready, defer_l
     dh1 = ops.ln_bwd(dl1, ctx["h1"], ctx["m1"], ctx["s1"], P[prefix + "ln1.weight"], rows, H, g,
                      G[prefix + "ln1.weight"], G[prefix + "ln1.bias"])
     layer_bwd(dh1, "gru_list1", ctx["x"], ctx["h1"], ctx["c1"], ctx["a1"], ctx["z1"], need_dx, True)
+    if join:
+        SIDE.join()
+    return dx
 
 
 # ======================================================================================
@@ -643,13 +541,30 @@ def _bn_act(y, rows, C, F, P, Bf, name, training, update_running, skip=None, sum
     return ops.bn_act_fwd(y, mean, rstd, gamma, beta, skip, rows, C, F, relu=True), mean, rstd
 
 
+def _conv_fwd(kind, scatter, src, w, bias, B, T, Cin, Fin, Cout, prec, KT, pad, S=2, copy_bf16=None, out=None):
+    """One forward conv of the U-Net in the form the plan names (step_plan.LevelPlan.conv_kind) -> (y, BatchNorm sums of y or None).
+    scatter: the stride-2 transposed conv (conv_scatter2), else conv_gather at stride S.  bnin: src is the ops.BnIn of a VIRTUAL input; its
+    ONE publishing consumer is handed copy_bf16 and delivers the sums of y, any other reader (out: a skip conv) neither."""
+    fn = {"bnin": (ops.conv_gather_bnin, ops.conv_scatter2_bnin), "bnstats": (ops.conv_gather_bnstats, ops.conv_scatter2_bnstats),
+          "plain": (ops.conv_gather, ops.conv_scatter2)}[kind][scatter]
+    geom = (B, T, Cin, Fin, Cout) if scatter else (B, T, Cin, Fin, Cout, Fin // S)
+    kw = dict(KT=KT, pad=pad, prec=prec) if scatter else dict(KT=KT, S=S, pad=pad, prec=prec)
+    if kind == "bnin" and out is None:                   # the ONE publishing consumer
+        return fn(src, w, bias, *geom, publish=True, copy_bf16=copy_bf16, want_sums=True, **kw)
+    if kind == "bnstats":
+        return fn(src, w, bias, *geom, **kw)
+    if out is not None:                                  # a skip conv (gather forms)
+        kw["out"] = out
+    return fn(src, w, bias, *geom, **kw), None
+
+
 def unet2_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], Bf: Dict[str, torch.Tensor], ch, groups: int,
                   prec, training: bool, save: bool = True, update_running: bool = True, dec_mode: str = "transposed",
                   defer_head: bool = False):
     """x [B,1,T,F0] (== frame-major [B,T,1,F0]) -> (mask [B,1,T,F0], ctx).  cruse_net.py:147-165.
 
     defer_head (the WO-MALE training step, EngineConfig.fuse_mask_head): where the shapes allow it the forward pass stops in front of the
-    last decoder BatchNorm -- u_1 stays virtual (ctx["head"], an ops.BnIn like `pend` below), the returned mask is None -- and
+    last decoder BatchNorm -- u_1 stays virtual (ctx["head"], an ops.BnIn like `src` below), the returned mask is None -- and
     unet2_mask_head() runs that BatchNorm, the mask conv, the loss and the first data gradient of the backward pass in one kernel.
 
     dec_mode "upsample": the decoder of model/cruse.py:14 (CRUSE4MagAddSkipUpsample) -- cust_conv.convkxf(mode="upsample"),
@@ -669,17 +584,15 @@ def unet2_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], Bf: Dict[str, tor
         raise RuntimeError(f"unet_2: {F0} input bins are not divisible by 2**{L} (the network runs on in_feat//2*2 bins)")
     rows = B * T
     Fk = [F0 >> k for k in range(L + 1)]
-    ctx = dict(B=B, T=T, F=Fk, ch=tuple(ch), L=L, prec=prec, training=training, x=x)
-    cur = x
+    plan = unet_plan(ch, F0, groups, prec, config.get(), training, save, update_running, dec_mode, defer_head, B, T)
+    ctx = dict(B=B, T=T, F=Fk, ch=tuple(ch), L=L, prec=prec, training=training, x=x, plan=plan)
     _PENDING_COUNTERS.clear()
     ys, es, ss, stats = [None], [x], [None], [None]
     # EngineConfig.fuse_bn_fwd (bf16 mode, training): BatchNorm-apply + ReLU (+ skip add) of a level run inside the staging of the
-    # convs that consume it -- `pend` describes such a VIRTUAL tensor (ops.BnIn); es[k] / us[k] are then the bf16 copies the
+    # convs that consume it -- `src` is then the ops.BnIn that describes such a VIRTUAL tensor; es[k] / us[k] are then the bf16 copies the
     # consuming conv writes for the weight gradients, mean / rstd are published by that conv's block 0
-    # (the MFMA convs stage whole frame rows: up to 640 elements per row and level -- wider networks run the VALU kernels, unfused)
-    fz = (training and save and config.get().fuse_bn_fwd and config.get().fuse_bn_stats
-          and all(ch[k] * Fk[k] <= 640 for k in range(1, L + 1)))
     dev = x.device
+    src, e_bf = x, None                  # src: what the next conv reads -- a tensor, or the ops.BnIn of a virtual one
 
     def virtual(y_, sums_, C, F, name, add=None):
         mean_ = torch.empty(C, device=dev, dtype=torch.float32); rstd_ = torch.empty(C, device=dev, dtype=torch.float32)
@@ -689,88 +602,53 @@ def unet2_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], Bf: Dict[str, tor
             _PENDING_COUNTERS.append(Bf[name + ".num_batches_tracked"])
         return ops.BnIn(y_, sums_, ops.BN_STAT_REPLICAS, rows * F, BN_EPS, BN_MOMENTUM, P[name + ".weight"], P[name + ".bias"], mean_, rstd_,
                         rm, rv, add=add)
-    pend = None
-    e_bf = None
     for k in range(1, L + 1):
-        if pend is not None:
-            y, sums = ops.conv_gather_bnin(pend, P[f"conv{k}.weight"], P[f"conv{k}.bias"], B, T, ch[k - 1], Fk[k - 1], ch[k], Fk[k], KT=2, S=2,
-                                           pad=1, prec=prec, publish=True, copy_bf16=es[k - 1], want_sums=True)
-        elif training and config.get().fuse_bn_stats:
-            y, sums = ops.conv_gather_bnstats(cur, P[f"conv{k}.weight"], P[f"conv{k}.bias"], B, T, ch[k - 1], Fk[k - 1], ch[k],
-                                              Fk[k], KT=2, S=2, pad=1, prec=prec)
-        else:
-            y, sums = ops.conv_gather(cur, P[f"conv{k}.weight"], P[f"conv{k}.bias"], B, T, ch[k - 1], Fk[k - 1], ch[k], Fk[k],
-                                      KT=2, S=2, pad=1, prec=prec), None
+        lv = plan.enc[k]
+        y, sums = _conv_fwd(lv.conv_kind, False, src, P[f"conv{k}.weight"], P[f"conv{k}.bias"], B, T, ch[k - 1], Fk[k - 1], ch[k], prec,
+                            KT=2, pad=1, copy_bf16=es[k - 1])
         s = torch.empty(B, T, ch[k], Fk[k], device=x.device, dtype=torch.float32)
-        # e_k stays virtual when both of its forward consumers -- conv_{k+1} and skip_k -- take it fused (level L feeds the GGRU)
-        if fz and k < L and ops.bnin_eligible(prec, ch[k], ch[k + 1]) and ops.bnin_eligible(prec, ch[k], ch[k]):
-            pend = virtual(y, sums, ch[k], Fk[k], f"bn{k}")
+        if lv.virtual:
+            src = virtual(y, sums, ch[k], Fk[k], f"bn{k}")
             e = torch.empty(B, T, ch[k], Fk[k], device=dev, dtype=torch.bfloat16)        # written by conv_{k+1} while it stages
-            mean, rstd = pend.mean, pend.rstd
-
-            def skip_conv(bn=pend, s=s, k=k):
-                ops.conv_gather_bnin(bn, P[f"skip_connect_{k}.weight"], None, B, T, ch[k], Fk[k], ch[k], Fk[k], KT=1, S=1, pad=1,
-                                     prec=prec, out=s)
-            SIDE.defer(skip_conv, y, s, kind=1, lane=1)
+            mean, rstd = src.mean, src.rstd
         else:
-            pend = None
-            e_bf = None
-            if k == L and training and _gi_takes_bf16_copy(prec, ch[L] * Fk[L] // groups):
-                e_bf = torch.empty(rows * ch[L] * Fk[L], device=x.device,                          # gate GEMM 1's operand
-                                   dtype=torch.float16 if _gi_f16(prec, ch[L] * Fk[L] // groups, 0) else torch.bfloat16)
-            e, mean, rstd = _bn_act(y, rows, ch[k], Fk[k], P, Bf, f"bn{k}", training, update_running, sums=sums, out_bf16=e_bf)
+            if k == L and plan.e_bf_dtype is not None:
+                e_bf = torch.empty(rows * ch[L] * Fk[L], device=x.device, dtype=plan.e_bf_dtype)      # gate GEMM 1's operand
+            src, mean, rstd = _bn_act(y, rows, ch[k], Fk[k], P, Bf, f"bn{k}", training, update_running, sums=sums, out_bf16=e_bf)
+            e = src
 
-            def skip_conv(e=e, s=s, k=k):
-                ops.conv_gather(e, P[f"skip_connect_{k}.weight"], None, B, T, ch[k], Fk[k], ch[k], Fk[k], KT=1, S=1, pad=1,
-                                out=s, prec=prec)
-            # needed by the decoder only (level L: by the layer norm that closes the GGRU block): issued with the GRU forward
-            SIDE.defer(skip_conv, e, s, kind=1, lane=1)
+        def skip_conv(kind="bnin" if lv.virtual else "plain", src=src, s=s, k=k):
+            _conv_fwd(kind, False, src, P[f"skip_connect_{k}.weight"], None, B, T, ch[k], Fk[k], ch[k], prec, KT=1, pad=1, S=1, out=s)
+        # needed by the decoder only (level L: by the layer norm that closes the GGRU block): issued with the GRU forward
+        SIDE.defer(skip_conv, y if lv.virtual else e, s, kind=1, lane=1)
         ys.append(y); es.append(e); ss.append(s); stats.append((mean, rstd))
-        cur = e
-    H = ch[L] * Fk[L]
-    late = []
-    u, gctx = ggru_forward(cur.view(B, T, H), P, "gru.", groups, prec, residual=ss[L].view(B, T, H), save=save,
-                           residual_ready=SIDE.join, late_leaves=late, x_bf16=e_bf)
+    H, late = ch[L] * Fk[L], []
+    u, gctx = ggru_forward(es[L].view(B, T, H), P, "gru.", groups, prec, residual=ss[L].view(B, T, H), save=save,
+                           residual_ready=SIDE.join, late_leaves=late, x_bf16=e_bf, plan=plan.ggru)
     u = u.view(B, T, ch[L], Fk[L])
     SIDE.join()
     for fn, keep in late:                               # beside the decoder: nothing on the main stream waits for these
         SIDE.run(fn, *keep, lane=2)
     us, vs, dstats, uus = {L: u}, {}, {}, {}
-    pend = None
-    head = None
+    src, head = u, None
     for k in range(L, 1, -1):
+        lv, w, bias = plan.dec[k], P[f"conv{k}_t.weight"], P.get(f"conv{k}_t.bias")
         if ups:
             uus[k] = ops.upsample_w(u, rows * ch[k], Fk[k], 2).view(B, T, ch[k], Fk[k - 1])
-            if training and config.get().fuse_bn_stats:
-                v, sums = ops.conv_gather_bnstats(uus[k], P[f"conv{k}_t.weight"], P.get(f"conv{k}_t.bias"), B, T, ch[k], Fk[k - 1], ch[k - 1],
-                                                  Fk[k - 1], KT=1, S=1, pad=1, prec=prec)
-            else:
-                v, sums = ops.conv_gather(uus[k], P[f"conv{k}_t.weight"], P.get(f"conv{k}_t.bias"), B, T, ch[k], Fk[k - 1], ch[k - 1],
-                                          Fk[k - 1], KT=1, S=1, pad=1, prec=prec), None
-        elif pend is not None:                            # u_k = relu(bn(v_{k+1})) + skip_k applied while conv{k}_t stages v_{k+1} and skip_k
-            v, sums = ops.conv_scatter2_bnin(pend, P[f"conv{k}_t.weight"], P[f"conv{k}_t.bias"], B, T, ch[k], Fk[k], ch[k - 1], KT=1, pad=0,
-                                             prec=prec, publish=True, copy_bf16=us[k], want_sums=True)
-        elif training and config.get().fuse_bn_stats:
-            v, sums = ops.conv_scatter2_bnstats(u, P[f"conv{k}_t.weight"], P[f"conv{k}_t.bias"], B, T, ch[k], Fk[k], ch[k - 1],
-                                                KT=1, pad=0, prec=prec)
-        else:
-            v, sums = ops.conv_scatter2(u, P[f"conv{k}_t.weight"], P[f"conv{k}_t.bias"], B, T, ch[k], Fk[k], ch[k - 1], KT=1,
-                                        pad=0, prec=prec), None
-        # u_{k-1} stays virtual when its consumer conv{k-1}_t takes it fused (the last decoder layer, Cout = 1, is a VALU kernel)
-        if fz and not ups and k - 1 >= 2 and ops.bnin_eligible(prec, ch[k - 1], ch[k - 2]):
-            pend = virtual(v, sums, ch[k - 1], Fk[k - 1], f"bn{k}_t", add=ss[k - 1])
+            v, sums = _conv_fwd(lv.conv_kind, False, uus[k], w, bias, B, T, ch[k], Fk[k - 1], ch[k - 1], prec, KT=1, pad=1, S=1)
+        else:       # (bnin: u_k = relu(bn(v_{k+1})) + skip_k applied while conv{k}_t stages v_{k+1} and skip_k)
+            v, sums = _conv_fwd(lv.conv_kind, True, src, w, bias, B, T, ch[k], Fk[k], ch[k - 1], prec, KT=1, pad=0, copy_bf16=us[k])
+        if lv.virtual:
+            src = virtual(v, sums, ch[k - 1], Fk[k - 1], f"bn{k}_t", add=ss[k - 1])
             u = torch.empty(B, T, ch[k - 1], Fk[k - 1], device=dev, dtype=torch.bfloat16)      # written by conv{k-1}_t while it stages
-            mean, rstd = pend.mean, pend.rstd
-        elif (defer_head and k == 2 and training and save and not ups and sums is not None and config.get().fuse_bn_bwd_stats
-              and ops.mask_head_eligible(ch[1], Fk[1], Fk[0] + 1)):
-            pend = None
+            mean, rstd = src.mean, src.rstd
+        elif lv.head_deferred:
             head = virtual(v, sums, ch[1], Fk[1], "bn2_t", add=ss[1])          # u_1 is written (f32) by the mask-head kernel
             u = None
             mean, rstd = head.mean, head.rstd
         else:
-            pend = None
-            u, mean, rstd = _bn_act(v, rows, ch[k - 1], Fk[k - 1], P, Bf, f"bn{k}_t", training, update_running, skip=ss[k - 1],
-                                    sums=sums)
+            src, mean, rstd = _bn_act(v, rows, ch[k - 1], Fk[k - 1], P, Bf, f"bn{k}_t", training, update_running, skip=ss[k - 1], sums=sums)
+            u = src
         vs[k] = v; dstats[k] = (mean, rstd); us[k - 1] = u
     if head is not None:
         mask = None
@@ -784,7 +662,7 @@ def unet2_forward(x: torch.Tensor, P: Dict[str, torch.Tensor], Bf: Dict[str, tor
     _flush_counters()
     if save:
         ctx.update(ys=ys, es=es, stats=stats, gctx=gctx, us=us, vs=vs, dstats=dstats, mask=mask, uus=uus, dec_mode=dec_mode, head=head)
-        if e_bf is not None and e_bf.dtype == torch.bfloat16:
+        if plan.e_bf_dtype == torch.bfloat16:
             ctx["e_bf"] = e_bf.view(B, T, ch[L], Fk[L])        # RNE(e_L): the operand bits the bf16 weight gradient forms from e_L anyway
     return (mask.view(B, ch[0], T, F0) if mask is not None else None), ctx
 
@@ -826,21 +704,10 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
     callback must SIDE.join(flush=False), may end a graph capture / launch the bucket's all-reduce, and must
     SIDE.flush() before returning.  Bucket 2 is final when this function returns."""
     B, T, Fk, ch, L, training = ctx["B"], ctx["T"], ctx["F"], ctx["ch"], ctx["L"], ctx["training"]
-    prec = ctx["prec"]
-    # data-gradient convolutions of the bf16 mode: plain bf16 operands (one MFMA, one conversion per element) like every
-    # other backward contraction of that mode -- the split-bf16 x3 form is what the FORWARD convs need for the 1e-3 bar
-    dprec = prec
-    if ops.prec_code(prec) == ops.PREC_BF16:
-        dprec = ops.PREC_BF16
+    prec, plan = ctx["prec"], ctx["plan"]
+    dprec, dy_bf16, _INLINE, ups = plan.dprec, plan.dy_bf16, plan.inline_mask, ctx.get("dec_mode", "transposed") == "upsample"
     rows = B * T
     ys, es, stats, us, vs, dstats = ctx["ys"], ctx["es"], ctx["stats"], ctx["us"], ctx["vs"], ctx["dstats"]
-    _INLINE = config.get().inline_mask
-    # backward-only tensors in bf16 (EngineConfig.bf16_dy): only where every consumer rounds them to bf16 operands anyway
-    # ... and every consumer is an MFMA kernel (the VALU fallbacks of the convs and weight gradients take f32 only: channel counts
-    # beyond 64 or not a power of two keep the f32 tensors -- ADVICE r4)
-    all_mfma = all(8 <= c <= 64 and (c & (c - 1)) == 0 for c in ch[1:]) and all(ch[k] * Fk[k] <= 640 for k in range(1, L + 1))
-    dy_bf16 = bool(config.get().bf16_dy) and ops.prec_code(prec) == ops.PREC_BF16 and dprec == ops.PREC_BF16 and all_mfma
-    ups = ctx.get("dec_mode", "transposed") == "upsample"
     uus = ctx.get("uus", {})
 
     def dec_wgrad(k, dv_):
@@ -875,10 +742,8 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
     # A data gradient that feeds a BatchNorm backward accumulates that BatchNorm's backward sums (sum g, sum g*xhat per channel)
     # in its own epilogue (cruse_conv_*_bnbwd): the reduce pass over (du, v) / (de, y) -- 132 MB and ~47 us per level -- is only
     # left for the level the GGRU feeds.  EngineConfig.fuse_bn_bwd_stats.
-    fuse_bwd = config.get().fuse_bn_bwd_stats
-
     def bn_of(k, dec):
-        if not fuse_bwd:
+        if not plan.fuse_bwd:
             return None
         mean_, rstd_ = dstats[k] if dec else stats[k]
         nm = f"bn{k}_t" if dec else f"bn{k}"
@@ -886,11 +751,6 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
 
     def split(r):
         return r if isinstance(r, tuple) else (r, None)
-    # ... and the data gradients of the levels between two MFMA kernels (EngineConfig.bf16_de): du_k / de_k for 2 <= k < L
-    de_bf16 = dy_bf16 and bool(config.get().bf16_de) and fuse_bwd and not ups
-
-    def lvl_bf16(k):
-        return de_bf16 and 2 <= k < L
     if ctx.get("du1") is not None:                      # unet2_mask_head has formed du_1 and the bn2_t backward sums with the loss
         du, du_sums = ctx["du1"]
     else:
@@ -902,7 +762,7 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
     de_pre = {}
 
     def skip_leaves(k):
-        de_pre[k] = torch.empty(B, T, ch[k], Fk[k], device=dlogit.device, dtype=torch.bfloat16 if lvl_bf16(k) else torch.float32)
+        de_pre[k] = torch.empty(B, T, ch[k], Fk[k], device=dlogit.device, dtype=torch.bfloat16 if k in plan.bf16_levels else torch.float32)
 
         def dgrad(k=k, dsk=ds[k], out=de_pre[k]):
             ops.conv_gather(dsk, P[f"skip_connect_{k}.weight"], None, B, T, ch[k], Fk[k], ch[k], Fk[k], KT=1, S=1, pad=1,
@@ -910,7 +770,7 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
 
         def wgrad(k=k, dsk=ds[k]):
             ek = es[k]
-            if k == L and "e_bf" in ctx and ops.prec_code(prec) == ops.PREC_BF16 and all_mfma:
+            if k == L and "e_bf" in ctx and plan.all_mfma:
                 ek = ctx["e_bf"]                            # (the gate GEMM's bf16 copy of e_L: half the bytes, the same operand bits)
             ops.conv_wgrad(dsk, ek, G[f"skip_connect_{k}.weight"], B, T, ch[k], Fk[k], ch[k], Fk[k], KT=1, S=1, pad=1,
                            prec=prec)
@@ -930,17 +790,17 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
     skip_leaves(1)
     # ---- decoder levels 2..L ------------------------------------------------------------
     # EngineConfig.fuse_bn_bwd_apply: where the incoming gradient is a bf16 tensor that arrived with its sums, the BatchNorm-backward apply
-    # pass runs inside the staging of the data-gradient conv (which also writes the bf16 dy for the weight gradient)
-    fuse_apply = bool(config.get().fuse_bn_bwd_apply) and dy_bf16 and fuse_bwd and not ups
+    # pass runs inside the staging of the data-gradient conv (which also writes the bf16 dy for the weight gradient).  The plan and the
+    # tensors cannot disagree: a conv given bn_bwd always returns its sums and out_bf16 follows the same plan.bf16_levels
     for k in range(2, L + 1):
         mean, rstd = dstats[k]
-        fused = fuse_apply and du.dtype == torch.bfloat16 and du_sums is not None
+        fused = plan.fuse_apply and (k - 1) in plan.bf16_levels            # (du_1 is f32)
         if fused:
             du, du_sums, dv = ops.conv_gather_bwd_in(
                 du, (vs[k], mean, rstd, P[f"bn{k}_t.weight"], P[f"bn{k}_t.bias"], du_sums, True, training, G[f"bn{k}_t.weight"],
                      G[f"bn{k}_t.bias"], G.get(f"conv{k}_t.bias")),
                 P[f"conv{k}_t.weight"], B, T, ch[k - 1], Fk[k - 1], ch[k], Fk[k], KT=1, S=2, pad=0, prec=dprec,
-                bn_bwd=bn_of(k + 1, True) if k < L else None, out_bf16=lvl_bf16(k))
+                bn_bwd=bn_of(k + 1, True) if k < L else None, out_bf16=k in plan.bf16_levels)
         else:
             dv = ops.bn_act_bwd(du, vs[k], mean, rstd, P[f"bn{k}_t.weight"], P[f"bn{k}_t.bias"], rows, ch[k - 1],
                                 Fk[k - 1], True, training, G[f"bn{k}_t.weight"], G[f"bn{k}_t.bias"],
@@ -953,7 +813,7 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
         else:
             SIDE.defer(leaf_dec, dv, kind=2, lane=0)
         if not fused:
-            du, du_sums = dec_dgrad(k, dv, bn_of(k + 1, True) if k < L else None, out_bf16=lvl_bf16(k))
+            du, du_sums = dec_dgrad(k, dv, bn_of(k + 1, True) if k < L else None, out_bf16=k in plan.bf16_levels)
         ds[k] = du
         skip_leaves(k)
     # ---- bottleneck: u_L = ggru(e_L) + skip_L --------------------------------------------
@@ -976,7 +836,7 @@ def unet2_backward(ctx, dlogit: torch.Tensor, P: Dict[str, torch.Tensor], G: Dic
     de_sums = None
     for k in range(L, 0, -1):
         mean, rstd = stats[k]
-        fused = fuse_apply and k > 1 and de.dtype == torch.bfloat16 and de_sums is not None
+        fused = plan.fuse_apply and k in plan.bf16_levels                  # (de_L is f32)
         if fused:
             de_new, de_sums_new, dy = ops.conv_scatter2_bwd_in(
                 de, (ys[k], mean, rstd, P[f"bn{k}.weight"], P[f"bn{k}.bias"], de_sums, True, training, G[f"bn{k}.weight"], G[f"bn{k}.bias"],
