@@ -194,6 +194,10 @@ SIGNATURES = {
     "cruse_grouped_linear_bwd_dw": ("pppiiiiiipqqqppzp", "i"),
     "cruse_band_pool": ("ppiiiipp", "i"),
     "cruse_band_expand": ("ppiiiipp", "i"),
+    "cruse_screen_ws_bytes": ("iq", "q"),
+    "cruse_screen_clips": ("ppppiqifddppp", "i"),
+    "cruse_rt60_ws_bytes": ("ii", "q"),
+    "cruse_rt60": ("pppiiiddppp", "i"),
 }
 
 

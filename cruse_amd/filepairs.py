@@ -237,6 +237,32 @@ class DeviceFilePairs(DevicePairs):
     def _noise_rir_bank(self, device):
         return self._ensure_noise_rirs(device)[2]
 
+    # ---- report ------------------------------------------------------------------------------------------------------
+    def screen(self, device) -> dict:
+        """The statistics table of cruse_amd.screen.screen_files for what this dataset holds on `device` (preloading it if no batch
+        was drawn yet; no file is read twice): {"clean": table, "noise": table, "rir": table, "rir_noise": table}, the last two only
+        where their lists were given, and with the RT60 columns.  The clean and noise tables are over the flat pools; the RIR tables
+        over the bank rows as the reverberation uses them, i.e. every response cut to rir_len.  Report only: nothing is filtered
+        (every reason is "", keep names every file), no generator is consumed and no batch changes."""
+        from . import screen as S
+        device = torch.device(device)
+        pools = self._ensure(device)
+        out = {}
+        with torch.cuda.device(device):
+            for name, paths in (("clean", self.clean_dataset_list), ("noise", self.noise_dataset_list)):
+                start, lens = getattr(self, name + "_utt_start"), getattr(self, name + "_utt_len")
+                stats, _ = S.stats_of(pools[name], start, lens, self.SR)
+                out[name] = S.table(paths, lens, self.SR, stats, None)
+            for name, paths, bank in (("rir", self.rir_dataset_list, self._ensure_rirs),
+                                      ("rir_noise", self.rir_noise_dataset_list, self._ensure_noise_rirs)):
+                if not paths:
+                    continue
+                rirs = bank(device)[0]                         # [n, rir_len], cut or zero-padded
+                lens = np.minimum(getattr(self, name + "_utt_len"), self.rir_len)
+                stats, rt = S.stats_of(rirs.reshape(-1), np.arange(len(paths), dtype=np.int64) * self.rir_len, lens, self.SR, with_rt60=True)
+                out[name] = S.table(paths, lens, self.SR, stats, rt)
+        return out
+
     # ---- draws -------------------------------------------------------------------------------------------------------
     def _rows(self, rng, proportion: float, n: int) -> int:
         """SynDataset._select_rir (:205-213) as a row: a response with probability `proportion`, else -1"""

@@ -2073,3 +2073,126 @@ class BandExpandFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         return band_pool(dy.contiguous(), ctx.starts, ctx.mean), None, None, None
+
+
+# ======================================================================================================================
+# per-file statistics of a pool of recordings (cruse_screen_clips, cruse_rt60; cruse_amd/screen.py builds the reference's list builder
+# dataset/preprocess_dataset.py on them)
+# ======================================================================================================================
+SCREEN_COLUMNS = ("peak", "n_clipped", "rms", "n_windows", "n_active", "activity")
+RT60_COLUMNS = ("rt60", "t_peak", "edc_floor_db")
+
+
+class RaggedPlan:
+    """Where the utterances of a flat pool lie: the HOST tables (judged here: 0 <= start, 0 <= len, start + len <= pool_len) and their
+    device copies, made once; the per-window-size prefix tables and the workspaces of the two kernels are built on first use and kept,
+    so a call that is handed its plan allocates and copies nothing (it captures into a HIP graph)."""
+
+    def __init__(self, pool_len: int, start, length, device):
+        import numpy as np
+        dev_in = [t if isinstance(t, torch.Tensor) and t.is_cuda else None for t in (start, length)]
+        host = [np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for t in (start, length)]
+        host = [h.astype(np.int64) if h.size == 0 else h for h in host]       # an empty list has no integer type of its own
+        for h, name in zip(host, ("start", "length")):
+            if h.ndim != 1 or h.dtype.kind not in "iu":
+                raise ValueError(f"screen: {name} must be a flat integer table, got {h.dtype} {h.shape}")
+        self.start_h, self.len_h = (h.astype(np.int64) for h in host)
+        if self.start_h.shape != self.len_h.shape:
+            raise ValueError(f"screen: start {self.start_h.shape} and length {self.len_h.shape} differ")
+        if np.any(self.start_h < 0) or np.any(self.len_h < 0) or np.any(self.start_h + self.len_h > int(pool_len)):
+            raise ValueError(f"screen: an utterance leaves the pool [0, {int(pool_len)})")
+        self.n, self.pool_len, self.device = int(self.start_h.shape[0]), int(pool_len), torch.device(device)
+        self.max_len = int(self.len_h.max()) if self.n else 0
+        dev = []
+        for t, h in zip(dev_in, (self.start_h, self.len_h)):
+            if t is None or t.dtype != torch.int64 or not t.is_contiguous():
+                t = torch.from_numpy(h).to(self.device)
+            dev.append(t)
+        self.start, self.length = dev
+        self._windows = {}
+        self._rt60_ws = None
+
+    def windows(self, window: int):
+        """-> (win_first int64 [n + 1] on the device, total windows, the window pass's workspace)"""
+        import numpy as np
+        window = int(window)
+        if window not in self._windows:
+            first = np.concatenate([[0], np.cumsum(-(-self.len_h // max(window, 1)))]).astype(np.int64)
+            total = int(first[-1])
+            nbytes = lib.cruse_screen_ws_bytes(self.n, total)
+            if nbytes < 0:
+                raise RuntimeError(f"screen_clips: {self.n} utterances in {total} windows of {window} samples are refused "
+                                   "(cruse_screen_ws_bytes)")
+            self._windows[window] = (torch.from_numpy(first).to(self.device), total,
+                                     torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device))
+        return self._windows[window]
+
+    def rt60_ws(self):
+        if self._rt60_ws is None:
+            nbytes = lib.cruse_rt60_ws_bytes(self.n, self.max_len)
+            if nbytes < 0:
+                raise RuntimeError(f"rt60: {self.n} responses of up to {self.max_len} samples are refused (cruse_rt60_ws_bytes)")
+            self._rt60_ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+        return self._rt60_ws
+
+
+def ragged_plan(pool: torch.Tensor, start, length) -> RaggedPlan:
+    """start / length: host sequences or numpy arrays (validated, copied to the device once), or int64 device tensors (read back once
+    for the validation, then used as they are)"""
+    if pool.dim() != 1:
+        raise RuntimeError(f"screen: the pool must be flat, got {tuple(pool.shape)}")
+    return RaggedPlan(pool.numel(), start, length, pool.device)
+
+
+def _screen_out(out, n: int, cols: int, device, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(n, cols, device=device, dtype=torch.float64)
+    if out.shape != (n, cols) or out.dtype != torch.float64 or out.device != device:
+        raise RuntimeError(f"{name}: out must be float64 [{n}, {cols}] on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def _screen_plan(pool, start, length, plan, name):
+    _f32(pool, name)
+    if plan is None:
+        plan = ragged_plan(pool, start, length)
+    elif plan.pool_len != pool.numel() or plan.device != pool.device:
+        raise RuntimeError(f"{name}: the plan was made for a pool of {plan.pool_len} samples on {plan.device}")
+    return plan
+
+
+def screen_clips(pool: torch.Tensor, start=None, length=None, sr: int = 16000, clip_threshold: float = 0.999, target_dB_FS: float = -25.0,
+                 activity_threshold: float = 0.13, plan: Optional[RaggedPlan] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per utterance pool[start[i] : start[i] + length[i]] -> float64 [n, 6] on the device, columns SCREEN_COLUMNS: peak = max |x| and
+    n_clipped = #{|x| > clip_threshold} (feature.is_clipped is n_clipped > 0), rms (feature.tailor_dB_FS), and n_windows, n_active,
+    activity = feature.activity_detector's perc_active over windows of int(sr * 0.05) samples, in float64 (include/cruse_hip.h states the
+    formulas).  An empty utterance gives 0, 0, 0, 0, 0, NaN.  `plan`: ragged_plan(pool, start, length) made beforehand -- with it and
+    `out` the call copies and allocates nothing."""
+    plan = _screen_plan(pool, start, length, plan, "screen_clips")
+    out = _screen_out(out, plan.n, len(SCREEN_COLUMNS), pool.device, "screen_clips")
+    if plan.n == 0:
+        return out
+    window = int(sr * 0.05)
+    first, total, ws = plan.windows(window)
+    check(lib.cruse_screen_clips(_p(pool), _p(plan.start), _p(plan.length), _p(first), plan.n, total, window, float(clip_threshold),
+                                 float(target_dB_FS), float(activity_threshold), _p(ws), _p(out), _stream()))
+    return out
+
+
+def rt60(pool: torch.Tensor, start=None, length=None, sr: int = 16000, lo_db: float = -5.0, hi_db: float = -25.0,
+         plan: Optional[RaggedPlan] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Reverberation time of every impulse response pool[start[i] : start[i] + length[i]] -> float64 [n, 3] on the device, columns
+    RT60_COLUMNS: from the peak t_peak on, Schroeder's backward integral E[t] = sum_{m >= t} h[m]^2, D = 10 log10(E / E[t_peak]), a
+    least-squares line through D where lo_db >= D > hi_db, rt60 = -60 / (slope sr); edc_floor_db = D at the last sample.  The defaults
+    are T20 (ISO 3382-2).  NaN for an empty or all-zero response, a range of fewer than 2 points and a decay that never reaches hi_db.
+
+    Departure from the reference's utils.cal_rt60 (utils/utils.py:270-320), which cannot run (stats.Linregress; a band mask that zeroes
+    every bin below hifreq): its 15 third-octave brick-wall bands, 2500-sample smoothing of |h| in dB and median over bands are not
+    restated.  The quantity here is the BROADBAND T20 of the energy decay curve; banded RT60 is not built."""
+    plan = _screen_plan(pool, start, length, plan, "rt60")
+    out = _screen_out(out, plan.n, len(RT60_COLUMNS), pool.device, "rt60")
+    if plan.n == 0:
+        return out
+    check(lib.cruse_rt60(_p(pool), _p(plan.start), _p(plan.length), plan.n, plan.max_len, int(sr), float(lo_db), float(hi_db),
+                         _p(plan.rt60_ws()), _p(out), _stream()))
+    return out

@@ -1279,6 +1279,53 @@ int cruse_grouped_linear_bwd_dw(const float* dy, const float* y, const float* x,
 int cruse_band_pool(const float* x, const int* starts, int rows, int F, int n_bands, int mean, float* y, void* stream);
 int cruse_band_expand(const float* m, const int* starts, int rows, int F, int n_bands, int mean, float* y, void* stream);
 
+/* ---- per-file statistics of a pool of recordings (ABI 15, additive; csrc/screen.hip) ---------------------------
+ * What the reference's list builder (dataset/preprocess_dataset.py:118-153) needs to reject a file; its four tests are stubs set to 0
+ * there (:130-133).  pool: flat f32 on the device (filepairs.load_pool); utterance i is pool[start[i] .. start[i] + len[i]); start, len:
+ * int64 [n] on the device, start arbitrary (no alignment assumed), len >= 0.  The device validates neither: the tables are judged on the
+ * host from the arrays they were uploaded from (cruse_amd.ops.ragged_plan).  No sample outside an utterance is loaded.  Every sum is
+ * f64 in an order that follows from the tables alone, no atomics: bit-identical from run to run.  No allocation, no host synchronisation,
+ * no host read of a device buffer: the calls capture into a HIP graph.  ws needs no initialisation.
+ *
+ * cruse_screen_clips -> out f64 [n][6] = peak = max |x| (train_base/acoustics/feature.py:106-107 is_clipped's operand), n_clipped =
+ * #{|x| > clip_thr} compared in f32 (:107; is_clipped = n_clipped > 0), rms = sqrt(mean x^2) (:100 tailor_dB_FS), n_windows =
+ * ceil(len / window), n_active, activity = n_active / n_windows (:194-236 activity_detector's perc_active, line for line in f64):
+ *     scalar = 10^(target_db / 20) / (rms + 1e-6)                        (:101; the scaling of :102 is folded into the window sums)
+ *     e_w = 20 log10(scalar^2 S_w + 1e-6), S_w = the window's sum of x^2  (:221)
+ *     p_w = 1 / (1 + exp(-(-1 + 0.2 e_w)))                               (:222)
+ *     smoothed_w = 0.8 p_w + 0.2 p_{w-1} if p_w > p_{w-1} else 0.05 p_w + 0.95 p_{w-1}, p_{-1} = 0     (:224-227, :231)
+ *     active where smoothed_w > act_thr                                  (:229)
+ * The smoother reads the UNSMOOTHED p of the window before (:231), so windows are independent.  len = 0: the row 0, 0, 0, 0, 0, NaN.
+ * win_first: int64 [n + 1] on the device, the exclusive prefix of ceil(len / window), win_first[n] = total_windows (the host's sum: it
+ * sizes the grid).  Two launches: one wavefront per window reads its samples once and writes one row of CRUSE_SCREEN_WS_ROW bytes of
+ * ws; one workgroup per utterance finishes.  ws: cruse_screen_ws_bytes(n, total_windows) bytes.
+ *
+ * cruse_rt60 -> out f64 [n][3] = rt60 in seconds, t_peak = t0 = the first index of max |h|, edc_floor_db = D at the last sample:
+ *     E[t] = sum_{m >= t} h[m]^2, t >= t0 (Schroeder's backward integral);  D[t] = 10 log10(E[t] / E[t0])
+ *     t_lo = t0 + #{t : D[t] > lo_db}, t_hi = t0 + #{t : D[t] > hi_db}    (E does not rise, so the counts are the crossings)
+ *     slope = least-squares slope of D on t over [t_lo, t_hi), t centred on the range's midpoint;  rt60 = -60 / (slope sr)
+ * lo_db = -5, hi_db = -25 is T20 of ISO 3382-2.  This stands where utils/utils.py:270-320 cal_rt60 stands in the reference; that
+ * function cannot run (stats.Linregress, :314) and its band mask zeroes every bin below hifreq (:292-293), so its 15 third-octave
+ * bands, 2500-sample smoothing and median are NOT restated: the quantity here is broadband.  rt60 = NaN, nothing faults: len = 0 (all
+ * three NaN), an all-zero response, fewer than 2 points in the range, a decay that never reaches hi_db, len > max_len.  One launch, one
+ * workgroup per response; E is rebuilt chunk by chunk (CRUSE_RT60_CHUNK samples) from per-chunk suffix sums kept in ws:
+ * cruse_rt60_ws_bytes(n, max_len) bytes, max_len >= every len.
+ *
+ * Refused with CRUSE_E_SHAPE before any launch, cruse_last_error naming the argument: n < 0, window < 1 or > 2^30, total_windows < 0 or
+ * > CRUSE_SCREEN_MAX_WINDOWS, max_len < 0 or > CRUSE_RT60_MAX_LEN, sr < 1, lo_db <= hi_db, a null pointer; CRUSE_E_ALIGN: pool not
+ * 4-byte, a table, ws or out not 8-byte aligned.  The two _ws_bytes return -1 for a shape the calls refuse.  n = 0 launches nothing. */
+#define CRUSE_SCREEN_MAX_WINDOWS 2147483647LL
+#define CRUSE_SCREEN_WS_ROW 16
+#define CRUSE_RT60_CHUNK 2048
+#define CRUSE_RT60_MAX_LEN 16777216
+long long cruse_screen_ws_bytes(int n, long long total_windows);
+int cruse_screen_clips(const float* pool, const long long* start, const long long* len, const long long* win_first, int n,
+                       long long total_windows, int window, float clip_thr, double target_db, double act_thr, void* ws, double* out,
+                       void* stream);
+long long cruse_rt60_ws_bytes(int n, int max_len);
+int cruse_rt60(const float* pool, const long long* start, const long long* len, int n, int max_len, int sr, double lo_db, double hi_db,
+               void* ws, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
