@@ -198,6 +198,8 @@ SIGNATURES = {
     "cruse_screen_clips": ("ppppiqifddppp", "i"),
     "cruse_rt60_ws_bytes": ("ii", "q"),
     "cruse_rt60": ("pppiiiddppp", "i"),
+    "cruse_mrspec_ws_bytes": ("iipi", "z"),
+    "cruse_mrspec_loss": ("ppiipiffppzppfp", "i"),
 }
 
 

@@ -34,8 +34,8 @@ from .model.cruse_net import N_BUCKETS, bucket_of, unet2_backward, unet2_forward
 
 ALIGN = 64  # floats
 
-LOSSES = ("wo_male", "si_snr", "sdnr", "wo_male_df", "l1", "mse")
-WAVE_LOSSES = ("si_snr", "l1", "mse")            # waveform in -> waveform loss: the estimate goes through the iSTFT
+LOSSES = ("wo_male", "si_snr", "sdnr", "wo_male_df", "l1", "mse", "mrspec")
+WAVE_LOSSES = ("si_snr", "l1", "mse", "mrspec")            # waveform in -> waveform loss: the estimate goes through the iSTFT
 
 
 def unused_parameter(name: str) -> bool:
@@ -177,7 +177,8 @@ class TrainEngine:
     "sdnr" (loss_func/loss.py:151-175 with the mask as gain; `snr_db`, `sdnr_beta_db`) or "wo_male_df" -- BASELINE
     config 4: the mask is the real part of a DeepFilter(t_dim=1, f_dim=5) coefficient field (model/deep_filter.py:15-41;
     DECISION recorded in oracle.train_step_loss: filters = (mask padded to 161 bins, 0)), the enhanced spectrum is the
-    filter output and WO-MALE is taken on it.
+    filter output and WO-MALE is taken on it.  "mrspec": MultResSpecLoss (test/test_loss.py:193-229) on the enhanced waveform through the
+    iSTFT; mrs_ffts / mrs_gamma / mrs_factor / mrs_f_complex are its constructor's n_ffts / gamma / factor / f_complex.
     use_graph: replay the step from HIP graph(s) (True) or launch its ~170 kernels eagerly (False).  On the bench step the
     eager form is the faster one once the host keeps ahead (6.08 vs 6.3 ms); a busy or slow host favours the
     graph.  "auto" decides by measurement on the first real steps: 1 + 3 steps from the graph, 1 + 3 launched eagerly
@@ -191,7 +192,8 @@ class TrainEngine:
                  n_fft=320, hop=160, precision: Optional[str] = None, use_graph=True,
                  loss_alpha=2.0, loss_beta=1.0, loss: str = "wo_male", clip_grad_norm: float = 0.0,
                  snr_db: float = 0.0, sdnr_beta_db: float = 20.0, bucketed: Optional[bool] = None,
-                 config: Optional[EngineConfig] = None):
+                 config: Optional[EngineConfig] = None, mrs_ffts=(128, 256, 512), mrs_gamma: float = 0.3, mrs_factor: float = 1.0,
+                 mrs_f_complex=None):
         if not torch.cuda.is_available():
             raise RuntimeError("cruse_amd.TrainEngine needs a HIP device (there is no CPU path)")
         self.model = model
@@ -210,6 +212,7 @@ class TrainEngine:
         if loss not in LOSSES:
             raise ValueError(f"unknown loss {loss!r} ({' | '.join(LOSSES)})")
         self.loss = loss
+        self.mrs = ops.mrspec_args(mrs_ffts, mrs_gamma, mrs_factor, mrs_f_complex) if loss == "mrspec" else None
         self.clip = float(clip_grad_norm or 0.0)
         self.flat = FlatParams(model)
         self.flat.broadcast(0)
@@ -301,6 +304,9 @@ class TrainEngine:
             if self.loss == "si_snr":
                 loss_sum, coef = ops.sisnr_fwd(est, clean)
                 dwave = ops.sisnr_bwd(est, clean, coef) if training else None
+                self._norm = 1.0
+            elif self.loss == "mrspec":
+                loss_sum, dwave = ops.mrspec_loss(est, clean, *self.mrs, want_grad=training)
                 self._norm = 1.0
             else:                                                     # reduction "mean" over all B * L samples
                 loss_sum, dwave = ops.wave_l1_mse(est, clean, self.loss == "mse", want_grad=training)

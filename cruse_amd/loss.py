@@ -95,6 +95,45 @@ def si_snr_loss():
     return si_snr
 
 
+class _MrSpecFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, s, n_ffts, gamma, factor, f_complex):
+        x = x.contiguous().float(); s = s.contiguous().float()
+        loss, dx = ops.mrspec_loss(x, s, n_ffts, gamma, factor, f_complex, want_grad=x.requires_grad)
+        ctx.dx = dx
+        return loss.to(torch.float32).reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.dx * g, None, None, None, None, None
+
+
+def multi_res_spec_loss(n_ffts=(128, 256, 512), gamma=0.3, factor=1.0, f_complex=None):
+    """MultResSpecLoss(n_ffts, gamma, factor, f_complex) of test/test_loss.py:193-229 (DeepFilterNet's multi-resolution spectral loss) on
+    HIP kernels: returns fn(input, target) on [B,L] waveforms (leading dimensions are flattened, as the reference's Stft does), usable
+    through autograd; no gradient is produced for the target.  The default sizes are the 16 kHz analogue of DeepFilterNet's 48 kHz ones."""
+    n_ffts, gamma, factor, f_complex = ops.mrspec_args(n_ffts, gamma, factor, f_complex)
+
+    def fn(input, target):
+        if input.shape != target.shape:
+            raise RuntimeError(f"Dimension mismatch when calculate the multi-resolution spectral loss, {input.shape} vs {target.shape}")
+        L = input.shape[-1]
+        return _MrSpecFn.apply(input.reshape(-1, L), target.detach().reshape(-1, L), n_ffts, gamma, factor, f_complex)
+    return fn
+
+
+class MultiResSpecLoss(torch.nn.Module):
+    """the reference's module form (constructor arguments of test/test_loss.py:198) around multi_res_spec_loss"""
+
+    def __init__(self, n_ffts, gamma, factor, f_complex=None):
+        super().__init__()
+        self.n_ffts, self.gamma, self.f, self.f_complex = ops.mrspec_args(n_ffts, gamma, factor, f_complex)
+        self._fn = multi_res_spec_loss(self.n_ffts, self.gamma, self.f, self.f_complex)
+
+    def forward(self, input, target):
+        return self._fn(input, target)
+
+
 class _MaskedSdnrFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mask, cre, cim, nre, nim, snr_db, beta_db):

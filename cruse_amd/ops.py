@@ -1037,6 +1037,66 @@ def wave_l1_mse(est, ref, mse: bool, want_grad=True):
     return loss, dest
 
 
+MRSPEC_MIN_N, MRSPEC_MAX_N, MRSPEC_MAX_R = 128, 2048, 8
+
+
+def mrspec_args(n_ffts, gamma=0.3, factor=1.0, f_complex=None):
+    """-> (n_ffts tuple, gamma, factor, f_complex: None or a tuple of one weight per resolution), as MultResSpecLoss's constructor reads
+    them (test/test_loss.py:198-210: None or 0 = no complex term, a scalar = that weight for every resolution, a list = one each).
+    ValueError naming the argument for what cruse_mrspec_loss would refuse."""
+    try:
+        ns = tuple(int(n) for n in n_ffts)
+    except TypeError:
+        raise ValueError(f"n_ffts must be a sequence of FFT sizes, got {n_ffts!r}") from None
+    if not 1 <= len(ns) <= MRSPEC_MAX_R:
+        raise ValueError(f"n_ffts must hold 1..{MRSPEC_MAX_R} sizes, got {len(ns)}")
+    for n in ns:
+        if n < MRSPEC_MIN_N or n > MRSPEC_MAX_N or n & (n - 1):
+            raise ValueError(f"n_ffts: {n} is not a power of two in [{MRSPEC_MIN_N}, {MRSPEC_MAX_N}]")
+    gamma, factor = float(gamma), float(factor)
+    if not gamma > 0.0:
+        raise ValueError(f"gamma must be positive, got {gamma!r}")
+    if isinstance(f_complex, (list, tuple)):
+        fc = tuple(float(v) for v in f_complex)
+        if len(fc) != len(ns):
+            raise ValueError(f"f_complex has {len(fc)} values for {len(ns)} resolutions (n_ffts)")
+    elif f_complex is None or f_complex == 0:
+        fc = None
+    else:
+        fc = (float(f_complex),) * len(ns)
+    return ns, gamma, factor, fc
+
+
+def mrspec_ws_bytes(B, L, n_ffts) -> int:
+    """cruse_mrspec_ws_bytes(B, L, n_ffts): 0 for a shape the call refuses"""
+    arr = (ctypes.c_int * len(n_ffts))(*[int(n) for n in n_ffts])
+    return int(lib.cruse_mrspec_ws_bytes(int(B), int(L), ctypes.cast(arr, ctypes.c_void_p), len(n_ffts)))
+
+
+def mrspec_loss(est, ref, n_ffts, gamma=0.3, factor=1.0, f_complex=None, want_grad=True, grad_scale=1.0):
+    """The multi-resolution spectral loss (MultResSpecLoss, test/test_loss.py:193-229) of waveforms est, ref [B,L] f32
+    -> (loss f64[1], dloss/dest * grad_scale [B,L] or None).  R + 2 launches (R + 1 without the gradient), deterministic."""
+    ns, gamma, factor, fc = mrspec_args(n_ffts, gamma, factor, f_complex)
+    if est.dim() != 2 or est.shape != ref.shape:
+        raise RuntimeError(f"Dimension mismatch when calculate the multi-resolution spectral loss, {tuple(est.shape)} vs {tuple(ref.shape)}")
+    B, L = est.shape
+    if L <= max(ns) // 2:
+        raise ValueError(f"clips of {L} samples are too short for n_ffts {ns}: reflect padding needs more than {max(ns) // 2}")
+    R = len(ns)
+    n_arr = (ctypes.c_int * R)(*ns)
+    fc_arr = (ctypes.c_float * R)(*fc) if fc is not None else None
+    need = int(lib.cruse_mrspec_ws_bytes(B, L, ctypes.cast(n_arr, ctypes.c_void_p), R))
+    if need == 0:
+        check(-1)
+    ws = _ws(("mrspec", _stream()), need, est.device, zero=False)
+    loss = torch.empty(1, device=est.device, dtype=torch.float64)
+    dest = torch.empty_like(est) if want_grad else None
+    check(lib.cruse_mrspec_loss(_p(est), _p(ref), B, L, ctypes.cast(n_arr, ctypes.c_void_p), R, gamma, factor,
+                                ctypes.cast(fc_arr, ctypes.c_void_p) if fc_arr is not None else None, _p(ws), need, _p(loss), _p(dest),
+                                float(grad_scale), _stream()))
+    return loss, dest
+
+
 def deepfilter_fwd(xr, xi, hr, hi, f_dim, t_dim, out=None):
     B, F, T = xr.shape
     o_r, o_i = (torch.empty_like(xr), torch.empty_like(xr)) if out is None else out

@@ -356,7 +356,7 @@ class Trainer:
             tag = ("l1" if isinstance(loss_function, torch.nn.L1Loss) else "mse", {})
         if tag is None:
             raise RuntimeError(f"loss_function {loss_function!r} has no fused HIP form: use l1_loss, mse_loss, wo_male_loss, "
-                               "wo_male_df_loss, si_snr_loss or sdnr_loss from train_base.loss (config [loss_function].name)")
+                               "wo_male_df_loss, si_snr_loss, sdnr_loss or multi_res_spec_loss from train_base.loss (config [loss_function].name)")
         loss_name, loss_kwargs = tag
         # how validation turns the network output into audio: a model trained on the DeepFilter(1, 5) head is scored through that head
         self.validation_head = "df" if loss_name == "wo_male_df" else "mask"

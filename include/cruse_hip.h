@@ -1326,6 +1326,33 @@ long long cruse_rt60_ws_bytes(int n, int max_len);
 int cruse_rt60(const float* pool, const long long* start, const long long* len, int n, int max_len, int sr, double lo_db, double hi_db,
                void* ws, double* out, void* stream);
 
+/* ---- multi-resolution spectral loss (cruse_amd/csrc/mrspec.hip) --------------------------------------------------
+ * MultResSpecLoss of test/test_loss.py:193-229 (with Stft :140-165 and angle :232-243; its two one-token repairs: torch.zeros() -> a
+ * scalar zero, save_for_backend -> save_for_backward) on waveforms est, ref [B,L] f32:
+ *     loss = sum_r factor * mean (|Y|^g - |S|^g)^2 + f_complex[r] * mean |(|Y|^g e^{i arg Y}) - (|S|^g e^{i arg S})|^2
+ * Y = STFT_N(est), S = STFT_N(ref) as torch.stft(n_fft = N, hop = N / 4, periodic Hann, center = True (reflect), normalized = True,
+ * onesided) for every N of n_ffts (HOST array of R values, each a power of two in [CRUSE_MRSPEC_MIN_N, CRUSE_MRSPEC_MAX_N]); |.| is clamped
+ * at 1e-12 before the power unless gamma == 1, where the terms are (|Y| - |S|)^2 and |Y - S|^2.  f_complex: HOST array of R weights or
+ * NULL (no complex term).  loss (device, f64[1]) receives the value; dest (device [B,L], or NULL: evaluation, the inverse half is
+ * skipped) receives grad_scale * dloss/dest as torch autograd gives it on that code (angle.backward's clamp_min(1e-10) on |x|^2,
+ * clamp_min's zero gradient below 1e-12, abs's zero gradient at 0): est == ref and all-zero inputs give loss 0 and an all-zero gradient,
+ * nothing is ever NaN or Inf.  No gradient wrt ref.
+ * Deterministic (owner computes, no float atomics); R + 2 launches on `stream` (R + 1 without dest), no allocation, no synchronisation,
+ * capturable.  ws: cruse_mrspec_ws_bytes(B, L, n_ffts, R) bytes, 256-byte aligned, laid out as
+ *     | f64 loss partial sums, resolution after resolution: B * runs_r each | up to a multiple of 256 bytes |
+ *     | f32 padded gradients [B, L + N_r] per resolution, each rounded up to a multiple of 256 bytes |
+ * with runs_r = ceil((L + N_r) / (hops(N_r) * N_r / 4)) and hops(128 .. 2048) = 29, 13, 13, 9, 8.
+ * Refused with CRUSE_E_SHAPE before any device call, cruse_last_error naming the argument and its value: a null est, ref, ws or loss;
+ * B < 1 or > CRUSE_MRSPEC_MAX_B; R outside 1..CRUSE_MRSPEC_MAX_R; an N that is not such a power of two; L <= max N / 2 (reflect padding)
+ * or > 2^30; B * L > 2^36; gamma <= 0; ws_bytes too small.  cruse_mrspec_ws_bytes returns 0 for a shape the call refuses. */
+#define CRUSE_MRSPEC_MIN_N 128
+#define CRUSE_MRSPEC_MAX_N 2048
+#define CRUSE_MRSPEC_MAX_R 8
+#define CRUSE_MRSPEC_MAX_B 65535
+size_t cruse_mrspec_ws_bytes(int B, int L, const int* n_ffts, int R);
+int cruse_mrspec_loss(const float* est, const float* ref, int B, int L, const int* n_ffts, int R, float gamma, float factor,
+                      const float* f_complex, void* ws, size_t ws_bytes, double* loss, float* dest, float grad_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,3 +51,13 @@ def sdnr_loss(snr=0.0, beta=20.0):
         return masked_sdnr(mask, clean_real, clean_imag, noisy_real, noisy_imag, snr, beta)
     fn.cruse_loss = ("sdnr", dict(snr_db=float(snr), sdnr_beta_db=float(beta)))
     return fn
+
+
+def multi_res_spec_loss(n_ffts=(128, 256, 512), gamma=0.3, factor=1.0, f_complex=None):
+    """MultResSpecLoss (test/test_loss.py:193-229) on the enhanced waveform: the engine runs it through the iSTFT like si_snr_loss."""
+    from cruse_amd import ops
+    from cruse_amd.loss import multi_res_spec_loss as _f
+    fn = _f(n_ffts, gamma, factor, f_complex)
+    ns, g, f, fc = ops.mrspec_args(n_ffts, gamma, factor, f_complex)
+    fn.cruse_loss = ("mrspec", dict(mrs_ffts=ns, mrs_gamma=g, mrs_factor=f, mrs_f_complex=fc))
+    return fn
