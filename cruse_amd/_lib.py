@@ -43,6 +43,7 @@ SIGNATURES = {
     "cruse_conv_gather_bnin": ("ppiqffpppppppppppiiiiiiiiiipip", "i"),
     "cruse_conv_scatter2_bnin": ("ppiqffpppppppppppiiiiiiiiipip", "i"),
     "cruse_conv_wgrad": ("pppiiiiiiiiiiiipp", "i"),
+    "cruse_conv_wgrad_plan": ("i" * 14 + "zp", "i"),
     "cruse_channel_sum": ("pqiipp", "i"),
     "cruse_col_sum": ("pqiipp", "i"),
     "cruse_bn_stats": ("pqiipip", "i"),

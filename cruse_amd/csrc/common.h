@@ -39,6 +39,32 @@ enum { CRUSE_CP_ROUTE, CRUSE_CP_FUSED, CRUSE_CP_MT, CRUSE_CP_NW, CRUSE_CP_GRID, 
 // plan != null: nothing is launched, plan[CRUSE_CP_MT .. CRUSE_CP_LDS] receive what would have been (conv_mfma.hip)
 int cruse_conv_mfma_try(const CruseConvCall& c, int* plan);
 
+// one frame-major weight-gradient call (cruse_conv_wgrad): a / bt hold a_dtype / bt_dtype elements (CRUSE_DT_F32 or CRUSE_DT_BF16), ws is the
+// scratch for the partial slabs and ws_bytes its size
+struct CruseWgradCall {
+    const void* a; const void* bt; int a_dtype, bt_dtype;
+    float* dw; void* ws; size_t ws_bytes;
+    int B, T, Ca, Fa, Cb, Fb, KT, S, pad, prec;
+    hipStream_t stream;
+};
+constexpr int CRUSE_WGRAD_MAX_SLABS = 1024;      // cruse_conv_wgrad_ws_bytes holds this many [Ca][Cb][KT][3] slabs (channels rounded up to 16)
+// what a weight-gradient call launches, as cruse_conv_wgrad_plan reports it: the kernel, its template integers (VALU: CB_T, KT; LDS-staged
+// MFMA: TFW, MT, NTW; register-direct: MTW, NWP, U, F32IN), its grid, block and dynamic LDS bytes, the partial slabs it writes, the
+// register-direct kernel's workgroups per slab and frames per slab, and the reduce kernel that sums the slabs into dw with its grid
+enum { CRUSE_WP_KERNEL, CRUSE_WP_T0, CRUSE_WP_T1, CRUSE_WP_T2, CRUSE_WP_T3, CRUSE_WP_GRID, CRUSE_WP_BLOCK, CRUSE_WP_LDS, CRUSE_WP_SLABS, CRUSE_WP_TG,
+       CRUSE_WP_FPW, CRUSE_WP_REDUCE, CRUSE_WP_RGX, CRUSE_WP_RGY, CRUSE_WP_N };
+enum { CRUSE_WK_VALU, CRUSE_WK_MFMA, CRUSE_WK_RD };                   // conv_wgrad_kernel, wgrad_mfma_kernel, wgrad_rd_kernel
+enum { CRUSE_WR_SLABS = 1, CRUSE_WR_RD = 2 };                         // wgrad_reduce_kernel, wgrad_rd_reduce_kernel
+struct CruseWgradPlan { int v[CRUSE_WP_N]; };
+// The deciders of the two MFMA kernels: 1 the kernel takes the call and `p` is filled, 0 the shape / mode is not eligible (the next kernel
+// is asked), < 0 error.  They launch nothing; the _launch functions launch the planned kernel and leave the launch check to the caller
+// (conv.hip, wgrad_run).
+int cruse_wgrad_rd_plan(const CruseWgradCall& c, CruseWgradPlan& p);
+int cruse_wgrad_rd_launch(const CruseWgradCall& c, const CruseWgradPlan& p);
+void cruse_wgrad_rd_reduce(const CruseWgradCall& c, const CruseWgradPlan& p);
+int cruse_wgrad_mfma_plan(const CruseWgradCall& c, CruseWgradPlan& p);
+int cruse_wgrad_mfma_launch(const CruseWgradCall& c, const CruseWgradPlan& p);
+
 // what a general NCHW convolution / weight-gradient call would launch, as cruse_conv2d_nchw_plan reports it (generic.hip):
 // form id, two template integers, grid, block, dynamic LDS bytes, an auxiliary integer (conv: the epilogue instance of the LDS-transposed
 // pointwise kernel; wgrad: `run` of the pointwise MFMA kernel, `band` of the depthwise one), the requests the kernel serves in its

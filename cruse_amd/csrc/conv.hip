@@ -297,7 +297,6 @@ struct WgradArgs {
 };
 
 constexpr int WG_THREADS = 256;
-constexpr int WG_MAX_BLOCKS = 1024;
 
 template <int CB_T, int KT>
 __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgradArgs p) {
@@ -701,79 +700,105 @@ extern "C" int cruse_conv_plan(int scatter, int Cin, int Fin, int Cout, int Fout
 
 extern "C" size_t cruse_conv_wgrad_ws_bytes(int Ca, int Cb, int KT) {
     // partial slabs: [slab][Ca][Cb][KT][3] (LDS-staged and VALU kernels) or accumulator images of 16 x 16 tiles (register-direct kernel)
-    return (size_t)WG_MAX_BLOCKS * ((Ca + 15) / 16 * 16) * ((Cb + 15) / 16 * 16) * KT * 3 * sizeof(float);
+    return (size_t)CRUSE_WGRAD_MAX_SLABS * ((Ca + 15) / 16 * 16) * ((Cb + 15) / 16 * 16) * KT * 3 * sizeof(float);
 }
 
-int cruse_wgrad_mfma_try(const float* a, const float* bt, float* partial, int max_slabs,
-                         int B, int T, int Ca, int Fa, int Cb, int Fb, int KT, int S, int pad, int prec, int a_bf16, int bt_bf16,
-                         int* nblk_out, hipStream_t stream);
-int cruse_wgrad_rd_try(const float* a, const float* bt, float* partial, size_t ws_bytes, float* dw,
-                       int B, int T, int Ca, int Fa, int Cb, int Fb, int KT, int S, int pad, int prec, int a_bf16, int bt_bf16,
-                       int* nblk_out, hipStream_t stream);
+namespace {
+
+// the VALU kernel's decider: it is asked last, so what it cannot take is refused (f32 operands, 4-channel output tiles that divide the block)
+int wgrad_valu_plan(const CruseWgradCall& c, CruseWgradPlan& p) {
+    CRUSE_REQUIRE(c.a_dtype == CRUSE_DT_F32 && c.bt_dtype == CRUSE_DT_F32, CRUSE_E_DTYPE,
+                  "conv_wgrad: bf16 operands need the MFMA kernel (Ca %d, Cb %d, prec %d)", c.Ca, c.Cb, c.prec);
+    CRUSE_REQUIRE(c.Ca % 4 == 0 && (c.Cb % 4 == 0 || c.Cb == 1), CRUSE_E_SHAPE,
+                  "conv_wgrad: Ca=%d must be a multiple of 4 and Cb=%d a multiple of 4 or 1", c.Ca, c.Cb);
+    const int cbt = (c.Cb % 4 == 0) ? 4 : 1;
+    const int NT = (c.Ca / 4) * (c.Cb / cbt);
+    // a thread must keep one output tile: items w = tid + n*256 have ot = w % NT = tid % NT iff 256 % NT == 0
+    CRUSE_REQUIRE(WG_THREADS % NT == 0, CRUSE_E_SHAPE,
+                  NT % WG_THREADS == 0 ? "conv_wgrad: %d output tiles > %d threads" : "conv_wgrad: %d output tiles do not divide the %d-thread block",
+                  NT, WG_THREADS);
+    const int CaP = c.Ca + 4, CbP = (cbt == 4) ? c.Cb + 4 : c.Cb;
+    const size_t lds_stage = ((size_t)TF * c.Fa * CaP + (size_t)(TF + c.KT - 1) * (c.Fb + 2) * CbP) * 4;
+    const size_t lds_red = (size_t)c.Ca * c.Cb * c.KT * 3 * 4;
+    const size_t lds = lds_stage > lds_red ? lds_stage : lds_red;
+    CRUSE_REQUIRE(lds <= 160 * 1024, CRUSE_E_SHAPE, "conv_wgrad: needs %zu B of LDS", lds);
+    const int ntiles = c.B * cdiv(c.T, TF);
+    const int grid = ntiles < CRUSE_WGRAD_MAX_SLABS ? ntiles : CRUSE_WGRAD_MAX_SLABS;
+    int* v = p.v;
+    v[CRUSE_WP_KERNEL] = CRUSE_WK_VALU;
+    v[CRUSE_WP_T0] = cbt; v[CRUSE_WP_T1] = c.KT; v[CRUSE_WP_T2] = 0; v[CRUSE_WP_T3] = 0;
+    v[CRUSE_WP_GRID] = grid; v[CRUSE_WP_BLOCK] = WG_THREADS; v[CRUSE_WP_LDS] = (int)lds;
+    v[CRUSE_WP_SLABS] = grid; v[CRUSE_WP_TG] = 0; v[CRUSE_WP_FPW] = 0;
+    v[CRUSE_WP_REDUCE] = CRUSE_WR_SLABS; v[CRUSE_WP_RGX] = cdiv(c.Ca * c.Cb * c.KT * 3, 256); v[CRUSE_WP_RGY] = cdiv(grid, 16);
+    return 1;
+}
+
+int wgrad_valu_launch(const CruseWgradCall& c, const CruseWgradPlan& pl) {
+    const int* v = pl.v;
+    WgradArgs p{(const float*)c.a, (const float*)c.bt, (float*)c.ws, c.B, c.T, c.Ca, c.Fa, c.Cb, c.Fb, c.S, c.pad, c.B * cdiv(c.T, TF)};
+    void (*kern)(WgradArgs) = v[CRUSE_WP_T0] == 4 ? (c.KT == 2 ? conv_wgrad_kernel<4, 2> : conv_wgrad_kernel<4, 1>)
+                                                  : (c.KT == 2 ? conv_wgrad_kernel<1, 2> : conv_wgrad_kernel<1, 1>);
+    const int rc = set_smem(kern, v[CRUSE_WP_LDS], "conv_wgrad");
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(v[CRUSE_WP_GRID]), dim3(v[CRUSE_WP_BLOCK]), v[CRUSE_WP_LDS], c.stream, p);
+    return CRUSE_OK;
+}
+
+// The one host path of cruse_conv_wgrad: validate, ask the three deciders in turn (register-direct: the plain bf16 mode, the bench shapes;
+// LDS-staged MFMA; VALU), launch the kernel that took the call and the reduce that sums its slabs into dw.
+// plan != null (cruse_conv_wgrad_plan): decide the same way, write what would be launched and launch nothing.
+int wgrad_run(const CruseWgradCall& c, int* plan = nullptr) {
+    CRUSE_REQUIRE(c.B > 0 && c.T > 0 && c.Ca > 0 && c.Cb > 0, CRUSE_E_SHAPE, "conv_wgrad: empty shape");
+    CRUSE_REQUIRE((c.a_dtype == CRUSE_DT_F32 || c.a_dtype == CRUSE_DT_BF16) && (c.bt_dtype == CRUSE_DT_F32 || c.bt_dtype == CRUSE_DT_BF16),
+                  CRUSE_E_DTYPE, "conv_wgrad: operand dtypes %d / %d (f32 or bf16)", c.a_dtype, c.bt_dtype);
+    CRUSE_REQUIRE((c.KT == 1 || c.KT == 2) && (c.S == 1 || c.S == 2) && (c.pad == 0 || c.pad == 1), CRUSE_E_SHAPE,
+                  "conv_wgrad: unsupported KT=%d S=%d pad=%d", c.KT, c.S, c.pad);
+    CruseWgradPlan p = {};
+    int r = 0;
+    if (c.prec >= 0) {
+        r = cruse_wgrad_rd_plan(c, p);
+        if (r == 0) r = cruse_wgrad_mfma_plan(c, p);
+    }
+    if (r == 0) r = wgrad_valu_plan(c, p);
+    if (r < 0) return r;
+    if (plan) {
+        for (int i = 0; i < CRUSE_WP_N; ++i) plan[i] = p.v[i];
+        return CRUSE_OK;
+    }
+    const int kernel = p.v[CRUSE_WP_KERNEL];
+    const int rc = kernel == CRUSE_WK_RD ? cruse_wgrad_rd_launch(c, p) : kernel == CRUSE_WK_MFMA ? cruse_wgrad_mfma_launch(c, p) : wgrad_valu_launch(c, p);
+    if (rc) return rc;
+    CRUSE_LAUNCH_CHECK(kernel == CRUSE_WK_RD ? "wgrad_rd" : kernel == CRUSE_WK_MFMA ? "wgrad_mfma" : "conv_wgrad");
+    if (p.v[CRUSE_WP_REDUCE] == CRUSE_WR_RD) {
+        cruse_wgrad_rd_reduce(c, p);
+        CRUSE_LAUNCH_CHECK("wgrad_rd_reduce");
+    } else {
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.v[CRUSE_WP_RGX], p.v[CRUSE_WP_RGY]), dim3(256), 0, c.stream, (const float*)c.ws,
+                           p.v[CRUSE_WP_SLABS], c.Ca * c.Cb * c.KT * 3, c.dw);
+        CRUSE_LAUNCH_CHECK("conv_wgrad_reduce");
+    }
+    return CRUSE_OK;
+}
+
+}  // namespace
 
 extern "C" int cruse_conv_wgrad(const float* a, const float* bt, float* dw,
                                 int B, int T, int Ca, int Fa, int Cb, int Fb,
                                 int KT, int S, int pad, int prec, int a_dtype, int bt_dtype, void* ws, void* stream) {
-    CRUSE_REQUIRE(B > 0 && T > 0 && Ca > 0 && Cb > 0, CRUSE_E_SHAPE, "conv_wgrad: empty shape");
-    CRUSE_REQUIRE((a_dtype == CRUSE_DT_F32 || a_dtype == CRUSE_DT_BF16) && (bt_dtype == CRUSE_DT_F32 || bt_dtype == CRUSE_DT_BF16),
-                  CRUSE_E_DTYPE, "conv_wgrad: operand dtypes %d / %d (f32 or bf16)", a_dtype, bt_dtype);
-    CRUSE_REQUIRE((KT == 1 || KT == 2) && (S == 1 || S == 2) && (pad == 0 || pad == 1), CRUSE_E_SHAPE,
-                  "conv_wgrad: unsupported KT=%d S=%d pad=%d", KT, S, pad);
-    if (prec >= 0) {
-        int nblk = 0;
-        // register-direct stream (plain bf16 mode, the bench shapes), else the LDS-staged kernel
-        int r = cruse_wgrad_rd_try(a, bt, (float*)ws, cruse_conv_wgrad_ws_bytes(Ca, Cb, KT), dw, B, T, Ca, Fa, Cb, Fb, KT, S, pad, prec,
-                                   a_dtype == CRUSE_DT_BF16, bt_dtype == CRUSE_DT_BF16, &nblk, (hipStream_t)stream);
-        if (r == 0) r = cruse_wgrad_mfma_try(a, bt, (float*)ws, WG_MAX_BLOCKS, B, T, Ca, Fa, Cb, Fb, KT, S, pad, prec,
-                                             a_dtype == CRUSE_DT_BF16, bt_dtype == CRUSE_DT_BF16, &nblk, (hipStream_t)stream);
-        if (r < 0) return r;
-        if (r == 1 && nblk == 0) return CRUSE_OK;      // (the register-direct kernel reduces its slabs itself)
-        if (r == 1) {
-            const int nout = Ca * Cb * KT * 3;
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(nout, 256), cdiv(nblk, 16)), dim3(256), 0, (hipStream_t)stream,
-                               (const float*)ws, nblk, nout, dw);
-            CRUSE_LAUNCH_CHECK("conv_wgrad_reduce");
-            return CRUSE_OK;
-        }
-    }
-    CRUSE_REQUIRE(a_dtype == CRUSE_DT_F32 && bt_dtype == CRUSE_DT_F32, CRUSE_E_DTYPE,
-                  "conv_wgrad: bf16 operands need the MFMA kernel (Ca %d, Cb %d, prec %d)", Ca, Cb, prec);
-    CRUSE_REQUIRE(Ca % 4 == 0 && (Cb % 4 == 0 || Cb == 1), CRUSE_E_SHAPE,
-                  "conv_wgrad: Ca=%d must be a multiple of 4 and Cb=%d a multiple of 4 or 1", Ca, Cb);
-    CRUSE_REQUIRE((KT == 1 || KT == 2) && (S == 1 || S == 2) && (pad == 0 || pad == 1), CRUSE_E_SHAPE,
-                  "conv_wgrad: unsupported KT=%d S=%d pad=%d", KT, S, pad);
-    const int cbt = (Cb % 4 == 0) ? 4 : 1;
-    const int NT = (Ca / 4) * (Cb / cbt);
-    CRUSE_REQUIRE(WG_THREADS % NT == 0 || NT % WG_THREADS == 0, CRUSE_E_SHAPE,
-                  "conv_wgrad: %d output tiles do not divide the %d-thread block", NT, WG_THREADS);
-    // a thread must keep one output tile: items w = tid + n*256 have ot = w % NT = tid % NT iff 256 % NT == 0
-    CRUSE_REQUIRE(WG_THREADS % NT == 0, CRUSE_E_SHAPE, "conv_wgrad: %d output tiles > %d threads", NT, WG_THREADS);
-    const int CaP = Ca + 4, CbP = (cbt == 4) ? Cb + 4 : Cb;
-    const size_t lds_stage = ((size_t)TF * Fa * CaP + (size_t)(TF + KT - 1) * (Fb + 2) * CbP) * 4;
-    const size_t lds_red = (size_t)Ca * Cb * KT * 3 * 4;
-    const size_t lds = lds_stage > lds_red ? lds_stage : lds_red;
-    CRUSE_REQUIRE(lds <= 160 * 1024, CRUSE_E_SHAPE, "conv_wgrad: needs %zu B of LDS", lds);
-    const int ntiles = B * cdiv(T, TF);
-    const int grid = ntiles < WG_MAX_BLOCKS ? ntiles : WG_MAX_BLOCKS;
-    WgradArgs p{a, bt, (float*)ws, B, T, Ca, Fa, Cb, Fb, S, pad, ntiles};
-    int rc;
-#define LAUNCH_WG(CBT, KTT)                                                                             \
-    do {                                                                                                \
-        if ((rc = set_smem(conv_wgrad_kernel<CBT, KTT>, lds, "conv_wgrad"))) return rc;                 \
-        hipLaunchKernelGGL((conv_wgrad_kernel<CBT, KTT>), dim3(grid), dim3(WG_THREADS), lds,            \
-                           (hipStream_t)stream, p);                                                     \
-    } while (0)
-    if (cbt == 4 && KT == 2) LAUNCH_WG(4, 2);
-    else if (cbt == 4 && KT == 1) LAUNCH_WG(4, 1);
-    else if (cbt == 1 && KT == 2) LAUNCH_WG(1, 2);
-    else LAUNCH_WG(1, 1);
-#undef LAUNCH_WG
-    CRUSE_LAUNCH_CHECK("conv_wgrad");
-    const int nout = Ca * Cb * KT * 3;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(nout, 256), cdiv(grid, 16)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)ws, grid, nout, dw);
-    CRUSE_LAUNCH_CHECK("conv_wgrad_reduce");
-    return CRUSE_OK;
+    return wgrad_run({a, bt, a_dtype, bt_dtype, dw, ws, cruse_conv_wgrad_ws_bytes(Ca, Cb, KT), B, T, Ca, Fa, Cb, Fb, KT, S, pad, prec, (hipStream_t)stream});
+}
+
+// Host-only (no device is touched): what a weight-gradient call of this shape, mode and operand dtypes would launch -- wgrad_run's own
+// decision with the launches left out.  a_misalign / bt_misalign: the operand addresses modulo 16 (alignment selects between the kernels);
+// ws_bytes 0: the workspace of cruse_conv_wgrad_ws_bytes, as the entry point assumes.
+extern "C" int cruse_conv_wgrad_plan(int B, int T, int Ca, int Fa, int Cb, int Fb, int KT, int S, int pad, int prec, int a_dtype, int bt_dtype,
+                                     int a_misalign, int bt_misalign, size_t ws_bytes, int* out) {
+    CRUSE_REQUIRE(out != nullptr && a_misalign >= 0 && a_misalign < 16 && bt_misalign >= 0 && bt_misalign < 16, CRUSE_E_SHAPE,
+                  "conv_wgrad_plan: out is NULL or misalignments %d / %d (0..15)", a_misalign, bt_misalign);
+    alignas(16) static char buf[32];                 // stands for every tensor: never dereferenced
+    for (int i = 0; i < CRUSE_WP_N; ++i) out[i] = 0;
+    return wgrad_run({buf + a_misalign, buf + bt_misalign, a_dtype, bt_dtype, nullptr, buf, ws_bytes ? ws_bytes : cruse_conv_wgrad_ws_bytes(Ca, Cb, KT),
+                      B, T, Ca, Fa, Cb, Fb, KT, S, pad, prec, nullptr}, out);
 }
 
 extern "C" int cruse_channel_sum(const float* g, long long rows, int C, int F, float* out, void* stream) {

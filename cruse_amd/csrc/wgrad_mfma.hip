@@ -344,44 +344,28 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WMArgs p) {
         }
 }
 
-template <int PREC, int TFW, int MT>
-int launch_ntw(const WMArgs& p, int ntw, int grid, size_t lds, hipStream_t s) {
-    int rc;
-#define WM_LAUNCH(NTWV)                                                                                       \
-    do {                                                                                                      \
-        if ((rc = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(wgrad_mfma_kernel<PREC, TFW, MT, NTWV>), lds, \
-                                       "wgrad_mfma"))) return rc;                                             \
-        hipLaunchKernelGGL((wgrad_mfma_kernel<PREC, TFW, MT, NTWV>), dim3(grid), dim3(256), lds, s, p);       \
-    } while (0)
-    if (ntw <= 1) WM_LAUNCH(1);
-    else if (ntw == 2) WM_LAUNCH(2);
-    else WM_LAUNCH(3);
-#undef WM_LAUNCH
-    return CRUSE_OK;
-}
-
+// the instance of a plan: TFW is 4 in the f32 / split-bf16 modes, 4 or 8 in the bf16 mode; MT in {1, 2, 4}, NTW in {1, 2, 3}
 template <int PREC, int TFW>
-int launch_mt(const WMArgs& p, int mt, int ntw, int grid, size_t lds, hipStream_t s) {
-    if (mt <= 1) return launch_ntw<PREC, TFW, 1>(p, ntw, grid, lds, s);
-    if (mt == 2) return launch_ntw<PREC, TFW, 2>(p, ntw, grid, lds, s);
-    return launch_ntw<PREC, TFW, 4>(p, ntw, grid, lds, s);
+auto mfma_form(int mt, int ntw) -> void (*)(WMArgs) {
+    void (*kern)(WMArgs) = nullptr;
+    dispatch_int<1, 2, 4>(mt, [&](auto MT) {
+        return dispatch_int<1, 2, 3>(ntw, [&](auto NTW) { kern = wgrad_mfma_kernel<PREC, TFW, MT(), NTW()>; return 0; });
+    });
+    return kern;
 }
 
 }  // namespace
 
-// 1 = handled (partial slabs written, *nblk_out = number of slabs), 0 = not eligible, < 0 error
-int cruse_wgrad_mfma_try(const float* a, const float* bt, float* partial, int max_slabs,
-                         int B, int T, int Ca, int Fa, int Cb, int Fb, int KT, int S, int pad, int prec, int a_bf16, int bt_bf16,
-                         int* nblk_out, hipStream_t stream) {
-    if ((a_bf16 || bt_bf16) && prec != CRUSE_PREC_BF16) return 0;      // (bf16-stored tensors belong to the bf16 mode)
+int cruse_wgrad_mfma_plan(const CruseWgradCall& c, CruseWgradPlan& p) {
+    const int Ca = c.Ca, Fa = c.Fa, Cb = c.Cb, Fb = c.Fb, KT = c.KT, prec = c.prec;
+    if ((c.a_dtype == CRUSE_DT_BF16 || c.bt_dtype == CRUSE_DT_BF16) && prec != CRUSE_PREC_BF16) return 0;      // (bf16-stored tensors belong to the bf16 mode)
     const int FaP = (Fa + 7) / 8 * 8, NCH = FaP / 8;
-    const int ntaps = KT * 3;
     const int mt = Ca <= 16 ? 1 : (Ca <= 32 ? 2 : 4);
-    const int ntiles_n = (ntaps * Cb + 15) / 16;
+    const int ntiles_n = (KT * 3 * Cb + 15) / 16;
     const int ntw = (ntiles_n + 3) / 4;
     if (Ca > 64 || ntw > 3) return 0;
     if (Fa & 1) return 0;            // the staging works on PAIRS of bins of one row (kernel: "Fa is even"): odd widths go to the exact VALU kernel
-    if ((Ca * Fa) % 4 != 0 || (Cb * Fb) % 4 != 0 || ((uintptr_t)a % 16) != 0 || ((uintptr_t)bt % 16) != 0) return 0;
+    if ((Ca * Fa) % 4 != 0 || (Cb * Fb) % 4 != 0 || ((uintptr_t)c.a % 16) != 0 || ((uintptr_t)c.bt % 16) != 0) return 0;
     const int esz = (prec == CRUSE_PREC_F32) ? 4 : 2, npl = (prec == CRUSE_PREC_BF16X3) ? 2 : 1;
     auto lds_of = [&](int tf) {
         return ((size_t)mt * 16 + (size_t)ntw * 64) * (tf * FaP + RPAD) * esz * npl + (size_t)(tf + KT - 1) * Cb * Fb * 4;
@@ -404,24 +388,34 @@ int cruse_wgrad_mfma_try(const float* a, const float* bt, float* partial, int ma
         gcap = 512;
     }
     if (!fits(tfw)) return 0;
-    const size_t lds = lds_of(tfw);
-    WMArgs p = {};
-    p.a = a; p.bt = bt; p.partial = partial;
-    p.B = B; p.T = T; p.Ca = Ca; p.Fa = Fa; p.Cb = Cb; p.Fb = Fb; p.KT = KT; p.S = S; p.pad = pad;
-    p.FaP = FaP; p.NCH = NCH; p.ntaps = ntaps; p.nrows = tfw + KT - 1;
-    p.ntiles_total = B * ((T + tfw - 1) / tfw);
-    p.dbg = cruse_opt(CRUSE_OPT_wg_dbg, 0);
-    p.a_bf16 = a_bf16 ? 1 : 0; p.bt_bf16 = bt_bf16 ? 1 : 0;
-    int grid = p.ntiles_total < max_slabs ? p.ntiles_total : max_slabs;
+    const int ntiles = c.B * ((c.T + tfw - 1) / tfw);
+    int grid = ntiles < CRUSE_WGRAD_MAX_SLABS ? ntiles : CRUSE_WGRAD_MAX_SLABS;
     if (grid > gcap) grid = gcap;               // resident blocks only; fewer partial slabs to reduce
-    int rc;
-    if (prec == CRUSE_PREC_F32) rc = launch_mt<CRUSE_PREC_F32, 4>(p, mt, ntw, grid, lds, stream);
-    else if (prec == CRUSE_PREC_BF16X3) rc = launch_mt<CRUSE_PREC_BF16X3, 4>(p, mt, ntw, grid, lds, stream);
-    else if (tfw == 4) rc = launch_mt<CRUSE_PREC_BF16, 4>(p, mt, ntw, grid, lds, stream);
-    else rc = launch_mt<CRUSE_PREC_BF16, 8>(p, mt, ntw, grid, lds, stream);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { cruse_set_error("wgrad_mfma: HIP launch failed: %s", hipGetErrorString(e)); return CRUSE_E_HIP; }
-    *nblk_out = grid;
+    int* v = p.v;
+    v[CRUSE_WP_KERNEL] = CRUSE_WK_MFMA;
+    v[CRUSE_WP_T0] = tfw; v[CRUSE_WP_T1] = mt; v[CRUSE_WP_T2] = ntw; v[CRUSE_WP_T3] = 0;
+    v[CRUSE_WP_GRID] = grid; v[CRUSE_WP_BLOCK] = 256; v[CRUSE_WP_LDS] = (int)lds_of(tfw);
+    v[CRUSE_WP_SLABS] = grid; v[CRUSE_WP_TG] = 0; v[CRUSE_WP_FPW] = 0;
+    v[CRUSE_WP_REDUCE] = CRUSE_WR_SLABS; v[CRUSE_WP_RGX] = cdiv(Ca * Cb * KT * 3, 256); v[CRUSE_WP_RGY] = cdiv(grid, 16);
     return 1;
+}
+
+int cruse_wgrad_mfma_launch(const CruseWgradCall& c, const CruseWgradPlan& pl) {
+    const int* v = pl.v;
+    const int tfw = v[CRUSE_WP_T0], mt = v[CRUSE_WP_T1], ntw = v[CRUSE_WP_T2];
+    WMArgs p = {};
+    p.a = (const float*)c.a; p.bt = (const float*)c.bt; p.partial = (float*)c.ws;
+    p.B = c.B; p.T = c.T; p.Ca = c.Ca; p.Fa = c.Fa; p.Cb = c.Cb; p.Fb = c.Fb; p.KT = c.KT; p.S = c.S; p.pad = c.pad;
+    p.FaP = (c.Fa + 7) / 8 * 8; p.NCH = p.FaP / 8; p.ntaps = c.KT * 3; p.nrows = tfw + c.KT - 1;
+    p.ntiles_total = c.B * ((c.T + tfw - 1) / tfw);
+    p.dbg = cruse_opt(CRUSE_OPT_wg_dbg, 0);
+    p.a_bf16 = c.a_dtype == CRUSE_DT_BF16; p.bt_bf16 = c.bt_dtype == CRUSE_DT_BF16;
+    void (*kern)(WMArgs) = c.prec == CRUSE_PREC_F32      ? mfma_form<CRUSE_PREC_F32, 4>(mt, ntw)
+                           : c.prec == CRUSE_PREC_BF16X3 ? mfma_form<CRUSE_PREC_BF16X3, 4>(mt, ntw)
+                           : tfw == 4                    ? mfma_form<CRUSE_PREC_BF16, 4>(mt, ntw)
+                                                         : mfma_form<CRUSE_PREC_BF16, 8>(mt, ntw);
+    const int rc = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(kern), v[CRUSE_WP_LDS], "wgrad_mfma");
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(v[CRUSE_WP_GRID]), dim3(v[CRUSE_WP_BLOCK]), v[CRUSE_WP_LDS], c.stream, p);
+    return CRUSE_OK;
 }

@@ -19,7 +19,7 @@
 // A workgroup is 8 wavefronts that interleave 32-position steps of one contiguous range of frames and share nothing until the end,
 // where their accumulators are summed through LDS (a fixed tree) into one slab -- the accumulator image itself, 256-byte stores -- that
 // wgrad_rd_reduce_kernel sums over the slabs and scatters to dw[ca][cb][kt][kf].  ONE workgroup per CU: the per-workgroup costs (index
-// set-up, LDS tree, slab + its reduction) outweigh what more resident waves hide (cruse_wgrad_rd_try).  Layers whose 3 * MT * pairs
+// set-up, LDS tree, slab + its reduction) outweigh what more resident waves hide (cruse_wgrad_rd_plan).  Layers whose 3 * MT * pairs
 // accumulator tiles exceed 12 per wave split their source windows over TG workgroups per slab, placed on one XCD (shared L2 for `a`).
 #include "common.h"
 #include <stdlib.h>
@@ -316,77 +316,75 @@ __global__ __launch_bounds__(256) void wgrad_rd_reduce_kernel(const float* parti
     atomicAdd(dw + (ca * Cb + cb) * (KT * 3) + kt * 3 + k, sum);
 }
 
-template <int MTW, int NWP, int U>
-int launch_form(const WRArgs& p, int S, int pad, int grid, hipStream_t s) {
-    const size_t lds = (size_t)4 * MTW * NWP * 3 * 256 * sizeof(float);
-    int rc;
-#define WR_LAUNCH(SV, PV)                                                                                                  \
-    do {                                                                                                                   \
-        if (p.a_bf16 && p.bt_bf16) {                                                                                       \
-            if ((rc = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(wgrad_rd_kernel<MTW, NWP, SV, PV, U, false>), lds, "wgrad_rd"))) return rc; \
-            hipLaunchKernelGGL((wgrad_rd_kernel<MTW, NWP, SV, PV, U, false>), dim3(grid), dim3(512), lds, s, p);           \
-        } else {                                                                                                           \
-            if ((rc = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(wgrad_rd_kernel<MTW, NWP, SV, PV, U, true>), lds, "wgrad_rd"))) return rc; \
-            hipLaunchKernelGGL((wgrad_rd_kernel<MTW, NWP, SV, PV, U, true>), dim3(grid), dim3(512), lds, s, p);            \
-        }                                                                                                                  \
-    } while (0)
-    if (S == 1) WR_LAUNCH(1, 1);
-    else if (pad == 1) WR_LAUNCH(2, 1);
-    else WR_LAUNCH(2, 0);
-#undef WR_LAUNCH
-    return CRUSE_OK;
+// the instance of a plan: (MTW, NWP, U) is one of five forms, S / PAD the conv form, F32IN whether an operand tensor holds f32
+template <int MTW, int NWP, int U, bool F32IN>
+auto rd_form(int S, int pad) -> void (*)(const WRArgs) {
+    if (S == 1) return wgrad_rd_kernel<MTW, NWP, 1, 1, U, F32IN>;
+    return pad == 1 ? wgrad_rd_kernel<MTW, NWP, 2, 1, U, F32IN> : wgrad_rd_kernel<MTW, NWP, 2, 0, U, F32IN>;
 }
+template <int MTW, int NWP, int U>
+auto rd_form(int S, int pad, bool f32in) { return f32in ? rd_form<MTW, NWP, U, true>(S, pad) : rd_form<MTW, NWP, U, false>(S, pad); }
 
 }  // namespace
 
-// 1 = handled (dw updated: *nblk_out = 0 slabs left to reduce), 0 = not eligible, < 0 error
-int cruse_wgrad_rd_try(const float* a, const float* bt, float* partial, size_t ws_bytes, float* dw,
-                       int B, int T, int Ca, int Fa, int Cb, int Fb, int KT, int S, int pad, int prec, int a_bf16, int bt_bf16,
-                       int* nblk_out, hipStream_t stream) {
-    if (prec != CRUSE_PREC_BF16 || cruse_opt(CRUSE_OPT_wg_rd, 1) == 0) return 0;
-    const int ntaps = KT * 3;
-    const int MT = (Ca + 15) / 16, npairs = KT * ((Cb + 15) / 16);        // row tiles; source windows (frame offset, 16 channels of bt)
-    if (Ca > 64 || npairs > 4 || Fa < 8 || (Fa & 1) || Fb != S * Fa || !((S == 1 && pad == 1) || S == 2) || (KT != 1 && KT != 2)) return 0;
-    if ((reinterpret_cast<uintptr_t>(a) & 3) || (reinterpret_cast<uintptr_t>(bt) & 3)) return 0;
-    const long long nframes = (long long)B * T;
+int cruse_wgrad_rd_plan(const CruseWgradCall& c, CruseWgradPlan& p) {
+    if (c.prec != CRUSE_PREC_BF16 || cruse_opt(CRUSE_OPT_wg_rd, 1) == 0) return 0;
+    const int MT = (c.Ca + 15) / 16, npairs = c.KT * ((c.Cb + 15) / 16);  // row tiles; source windows (frame offset, 16 channels of bt)
+    if (c.Ca > 64 || npairs > 4 || c.Fa < 8 || (c.Fa & 1) || c.Fb != c.S * c.Fa || !((c.S == 1 && c.pad == 1) || c.S == 2)) return 0;
+    if ((reinterpret_cast<uintptr_t>(c.a) & 3) || (reinterpret_cast<uintptr_t>(c.bt) & 3)) return 0;
+    const long long nframes = (long long)c.B * c.T, bt_elems = nframes * c.Cb * c.Fb;
     const int mtw = MT <= 1 ? 1 : (MT == 2 ? 2 : 4);
     const int nwp = mtw == 4 ? 1 : (npairs >= 2 ? 2 : 1);                // 3 * mtw * nwp accumulator tiles per wave (<= 12)
-    const int TG = (npairs + nwp - 1) / nwp;
-    WRArgs p = {};
-    p.a = a; p.bt = bt; p.partial = partial;
-    p.T = T; p.Ca = Ca; p.Fa = Fa; p.Cb = Cb; p.Fb = Fb; p.KT = KT;
-    p.NCH = (Fa + 7) / 8; p.ntaps = ntaps; p.TG = TG;
-    p.a_bf16 = a_bf16 ? 1 : 0; p.bt_bf16 = bt_bf16 ? 1 : 0;
-    p.nframes = nframes; p.bt_elems = nframes * Cb * Fb;
-    p.fr_inc = 32 / p.NCH; p.c_inc = 32 % p.NCH;
+    const int TG = (npairs + nwp - 1) / nwp, ntl = mtw * nwp * 3;
     // ONE 8-wave workgroup per CU (256 in all; a slab is written by TG of them, one per group of source windows): measured at the bench shapes,
     // 128 / 256 / 512 / 1024 workgroups: 363 / 266 / 322 / 447 us for the twelve launches of a step (tools/wgrad_probe.py) -- the per-workgroup
     // costs (index set-up, the LDS tree, the slab and its reduction) outweigh what more waves hide; deeper unrolling (U x 2) measured equal
     int ns = cruse_opt(CRUSE_OPT_wg_grid, 0) > 0 ? cruse_opt(CRUSE_OPT_wg_grid, 0) : 256 / TG;
-    const size_t slab_bytes = (size_t)TG * mtw * nwp * 3 * 256 * sizeof(float);
-    if (slab_bytes > ws_bytes) return 0;
-    if ((size_t)ns * slab_bytes > ws_bytes) ns = (int)(ws_bytes / slab_bytes);
+    const size_t slab_bytes = (size_t)TG * ntl * 256 * sizeof(float);
+    if (slab_bytes > c.ws_bytes) return 0;
+    if ((size_t)ns * slab_bytes > c.ws_bytes) ns = (int)(c.ws_bytes / slab_bytes);
     if ((long long)ns > nframes / 4) ns = (int)(nframes / 4);   // (small problems: <= 16 slabs, i.e. one chunk of the reduction -- a fixed summation order)
     if (ns < 1) ns = 1;
-    p.fpw = (int)((nframes + ns - 1) / ns);
-    ns = (int)((nframes + p.fpw - 1) / p.fpw);
-    if ((long long)p.fpw * p.NCH > (1ll << 30) || nframes * Ca * Fa >= (1ll << 31) - 64 || p.bt_elems >= (1ll << 31) - 64 || p.bt_elems < 16) return 0;
-    p.ns = ns;
-    const int grid = ((ns + 7) / 8) * 8 * TG;                  // (slab = (block / 8 / TG) * 8 + block % 8: whole rounds of the 8 XCDs)
-    int rc;
-    if (mtw == 1 && nwp == 1) rc = launch_form<1, 1, 4>(p, S, pad, grid, stream);
-    else if (mtw == 1) rc = launch_form<1, 2, 2>(p, S, pad, grid, stream);
-    else if (mtw == 2 && nwp == 1) rc = launch_form<2, 1, 2>(p, S, pad, grid, stream);
-    else if (mtw == 2) rc = launch_form<2, 2, 1>(p, S, pad, grid, stream);
-    else rc = launch_form<4, 1, 1>(p, S, pad, grid, stream);
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { cruse_set_error("wgrad_rd: HIP launch failed: %s", hipGetErrorString(e)); return CRUSE_E_HIP; }
-    const int ntl = mtw * nwp * 3;
-    hipLaunchKernelGGL(wgrad_rd_reduce_kernel, dim3((TG * ntl * 256 + 255) / 256, (ns + 15) / 16), dim3(256), 0, stream,
-                       (const float*)partial, ns, TG, nwp, ntl, Ca, Cb, KT, dw);
-    e = hipGetLastError();
-    if (e != hipSuccess) { cruse_set_error("wgrad_rd_reduce: HIP launch failed: %s", hipGetErrorString(e)); return CRUSE_E_HIP; }
-    *nblk_out = 0;                                             // (nothing left for wgrad_reduce_kernel)
+    const int fpw = (int)((nframes + ns - 1) / ns);
+    ns = (int)((nframes + fpw - 1) / fpw);
+    if ((long long)fpw * ((c.Fa + 7) / 8) > (1ll << 30) || nframes * c.Ca * c.Fa >= (1ll << 31) - 64 || bt_elems >= (1ll << 31) - 64 || bt_elems < 16) return 0;
+    int* v = p.v;
+    v[CRUSE_WP_KERNEL] = CRUSE_WK_RD;
+    v[CRUSE_WP_T0] = mtw; v[CRUSE_WP_T1] = nwp; v[CRUSE_WP_T2] = ntl == 3 ? 4 : (ntl == 12 ? 1 : 2);      // U: steps whose loads are in flight together
+    v[CRUSE_WP_T3] = !(c.a_dtype == CRUSE_DT_BF16 && c.bt_dtype == CRUSE_DT_BF16);
+    v[CRUSE_WP_GRID] = ((ns + 7) / 8) * 8 * TG;                // (slab = (block / 8 / TG) * 8 + block % 8: whole rounds of the 8 XCDs)
+    v[CRUSE_WP_BLOCK] = 512; v[CRUSE_WP_LDS] = 4 * ntl * 256 * (int)sizeof(float);
+    v[CRUSE_WP_SLABS] = ns; v[CRUSE_WP_TG] = TG; v[CRUSE_WP_FPW] = fpw;
+    v[CRUSE_WP_REDUCE] = CRUSE_WR_RD; v[CRUSE_WP_RGX] = (TG * ntl * 256 + 255) / 256; v[CRUSE_WP_RGY] = (ns + 15) / 16;
     return 1;
+}
+
+int cruse_wgrad_rd_launch(const CruseWgradCall& c, const CruseWgradPlan& pl) {
+    const int* v = pl.v;
+    WRArgs p = {};
+    p.a = c.a; p.bt = c.bt; p.partial = (float*)c.ws;
+    p.T = c.T; p.Ca = c.Ca; p.Fa = c.Fa; p.Cb = c.Cb; p.Fb = c.Fb; p.KT = c.KT;
+    p.NCH = (c.Fa + 7) / 8; p.ntaps = c.KT * 3; p.TG = v[CRUSE_WP_TG];
+    p.a_bf16 = c.a_dtype == CRUSE_DT_BF16; p.bt_bf16 = c.bt_dtype == CRUSE_DT_BF16;
+    p.fpw = v[CRUSE_WP_FPW];
+    p.nframes = (long long)c.B * c.T; p.bt_elems = p.nframes * c.Cb * c.Fb;
+    p.fr_inc = 32 / p.NCH; p.c_inc = 32 % p.NCH;
+    p.ns = v[CRUSE_WP_SLABS];
+    const int mtw = v[CRUSE_WP_T0], nwp = v[CRUSE_WP_T1];
+    const bool f32in = v[CRUSE_WP_T3] != 0;
+    void (*kern)(const WRArgs) = mtw == 1 && nwp == 1 ? rd_form<1, 1, 4>(c.S, c.pad, f32in)
+                                 : mtw == 1           ? rd_form<1, 2, 2>(c.S, c.pad, f32in)
+                                 : mtw == 2 && nwp == 1 ? rd_form<2, 1, 2>(c.S, c.pad, f32in)
+                                 : mtw == 2           ? rd_form<2, 2, 1>(c.S, c.pad, f32in)
+                                                      : rd_form<4, 1, 1>(c.S, c.pad, f32in);
+    const int rc = cruse_ensure_dyn_lds(reinterpret_cast<const void*>(kern), v[CRUSE_WP_LDS], "wgrad_rd");
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(v[CRUSE_WP_GRID]), dim3(v[CRUSE_WP_BLOCK]), v[CRUSE_WP_LDS], c.stream, p);
+    return CRUSE_OK;
+}
+
+void cruse_wgrad_rd_reduce(const CruseWgradCall& c, const CruseWgradPlan& pl) {
+    const int* v = pl.v;
+    hipLaunchKernelGGL(wgrad_rd_reduce_kernel, dim3(v[CRUSE_WP_RGX], v[CRUSE_WP_RGY]), dim3(256), 0, c.stream, (const float*)c.ws,
+                       v[CRUSE_WP_SLABS], v[CRUSE_WP_TG], v[CRUSE_WP_T1], v[CRUSE_WP_T0] * v[CRUSE_WP_T1] * 3, c.Ca, c.Cb, c.KT, c.dw);
 }

@@ -294,6 +294,23 @@ def conv_plan(scatter, Cin, Fin, Cout, Fout, KT, S, pad, w_layout, B, T, prec, x
             "co_t": out[6]}
 
 
+WGRAD_KERNELS = ("valu", "mfma", "rd")
+WGRAD_REDUCES = (None, "wgrad_reduce", "wgrad_rd_reduce")
+
+
+def conv_wgrad_plan(B, T, Ca, Fa, Cb, Fb, KT, S, pad, prec=None, a_dtype=0, bt_dtype=0, a_misalign=0, bt_misalign=0, ws_bytes=0) -> dict:
+    """what a conv_wgrad call launches (cruse_conv_wgrad_plan; host-only): the kernel ("valu", "mfma" the LDS-staged one, "rd" the
+    register-direct one), its template integers `t`, grid, block and LDS bytes, the partial slabs, the register-direct kernel's workgroups
+    per slab and frames per slab, and the reduce kernel with its grid.  a_dtype / bt_dtype: DT_F32 / DT_BF16; a_misalign / bt_misalign:
+    the operand addresses modulo 16; ws_bytes 0: the workspace conv_wgrad passes.  "raw" is the array as the library wrote it."""
+    out = (ctypes.c_int * 14)()
+    pc = -1 if prec is None else (WGRAD_PREC[prec] if isinstance(prec, str) else int(prec))
+    check(lib.cruse_conv_wgrad_plan(B, T, Ca, Fa, Cb, Fb, KT, S, pad, pc, a_dtype, bt_dtype, a_misalign, bt_misalign, ws_bytes,
+                                    ctypes.cast(out, ctypes.c_void_p)))
+    return {"kernel": WGRAD_KERNELS[out[0]], "t": tuple(out[1:5]), "grid": out[5], "block": out[6], "lds_bytes": out[7], "slabs": out[8],
+            "tg": out[9], "frames_per_slab": out[10], "reduce": WGRAD_REDUCES[out[11]], "reduce_grid": (out[12], out[13]), "raw": list(out)}
+
+
 NCHW_REQ_BN_SUMS, NCHW_REQ_RESIDUAL, NCHW_REQ_BNBWD, NCHW_REQ_DB = 1, 2, 4, 1      # cruse_conv2d_nchw_plan
 NCHW_CONV_FORMS = ("pw_tr_f16", "pw_mfma_f16", "pw", "dw_lds_f16", "dw", "general")
 NCHW_WGRAD_FORMS = ("pw_mfma_f16", "dw_lds_f16", "dw", "rows", "weight")

@@ -218,13 +218,31 @@ int cruse_conv_plan(int scatter, int Cin, int Fin, int Cout, int Fout, int KT, i
 
 /* weight gradient of either form:
  *   dw[ca][cb][kt][kf] += sum_{b,t,fa} a[b,t,ca,fa] * bt[b, t-(KT-1)+kt, cb, fa*S - pad + kf]
- * ws: scratch of cruse_conv_wgrad_ws_bytes() bytes.  prec: CRUSE_PREC_* selects an MFMA kernel -- CRUSE_PREC_BF16 with rows of >= 8
- * (even) positions and Fb == S * Fa: fragments loaded straight from the two tensors (wgrad_rd.hip); otherwise the patch matrix is
- * materialised in LDS (wgrad_mfma.hip); prec < 0 or an ineligible shape runs the f32 VALU kernel. */
+ * ws: scratch of cruse_conv_wgrad_ws_bytes() bytes; a / bt hold a_dtype / bt_dtype elements (CRUSE_DT_F32 or CRUSE_DT_BF16).  One of three
+ * kernels takes the call; they are asked in this order and cruse_conv_wgrad_plan tells which one answers (DESIGN.md section 4 has the table):
+ *   register-direct MFMA (wgrad_rd.hip; fragments loaded straight from the two tensors): prec == CRUSE_PREC_BF16, Ca <= 64,
+ *     KT * ceil(Cb / 16) <= 4, rows of >= 8 (even) positions, Fb == S * Fa, not (S 1, pad 0), both tensors 4-byte aligned
+ *   LDS-staged MFMA (wgrad_mfma.hip; the patch matrix is materialised in LDS): prec >= 0, Ca <= 64, KT * 3 * Cb <= 192, Fa even, both
+ *     tensors 16-byte aligned with rows of whole float4s, a frame tile that fits the LDS; bf16 operands only with CRUSE_PREC_BF16
+ *   f32 VALU (conv.hip): everything else -- f32 operands, Ca a multiple of 4, Cb a multiple of 4 or 1; refused otherwise. */
 size_t cruse_conv_wgrad_ws_bytes(int Ca, int Cb, int KT);
 int cruse_conv_wgrad(const float* a, const float* bt, float* dw,
                      int B, int T, int Ca, int Fa, int Cb, int Fb,
                      int KT, int S, int pad, int prec, int a_dtype, int bt_dtype, void* ws, void* stream);
+
+/* Host-only, touches no device: what a cruse_conv_wgrad call of this shape, mode and operand dtypes launches -- the decision the entry
+ * point makes, without the launches.  a_misalign / bt_misalign: the addresses of a / bt modulo 16 (alignment selects between the kernels);
+ * ws_bytes: the size of ws, 0 = cruse_conv_wgrad_ws_bytes(Ca, Cb, KT), which is what the entry point assumes.  Honours the options
+ * "wg_rd" and "wg_grid".  out[14]:
+ *   [0] kernel: 0 VALU, 1 LDS-staged MFMA, 2 register-direct MFMA
+ *   [1..4] its template integers: VALU CB_T, KT | LDS-staged TFW (frames per tile), MT, NTW | register-direct MTW, NWP, U and
+ *          1 where the instance that converts f32 operands is used; unused ones are 0
+ *   [5] grid (workgroups)   [6] block (threads)   [7] dynamic LDS bytes   [8] partial slabs written to ws
+ *   [9] TG, the workgroups that share a slab, and [10] frames per slab    -- register-direct kernel, else 0
+ *   [11] the reduce kernel that follows: 1 wgrad_reduce_kernel, 2 wgrad_rd_reduce_kernel   [12] its grid x   [13] its grid y (chunks of 16 slabs)
+ * Returns what the entry point would: an error code and cruse_last_error() where the call is refused. */
+int cruse_conv_wgrad_plan(int B, int T, int Ca, int Fa, int Cb, int Fb, int KT, int S, int pad, int prec, int a_dtype, int bt_dtype,
+                          int a_misalign, int bt_misalign, size_t ws_bytes, int* out);
 
 /* out[c] += sum_{rows,f} g[row,c,f]   (bias gradients; F=1 gives a column sum) */
 int cruse_channel_sum(const float* g, long long rows, int C, int F, float* out, void* stream);

@@ -1,5 +1,7 @@
 """GPU parity tests, kernel by kernel, through the C ABI (cruse_amd.ops -> libcruse_hip.so)
 against torch-CPU f32 references of the same op at the reference's call sites."""
+import json
+
 import numpy as np
 import pytest
 import torch
@@ -1245,6 +1247,22 @@ def _wgrad_ref(a, bt, KT, S, pad):
     return dw
 
 
+def _wgrad_recorded_kernels(geom):
+    """{(wg_rd, (a_dtype, bt_dtype)): kernel name}: what the plans recorded from the parent (tests/golden/wgrad_plan_parent.json) name for this
+    geometry in the bf16 mode, at every (B, T) of the file that has the 16 elements of bt the register-direct kernel asks for"""
+    from tests import test_wgrad_route_host as W
+    with open(W.GOLDEN) as f:
+        d = json.load(f)
+    rows = {W.key(c): [d["results"][j] for j in d["per_bt"][i]] for c, i in zip(W.cases(), d["index"])}
+    out = {}
+    for rd, opt in ((1, None), (0, ("wg_rd", 0))):
+        for dt in W.DTYPES:
+            names = {("valu", "mfma", "rd")[r[0]] for r, (B, T) in zip(rows[W.key((opt, geom, 2, dt, (0, 0), 0))], W.BT) if B * T * geom[2] * geom[3] >= 16}
+            assert len(names) == 1, (geom, opt, dt, names)
+            out[(rd, dt)] = names.pop()
+    return out
+
+
 @pytest.mark.parametrize("shape", [
     # (B, T, Ca, Fa, Cb, KT, S, pad): the three conv forms at ragged sizes -- rows of 8 / 12 / 20 / 10 positions (one window; an end-aligned
     # last window that overlaps the one before it by 4 / 4 / 6 positions), channel counts that leave padding rows / columns in the
@@ -1264,12 +1282,20 @@ def test_conv_wgrad_register_direct_kernel(ops, shape):
     bt = torch.randn(B, T, Cb, Fb, generator=gen).to(torch.bfloat16)
     ref = _wgrad_ref(a.float(), bt.float(), KT, S, pad)
     outs = {}
+    codes = {(da, db): (2 if da == torch.bfloat16 else 0, 2 if db == torch.bfloat16 else 0)                     # CRUSE_DT_BF16 / _F32
+             for da in (torch.bfloat16, torch.float32) for db in (torch.bfloat16, torch.float32)}
+    recorded = _wgrad_recorded_kernels((Ca, Fa, Cb, Fb, KT, S, pad))
     for rd in (1, 0):
         ops.set_option("wg_rd", rd)
         try:
             for da, db in ((torch.bfloat16, torch.bfloat16), (torch.float32, torch.bfloat16), (torch.bfloat16, torch.float32), (torch.float32, torch.float32)):
                 dw = torch.zeros(Ca, Cb, KT, 3).cuda()
-                ops.conv_wgrad(a.to(da).cuda(), bt.to(db).cuda(), dw, B, T, Ca, Fa, Cb, Fb, KT=KT, S=S, pad=pad, prec="bf16")
+                ad, bd = a.to(da).cuda(), bt.to(db).cuda()
+                # the kernel this run takes, by the library's own statement: the register-direct one, the LDS-staged one with it switched off --
+                # and what the parent-recorded plans say of this geometry and operand dtypes (tests/test_wgrad_route_host.py)
+                plan = ops.conv_wgrad_plan(B, T, Ca, Fa, Cb, Fb, KT, S, pad, "bf16", *codes[(da, db)], ad.data_ptr() % 16, bd.data_ptr() % 16)
+                assert plan["kernel"] == ("rd" if rd else "mfma") == recorded[(rd, codes[(da, db)])], (rd, da, db, plan)
+                ops.conv_wgrad(ad, bd, dw, B, T, Ca, Fa, Cb, Fb, KT=KT, S=S, pad=pad, prec="bf16")
                 outs[(rd, da, db)] = dw.cpu()
         finally:
             ops.set_option("wg_rd", None)

@@ -432,7 +432,7 @@ def test_convolutions_write_y_and_clear_their_sums_and_scratch_themselves(hip, r
     (8, 16) is added to the issue's channel pairs: it is the smallest pair the MFMA kernel takes."""
     rnd, L = rnd_(24), Log()
     NREP, B = 16, 2
-    wg_refused, sum_refused, mfma_fwd, wg_slab = [], [], set(), []
+    wg_refused, sum_refused, mfma_fwd, wg_slab, wg_kernel = [], [], set(), [], {}
     for prec in (-1, 0, 1, 2):
         tol = CONV_TOL[prec]
         for Cin, Cout in ((1, 16), (24, 40), (8, 16)):    # (8, 16): the MFMA kernel -- it wants Cin a power of two, so (24, 40) runs the VALU kernel at every prec
@@ -502,8 +502,12 @@ def test_convolutions_write_y_and_clear_their_sums_and_scratch_themselves(hip, r
                         for fill in (False, True):
                             dw, cdw = embed(torch.from_numpy(dw0)); ws, cws = embed(torch.zeros(nws, dtype=torch.uint8), lead=256, trail=256, fill=fill)
                             if fill: poison_(ws)
+                            wplan = (ctypes.c_int * 14)()
+                            rc_plan = hip.cruse_conv_wgrad_plan(B, T, Cout, Fout, Cin, Fin, KT, S, pad, prec, 0, 0, P(ad) % 16, P(xd) % 16, 0, ctypes.cast(wplan, ctypes.c_void_p))
                             rc = hip.cruse_conv_wgrad(P(ad), P(xd), P(dw), B, T, Cout, Fout, Cin, Fin, KT, S, pad, prec, 0, 0, P(ws), st()); torch.cuda.synchronize()
+                            if (rc != 0) != (rc_plan != 0): L.bad.append(("refusal differs from cruse_conv_wgrad_plan", prec) + geo + (rc, rc_plan))
                             if rc: L.refused += 1; wg_refused.append((prec, Cout, Cin, Fin, T)); break
+                            if fill: wg_kernel[(prec, Cout, Cin, Fin, T)] = wplan[0]
                             if fill and (Cout, Cin) == (40, 24): wg_slab.append((prec, Fin, T))
                             L.guard(("conv_wgrad", prec) + geo, cdw, cws)
                             got = dw.double().cpu().numpy()
@@ -519,6 +523,10 @@ def test_convolutions_write_y_and_clear_their_sums_and_scratch_themselves(hip, r
     # ... and SERVED there at Fin = 16 for prec 0, 1, 2: the VALU kernel refuses 60 output tiles, so these six ran a slab kernel (wgrad_mfma.hip for
     # prec 0 / 1, wgrad_rd.hip for prec 2: Fa = 8 even, Fb == S * Fa) on the poisoned scratch; (16, 1) and (16, 8) at Fin = 16 pass the same checks
     assert sorted(wg_slab) == sorted((p_, 16, t_) for p_ in (0, 1, 2) for t_ in (1, 4)), wg_slab
+    # which kernel each served case ran on the poisoned scratch, by the library's own statement of it (cruse_conv_wgrad_plan: 0 VALU, 1 LDS-staged
+    # MFMA, 2 register-direct): together the cases reach all three, prec -1 only ever the VALU kernel, and the six above are the slab kernels named
+    assert set(wg_kernel.values()) == {0, 1, 2} and all(k == 0 for c_, k in wg_kernel.items() if c_[0] == -1), wg_kernel
+    assert all(wg_kernel[(p_, 40, 24, 16, t_)] == (2 if p_ == 2 else 1) for p_ in (0, 1, 2) for t_ in (1, 4)), wg_kernel
     # forward forms: what cruse_conv_plan says ran the MFMA kernel at prec >= 0 (by reading: Cin a power of two >= 8, 8 frames x positions % 16 == 0)
     assert mfma_fwd == {(8, 16, 2, 1), (8, 16, 16, 0), (8, 16, 16, 1)}, mfma_fwd
     assert len(sum_refused) == 32 and L.refused == 32 + 18, (L.refused, wg_refused, sum_refused)
