@@ -201,6 +201,7 @@ SIGNATURES = {
     "cruse_rt60": ("pppiiiddppp", "i"),
     "cruse_mrspec_ws_bytes": ("iipi", "z"),
     "cruse_mrspec_loss": ("ppiipiffppzppfp", "i"),
+    "cruse_df_feat": ("ppqqiiipiidfffppppp", "i"),
 }
 
 

@@ -1,0 +1,1 @@
+from .df_features import DfFeatures, ExponentialUnitNorm, get_norm_alpha  # noqa: F401

@@ -2152,6 +2152,101 @@ class BandExpandFn(torch.autograd.Function):
         return band_pool(dy.contiguous(), ctx.starts, ctx.mean), None, None, None
 
 
+# ---------------------------------------------------------------- DeepFilterNet's input features (cruse_df_feat)
+DF_FEAT_TC = 64                          # CRUSE_DF_FEAT_TC: the kernel's frame tile (tests place their lengths around it)
+DF_ERB_INIT = (-60.0, -90.0)             # DeepFilterNet's published initial ERB mean, linspace over the bands (not in the reference)
+DF_UNIT_INIT = (0.001, 0.0001)           # ExponentialUnitNorm.UNIT_NORN_INIT (test/test_norm.py:43), linspace over the bins
+
+
+def df_feat_states(B: int, nb_erb: int, nb_df: int, device):
+    """(erb_state [B, nb_erb], unit_state [B, nb_df]) at their defaults, linspace(*DF_ERB_INIT) and linspace(*DF_UNIT_INIT); None for a
+    feature of size 0"""
+    def lin(init, n):
+        return None if n == 0 else torch.linspace(init[0], init[1], n, dtype=torch.float32).to(device).repeat(int(B), 1)
+    return lin(DF_ERB_INIT, int(nb_erb)), lin(DF_UNIT_INIT, int(nb_df))
+
+
+def _df_planes(re: torch.Tensor, im: torch.Tensor):
+    """(re, im, bin stride, frame stride) of two [B,T,F] planes that cruse_df_feat reads in place: element (b, t, f) at
+    (b T + t) frame_stride + f bin_stride.  Planar tensors and the [..., 0] / [..., 1] views of an interleaved one are; anything else is
+    copied."""
+    B, T, F = re.shape
+
+    def strides(t):
+        es = t.stride(2) if F > 1 else 1
+        fs = t.stride(1) if T > 1 else (t.stride(0) if B > 1 else (F - 1) * es + 1)
+        ok = es >= 1 and fs >= (F - 1) * es + 1 and (B == 1 or T <= 1 or t.stride(0) == T * fs)
+        return es, fs, ok
+    er, fr, okr = strides(re)
+    ei, fi, oki = strides(im)
+    if okr and oki and (er, fr) == (ei, fi):
+        return re, im, er, fr
+    return re.contiguous(), im.contiguous(), 1, F
+
+
+def df_feat(re: torch.Tensor, im: torch.Tensor, starts: Optional[torch.Tensor], nb_df: int, alpha: float,
+            erb_state: Optional[torch.Tensor] = None, unit_state: Optional[torch.Tensor] = None, log_eps: float = 1e-10,
+            erb_scale: float = 40.0, unit_eps: float = 1e-14, out=None, ws=None):
+    """DeepFilterNet's two input features of a spectrum re, im [B,T,F] -> (feat_erb [B,T,nb_erb], feat_spec [B,T,nb_df,2]), one kernel
+    (include/cruse_hip.h states the formulas).  starts: the int32 [nb_erb + 1] device band table (cust_conv._band_table), or None: no ERB
+    feature, feat_erb is None.  nb_df = 0: feat_spec is None.  erb_state [B,nb_erb] / unit_state [B,nb_df]: the state before the first
+    frame, overwritten with the state after the last; absent, the call starts from df_feat_states' defaults in a temporary.  re, im may
+    be the [..., 0] and [..., 1] views of an interleaved [B,T,F,2] tensor: they are read in place.  out = (feat_erb, feat_spec): write
+    into these.  ws: accepted and unused, the kernel needs no workspace.  Inference only: an input that requires grad raises."""
+    if re.requires_grad or im.requires_grad:
+        raise RuntimeError("df_feat is inference-only (no backward kernel): the spectrum requires grad")
+    if re.dim() != 3 or im.shape != re.shape or re.dtype != torch.float32 or im.dtype != torch.float32 or re.device != im.device:
+        raise RuntimeError(f"df_feat: re and im must be float32 [B,T,F] of one shape and device, got {re.dtype} {tuple(re.shape)} and "
+                           f"{im.dtype} {tuple(im.shape)}")
+    B, T, F = (int(v) for v in re.shape)
+    if B < 1 or F < 1 or F > BAND_MAX_F:
+        raise RuntimeError(f"df_feat: B = {B}, F = {F}: at least one clip and 1..{BAND_MAX_F} bins")
+    nb_df = int(nb_df)
+    if nb_df < 0 or nb_df > F:
+        raise RuntimeError(f"df_feat: nb_df = {nb_df} outside 0..F = {F}")
+    nb_erb = 0
+    if starts is not None:
+        if starts.dtype != torch.int32 or starts.dim() != 1 or starts.numel() < 2 or starts.device != re.device or not starts.is_contiguous():
+            raise RuntimeError(f"df_feat: the band table must be contiguous int32 [nb_erb + 1] on {re.device}")
+        nb_erb = int(starts.numel()) - 1
+        if nb_erb > F:
+            raise RuntimeError(f"df_feat: nb_erb = {nb_erb} bands over F = {F} bins")
+    if nb_erb == 0 and nb_df == 0:
+        raise RuntimeError("df_feat: no output is requested (starts is None and nb_df = 0)")
+    alpha = float(alpha)
+    if not 0.0 <= alpha < 1.0:
+        raise RuntimeError(f"df_feat: alpha = {alpha} outside [0, 1)")
+    dflt = None
+    states = []
+    for name, st, n in (("erb_state", erb_state, nb_erb), ("unit_state", unit_state, nb_df)):
+        if n == 0:
+            st = None
+        elif st is None:
+            dflt = dflt or df_feat_states(B, nb_erb, nb_df, re.device)
+            st = dflt[len(states)]
+        elif st.dtype != torch.float32 or tuple(st.shape) != (B, n) or not st.is_contiguous() or st.device != re.device:
+            raise RuntimeError(f"df_feat: {name} must be contiguous float32 [{B}, {n}] on {re.device}, got {st.dtype} {tuple(st.shape)}")
+        states.append(st)
+    outs = []
+    for i, (name, shape) in enumerate((("feat_erb", (B, T, nb_erb)), ("feat_spec", (B, T, nb_df, 2)))):
+        o = None if out is None else out[i]
+        if shape[2] == 0:
+            o = None
+        elif o is None:
+            o = torch.empty(shape, device=re.device, dtype=torch.float32)
+        elif o.dtype != torch.float32 or tuple(o.shape) != shape or not o.is_contiguous() or o.device != re.device:
+            raise RuntimeError(f"df_feat: out {name} must be contiguous float32 {list(shape)} on {re.device}, got {o.dtype} {tuple(o.shape)}")
+        outs.append(o)
+    if not re.is_cuda:
+        raise RuntimeError("cruse_amd ops need tensors on the HIP device (no CPU fallback)")
+    if T == 0:                                                            # nothing to write, the states stay
+        return outs[0], outs[1]
+    re, im, es, fs = _df_planes(re, im)
+    check(lib.cruse_df_feat(re.data_ptr(), im.data_ptr(), es, fs, B, T, F, _p(starts), nb_erb, nb_df, alpha, float(log_eps), float(erb_scale),
+                            float(unit_eps), _p(states[0]), _p(states[1]), _p(outs[0]), _p(outs[1]), _stream()))
+    return outs[0], outs[1]
+
+
 # ======================================================================================================================
 # per-file statistics of a pool of recordings (cruse_screen_clips, cruse_rt60; cruse_amd/screen.py builds the reference's list builder
 # dataset/preprocess_dataset.py on them; DESIGN section 19)

@@ -1371,6 +1371,44 @@ size_t cruse_mrspec_ws_bytes(int B, int L, const int* n_ffts, int R);
 int cruse_mrspec_loss(const float* est, const float* ref, int B, int L, const int* n_ffts, int R, float gamma, float factor,
                       const float* f_complex, void* ws, size_t ws_bytes, double* loss, float* dest, float grad_scale, void* stream);
 
+/* ---- DeepFilterNet's normalised input features (ABI 15, additive; csrc/df_feat.hip) ---------------------------------
+ * The spectrum is two f32 planes re, im of B clips, T frames and F bins: element (b, t, f) sits at ((b T + t) frame_stride + f bin_stride)
+ * of each.  Planar [B,T,F] planes are (1, F); re = x, im = x + 1 of an interleaved [B,T,F,2] tensor are (2, 2 F): neither is copied.
+ * ERB feature (nb_erb > 0; band j = bins [starts[j], starts[j + 1]) of width w_j, starts: int32 [nb_erb + 1] on the device, every entry
+ * clamped into [0, F] by the kernel, an empty band has mean power 0):
+ *     e[t,j] = 10 log10((1 / w_j) sum_f (re^2 + im^2) + log_eps)          DeepFilterNet's published front end (not in the reference)
+ *     m[t,j] = e[t,j] (1 - alpha) + alpha m[t-1,j],  m[-1] = erb_state     test/test_erb.py:104
+ *     feat_erb[t,j] = (e[t,j] - m[t,j]) / erb_scale                        :105-106 REPAIRED: the reference starts out_xs from zeros, not
+ *                                                                          from xs, and so returns -state / 40
+ * Complex feature (nb_df > 0, bins f < nb_df), ExponentialUnitNorm.forward line for line (test/test_norm.py:52-61):
+ *     a[t,f] = sqrt(max(re^2 + im^2, unit_eps))                            :54-55
+ *     s[t,f] = a[t,f] (1 - alpha) + alpha s[t-1,f],  s[-1] = unit_state    :59
+ *     feat_spec[t,f] = (re, im) / sqrt(s[t,f])                             :61
+ * (band_unit_norm's norm(x) (1 - alpha + s alpha), test_erb.py:116, is a misplaced parenthesis and is not restated.)
+ * erb_state [B, nb_erb] and unit_state [B, nb_df] are read as the state before frame 0 and overwritten with the state after frame T - 1;
+ * feat_erb [B,T,nb_erb]; feat_spec [B,T,nb_df,2] interleaved, 8-byte aligned.  nb_erb = 0 / nb_df = 0 skips that feature: its pointers
+ * may be null and nothing of it is read or written.
+ * alpha is a double because the reference's line 59 multiplies by the Python scalars alpha and 1 - alpha, each rounded to f32 on its own:
+ * 1 - (float)alpha is off by up to 1e-6 of 1 - alpha at alpha = 0.99.  Split invariance: with alpha_f = (float)alpha and oma =
+ * (float)(1 - alpha) rounded on the host, every step is, in f32 with no contraction other than the fma written here (alpha there is
+ * alpha_f) and correctly rounded sqrt and division,
+ *     p = re re + im im (two products, one add);  mean = (p_lo + p_lo+1 + ... added in ascending f from 0) * (1 / w_j)
+ *     e = 10 * log10f(mean + log_eps);  m = fma(alpha, m, e * oma);  feat_erb = (e - m) / erb_scale
+ *     a = sqrt(max(p, unit_eps));       s = fma(alpha, s, a * oma);  feat_spec = re / sqrt(s), im / sqrt(s)
+ * so the values of frame t and the states depend on the incoming state and the frames up to t alone, never on T or on where a frame
+ * falls in the kernel's tiles of CRUSE_DF_FEAT_TC frames: one call over T frames and calls over T1 + T2 + ... frames with the state
+ * carried write the same bits, down to one frame per call.  No atomics, no workspace, one launch, no synchronisation: capturable.
+ * An all-zero spectrum gives feat_spec = 0 and a finite feat_erb from any non-negative state (unit_eps > 0 keeps s > 0).
+ * T = 0 writes nothing, leaves the states and returns CRUSE_OK.  Refused before any launch, cruse_last_error naming the argument
+ * (CRUSE_E_SHAPE): B < 1, T < 0, F outside 1..CRUSE_BAND_MAX_F; nb_erb or nb_df outside 0..F, or both 0; alpha outside [0, 1) (NaN
+ * included); log_eps or unit_eps < 0, erb_scale 0; a null re or im, a null starts / state / output of a requested feature; bin_stride
+ * < 1, frame_stride < (F - 1) bin_stride + 1; B * T > 2^31.  CRUSE_E_ALIGN: feat_spec not 8-byte aligned.  Whether starts covers
+ * [0, F] is judged on the host where the table is built (cruse_amd _band_table). */
+#define CRUSE_DF_FEAT_TC 64
+int cruse_df_feat(const float* re, const float* im, long long bin_stride, long long frame_stride, int B, int T, int F, const int* starts,
+                  int nb_erb, int nb_df, double alpha, float log_eps, float erb_scale, float unit_eps, float* erb_state, float* unit_state,
+                  float* feat_erb, float* feat_spec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
