@@ -475,6 +475,23 @@ namespace {
 // conv_run's "the fused BatchNorm-backward input was not taken": the caller runs the separate pass (conv_bnbwd_in)
 constexpr int CONV_NOT_FUSED = 1;
 
+// Operands on which a kernel of this path does 8- or 16-byte accesses without choosing a route from the address: refused when misaligned,
+// ahead of every launch (the memset of the sums included).  x and the f32 gather output are not here: they select a route (stage_rows,
+// cm_plan, launch_mt).  bn_y: the swapped-role MFMA forms and the VALU path's statistics pass read it in vectors.
+int conv_aligned(const char* who, const CruseConvCall& c, const CruseBnBwd* bnb, const CruseBnIn* bni, const CruseBnBwdIn* bbi) {
+    auto off = [](const void* p, unsigned m) { return ((uintptr_t)p & (m - 1)) != 0; };
+    CRUSE_REQUIRE(!off(c.sums, 8), CRUSE_E_ALIGN, "%s: sums must be 8-byte aligned (f64 atomics)", who);
+    CRUSE_REQUIRE(!(c.scatter && off(c.y, 8)), CRUSE_E_ALIGN, "%s: out must be 8-byte aligned (the scatter kernels store pairs)", who);
+    CRUSE_REQUIRE(!(bnb && off(bnb->y, 16)), CRUSE_E_ALIGN, "%s: bn_y must be 16-byte aligned", who);
+    CRUSE_REQUIRE(!(bni && off(bni->sums, 8)), CRUSE_E_ALIGN, "%s: in_sums must be 8-byte aligned (f64 loads)", who);
+    CRUSE_REQUIRE(!(bni && off(bni->add, 16)), CRUSE_E_ALIGN, "%s: in_add must be 16-byte aligned", who);
+    CRUSE_REQUIRE(!(bni && off(bni->copy_bf16, 16)), CRUSE_E_ALIGN, "%s: the bf16 copy must be 16-byte aligned", who);
+    CRUSE_REQUIRE(!(bbi && off(bbi->sums, 8)), CRUSE_E_ALIGN, "%s: bb_sums must be 8-byte aligned (f64 loads)", who);
+    CRUSE_REQUIRE(!(bbi && off(bbi->y, 16)), CRUSE_E_ALIGN, "%s: bb_y must be 16-byte aligned", who);
+    CRUSE_REQUIRE(!(bbi && off(bbi->copy_bf16, 16)), CRUSE_E_ALIGN, "%s: dy_bf16 must be 16-byte aligned", who);
+    return CRUSE_OK;
+}
+
 // The one host path of the ten entry points: validate, try the MFMA kernel, else the VALU kernel and the statistics pass it lacks.
 // plan != null (cruse_conv_plan): decide the same way, write what would be launched and launch nothing.
 // Where the two forms differ they branch on c.scatter; every such branch is behaviour, not an oversight.
@@ -496,6 +513,7 @@ int conv_run(const CruseConvCall& c, int* plan = nullptr) {
         CRUSE_REQUIRE(c.w_layout == 0 || (c.KT == 1 && c.S == 1), CRUSE_E_SHAPE, "conv_gather: w_layout 1 needs KT=1,S=1");
     }
     CRUSE_REQUIRE(!(c.accum && c.act), CRUSE_E_SHAPE, "%s: accum with activation", who);
+    if (const int arc = conv_aligned(who, c, c.bnb, c.bni, c.bbi)) return arc;
     if (plan) plan[CRUSE_CP_FUSED] = c.bbi != nullptr;
     if (c.prec >= 0) {
         const int r = cruse_conv_mfma_try(c, plan);
@@ -543,12 +561,14 @@ int prep_sums(const char* who, const CruseConvCall& c, int zeroed) {
 }
 
 int conv_bnstats(const char* who, const CruseConvCall& c, int zeroed) {
+    if (const int arc = conv_aligned(who, c, nullptr, nullptr, nullptr)) return arc;
     const int rc = prep_sums(who, c, zeroed);
     return rc ? rc : conv_run(c);
 }
 
 int conv_bnbwd(const char* who, CruseConvCall c, const CruseBnBwd& bnb, int zeroed) {
     CRUSE_REQUIRE(bnb.y && bnb.mean && bnb.rstd && bnb.gamma && bnb.beta, CRUSE_E_SHAPE, "%s: BatchNorm tensors missing", who);
+    if (const int arc = conv_aligned(who, c, &bnb, nullptr, nullptr)) return arc;
     const int rc = prep_sums(who, c, zeroed);
     if (rc) return rc;
     c.bnb = &bnb;
@@ -559,6 +579,7 @@ int conv_bnin(const char* who, CruseConvCall c, const CruseBnIn& bni, int zeroed
     CRUSE_REQUIRE(c.x && bni.sums && bni.gamma && bni.beta && bni.nrep >= 1 && bni.count > 0, CRUSE_E_SHAPE, "%s: input BatchNorm tensors missing", who);
     CRUSE_REQUIRE((bni.mean_o == nullptr) == (bni.rstd_o == nullptr) && (bni.rmean == nullptr) == (bni.rvar == nullptr), CRUSE_E_SHAPE,
                   "%s: mean / rstd and the running statistics come in pairs", who);
+    if (const int arc = conv_aligned(who, c, nullptr, &bni, nullptr)) return arc;
     if (c.sums) { const int rc = prep_sums(who, c, zeroed); if (rc) return rc; }
     c.bni = &bni;
     return conv_run(c);
@@ -571,6 +592,7 @@ int conv_bnbwd_in(const char* who, CruseConvCall c, CruseBnBwdIn bb, const Cruse
     CRUSE_REQUIRE(c.x && bb.y && bb.mean && bb.rstd && bb.gamma && bb.beta && bb.sums && bb.nrep >= 1, CRUSE_E_SHAPE,
                   "%s: input BatchNorm tensors missing", who);
     CRUSE_REQUIRE((bnb.y == nullptr) == (c.sums == nullptr), CRUSE_E_SHAPE, "%s: bn_y and sums come together", who);
+    if (const int arc = conv_aligned(who, c, bnb.y ? &bnb : nullptr, nullptr, &bb)) return arc;
     if (c.sums) { const int rc = prep_sums(who, c, zeroed); if (rc) return rc; }
     bb.count = (long long)c.B * c.T * c.Fin;
     c.bnb = bnb.y ? &bnb : nullptr;

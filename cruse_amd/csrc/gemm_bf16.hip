@@ -514,9 +514,10 @@ int gemm_run(const GbCall& c, int* plan = nullptr) {
     CRUSE_REQUIRE(c.a_kstride >= BK && c.b_kstride >= BK && c.ldc >= N, CRUSE_E_SHAPE, "gemm_bf16_nt: strides too small");
     CRUSE_REQUIRE((c.a_kstride == BK ? c.lda >= K : c.lda >= BK) && (c.b_kstride == BK ? c.ldb >= K : c.ldb >= BK), CRUSE_E_SHAPE,
                   "gemm_bf16_nt: lda=%lld / ldb=%lld too small for the operand layout", c.lda, c.ldb);
-    CRUSE_REQUIRE(c.lda % 8 == 0 && c.ldb % 8 == 0 && c.a_kstride % 8 == 0 && c.b_kstride % 8 == 0 &&
-                  ((uintptr_t)c.A % 16) == 0 && ((uintptr_t)c.B % 16) == 0, CRUSE_E_ALIGN,
+    CRUSE_REQUIRE(c.lda % 8 == 0 && c.ldb % 8 == 0 && c.a_kstride % 8 == 0 && c.b_kstride % 8 == 0, CRUSE_E_ALIGN,
                   "gemm_bf16_nt: operands need 16-byte aligned rows and k-tiles (strides multiples of 8)");
+    CRUSE_REQUIRE(((uintptr_t)c.A % 16) == 0, CRUSE_E_ALIGN, "gemm_bf16_nt: A must be 16-byte aligned");
+    CRUSE_REQUIRE(((uintptr_t)c.B % 16) == 0, CRUSE_E_ALIGN, "gemm_bf16_nt: B must be 16-byte aligned");
     // (the k-slices and the grid they make, on which the last checks rest: plain arithmetic, filled into GbArgs below)
     const int nkt = K / BK;
     const bool pinned = c.splitk < -1;         // negative: |splitk| k-slices pinned to XCDs
@@ -532,7 +533,8 @@ int gemm_run(const GbCall& c, int* plan = nullptr) {
     const long long nblk = xcdk ? (long long)cdiv(splitk, 8) * 8 * tiles_m * tiles_n : (long long)cdiv(nunits, 8) * 8 * inner;
     const bool use_slabs = c.slabs.scratch != nullptr && splitk > 1;
     if (use_slabs) {                           // partial sums [slice][M][N] in the caller's scratch, then one ordered sum into C
-        CRUSE_REQUIRE(N % 4 == 0 && ((uintptr_t)c.slabs.scratch % 16) == 0 && c.seg.len == 0, CRUSE_E_ALIGN, "gemm_bf16_nt: slab form needs N %% 4 == 0");
+        CRUSE_REQUIRE(N % 4 == 0 && c.seg.len == 0, CRUSE_E_ALIGN, "gemm_bf16_nt: slab form needs N %% 4 == 0");
+        CRUSE_REQUIRE(((uintptr_t)c.slabs.scratch % 16) == 0, CRUSE_E_ALIGN, "gemm_bf16_nt: the slab scratch must be 16-byte aligned");
         CRUSE_REQUIRE((size_t)splitk * M_out * N * sizeof(float) <= c.slabs.bytes, CRUSE_E_SHAPE,
                       "gemm_bf16_nt: %d slabs of %d x %d floats do not fit the %zu-byte scratch", splitk, M_out, N, c.slabs.bytes);
         CRUSE_REQUIRE(c.bias == nullptr, CRUSE_E_SHAPE, "gemm_bf16_nt: slab form has no bias");
@@ -782,7 +784,7 @@ extern "C" int cruse_cast_bf16(const float* x, void* y, long long n, void* strea
 extern "C" int cruse_cast_bf16_split(const float* x, void* y, void* y_lo, long long n, void* stream) {
     CRUSE_REQUIRE(n > 0 && n % 4 == 0, CRUSE_E_SHAPE, "cast_bf16: n=%lld must be a positive multiple of 4", n);
     CRUSE_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0 && ((uintptr_t)y_lo % 8) == 0, CRUSE_E_ALIGN,
-                  "cast_bf16: unaligned buffers");
+                  "cast_bf16: x must be 16-byte, y and y_lo 8-byte aligned");
     long long nb = (n / 4 + 255) / 256;
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(cast_bf16_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, x, (__bf16*)y, (__bf16*)y_lo, n / 4);
@@ -798,7 +800,6 @@ extern "C" int cruse_transpose_bf16(const float* x, long long rows, int cols, lo
     CRUSE_REQUIRE(((uintptr_t)yT % 16) == 0, CRUSE_E_ALIGN, "transpose_bf16: yT must be 16-byte aligned");
     CRUSE_REQUIRE(shift_T >= 0 && (shift_T == 0 || rows % shift_T == 0), CRUSE_E_SHAPE,
                   "transpose_bf16: rows must be whole clips of shift_T frames");
-    CRUSE_REQUIRE(((uintptr_t)yT % 4) == 0, CRUSE_E_ALIGN, "transpose_bf16: unaligned output");
     dim3 grid((unsigned)(ldT / 64), (unsigned)cdiv(cols, 64));
     hipLaunchKernelGGL(transpose_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, rows, cols, ld, (__bf16*)yT,
                        ldT, shift_T);
@@ -808,7 +809,7 @@ extern "C" int cruse_transpose_bf16(const float* x, long long rows, int cols, lo
 
 extern "C" int cruse_ktile_bf16(const float* x, int rows, int cols, long long ld, void* y, void* y_lo, void* stream) {
     CRUSE_REQUIRE(rows > 0 && cols > 0 && ld >= cols, CRUSE_E_SHAPE, "ktile_bf16: bad shape");
-    CRUSE_REQUIRE(((uintptr_t)y % 8) == 0 && ((uintptr_t)y_lo % 8) == 0, CRUSE_E_ALIGN, "ktile_bf16: unaligned output");
+    CRUSE_REQUIRE(((uintptr_t)y % 8) == 0 && ((uintptr_t)y_lo % 8) == 0, CRUSE_E_ALIGN, "ktile_bf16: y and y_lo must be 8-byte aligned");
     const int kp = (cols + 63) / 64 * 64;
     long long nb = ((long long)rows * (kp / 4) + 255) / 256;
     if (nb > 2048) nb = 2048;
@@ -821,7 +822,7 @@ extern "C" int cruse_ktile_bf16(const float* x, int rows, int cols, long long ld
 // the same K-tiled layout with IEEE-f16 elements (the B operand of cruse_gemm_f16_nt)
 static int ktile_f16_impl(const float* x, int rows, int cols, long long ld, void* y, void* y_lo, void* stream) {
     CRUSE_REQUIRE(rows > 0 && cols > 0 && ld >= cols, CRUSE_E_SHAPE, "ktile_f16: bad shape");
-    CRUSE_REQUIRE(((uintptr_t)y % 8) == 0 && ((uintptr_t)y_lo % 8) == 0, CRUSE_E_ALIGN, "ktile_f16: unaligned output");
+    CRUSE_REQUIRE(((uintptr_t)y % 8) == 0 && ((uintptr_t)y_lo % 8) == 0, CRUSE_E_ALIGN, "ktile_f16: y and y_lo must be 8-byte aligned");
     const int kp = (cols + 63) / 64 * 64;
     long long nb = ((long long)rows * (kp / 4) + 255) / 256;
     if (nb > 2048) nb = 2048;

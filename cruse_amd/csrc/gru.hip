@@ -1686,7 +1686,7 @@ extern "C" int cruse_gru_gate_grads_bf16(const float* dh, const void* coef, cons
     CRUSE_REQUIRE(dgi != nullptr || dgT != nullptr, CRUSE_E_SHAPE, "gru_gate_grads_bf16: dgi and dgT are both NULL");
     CRUSE_REQUIRE(((uintptr_t)dh % 16) == 0 && ((uintptr_t)an % 16) == 0 && ((uintptr_t)coef % 8) == 0 &&
                   ((uintptr_t)dgi % 8) == 0 && ((uintptr_t)dgT % 16) == 0, CRUSE_E_ALIGN,
-                  "gru_gate_grads_bf16: unaligned buffers");
+                  "gru_gate_grads_bf16: dh, an and dgT must be 16-byte, coef and dgi 8-byte aligned");
     GateBiasPtrs bp = {};
     for (int g = 0; g < G; ++g) { bp.ih[g] = db_ih ? db_ih[g] : nullptr; bp.hh[g] = db_hh ? db_hh[g] : nullptr; }
     hipStream_t s = (hipStream_t)stream;

@@ -247,6 +247,8 @@ extern "C" int cruse_mask_head_fwd_bwd(const float* v, const double* bn_sums, in
     CRUSE_REQUIRE((running_mean == nullptr) == (running_var == nullptr), CRUSE_E_SHAPE, "mask_head: the running statistics come in pairs");
     CRUSE_REQUIRE(((uintptr_t)v % 16 | (uintptr_t)skip % 16 | (uintptr_t)u % 16 | (uintptr_t)du % 16 | (uintptr_t)mask % 8 | (uintptr_t)dlogit % 8) == 0,
                   CRUSE_E_ALIGN, "mask_head: v, skip, u, du must be 16-byte aligned, mask and dlogit 8-byte aligned");
+    CRUSE_REQUIRE((((uintptr_t)bn_sums | (uintptr_t)loss_sum | (uintptr_t)bwd_sums) & 7) == 0, CRUSE_E_ALIGN,
+                  "mask_head: bn_sums, loss_sum and bwd_sums must be 8-byte aligned (f64 accesses)");
     hipStream_t st = (hipStream_t)stream;
     if (!loss_zeroed) { int rc = cruse_zero_async(loss_sum, sizeof(double), st, "mask_head loss memset"); if (rc) return rc; }
     if (!bwd_zeroed) { int rc = cruse_zero_async(bwd_sums, 2 * (size_t)C * bwd_replicas * sizeof(double), st, "mask_head sums memset"); if (rc) return rc; }

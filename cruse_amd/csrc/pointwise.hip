@@ -435,6 +435,12 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* x, const float
     }
 }
 
+// y16[i] = bf16(x[i]) on 4-byte loads and 2-byte stores: the bf16 copy of cruse_ln_fwd where a pointer or the count rules out the
+// 16- and 8-byte accesses of cast_bf16_kernel (same rounding)
+__global__ __launch_bounds__(256) void cast_bf16_narrow_kernel(const float* x, __bf16* y16, long long n) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) y16[i] = (__bf16)x[i];
+}
+
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* dy, const float* x, const float* mean,
                                                      const float* rstd, const float* gamma, long long rows, int H,
                                                      int g, float* dx, float* dgamma, float* dbeta) {
@@ -817,6 +823,7 @@ extern "C" int cruse_cast_bf16_split(const float* x, void* y, void* y_lo, long l
 extern "C" int cruse_bn_stats(const float* y, long long rows, int C, int F, double* sums, int zeroed, void* stream) {
     CRUSE_REQUIRE(rows > 0 && C > 0 && C <= 256 && F > 0, CRUSE_E_SHAPE, "bn_stats: bad shape rows=%lld C=%d F=%d", rows, C, F);
     CRUSE_REQUIRE((C * F) % 4 == 0 && C * F <= 768, CRUSE_E_SHAPE, "bn_stats: C*F=%d must be a multiple of 4 and <= 768", C * F);
+    CRUSE_REQUIRE(((uintptr_t)sums & 7) == 0, CRUSE_E_ALIGN, "bn_stats: sums must be 8-byte aligned (f64 accesses)");
     if (!zeroed) { int zrc = cruse_zero_async(sums, 2 * C * sizeof(double), ST(stream), "bn_stats memset"); if (zrc) return zrc; }
     hipLaunchKernelGGL(bn_stats_kernel, dim3(grid_for(rows, 64, 256)), dim3(RED_THREADS), 0, ST(stream), y, rows, C, F, sums);
     CRUSE_LAUNCH_CHECK("bn_stats");
@@ -827,6 +834,7 @@ extern "C" int cruse_bn_finalize(const double* sums, long long count, int C, flo
                                  float* mean, float* rstd, float* running_mean, float* running_var, void* stream) {
     CRUSE_REQUIRE(count > 0 && C > 0, CRUSE_E_SHAPE, "bn_finalize: bad shape");
     CRUSE_REQUIRE((running_mean == nullptr) == (running_var == nullptr), CRUSE_E_SHAPE, "bn_finalize: running stats");
+    CRUSE_REQUIRE(((uintptr_t)sums & 7) == 0, CRUSE_E_ALIGN, "bn_finalize: sums must be 8-byte aligned (f64 accesses)");
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, ST(stream), sums, count, C, eps, momentum,
                        mean, rstd, running_mean, running_var);
     CRUSE_LAUNCH_CHECK("bn_finalize");
@@ -874,6 +882,7 @@ extern "C" int cruse_bn_finalize_act_fwd_c(const float* y, const double* sums, i
     CRUSE_REQUIRE(rows > 0 && C > 0 && C <= 256 && F > 0 && count > 0 && sum_replicas >= 1, CRUSE_E_SHAPE, "bn_finalize_act_fwd: bad shape");
     CRUSE_REQUIRE((C * F) % 4 == 0, CRUSE_E_ALIGN, "bn_finalize_act_fwd: C*F=%d must be a multiple of 4", C * F);
     CRUSE_REQUIRE((running_mean == nullptr) == (running_var == nullptr) && mean && rstd, CRUSE_E_SHAPE, "bn_finalize_act_fwd: statistics");
+    CRUSE_REQUIRE(((uintptr_t)sums & 7) == 0, CRUSE_E_ALIGN, "bn_finalize_act_fwd: sums must be 8-byte aligned (f64 accesses)");
     const double unb = count > 1 ? (double)count / (double)(count - 1) : 1.0;
     const bool rowwise = C * F <= 64 * CPR_MAXG * 4 && (C * F) % 4 == 0;
     hipLaunchKernelGGL(bn_fin_act_fwd_kernel, dim3(rowwise ? grid_for(rows, 8, 2048) : grid_for(rows * C * F / 4, 1024)), dim3(256), 4 * C * sizeof(float), ST(stream),
@@ -888,6 +897,7 @@ extern "C" int cruse_bn_act_bwd_reduce(const float* dout, const float* y, const 
                                        int relu, double* sums, int zeroed, void* stream) {
     CRUSE_REQUIRE(rows > 0 && C > 0 && C <= 256 && F > 0, CRUSE_E_SHAPE, "bn_act_bwd_reduce: bad shape");
     CRUSE_REQUIRE((C * F) % 4 == 0 && C * F <= 768, CRUSE_E_SHAPE, "bn_act_bwd_reduce: C*F=%d must be a multiple of 4 and <= 768", C * F);
+    CRUSE_REQUIRE(((uintptr_t)sums & 7) == 0, CRUSE_E_ALIGN, "bn_act_bwd_reduce: sums must be 8-byte aligned (f64 accesses)");
     if (!zeroed) { int zrc = cruse_zero_async(sums, 2 * C * sizeof(double), ST(stream), "bn_act_bwd_reduce memset"); if (zrc) return zrc; }
     hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, dim3(grid_for(rows, 64, 256)), dim3(RED_THREADS), 0, ST(stream), dout, y, mean,
                        rstd, gamma, beta, rows, C, F, relu, sums);
@@ -904,6 +914,7 @@ extern "C" int cruse_bn_act_bwd_apply(const float* dout, const float* y, const f
     CRUSE_REQUIRE(rows > 0 && C > 0 && C <= 256 && F > 0 && sum_replicas >= 1, CRUSE_E_SHAPE, "bn_act_bwd_apply: bad shape");
     CRUSE_REQUIRE((C * F) % 4 == 0 && C * F <= 768, CRUSE_E_SHAPE,
                   "bn_act_bwd_apply: C*F=%d must be a multiple of 4 and <= 768", C * F);
+    CRUSE_REQUIRE(((uintptr_t)sums & 7) == 0, CRUSE_E_ALIGN, "bn_act_bwd_apply: sums must be 8-byte aligned (f64 accesses)");
     hipLaunchKernelGGL(bn_act_bwd_apply_kernel, dim3(grid_for(rows, 8, 2048)), dim3(256), 0, ST(stream), dout, y,
                        mean, rstd, gamma, beta, sums, sum_replicas, rows, C, F, relu, training, (float*)dy,
                        dy_dtype == CRUSE_DT_BF16 ? 1 : 0, dout_dtype == CRUSE_DT_BF16 ? 1 : 0, dgamma, dbeta, dbias);
@@ -934,18 +945,25 @@ extern "C" int cruse_ln_fwd_c(const float* x, const float* gamma, const float* b
     const bool vec = interleave_g == 1 && H % 4 == 0 && H <= 256 * LNV_MAXQ &&
                      ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)res) & 15) == 0);
     const bool bf_inline = vec && y_bf16 && (((uintptr_t)y_bf16 & 7) == 0);
+    // (every refusal stands ahead of the launch: a refused call has written nothing)
+    CRUSE_REQUIRE(vec || seg_len == 0, CRUSE_E_SHAPE, "ln_fwd: row segments need the vector form (one group, H %% 4 == 0, aligned)");
+    CRUSE_REQUIRE(seg_len == 0 || !y_bf16 || bf_inline, CRUSE_E_ALIGN, "ln_fwd: row segments need an 8-byte aligned bf16 copy (y_bf16)");
+    CRUSE_REQUIRE(copy_dtype == CRUSE_DT_BF16 || !y_bf16 || bf_inline, CRUSE_E_DTYPE,
+                  "ln_fwd: the f16 copy needs the vector form (one group) and an 8-byte aligned y_copy");
     if (vec)
         hipLaunchKernelGGL(ln_fwd_vec_kernel, dim3(grid_for(rows, 16, 2048)), dim3(256), 0, ST(stream), x, gamma, beta,
                            res, y, bf_inline ? (__bf16*)y_bf16 : nullptr, mean, rstd, rows, H, eps, sg, copy_dtype == CRUSE_DT_F16 ? 1 : 0);
-    else {
-        CRUSE_REQUIRE(seg_len == 0, CRUSE_E_SHAPE, "ln_fwd: row segments need the vector form (one group, H %% 4 == 0, aligned)");
+    else
         hipLaunchKernelGGL(ln_fwd_kernel, dim3(grid_for(rows, 4, 2048)), dim3(256), 0, ST(stream), x, gamma, beta, res, y,
                            mean, rstd, rows, H, interleave_g, eps);
-    }
     CRUSE_LAUNCH_CHECK("ln_fwd");
-    CRUSE_REQUIRE(seg_len == 0 || !y_bf16 || bf_inline, CRUSE_E_ALIGN, "ln_fwd: row segments need an 8-byte aligned bf16 copy");
-    CRUSE_REQUIRE(copy_dtype == CRUSE_DT_BF16 || !y_bf16 || bf_inline, CRUSE_E_DTYPE, "ln_fwd: the f16 copy needs the vector form (one group)");
-    if (y_bf16 && !bf_inline) return cruse_cast_bf16_split(y, y_bf16, nullptr, rows * H, stream);     // interleaved form: one more pass
+    if (!y_bf16 || bf_inline) return CRUSE_OK;
+    // interleaved or unaligned form: one more pass -- the 8-byte stores of cruse_cast_bf16_split where y, y_bf16 and the count allow them
+    // (it refuses the rest, and would do so after y is written), 2-byte stores otherwise
+    const long long n = rows * H;
+    if (n % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)y_bf16 & 7) == 0) return cruse_cast_bf16_split(y, y_bf16, nullptr, n, stream);
+    hipLaunchKernelGGL(cast_bf16_narrow_kernel, dim3(grid_for(n, 1024, 2048)), dim3(256), 0, ST(stream), y, (__bf16*)y_bf16, n);
+    CRUSE_LAUNCH_CHECK("ln_fwd (bf16 copy)");
     return CRUSE_OK;
 }
 
@@ -987,6 +1005,7 @@ extern "C" int cruse_mask_loss_fwd(const float* mask, const float* nre, const fl
                                    double* loss_sum, float* dmask, float* dlogit, float* est_re, float* est_im,
                                    void* stream) {
     CRUSE_REQUIRE(rows > 0 && Fn > 0 && Fs >= Fn, CRUSE_E_SHAPE, "mask_loss: bad shape rows=%lld Fn=%d Fs=%d", rows, Fn, Fs);
+    CRUSE_REQUIRE(((uintptr_t)loss_sum & 7) == 0, CRUSE_E_ALIGN, "mask_loss: loss_sum must be 8-byte aligned (f64 accesses)");
     { int zrc = cruse_zero_async(loss_sum, sizeof(double), ST(stream), "mask_loss memset"); if (zrc) return zrc; }
     hipLaunchKernelGGL(mask_loss_kernel, dim3(grid_for(rows * Fs, 2048, 2048)), dim3(256), 0, ST(stream), mask, nre, nim,
                        cmag, rows, Fn, Fs, alpha, beta, loss_sum, dmask, dlogit, est_re, est_im);
@@ -1010,6 +1029,7 @@ extern "C" int cruse_axpby(float* out, const float* x, const float* y, float a, 
 
 extern "C" int cruse_accum_f64(double* acc, const double* x, int n, void* stream) {
     CRUSE_REQUIRE(n > 0, CRUSE_E_SHAPE, "accum_f64: n=%d", n);
+    CRUSE_REQUIRE((((uintptr_t)acc | (uintptr_t)x) & 7) == 0, CRUSE_E_ALIGN, "accum_f64: acc and x must be 8-byte aligned (f64 accesses)");
     hipLaunchKernelGGL(accum_f64_kernel, dim3(cdiv(n, 64)), dim3(64), 0, ST(stream), acc, x, n);
     CRUSE_LAUNCH_CHECK("accum_f64");
     return CRUSE_OK;
@@ -1064,6 +1084,7 @@ extern "C" int cruse_adam_step(float* p, const float* g, float* m, float* v, lon
 extern "C" int cruse_sumsq(const float* x, long long n, double* out, int accumulate, void* stream) {
     CRUSE_REQUIRE(n > 0, CRUSE_E_SHAPE, "sumsq: n=%lld", n);
     CRUSE_REQUIRE(((uintptr_t)x & 15) == 0, CRUSE_E_ALIGN, "sumsq: x must be 16-byte aligned");
+    CRUSE_REQUIRE(((uintptr_t)out & 7) == 0, CRUSE_E_ALIGN, "sumsq: out must be 8-byte aligned (f64 accesses)");
     if (!accumulate) { int zrc = cruse_zero_async(out, sizeof(double), ST(stream), "sumsq memset"); if (zrc) return zrc; }
     hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n, 4096 * 4, 256)), dim3(1024), 0, ST(stream), x, n, out);
     CRUSE_LAUNCH_CHECK("sumsq");

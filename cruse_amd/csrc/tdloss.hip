@@ -259,7 +259,8 @@ __global__ __launch_bounds__(256) void wave_l1mse_kernel(const float* x, const f
 extern "C" int cruse_wave_l1_mse(const float* est, const float* ref, long long n, int mse, float grad_scale,
                                  double* loss_sum, float* dest, void* stream) {
     CRUSE_REQUIRE(n > 0 && est != nullptr && ref != nullptr && loss_sum != nullptr, CRUSE_E_SHAPE, "wave_l1_mse: bad arguments");
-    CRUSE_REQUIRE((((uintptr_t)est | (uintptr_t)ref | (uintptr_t)dest) & 15) == 0, CRUSE_E_ALIGN, "wave_l1_mse: unaligned buffers");
+    CRUSE_REQUIRE((((uintptr_t)est | (uintptr_t)ref | (uintptr_t)dest) & 15) == 0, CRUSE_E_ALIGN, "wave_l1_mse: est, ref and dest must be 16-byte aligned");
+    CRUSE_REQUIRE(((uintptr_t)loss_sum & 7) == 0, CRUSE_E_ALIGN, "wave_l1_mse: loss_sum must be 8-byte aligned (f64 accesses)");
     hipStream_t st = (hipStream_t)stream;
     { int rc = cruse_zero_async(loss_sum, sizeof(double), st, "wave_l1_mse"); if (rc) return rc; }
     const int grid = blocks_for(n >> 2, 2048);

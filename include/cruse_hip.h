@@ -303,7 +303,10 @@ int cruse_bn_act_bwd_apply(const float* dout, const float* y, const float* mean,
  * y_bf16 (nullable): also a bf16 copy of y [rows, H] (the next gate GEMM's operand).
  * seg_len > 0 (interleave_g == 1): ROW SEGMENTS -- logical row r of every row-indexed array is physical row
  * (r / seg_len) * seg_stride + seg_off + r % seg_len: frames [seg_off, seg_off + seg_len) of every clip of [B, T = seg_stride]
- * tensors, i.e. one TIME CHUNK of the batch (run beside the recurrence of the next chunk); rows = B * seg_len. */
+ * tensors, i.e. one TIME CHUNK of the batch (run beside the recurrence of the next chunk); rows = B * seg_len.
+ * Alignment: 16-byte aligned x, y, gamma, beta, res (with interleave_g == 1, H % 4 == 0) take the vector kernel, anything else the
+ * 4-byte one; a y_bf16 that is 8-byte aligned is written by the vector kernel itself, any other by one more pass.  Row segments need
+ * the vector kernel (CRUSE_E_SHAPE) and an 8-byte aligned y_bf16 (CRUSE_E_ALIGN); a refused call has written nothing. */
 int cruse_ln_fwd(const float* x, const float* gamma, const float* beta, const float* res,
                  float* y, void* y_bf16, float* mean, float* rstd, long long rows, int H, int interleave_g,
                  float eps, int seg_len, long long seg_stride, long long seg_off, void* stream);
